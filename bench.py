@@ -8,17 +8,24 @@ process per GPU (torch.distributed, backend nccl = RCCL): either the driver star
 WORLD_SIZE) or, when `--gpus N` is given without that environment, this script starts them itself before it touches
 the GPU.  Patches shard by rank with no data-path collective, so scaling is "weak".
 
-After the timed describe steps every rank runs the rest of configs[3] once on the descriptors it just produced, and
-rank 0 reports it under "match_stage": the all-gather of the descriptor shards (the path's one collective; both the
-point-to-point form and RCCL's ring) and the cross-image brute-force match of the rank's own descriptors against the
-gathered set.
+A plain run sets up, warms up, times --steps describe steps, checks their output and prints the line (headline, roofline
+of the timed launches, per-rank figures).  --dump-outputs DIR also writes what the last timed step computed:
+DIR/descriptors.npy (DIR/descriptors_rank<r>.npy for N > 1), float32 [rows, 128] -- every row when a rank has at most
+65536 / N patches, otherwise a fixed seeded sample of that many rows in row order (at most 32 MiB in all).  The inputs
+are seeded: the same arguments give the same patches on every run.
+
+--full adds everything else, each in runs of its own after the headline: the other angle / pooling modes on the same
+workload, configs[3] in keypoint mode, the match stage, the secondary pipelines and the CPU baseline.  There, after the
+timed describe steps every rank runs the rest of configs[3] once on the descriptors it just produced, and rank 0 reports
+it under "match_stage": the all-gather of the descriptor shards (the path's one collective; both the point-to-point form
+and RCCL's ring) and the cross-image brute-force match of the rank's own descriptors against the gathered set.
 
 Extra objects on the line:
   roofline      the describe kernel (mkd_pool: blur .. whitening .. L2 fused in one launch) vs the
                 8 TB/s HBM roof: algorithmic bytes per launch (4608 B x descriptors) /
                 its mean launch time from HIP events recorded by the library on the launch stream
                 (lf_mkd_kernel_times)
-  cpu_baseline  the CPU oracle (a port of the reference's algorithm) timed on this host, rank 0, N=1,
+  cpu_baseline  (--full) the CPU oracle (a port of the reference's algorithm) timed on this host, rank 0, N=1,
                 on a bounded sample of the same workload
 """
 import argparse
@@ -34,6 +41,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 BYTES_PER_DESC = 4608          # 4096 B patch read + 512 B descriptor write
 FLOP_PER_DESC = 2 * 1024 * 238 + 2 * 238 * 128   # pooling (238 sums over 1024 pixels) + whitening, as f32 multiply-adds
 MFMA_F16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense f16/bf16 matrix peak
+DUMP_ROWS = 65536              # --dump-outputs: descriptor rows over all ranks (32 MiB of float32)
 
 
 def host_cores():
@@ -83,6 +91,17 @@ def cpu_baseline(seconds, seed):
                       f"oracle/mkd_cpu_fast.c (AVX2 + FMA, -march=x86-64-v3; single thread: {n1} patches, {dt1:.1f} s); "
                       f"the parity oracle oracle/mkd_oracle.c on the same cores: {n2} patches, {dt2:.1f} s; "
                       "LUTs and whitening matrix built once (the reference rebuilds them per patch)"}
+
+
+def dump_outputs(path, torch, out, rank, world):
+    """--dump-outputs: this rank's descriptors from the last timed step, float32 [rows, 128] (see the module docstring)."""
+    import numpy as np
+    n = out.shape[0]
+    k = min(n, DUMP_ROWS // world)
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0x4D4B44).choice(n, k, replace=False))
+    d = out[torch.from_numpy(rows).to(out.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "descriptors.npy" if world == 1 else f"descriptors_rank{rank}.npy"), d)
 
 
 def smooth_frames(torch, count, h, w, sigma, seed):
@@ -680,6 +699,8 @@ def main():
     ap.add_argument("--patches", type=int, default=1 << 20, help="patches per GPU per step")
     ap.add_argument("--angle", choices=["shader", "exact", "exact_zero"], default="shader")
     ap.add_argument("--pool", choices=["f32", "f16x3"], default=os.environ.get("LF_MKD_POOL", "f16x3"))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's descriptors to DIR (.npy)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary figure (the options below apply to it)")
     ap.add_argument("--cpu-sample", type=int, default=-1, help="seconds of CPU work for the CPU baseline (default ~12; 0: skip)")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary pipeline figures")
     ap.add_argument("--no-match", action="store_true", help="skip the all-gather + cross-image match stage")
@@ -778,7 +799,7 @@ def main():
         return n * args.steps / (time.perf_counter() - t1)
 
     alt = alt_f32 = alt_fp6 = None
-    if world == 1 and args.angle == "shader" and args.pool == "f16x3":
+    if args.full and world == 1 and args.angle == "shader" and args.pool == "f16x3":
         alt = side_figure(lfp.ANGLE_EXACT_ZERO, lfp.POOL_F16X3)
         # the same workload with the pooling contraction in exact f32 arithmetic (LF_MKD_POOL_F32, the verification mode)
         alt_f32 = side_figure(lfp.ANGLE_SHADER, lfp.POOL_F32)
@@ -791,6 +812,8 @@ def main():
     ok = bool(torch.isfinite(out).all().item()) and float((nrm - 1).abs().max().item()) < 1e-4
     if not ok:
         raise SystemExit("bench.py: descriptors are not finite / unit norm")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, out, rank, world)
 
     # The headline is complete at this point; what follows (the collective and the match stage, then the secondary pipelines)
     # must never cost it.  An exception is reported in place of the stage; a HANG -- a rank stuck in a collective its peers
@@ -827,7 +850,7 @@ def main():
 
     # configs[3] in its own form (keypoint mode, frames sharded by image): every rank runs its share, with no collective
     # inside; one object gather afterwards, reached by every rank whatever happened locally
-    if args.frames_per_gpu > 0:
+    if args.full and args.frames_per_gpu > 0:
         dog = threading.Timer(limit, emit_and_leave, args=(f"configs[3] keypoint-mode leg did not finish within {limit:.0f} s", "configs3_keypoint_mode"))
         dog.daemon = True
         dog.start()
@@ -884,7 +907,7 @@ def main():
                 failed = "configs[3] keypoint-mode leg failed on a rank"
             line["configs3_keypoint_mode"] = kp
 
-    if not args.no_match:
+    if args.full and not args.no_match:
         dog = threading.Timer(limit, emit_and_leave, args=(f"match stage did not finish within {limit:.0f} s",))
         dog.daemon = True
         dog.start()
@@ -903,14 +926,14 @@ def main():
 
     if rank == 0:
         line["match_stage"] = stage
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             del patches, out, gathered
             torch.cuda.empty_cache()
             try:
                 line["pipelines"] = pipeline_extras(lfp, torch, local_rank)
             except Exception as e:       # secondary figures must never cost the headline
                 line["pipelines"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1:
+        if args.full and world == 1:
             if args.cpu_sample != 0:                                  # seconds of CPU work (default about 12; 0: skip)
                 line["cpu_baseline"] = cpu_baseline(12.0 if args.cpu_sample < 0 else float(args.cpu_sample), 0x4D4B44)
         print(json.dumps(line), flush=True)

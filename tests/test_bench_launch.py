@@ -29,6 +29,25 @@ def test_world_size_must_match_gpus():
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: every row when they fit, else the same seeded sample of DUMP_ROWS / N rows on every run, in row order."""
+    import numpy as np
+    import torch
+    import bench
+    small, big = torch.randn((100, 128)), torch.randn((bench.DUMP_ROWS + 5000, 128))
+    big[:, 0] = torch.arange(len(big))                                   # column 0 names the row
+    bench.dump_outputs(str(tmp_path / "a"), torch, small, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "a" / "descriptors.npy"), small.numpy())
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), torch, big, 0, 1)
+    b, c = np.load(tmp_path / "b" / "descriptors.npy"), np.load(tmp_path / "c" / "descriptors.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_ROWS, 128) and np.array_equal(b, c)
+    rows = b[:, 0].astype(np.int64)
+    assert (np.diff(rows) > 0).all() and np.array_equal(b, big.numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "r"), torch, big, 3, 8)
+    assert np.load(tmp_path / "r" / "descriptors_rank3.npy").shape == (bench.DUMP_ROWS // 8, 128)
+
+
 def test_the_launcher_kills_ranks_that_do_not_finish_in_time():
     """A rank stuck in a collective must not hang the parent for ever: past LF_BENCH_LAUNCH_LIMIT_S the children's process
     group is killed and the parent exits non-zero (124), without launching anything again."""
