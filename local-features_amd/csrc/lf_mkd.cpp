@@ -7,11 +7,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lf_mkd_internal.h"
@@ -20,114 +20,227 @@
 
 using namespace lfmkd;
 
+namespace {
+
+enum Memory { kDevice, kPinned };
+
+// An array of T in device (or pinned host) memory and the elements it holds; freed when its owner goes.
+// Recorded: a recorded pipeline names the array by address and the array can grow while a recording exists, so allocating
+// it retires every recording first (grow).  An array a recording reads that is allocated once, at its final size, is not.
+template <typename T, Memory M = kDevice, bool Recorded = false>
+class HipArray {
+  public:
+    HipArray() = default;
+    HipArray(HipArray &&o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    HipArray &operator=(HipArray &&o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+        return *this;
+    }
+    ~HipArray() { reset(); }
+    operator T *() const { return p_; }
+    T *get() const { return p_; }
+    template <typename U>
+    U *as() const { return reinterpret_cast<U *>(p_); }
+    uint64_t cap() const { return cap_; }
+    void reset() {
+        if (p_) (void)(M == kPinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // frees what the array holds, then room for max(n, 1) elements; cap() is n once that succeeded
+    hipError_t allocate(uint64_t n) {
+        reset();
+        void *p = nullptr;
+        const size_t bytes = std::max<uint64_t>(n, 1) * sizeof(T);
+        const hipError_t e = M == kPinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (e != hipSuccess) return e;
+        p_ = static_cast<T *>(p);
+        cap_ = n;
+        return hipSuccess;
+    }
+
+  private:
+    T *p_ = nullptr;
+    uint64_t cap_ = 0;
+};
+template <typename T, Memory M = kDevice>
+using RecordedArray = HipArray<T, M, true>;
+
+// An instantiated recording.  Whoever drops one that may still be running waits for the device first.
+struct Recording {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    Recording() = default;
+    Recording(Recording &&o) noexcept : graph(std::exchange(o.graph, nullptr)), exec(std::exchange(o.exec, nullptr)) {}
+    Recording &operator=(Recording &&o) noexcept {
+        std::swap(graph, o.graph);
+        std::swap(exec, o.exec);
+        return *this;
+    }
+    ~Recording() { reset(); }
+    void reset() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+    }
+    explicit operator bool() const { return exec != nullptr; }
+};
+
+// A request of lf_mkd_detect / lf_mkd_detect_u8: what a recording of its pipeline is specific to
+struct DetectKey {
+    uint32_t w, h, top_n, min_size_bits;
+    uint64_t max_out;
+    bool u8;
+    bool operator==(const DetectKey &o) const {
+        return w == o.w && h == o.h && top_n == o.top_n && min_size_bits == o.min_size_bits && max_out == o.max_out && u8 == o.u8;
+    }
+};
+
+// At most Cap values by request; the least recently found or added one makes room for a new request.
+template <typename V, size_t Cap>
+class LruList {
+  public:
+    V *find(const DetectKey &key) {
+        for (Entry &e : items_)
+            if (e.key == key) {
+                e.stamp = ++clock_;
+                return &e.value;
+            }
+        return nullptr;
+    }
+    // Room for one more: when the list is full, before_drop() runs and then the least recently used entry goes (a nonzero
+    // code from before_drop is returned, and the entry stays).
+    template <typename F>
+    int make_room(F before_drop) {
+        if (items_.size() < Cap) return 0;
+        auto old = std::min_element(items_.begin(), items_.end(), [](const Entry &a, const Entry &b) { return a.stamp < b.stamp; });
+        if (int rc = before_drop()) return rc;
+        items_.erase(old);
+        return 0;
+    }
+    V &add(const DetectKey &key, V value) {
+        items_.push_back(Entry{key, std::move(value), ++clock_});
+        return items_.back().value;
+    }
+    void clear() { items_.clear(); }
+    size_t size() const { return items_.size(); }
+    template <typename F>
+    void for_each(F f) const {
+        for (const Entry &e : items_) f(e.value);
+    }
+
+  private:
+    struct Entry {
+        DetectKey key;
+        V value;
+        uint64_t stamp;
+    };
+    std::vector<Entry> items_;
+    uint64_t clock_ = 0;
+};
+
+// lf_mkd_detect's recording of one request.  Banded form (frames large enough to be worth it): the frame is uploaded in
+// pieces, rows [0, cuts[0]) first, then [cuts[0], cuts[1]) ...; heads[p] is the share of the pipeline's front the frame's
+// first cuts[p] rows allow beyond heads[p - 1]'s (RowBands) and runs while piece p + 1 is on its way, `graph` is then the
+// last piece's share + everything else
+struct DetectPlan {
+    Recording graph;
+    std::vector<uint32_t> cuts;
+    std::vector<Recording> heads;
+};
+
+}  // namespace
+
 struct lf_mkd {
     lf_mkd_params params{};
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;   // lf_mkd_detect / the recorded pipeline: pyramid levels >= 1 are built here beside the detector
     std::vector<hipEvent_t> side_events;
-    DeviceConsts dc;
-    uint64_t batch = 0;         // descriptors per internal batch (multiple of 64)
-    float *d_patches = nullptr; // [batch][1024] staging: host patches / sampled patches
-    float *d_out = nullptr;     // [batch][128]  staging for host output
-    float *d_kps = nullptr;     // [batch][5]
+    struct {                             // the model's constants, uploaded at creation ...
+        HipArray<short> colmap;
+        HipArray<float> pool_b_f32, white_a_f32, white_bias;
+        HipArray<uint16_t> pool_b_f16, pool_b_fp6, white_a_f16;
+    } consts;
+    DeviceConsts dc;                     // ... as the launchers take them
+    uint64_t batch = 0;                  // descriptors per internal batch (multiple of 64)
+    HipArray<float> d_patches;           // [batch][1024] staging: host patches / sampled patches
+    HipArray<float> d_out;               // [batch][128]  staging for host output
+    HipArray<float> d_kps;               // [batch][5]
     // keypoint mode
     PyramidDesc pd{};
-    float *d_image = nullptr, *d_pyr = nullptr, *d_tmp_a = nullptr, *d_tmp_b = nullptr;
+    HipArray<float> d_image, d_pyr, d_tmp_a, d_tmp_b;
     bool have_image = false;
     uint32_t max_frames = 1, n_frames = 0;  // frames held by the pyramid store / currently loaded
     long pyr_stride = 0;                    // floats between the pyramids of consecutive frames
     // keypoint orientation: a-trous layers 1 .. n_layers-1 per frame (layer 0 = pyramid level 0), allocated on first use
     int n_layers = 7;
-    float *d_coarse = nullptr;
+    HipArray<float> d_coarse;
     long layer_stride = 0, coarse_stride = 0;  // floats between layers / between frames
     bool coarse_valid = false, coarse_l1_valid = false;
-    uint64_t orient_cap = 0;                   // extrema the scratch arrays below hold
-    float *d_extrema = nullptr, *d_angles = nullptr, *d_kps_out = nullptr;
-    unsigned *d_counts = nullptr, *d_orient_sums = nullptr;
-    uint64_t kps_out_cap = 0;
-    unsigned long long *d_totals = nullptr;
-    unsigned long long *d_clk = nullptr;       // LF_MKD_FLAG_KERNEL_TIMING: clock stamps of the latest describe launch
+    // orientation scratch for max(n, batch) extrema, and the keypoint rows of lf_mkd_orient_keypoints / lf_mkd_detect
+    RecordedArray<lf_mkd_extremum> d_extrema;
+    RecordedArray<float> d_angles;
+    RecordedArray<unsigned> d_counts, d_orient_sums;
+    RecordedArray<lf_mkd_keypoint> d_kps_out;
+    RecordedArray<float> d_det_desc;           // [max_out][128] lf_mkd_detect's descriptor staging
+    HipArray<unsigned long long> d_totals;
+    HipArray<unsigned long long> d_clk;        // LF_MKD_FLAG_KERNEL_TIMING: clock stamps of the latest describe launch
     // the row-split form of the keypoint kernel (requests of at most 16 x CUs keypoints): partial sums and their counters
-    float *d_kp_xchg = nullptr;
-    unsigned *d_kp_words = nullptr;
+    HipArray<float> d_kp_xchg;
+    HipArray<unsigned> d_kp_words;
     // detector scratch (allocated on first use): per-cube slots and counts for max_frames frames of the maximum size
     uint64_t max_extrema = 8192;
-    float *d_slots = nullptr, *d_det_extrema = nullptr, *d_det_selected = nullptr, *d_det_desc = nullptr;
-    unsigned *d_cube_counts = nullptr, *d_cube_sums = nullptr, *d_sel_count = nullptr, *d_topk_work = nullptr;
-    uint64_t topk_work_cap = 0;
-    uint64_t det_out_cap = 0, det_sel_cap = 0;
+    HipArray<float> d_slots;
+    HipArray<unsigned> d_cube_counts, d_cube_sums, d_sel_count;
+    RecordedArray<lf_mkd_extremum> d_det_extrema, d_det_selected;
+    RecordedArray<unsigned> d_topk_work;
     // multi-frame detect (lf_mkd_detect_frames_device)
-    float *d_mf_padded = nullptr, *d_mf_list = nullptr;
-    unsigned *d_mf_frame_start = nullptr, *d_mf_offsets = nullptr, *d_mf_frame_of = nullptr;
-    uint64_t mf_padded_cap = 0, mf_list_cap = 0, mf_start_cap = 0, mf_off_cap = 0, mf_fo_cap = 0;
+    HipArray<lf_mkd_extremum> d_mf_padded, d_mf_list;
+    HipArray<unsigned> d_mf_frame_start, d_mf_offsets, d_mf_frame_of;
     // graph-captured per-frame pipeline (lf_mkd_stream_*)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
     PyramidDesc graph_pd{};     // frame geometry the recorded pipeline was captured for
-    float *d_stream_patches = nullptr;
-    uint64_t stream_patch_cap = 0;
-    // lf_mkd_detect / lf_mkd_detect_u8: the same launch sequence recorded once per (frame size, top_n, min_size, max_out,
-    // pixel type) and kept -- a call is one upload, one graph launch, one wait, the result copies
-    struct DetectPlan {
-        uint32_t w = 0, h = 0, top_n = 0, min_size_bits = 0;
-        uint64_t max_out = 0, stamp = 0;
-        bool u8 = false;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        // banded form (frames large enough to be worth it): the frame is uploaded in pieces, rows [0, cuts[0]) first, then
-        // [cuts[0], cuts[1]) ...; heads[p] is the share of the pipeline's front the frame's first cuts[p] rows allow beyond
-        // heads[p - 1]'s (RowBands) and runs while piece p + 1 is on its way, `graph` is then the last piece's share +
-        // everything else
-        std::vector<uint32_t> cuts;
-        std::vector<hipGraph_t> head_graphs;
-        std::vector<hipGraphExec_t> heads;
-        PyramidDesc pd{};
-    };
-    std::vector<DetectPlan> plans;
-    uint64_t plan_clock = 0;
+    RecordedArray<float> d_stream_patches;
+    // lf_mkd_detect / lf_mkd_detect_u8: the same launch sequence recorded once per request (DetectKey) and kept -- a call is
+    // one upload, one graph launch, one wait, the result copies.
     // Requests seen but not recorded yet.  Recording costs a capture and an instantiation (more when the upload is banded) --
     // several times the call itself -- so a request is served by the pipeline's plain launches until it has been seen record_after times
     // (default 1: the reference's match_images detects each image once, at its own size, and never pays a recording; a
     // camera loop records on its second frame and replays from the third).  LF_MKD_DETECT_RECORD_AFTER in the environment,
     // read at creation: 0 records on the first sighting.
-    struct Sighting {
-        uint32_t w, h, top_n, min_size_bits;
-        uint64_t max_out, count, stamp;
-        bool u8;
-    };
-    std::vector<Sighting> sightings;
     uint64_t record_after = 1;
-    unsigned char *d_image_u8 = nullptr;              // 8-bit frame(s) on their way to level 0, allocated on first use
-    unsigned long long *d_det_counts = nullptr;       // [8] the recorded detect pipeline's counts (as lf_mkd_stream_create's d_counts)
-    unsigned long long *h_det_counts = nullptr;       // the same in pinned host memory: the last node of a plan copies them here
+    HipArray<unsigned char> d_image_u8;               // 8-bit frame(s) on their way to level 0, allocated on first use
+    HipArray<unsigned long long> d_det_counts;        // [8] the recorded detect pipeline's counts (as lf_mkd_stream_create's d_counts)
+    HipArray<unsigned long long, kPinned> h_det_counts;   // the same in pinned host memory: the last node of a plan copies them here
     // ... and the keypoints, copied there by the pipeline's last node.
     // (The descriptors stay in device memory until the count is known: having the describe kernel store them straight into
     // pinned host memory was measured -- +20 us of kernel time at 100 keypoints, +45 us at 3000, PCIe writes stall its
     // epilogue -- and so was a copy node of all max_out rows followed by a host memcpy of n: reading memory the device has
     // just written runs at 25 GB/s on one core, 60 us for 3000 rows, where the runtime's own copy into the caller's array takes 15.)
-    lf_mkd_keypoint *h_res_kps = nullptr;
-    uint64_t h_res_cap = 0;
+    RecordedArray<lf_mkd_keypoint, kPinned> h_res_kps;
     hipStream_t copy_stream = nullptr;                    // the banded upload: pieces are copied here, the pipeline's parts wait for them
     std::vector<hipEvent_t> copy_ev;
     hipEvent_t det_ev[3] = {nullptr, nullptr, nullptr};   // LF_MKD_FLAG_KERNEL_TIMING: before the upload, after it, after the pipeline
     double det_upload_ms = 0, det_pipeline_ms = 0, det_readback_ms = 0;
     // matcher scratch
-    unsigned char *d_match_a = nullptr, *d_match_b = nullptr;
-    float *d_match_part = nullptr, *d_match_in = nullptr;
-    int *d_match_out = nullptr;
-    uint64_t match_a_cap = 0, match_b_cap = 0, match_part_cap = 0, match_in_cap = 0, match_out_cap = 0;
-    unsigned char *d_match_rec = nullptr;      // two-pass form: candidate records, their counts, |a| per row, two words
-    unsigned char *d_match_cnt = nullptr;      // (largest |b| as float bits, number of overflowed rows)
-    float *d_match_norm = nullptr, *d_match_floor = nullptr;   // (floor: the bounds the screen's b splits share, per a row)
-    unsigned *d_match_misc = nullptr;
-    unsigned char *d_match_few_tiles = nullptr;   // the overflowed rows' own tiles; their indices, exclusion ranges, partials
-    unsigned *d_match_few = nullptr;
-    uint64_t match_rec_cap = 0, match_cnt_cap = 0, match_norm_cap = 0, match_misc_cap = 0, match_few_tiles_cap = 0,
-             match_few_cap = 0, match_floor_cap = 0;
+    HipArray<unsigned char> d_match_a, d_match_b;
+    HipArray<float> d_match_part, d_match_in;
+    HipArray<int> d_match_out;
+    HipArray<unsigned char> d_match_rec;       // two-pass form: candidate records, their counts, |a| per row, two words
+    HipArray<unsigned char> d_match_cnt;       // (largest |b| as float bits, number of overflowed rows)
+    HipArray<float> d_match_norm, d_match_floor;   // (floor: the bounds the screen's b splits share, per a row)
+    HipArray<unsigned> d_match_misc;
+    HipArray<unsigned char> d_match_few_tiles;   // the overflowed rows' own tiles; their indices, exclusion ranges, partials
+    HipArray<unsigned> d_match_few;
     int num_cus = 256;
     // LF_MKD_FLAG_KERNEL_TIMING: (start, end) of the describe kernel per batch
     std::vector<hipEvent_t> ev_pending, ev_free;
     std::string err;
+    // The recordings, declared after every array they name: they are destroyed first.
+    Recording stream_graph;              // lf_mkd_stream_*
+    LruList<DetectPlan, 8> plans;        // lf_mkd_detect's recordings
+    LruList<uint64_t, 64> sightings;     // times a request not recorded yet was served by the plain launches
 };
 
 namespace {
@@ -155,10 +268,10 @@ int fail(lf_mkd *h, int code, const std::string &msg) {
 }
 
 template <typename T>
-hipError_t upload(T **dst, const void *src, size_t bytes) {
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), bytes);
+hipError_t upload(HipArray<T> &dst, const std::vector<T> &src) {
+    hipError_t e = dst.allocate(src.size());
     if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    return hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 long pyramid_levels(uint32_t w, uint32_t h) {  // mod.rs:271-277,372-373
@@ -247,19 +360,20 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
         LF_CREATE_HIP(hipGetDeviceProperties(&prop, params->device));
         h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    LF_CREATE_HIP(upload(&h->dc.colmap, hc.colmap.data(), hc.colmap.size() * 2));
-    LF_CREATE_HIP(upload(&h->dc.pool_b_f32, hc.pool_b_f32.data(), hc.pool_b_f32.size() * 4));
-    LF_CREATE_HIP(upload(&h->dc.pool_b_f16, hc.pool_b_f16.data(), hc.pool_b_f16.size() * 2));
-    if (h->params.pool_mode == LF_MKD_POOL_F16_FP6)
-        LF_CREATE_HIP(upload(&h->dc.pool_b_fp6, hc.pool_b_fp6.data(), hc.pool_b_fp6.size() * 2));
-    LF_CREATE_HIP(upload(&h->dc.white_a_f16, hc.white_a_f16.data(), hc.white_a_f16.size() * 2));
-    LF_CREATE_HIP(upload(&h->dc.white_a_f32, hc.white_a_f32.data(), hc.white_a_f32.size() * 4));
-    LF_CREATE_HIP(upload(&h->dc.white_bias, hc.white_bias.data(), hc.white_bias.size() * 4));
+    auto &c = h->consts;
+    LF_CREATE_HIP(upload(c.colmap, hc.colmap));
+    LF_CREATE_HIP(upload(c.pool_b_f32, hc.pool_b_f32));
+    LF_CREATE_HIP(upload(c.pool_b_f16, hc.pool_b_f16));
+    if (h->params.pool_mode == LF_MKD_POOL_F16_FP6) LF_CREATE_HIP(upload(c.pool_b_fp6, hc.pool_b_fp6));
+    LF_CREATE_HIP(upload(c.white_a_f16, hc.white_a_f16));
+    LF_CREATE_HIP(upload(c.white_a_f32, hc.white_a_f32));
+    LF_CREATE_HIP(upload(c.white_bias, hc.white_bias));
+    h->dc = DeviceConsts{c.colmap, c.pool_b_f32, c.pool_b_f16, c.pool_b_fp6, c.white_a_f16, c.white_a_f32, c.white_bias};
     // (the staging buffers of the host-pointer and keypoint entry points -- 4.6 KiB per descriptor of the internal batch --
     // are allocated on first use: a caller of the device-pointer patch API never needs them)
-    LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_totals), 8 * sizeof(unsigned long long)));
+    LF_CREATE_HIP(h->d_totals.allocate(8));
     if (h->params.flags & LF_MKD_FLAG_KERNEL_TIMING) {
-        LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_clk), 4 * sizeof(unsigned long long)));
+        LF_CREATE_HIP(h->d_clk.allocate(4));
         LF_CREATE_HIP(hipMemset(h->d_clk, 0, 4 * sizeof(unsigned long long)));
     }
     if (params->max_image_width && params->max_image_height) {
@@ -272,13 +386,15 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
         h->max_frames = params->max_frames ? params->max_frames : 1;
         const size_t px = size_t(params->max_image_width) * params->max_image_height * h->max_frames;
         h->pyr_stride = pyramid_floats(params->max_image_width, params->max_image_height);
-        LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_image), px * 4));
-        LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_tmp_a), px * 4));
-        LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_tmp_b), px * 4));
-        LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_pyr), size_t(h->pyr_stride) * h->max_frames * 4));
+        h->layer_stride = long(params->max_image_width) * params->max_image_height;
+        h->coarse_stride = h->layer_stride * (h->n_layers - 1);
+        LF_CREATE_HIP(h->d_image.allocate(px));
+        LF_CREATE_HIP(h->d_tmp_a.allocate(px));
+        LF_CREATE_HIP(h->d_tmp_b.allocate(px));
+        LF_CREATE_HIP(h->d_pyr.allocate(size_t(h->pyr_stride) * h->max_frames));
         if (h->params.pool_mode == LF_MKD_POOL_F16X3 && !(h->params.flags & LF_MKD_FLAG_UNFUSED_KEYPOINTS)) {
-            LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_kp_xchg), kp_split_exchange_bytes(h->num_cus)));
-            LF_CREATE_HIP(hipMalloc(reinterpret_cast<void **>(&h->d_kp_words), kp_split_counter_words(h->num_cus) * 4));
+            LF_CREATE_HIP(h->d_kp_xchg.allocate(kp_split_exchange_bytes(h->num_cus) / sizeof(float)));
+            LF_CREATE_HIP(h->d_kp_words.allocate(kp_split_counter_words(h->num_cus)));
             LF_CREATE_HIP(hipMemset(h->d_kp_words, 0, kp_split_counter_words(h->num_cus) * 4));
         }
     }
@@ -287,17 +403,30 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
     return LF_MKD_OK;
 }
 
-// staging for one internal batch: sampled / uploaded patches; descriptors on their way to the host and uploaded keypoints
-int ensure_patch_staging(lf_mkd *h) {
-    if (h->d_patches) return LF_MKD_OK;
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_patches), h->batch * kPx * 4));
+// A recorded pipeline holds raw pointers into the scratch buffers: re-allocating one of them retires the recordings
+// (lf_mkd_stream_frame then asks for a new lf_mkd_stream_create instead of touching freed memory, and lf_mkd_detect records anew).
+void retire_graph(lf_mkd *h) {
+    if (h->stream_graph || h->plans.size()) (void)hipDeviceSynchronize();   // a launch may still be running (on any stream)
+    h->stream_graph.reset();
+    h->plans.clear();
+}
+
+// The one growth path of the handle's arrays: an array that holds fewer than `want` elements (or none) is freed, then
+// allocated for max(want, 1).  Growing a Recorded array retires every recording first; growing any other (the matcher's and
+// the multi-frame detect's scratch, say) leaves the recordings alone and does not wait for the device.
+template <typename T, Memory M, bool Recorded>
+int grow(lf_mkd *h, HipArray<T, M, Recorded> &buf, uint64_t want) {
+    if (want <= buf.cap() && buf.get()) return LF_MKD_OK;
+    if (Recorded) retire_graph(h);
+    LF_HIP(h, buf.allocate(want));
     return LF_MKD_OK;
 }
+
+// staging for one internal batch: sampled / uploaded patches; descriptors on their way to the host and uploaded keypoints
+int ensure_patch_staging(lf_mkd *h) { return grow(h, h->d_patches, h->batch * kPx); }
 int ensure_io_staging(lf_mkd *h) {
-    if (h->d_out) return LF_MKD_OK;
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_out), h->batch * kOut * 4));
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_kps), h->batch * 5 * 4));
-    return LF_MKD_OK;
+    if (int rc = grow(h, h->d_out, h->batch * kOut)) return rc;
+    return grow(h, h->d_kps, h->batch * 5);
 }
 int ensure_staging(lf_mkd *h) {
     if (int rc = ensure_patch_staging(h)) return rc;
@@ -368,37 +497,13 @@ int describe_keypoints_on_device(lf_mkd *h, const float *d_kps, const uint32_t *
     return LF_MKD_OK;
 }
 
-void destroy_plan(lf_mkd::DetectPlan &p) {
-    if (p.exec) (void)hipGraphExecDestroy(p.exec);
-    if (p.graph) (void)hipGraphDestroy(p.graph);
-    for (hipGraphExec_t e : p.heads) (void)hipGraphExecDestroy(e);
-    for (hipGraph_t g : p.head_graphs) (void)hipGraphDestroy(g);
-    p.exec = nullptr;
-    p.graph = nullptr;
-    p.heads.clear();
-    p.head_graphs.clear();
-}
-
-// A recorded stream pipeline holds raw pointers into the scratch buffers: re-allocating one of them retires the graph
-// (lf_mkd_stream_frame then asks for a new lf_mkd_stream_create instead of touching freed memory).
-void retire_graph(lf_mkd *h) {
-    if (h->graph_exec || !h->plans.empty()) (void)hipDeviceSynchronize();   // a launch may still be running (on any stream)
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    h->graph_exec = nullptr;
-    h->graph = nullptr;
-    for (auto &p : h->plans) destroy_plan(p);   // lf_mkd_detect's recordings hold the same raw pointers: the next call records anew
-    h->plans.clear();
-}
+// the a-trous stack's store: max_frames frames of the maximum size, allocated on first use
+int ensure_coarse_store(lf_mkd *h) { return grow(h, h->d_coarse, size_t(h->coarse_stride) * h->max_frames); }
 
 // Extends the loaded frames' level 0 into the a-trous stack (once per set_image*), allocating it on first use.
 int ensure_coarse_stack(lf_mkd *h, hipStream_t s) {
     if (h->coarse_valid) return LF_MKD_OK;
-    if (!h->d_coarse) {
-        h->layer_stride = long(h->params.max_image_width) * h->params.max_image_height;
-        h->coarse_stride = h->layer_stride * (h->n_layers - 1);
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_coarse), size_t(h->coarse_stride) * h->max_frames * 4));
-    }
+    if (int rc = ensure_coarse_store(h)) return rc;
     launch_build_coarse_stack(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse, h->coarse_stride, h->layer_stride,
                               h->d_tmp_a, h->n_layers, h->coarse_l1_valid ? 1 : 0, h->pd.w[0], h->pd.h[0],
                               int(h->n_frames), s);
@@ -407,39 +512,24 @@ int ensure_coarse_stack(lf_mkd *h, hipStream_t s) {
     return LF_MKD_OK;
 }
 
+// the orientation scratch for n extrema (sized for max(n, batch) of them) and, with staging, the rows of max_out keypoints
 int ensure_orient_scratch(lf_mkd *h, uint64_t n, bool staging, uint64_t max_out) {
-    if (n > h->orient_cap) {
-        retire_graph(h);
-        for (void *p : {static_cast<void *>(h->d_extrema), static_cast<void *>(h->d_angles),
-                        static_cast<void *>(h->d_counts), static_cast<void *>(h->d_orient_sums)})
-            if (p) (void)hipFree(p);
-        h->d_extrema = h->d_angles = nullptr;
-        h->d_counts = h->d_orient_sums = nullptr;
-        h->orient_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(n, h->batch);
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_extrema), cap * sizeof(lf_mkd_extremum)));
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_angles), cap * LF_MKD_MAX_ANGLES_PER_EXTREMUM * 4));
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_counts), cap * 4));
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_orient_sums), (cap / 1024 + 2) * 4));
-        h->orient_cap = cap;
-    }
-    if (staging && max_out > h->kps_out_cap) {
-        retire_graph(h);
-        if (h->d_kps_out) (void)hipFree(h->d_kps_out);
-        h->d_kps_out = nullptr;
-        h->kps_out_cap = 0;
-        if (h->d_det_desc) (void)hipFree(h->d_det_desc);
-        h->d_det_desc = nullptr;
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_kps_out), max_out * sizeof(lf_mkd_keypoint)));
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_det_desc), max_out * kOut * 4));   // lf_mkd_detect's staging
-        h->kps_out_cap = max_out;
-    }
-    return LF_MKD_OK;
+    const uint64_t cap = std::max<uint64_t>(n, h->batch);
+    if (int rc = grow(h, h->d_extrema, cap)) return rc;
+    if (int rc = grow(h, h->d_angles, cap * LF_MKD_MAX_ANGLES_PER_EXTREMUM)) return rc;
+    if (int rc = grow(h, h->d_counts, cap)) return rc;
+    if (int rc = grow(h, h->d_orient_sums, cap / 1024 + 2)) return rc;
+    if (!staging) return LF_MKD_OK;
+    if (int rc = grow(h, h->d_kps_out, max_out)) return rc;
+    return grow(h, h->d_det_desc, max_out * kOut);
 }
 
 constexpr int kBorder = 5;                  // mod.rs:405
 constexpr float kContrastThreshold = 0.035f; // mod.rs:76
 constexpr int kSkipLayers = 0;              // mod.rs:398
+
+// the top-n selection's count per frame
+int ensure_sel_count(lf_mkd *h) { return grow(h, h->d_sel_count, h->max_frames); }
 
 int ensure_detect_scratch(lf_mkd *h) {
     if (h->d_slots) return LF_MKD_OK;
@@ -447,11 +537,10 @@ int ensure_detect_scratch(lf_mkd *h) {
     scan_grid(int(h->params.max_image_width), int(h->params.max_image_height), h->n_layers - 1, kBorder, kSkipLayers, gx,
               gy, gz);
     const size_t cubes = std::max<size_t>(size_t(gx) * gy * gz, 1) * h->max_frames;
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_slots), cubes * 8 * 4 * sizeof(float)));
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_cube_counts), cubes * 4));
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_cube_sums), ((cubes + 1023) / 1024 + 1) * 4));
-    if (!h->d_sel_count) LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_sel_count), 4 * h->max_frames));
-    return LF_MKD_OK;
+    if (int rc = grow(h, h->d_slots, cubes * 8 * 4)) return rc;
+    if (int rc = grow(h, h->d_cube_counts, cubes)) return rc;
+    if (int rc = grow(h, h->d_cube_sums, (cubes + 1023) / 1024 + 1)) return rc;
+    return ensure_sel_count(h);
 }
 
 // ordered extrema of all loaded frames into d_out (device), counts to the host
@@ -472,31 +561,14 @@ int detect_extrema_device(lf_mkd *h, float *d_out, uint32_t *d_frame_of, uint64_
     return LF_MKD_OK;
 }
 
-// recorded: the buffer is one a recorded pipeline names by address (record_pipeline: the detector's extrema and selection, the
-// top-n scratch, the staging patches; the orientation scratch, d_kps_out, d_det_desc and h_res_kps have their own sites) --
-// moving it retires every recording.  The matcher's and the multi-frame detect's scratch is named by no recording: growing it
-// leaves the recordings alone (and does not wait for the device).
-enum Recorded { kNotRecorded = 0, kRecorded = 1 };
-template <typename T>
-int grow(lf_mkd *h, T **p, uint64_t *cap, uint64_t want, size_t elem_bytes, Recorded recorded = kNotRecorded) {
-    if (want <= *cap && *p) return LF_MKD_OK;
-    if (recorded == kRecorded) retire_graph(h);
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(p), std::max<uint64_t>(want, 1) * elem_bytes));
-    *cap = want;
-    return LF_MKD_OK;
-}
-
 // scratch of the long-list top-n selection; its histograms are zero between uses (the selection's last launch leaves them
 // so), which a fresh allocation has to establish once
 // (zeroed on the stream the selection will run on, outside any capture: the consumers' streams are non-blocking, i.e. not
 // ordered with the null stream)
 int grow_topk_work(lf_mkd *h, uint64_t n_cap, hipStream_t s) {
-    const uint64_t before = h->topk_work_cap;
-    if (int rc = grow(h, &h->d_topk_work, &h->topk_work_cap, topk_work_words(n_cap), 4, kRecorded)) return rc;
-    if (h->topk_work_cap != before) LF_HIP(h, hipMemsetAsync(h->d_topk_work, 0, topk_work_words(n_cap) * 4, s));
+    const uint64_t before = h->d_topk_work.cap();
+    if (int rc = grow(h, h->d_topk_work, topk_work_words(n_cap))) return rc;
+    if (h->d_topk_work.cap() != before) LF_HIP(h, hipMemsetAsync(h->d_topk_work, 0, topk_work_words(n_cap) * 4, s));
     return LF_MKD_OK;
 }
 
@@ -505,7 +577,7 @@ int grow_topk_work(lf_mkd *h, uint64_t n_cap, hipStream_t s) {
 // the match will run on (so that a form that does not reset [2] adds to a defined value)
 int ensure_match_misc(lf_mkd *h, hipStream_t s) {
     if (h->d_match_misc) return LF_MKD_OK;
-    if (int rc = grow(h, &h->d_match_misc, &h->match_misc_cap, 3, sizeof(unsigned))) return rc;
+    if (int rc = grow(h, h->d_match_misc, 3)) return rc;
     LF_HIP(h, hipMemsetAsync(h->d_match_misc, 0, 3 * sizeof(unsigned), s));
     return LF_MKD_OK;
 }
@@ -548,7 +620,7 @@ bool piece_bands(const std::vector<uint32_t> &cuts, size_t p, int w, int hgt, in
 // What the pieces cost, from this chip's timelines of the reference benchmark's frame (4096 x 3072; profiles/r06_bands.md):
 // picoseconds per pixel of a stage's rows plus a floor per launch; the link's rate for a copy from pageable memory and what
 // an extra piece costs the link: ~11 us per copy call (r05_upload_probe.txt) + ~15 us in which the host, blocked in the
-// copy until then, records the event and launches the head (LF_MKD_BAND_TRACE prints the calls' host times).
+// copy until then, records the event and launches the head.
 struct FrontModel {
     double sep3 = 2.3, swt = 1.7, swt_deep = 2.3, floor_us = 5.0, link_gb_s = 56.0, gap_us = 26.0;
     double scan(int n_fine) const { return std::max(3.25 * n_fine - 6.85, 2.0); }
@@ -722,37 +794,14 @@ void lf_mkd_destroy(lf_mkd *h) {
     lfmkd::DeviceScope scope_;
     (void)scope_.enter(h->params.device);
     (void)hipDeviceSynchronize();   // work of this handle may be in flight on the caller's streams too
-    void *ptrs[] = {h->dc.colmap,     h->dc.pool_b_f32, h->dc.pool_b_f16, h->dc.pool_b_fp6, h->dc.white_a_f16,
-                    h->dc.white_a_f32, h->dc.white_bias, h->d_patches,     h->d_out,         h->d_kps,
-                    h->d_image,        h->d_pyr,         h->d_tmp_a,       h->d_tmp_b,       h->d_coarse,
-                    h->d_extrema,      h->d_angles,      h->d_counts,      h->d_kps_out,     h->d_totals,      h->d_clk,
-                    h->d_slots,        h->d_det_extrema, h->d_det_selected, h->d_det_desc,
-                    h->d_cube_counts,  h->d_cube_sums,   h->d_sel_count,   h->d_match_a,     h->d_match_b,
-                    h->d_orient_sums,  h->d_topk_work,
-                    h->d_match_part,   h->d_match_in,    h->d_match_out,   h->d_mf_padded,   h->d_mf_list,
-                    h->d_mf_frame_start, h->d_mf_offsets, h->d_mf_frame_of,
-                    h->d_match_rec,    h->d_match_cnt,   h->d_match_norm,  h->d_match_misc,
-                    h->d_match_few_tiles, h->d_match_few, h->d_kp_xchg, h->d_kp_words, h->d_match_floor};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    for (auto &p : h->plans) destroy_plan(p);
-    for (hipEvent_t e : h->copy_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->d_image_u8) (void)hipFree(h->d_image_u8);
+    h->stream_graph.reset();        // the recordings, then the events and streams; the arrays go with the handle
+    h->plans.clear();
+    for (const std::vector<hipEvent_t> *events : {&h->copy_ev, &h->ev_pending, &h->ev_free, &h->side_events})
+        for (hipEvent_t e : *events) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->det_ev)
         if (e) (void)hipEventDestroy(e);
-    if (h->d_det_counts) (void)hipFree(h->d_det_counts);
-    if (h->h_det_counts) (void)hipHostFree(h->h_det_counts);
-    if (h->h_res_kps) (void)hipHostFree(h->h_res_kps);
-    if (h->d_stream_patches) (void)hipFree(h->d_stream_patches);
-    for (hipEvent_t e : h->ev_pending) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->side_events) (void)hipEventDestroy(e);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    for (hipStream_t s : {h->copy_stream, h->side_stream, h->stream})
+        if (s) (void)hipStreamDestroy(s);
     delete h;
 }
 
@@ -866,9 +915,9 @@ static int set_images_impl(lf_mkd *h, const float *d_images, const unsigned char
     describe_pyramid(width, height, h->pd);
     // once the a-trous stack exists (orientation or the detector have been used on this handle) the pyramid's
     // a-trous layer 1 goes straight into it
-    const bool share = h->d_coarse != nullptr && h->pd.levels >= 2;
+    const bool share = h->d_coarse.get() != nullptr && h->pd.levels >= 2;
     launch_build_pyramid(d_images, long(width) * height, h->d_pyr, h->pyr_stride, h->d_tmp_a, h->d_tmp_b, h->pd,
-                         int(n_frames), share ? h->d_coarse : nullptr, h->coarse_stride, s, nullptr, nullptr, nullptr, {},
+                         int(n_frames), share ? h->d_coarse.get() : nullptr, h->coarse_stride, s, nullptr, nullptr, nullptr, {},
                          d_images_u8);
     h->coarse_l1_valid = share;
     LF_HIP(h, hipGetLastError());
@@ -895,12 +944,9 @@ int lf_mkd_set_image_device(lf_mkd *h, const float *d_image, uint32_t width, uin
 }
 
 // the 8-bit staging frame (1 B/px; lf_mkd_set_image_u8, lf_mkd_detect_u8), allocated on first use
+// (a recorded pipeline reads it by address: allocated once at the maximum frame size, it never moves)
 static int ensure_u8_staging(lf_mkd *h) {
-    if (h->d_image_u8) return LF_MKD_OK;
-    // (a recorded pipeline reads it by address: allocated once at the maximum frame size, it never moves)
-    LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_image_u8),
-                        (size_t(h->params.max_image_width) * h->params.max_image_height + 3) / 4 * 4));
-    return LF_MKD_OK;
+    return grow(h, h->d_image_u8, (size_t(h->params.max_image_width) * h->params.max_image_height + 3) / 4 * 4);
 }
 
 int lf_mkd_set_image(lf_mkd *h, const float *image, uint32_t width, uint32_t height) {
@@ -1014,7 +1060,8 @@ int lf_mkd_orient_keypoints(lf_mkd *h, const lf_mkd_extremum *extrema, uint64_t 
     LF_ENTER(h);
     if (int rc = ensure_orient_scratch(h, n, true, std::max<uint64_t>(max_out, 1))) return rc;
     LF_HIP(h, hipMemcpyAsync(h->d_extrema, extrema, n * sizeof(lf_mkd_extremum), hipMemcpyHostToDevice, h->stream));
-    if (int rc = orient_device(h, h->d_extrema, nullptr, n, h->d_kps_out, nullptr, max_out, n_out, n_dropped, h->stream))
+    if (int rc = orient_device(h, h->d_extrema.as<float>(), nullptr, n, h->d_kps_out.as<float>(), nullptr, max_out, n_out,
+                               n_dropped, h->stream))
         return rc;
     if (*n_out) LF_HIP(h, hipMemcpy(out, h->d_kps_out, *n_out * sizeof(lf_mkd_keypoint), hipMemcpyDeviceToHost));
     return LF_MKD_OK;
@@ -1041,8 +1088,8 @@ int lf_mkd_detect_extrema(lf_mkd *h, lf_mkd_extremum *out, uint64_t max_out, uin
     if (!h->have_image) return fail(h, LF_MKD_ERR_NO_IMAGE, "detect_extrema: call lf_mkd_set_image first");
     if (!out && max_out) return fail(h, LF_MKD_ERR_BAD_ARG, "detect_extrema: null pointer");
     LF_ENTER(h);
-    if (int rc = grow(h, &h->d_det_extrema, &h->det_out_cap, max_out, sizeof(lf_mkd_extremum), kRecorded)) return rc;
-    if (int rc = detect_extrema_device(h, h->d_det_extrema, nullptr, max_out, n_out, n_dropped, h->stream)) return rc;
+    if (int rc = grow(h, h->d_det_extrema, max_out)) return rc;
+    if (int rc = detect_extrema_device(h, h->d_det_extrema.as<float>(), nullptr, max_out, n_out, n_dropped, h->stream)) return rc;
     if (*n_out) LF_HIP(h, hipMemcpy(out, h->d_det_extrema, *n_out * sizeof(lf_mkd_extremum), hipMemcpyDeviceToHost));
     return LF_MKD_OK;
 }
@@ -1057,7 +1104,7 @@ int lf_mkd_filter_extrema_device(lf_mkd *h, const lf_mkd_extremum *d_extrema, ui
     if (n > 0xFFFFFFFFull) return fail(h, LF_MKD_ERR_BAD_ARG, "filter_extrema_device: more than 2^32 extrema");
     LF_ENTER(h);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (!h->d_sel_count) LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_sel_count), 4 * h->max_frames));
+    if (int rc = ensure_sel_count(h)) return rc;
     if (int rc = grow_topk_work(h, n, s)) return rc;
     launch_topk_filter(reinterpret_cast<const float *>(d_extrema), nullptr, nullptr, n, 1, 0xFFFFFFFFu, top_n, min_size,
                        reinterpret_cast<float *>(d_out), d_index, h->d_sel_count, nullptr, n, h->d_topk_work, s);
@@ -1079,7 +1126,7 @@ static int detect_stepwise(lf_mkd *h, bool u8, uint32_t width, uint32_t height, 
     // lf_mkd_set_image without its synchronisation, and -- once the a-trous stack exists, i.e. from the second call on --
     // with pyramid levels >= 1 (read by the sampler only) built on the side stream beside the a-trous passes and the scan
     describe_pyramid(width, height, h->pd);
-    const bool share = h->d_coarse != nullptr && h->pd.levels >= 2;
+    const bool share = h->d_coarse.get() != nullptr && h->pd.levels >= 2;
     if (share)
         if (int rc = ensure_side_stream(h, 2)) return rc;
     // (with the branch, the rest of the a-trous stack is queued from inside, ahead of it: see launch_build_pyramid)
@@ -1092,42 +1139,41 @@ static int detect_stepwise(lf_mkd *h, bool u8, uint32_t width, uint32_t height, 
             stack_queued = true;
         };
     launch_build_pyramid(h->d_image, long(width) * height, h->d_pyr, h->pyr_stride, h->d_tmp_a, h->d_tmp_b, h->pd, 1,
-                         share ? h->d_coarse : nullptr, h->coarse_stride, s, share ? h->side_stream : nullptr,
+                         share ? h->d_coarse.get() : nullptr, h->coarse_stride, s, share ? h->side_stream : nullptr,
                          share ? h->side_events[0] : nullptr, share ? h->side_events[1] : nullptr, stack_first,
-                         u8 ? h->d_image_u8 : nullptr);
+                         u8 ? h->d_image_u8.get() : nullptr);
     LF_HIP(h, hipGetLastError());
     h->coarse_l1_valid = share;
     h->have_image = true;
     h->coarse_valid = stack_queued;
     h->n_frames = 1;
     // detect graph: extrema, at most max_extrema of them (mod.rs:625-633)
-    if (int rc = grow(h, &h->d_det_extrema, &h->det_out_cap, h->max_extrema, sizeof(lf_mkd_extremum), kRecorded)) return rc;
+    if (int rc = grow(h, h->d_det_extrema, h->max_extrema)) return rc;
     uint64_t n_ext = 0;
-    const int rc_ext = detect_extrema_device(h, h->d_det_extrema, nullptr, h->max_extrema, &n_ext, dropped_blobs, s);
+    const int rc_ext = detect_extrema_device(h, h->d_det_extrema.as<float>(), nullptr, h->max_extrema, &n_ext, dropped_blobs, s);
     if (share) LF_HIP(h, hipStreamWaitEvent(s, h->side_events[1], 0));   // whatever follows on s sees the whole pyramid
     if (rc_ext) return rc_ext;
     // host blob filter of detect_top_n, on the device
-    const float *d_sel = h->d_det_extrema;
+    const float *d_sel = h->d_det_extrema.as<float>();
     if (top_n && n_ext) {
-        if (int rc = grow(h, &h->d_det_selected, &h->det_sel_cap, top_n, sizeof(lf_mkd_extremum), kRecorded)) return rc;
+        if (int rc = grow(h, h->d_det_selected, top_n)) return rc;
         uint64_t n_sel = 0;
-        if (int rc = lf_mkd_filter_extrema_device(h, reinterpret_cast<const lf_mkd_extremum *>(h->d_det_extrema), n_ext,
-                                                  top_n, min_size, reinterpret_cast<lf_mkd_extremum *>(h->d_det_selected),
-                                                  nullptr, &n_sel, s))
+        if (int rc = lf_mkd_filter_extrema_device(h, h->d_det_extrema, n_ext, top_n, min_size, h->d_det_selected, nullptr,
+                                                  &n_sel, s))
             return rc;
-        d_sel = h->d_det_selected;
+        d_sel = h->d_det_selected.as<float>();
         n_ext = n_sel;
     }
     if (n_ext == 0 || max_out == 0) return LF_MKD_OK;
     // extract graph: orientation, sampling, description
     if (int rc = ensure_orient_scratch(h, n_ext, true, max_out)) return rc;
     uint64_t n_kp = 0;
-    if (int rc = orient_device(h, d_sel, nullptr, n_ext, h->d_kps_out, nullptr, max_out, &n_kp, dropped_features, s))
+    if (int rc = orient_device(h, d_sel, nullptr, n_ext, h->d_kps_out.as<float>(), nullptr, max_out, &n_kp, dropped_features, s))
         return rc;
     if (n_kp == 0) return LF_MKD_OK;
     static_assert(sizeof(lf_mkd_keypoint) == 20, "keypoint layout");
     // (in the form the recorded pipeline takes for this request's max_out: the same bits)
-    if (int rc = describe_keypoints_on_device(h, h->d_kps_out, nullptr, n_kp, h->d_det_desc, s, max_out)) return rc;
+    if (int rc = describe_keypoints_on_device(h, h->d_kps_out.as<float>(), nullptr, n_kp, h->d_det_desc, s, max_out)) return rc;
     LF_HIP(h, hipMemcpyAsync(keypoints, h->d_kps_out, n_kp * sizeof(lf_mkd_keypoint), hipMemcpyDeviceToHost, s));
     LF_HIP(h, hipMemcpyAsync(descriptors, h->d_det_desc, n_kp * kOut * 4, hipMemcpyDeviceToHost, s));
     LF_HIP(h, hipStreamSynchronize(s));
@@ -1139,15 +1185,11 @@ static int detect_stepwise(lf_mkd *h, bool u8, uint32_t width, uint32_t height, 
 // Everything a recorded pipeline for frames of width x height touches, allocated BEFORE the capture starts (an allocation
 // inside a capture is an error, and one that moves a buffer retires every recording: retire_graph).
 static int prepare_pipeline(lf_mkd *h, uint32_t top_n, uint64_t cap) {
-    if (!h->d_coarse) {
-        h->layer_stride = long(h->params.max_image_width) * h->params.max_image_height;
-        h->coarse_stride = h->layer_stride * (h->n_layers - 1);
-        LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_coarse), size_t(h->coarse_stride) * h->max_frames * 4));
-    }
+    if (int rc = ensure_coarse_store(h)) return rc;
     if (int rc = ensure_detect_scratch(h)) return rc;
-    if (int rc = grow(h, &h->d_det_extrema, &h->det_out_cap, h->max_extrema, sizeof(lf_mkd_extremum), kRecorded)) return rc;
+    if (int rc = grow(h, h->d_det_extrema, h->max_extrema)) return rc;
     if (top_n) {
-        if (int rc = grow(h, &h->d_det_selected, &h->det_sel_cap, top_n, sizeof(lf_mkd_extremum), kRecorded)) return rc;
+        if (int rc = grow(h, h->d_det_selected, top_n)) return rc;
         if (int rc = grow_topk_work(h, h->max_extrema, h->stream)) return rc;
     }
     return ensure_orient_scratch(h, cap, false, 0);
@@ -1171,7 +1213,7 @@ static void enqueue_pipeline(lf_mkd *h, uint32_t width, uint32_t height, uint32_
     const bool fork = h->pd.levels >= 2 && !head_only;
     // (the a-trous stack is queued from inside, ahead of the branch: see launch_build_pyramid)
     launch_build_pyramid(d_image, long(width) * height, h->d_pyr, h->pyr_stride, h->d_tmp_a, h->d_tmp_b, h->pd, 1,
-                         h->pd.levels >= 2 ? h->d_coarse : nullptr, h->coarse_stride, s, fork ? h->side_stream : nullptr,
+                         h->pd.levels >= 2 ? h->d_coarse.get() : nullptr, h->coarse_stride, s, fork ? h->side_stream : nullptr,
                          fork ? h->side_events[0] : nullptr, fork ? h->side_events[1] : nullptr, [&] {
                              launch_build_coarse_stack(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse,
                                                        h->coarse_stride, h->layer_stride, h->d_tmp_a, h->n_layers,
@@ -1179,14 +1221,15 @@ static void enqueue_pipeline(lf_mkd *h, uint32_t width, uint32_t height, uint32_
                          }, d_image_u8, bands);
     launch_detect_extrema(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse, h->coarse_stride, h->layer_stride,
                           h->n_layers, int(width), int(height), 1, kBorder, kSkipLayers, kContrastThreshold, h->d_slots,
-                          h->d_cube_counts, h->d_cube_sums, h->d_det_extrema, nullptr, nullptr, h->max_extrema, cnt + 0, s, bands);
+                          h->d_cube_counts, h->d_cube_sums, h->d_det_extrema.as<float>(), nullptr, nullptr, h->max_extrema,
+                          cnt + 0, s, bands);
     if (head_only) return;
-    const float *d_sel = h->d_det_extrema;
+    const float *d_sel = h->d_det_extrema.as<float>();
     const unsigned long long *n_sel = cnt + 0;
     if (top_n) {
-        launch_topk_filter(h->d_det_extrema, nullptr, cnt + 0, 0, 1, 0xFFFFFFFFu, top_n, min_size, h->d_det_selected, nullptr,
+        launch_topk_filter(d_sel, nullptr, cnt + 0, 0, 1, 0xFFFFFFFFu, top_n, min_size, h->d_det_selected.as<float>(), nullptr,
                            h->d_sel_count, cnt + 2, h->max_extrema, h->d_topk_work, s);
-        d_sel = h->d_det_selected;
+        d_sel = h->d_det_selected.as<float>();
         n_sel = cnt + 2;
     }
     launch_orient(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse, h->coarse_stride, h->layer_stride, h->n_layers,
@@ -1215,259 +1258,114 @@ static void enqueue_pipeline(lf_mkd *h, uint32_t width, uint32_t height, uint32_
 static int record_pipeline(lf_mkd *h, uint32_t width, uint32_t height, uint32_t top_n, float min_size, uint64_t max_out,
                            const float *d_image, const unsigned char *d_image_u8, lf_mkd_keypoint *d_keypoints,
                            float *d_descriptors, unsigned long long *cnt, unsigned long long *host_counts,
-                           lf_mkd_keypoint *host_keypoints, hipGraph_t *graph_out, hipGraphExec_t *exec_out,
-                           const RowBands *bands = nullptr) {
+                           lf_mkd_keypoint *host_keypoints, Recording &out, const RowBands *bands = nullptr) {
     hipStream_t s = h->stream;
     if (h->pd.levels >= 2 && !(bands && !bands->last))
         if (int rc = ensure_side_stream(h, 2)) return rc;
     LF_HIP(h, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     enqueue_pipeline(h, width, height, top_n, min_size, max_out, d_image, d_image_u8, d_keypoints, d_descriptors, cnt, host_counts,
                      host_keypoints, bands);
-    hipGraph_t graph = nullptr;
-    hipError_t e_end = hipStreamEndCapture(s, &graph);
-    if (e_end != hipSuccess || !graph) {
+    Recording r;
+    hipError_t e_end = hipStreamEndCapture(s, &r.graph);
+    if (e_end != hipSuccess || !r.graph) {
         h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e_end);
         return LF_MKD_ERR_HIP;
     }
-    hipError_t e_inst = hipGraphInstantiate(exec_out, graph, nullptr, nullptr, 0);
+    hipGraphExec_t exec = nullptr;
+    hipError_t e_inst = hipGraphInstantiate(&exec, r.graph, nullptr, nullptr, 0);
     if (e_inst != hipSuccess) {
-        (void)hipGraphDestroy(graph);
         h->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(e_inst);
         return LF_MKD_ERR_HIP;
     }
-    *graph_out = graph;
+    r.exec = exec;
+    out = std::move(r);
     return LF_MKD_OK;
 }
 
-// LocalFeaturesVulkan::detect / detect_top_n (mod.rs:346-593) from a HOST frame, f32 or 8-bit.  A request -- (frame size, top_n,
-// min_size, max_out, pixel type) -- seen for the first time is served by the pipeline's own launches, not recorded (one
-// upload, ~20 launches, one wait: no capture and no instantiation, which cost several times the call); the second time the
-// pipeline is recorded (lf_mkd::Sighting), and from then on a call is one upload (in planned pieces when the frame is large:
-// plan_cuts), one launch of the recording, one wait, the result copies.  The reference's callers make this call per image
-// (examples/match_images/src/main.rs:44-76: once per image, at its own size -- never a recording) or per camera frame
-// (examples/webcam/src/main.rs:136-160).
-constexpr size_t kMaxPlans = 8;
+// LocalFeaturesVulkan::detect / detect_top_n (mod.rs:346-593) from a HOST frame, f32 or 8-bit.  A request (DetectKey) seen
+// for the first time is served by the pipeline's own launches, not recorded (one upload, ~20 launches, one wait: no capture
+// and no instantiation, which cost several times the call); the second time the pipeline is recorded (lf_mkd::sightings),
+// and from then on a call is one upload (in planned pieces when the frame is large: plan_cuts), one launch of the recording,
+// one wait, the result copies.  The reference's callers make this call per image (examples/match_images/src/main.rs:44-76:
+// once per image, at its own size -- never a recording) or per camera frame (examples/webcam/src/main.rs:136-160).
+enum class DetectForm { stepwise, direct, recorded };
 
-static int detect_host(lf_mkd *h, const float *image, const unsigned char *image_u8, uint32_t width, uint32_t height,
-                       uint32_t top_n, float min_size, lf_mkd_keypoint *keypoints, float *descriptors, uint64_t max_out,
-                       uint64_t *n_out, uint64_t *dropped_blobs, uint64_t *dropped_features) {
-    if (!h) return LF_MKD_ERR_BAD_ARG;
-    if (!n_out) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: n_out is null");
-    *n_out = 0;
-    if (dropped_blobs) *dropped_blobs = 0;
-    if (dropped_features) *dropped_features = 0;
-    if (max_out && (!keypoints || !descriptors)) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: null output pointer");
-    if (!image && !image_u8) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: null image");
-    if (!h->d_image || !h->d_pyr || width < 2 || height < 2 || width > h->params.max_image_width ||
-        height > h->params.max_image_height)
-        return fail(h, LF_MKD_ERR_BAD_ARG, "detect: image exceeds max_image_width/height given at creation");
-    LF_ENTER(h);
-    hipStream_t s = h->stream;
-    const bool u8 = image_u8 != nullptr;
-    if (u8)
-        if (int rc = ensure_u8_staging(h)) return rc;
-    // An extremum yields at most 18 keypoints: a capacity beyond that bound sizes nothing -- not the result staging, not
-    // the pinned keypoint rows a recording copies on every call, not the key of a recording.
-    max_out = std::min<uint64_t>(max_out, std::min<uint64_t>(top_n ? top_n : h->max_extrema, h->max_extrema) *
-                                              LF_MKD_MAX_ANGLES_PER_EXTREMUM);
-    uint32_t ms_bits;
-    std::memcpy(&ms_bits, &min_size, 4);
+static DetectForm choose_form(lf_mkd *h, const DetectKey &key) {
     // Stage by stage: when asked for (the verification flag), when only the counts are wanted, and on handles whose keypoint
     // mode takes the two-launch form (POOL_F32, F16_FP6, FLAG_UNFUSED_KEYPOINTS: verification forms whose staging patches
     // are sized by the internal batch there, by max_out x 4 KiB in a recording) ...
-    bool stepwise = (h->params.flags & LF_MKD_FLAG_DETECT_STEPWISE) || max_out == 0 || !fused_keypoints(h);
-    // ... or, a request not yet due for recording, as the recording's own launches without recording them (`direct`: every
-    // count handed on in device memory, one wait -- no capture, no instantiation, and none of the three waits either)
-    bool direct = false;
-    lf_mkd::DetectPlan *plan = nullptr;
-    if (!stepwise) {
-        for (auto &p : h->plans)
-            if (p.w == width && p.h == height && p.top_n == top_n && p.min_size_bits == ms_bits && p.max_out == max_out && p.u8 == u8)
-                plan = &p;
-        // ... and while a request has not been seen record_after times (see lf_mkd::Sighting)
-        if (!plan && h->record_after) {
-            lf_mkd::Sighting *seen = nullptr;
-            for (auto &g : h->sightings)
-                if (g.w == width && g.h == height && g.top_n == top_n && g.min_size_bits == ms_bits && g.max_out == max_out && g.u8 == u8)
-                    seen = &g;
-            if (!seen) {
-                if (h->sightings.size() >= 64) {     // the least recently seen request is forgotten
-                    size_t old = 0;
-                    for (size_t i = 1; i < h->sightings.size(); ++i)
-                        if (h->sightings[i].stamp < h->sightings[old].stamp) old = i;
-                    h->sightings.erase(h->sightings.begin() + long(old));
-                }
-                h->sightings.push_back(lf_mkd::Sighting{width, height, top_n, ms_bits, max_out, 0, 0, u8});
-                seen = &h->sightings.back();
-            }
-            seen->stamp = ++h->plan_clock;
-            if (seen->count < h->record_after) {
-                ++seen->count;
-                direct = true;
-            }
+    if ((h->params.flags & LF_MKD_FLAG_DETECT_STEPWISE) || key.max_out == 0 || !fused_keypoints(h)) return DetectForm::stepwise;
+    if (h->plans.find(key) || !h->record_after) return DetectForm::recorded;
+    // ... or, while a request has not been seen record_after times, as the recording's own launches without recording them
+    // (`direct`: every count handed on in device memory, one wait -- no capture, no instantiation, and none of the three
+    // waits either)
+    uint64_t *seen = h->sightings.find(key);
+    if (!seen) {
+        (void)h->sightings.make_room([] { return LF_MKD_OK; });
+        seen = &h->sightings.add(key, 0);
+    }
+    if (*seen >= h->record_after) return DetectForm::recorded;
+    ++*seen;
+    return DetectForm::direct;
+}
+
+// The recording of `key`: large frames go over PCIe in pieces, and the pipeline's front runs on the rows a piece completes
+// while the next one is on its way (RowBands; plan_cuts chooses the pieces).  h->pd must describe the frame.
+static int record_plan(lf_mkd *h, const DetectKey &key, float min_size, DetectPlan &p) {
+    p.cuts = h->pd.levels >= 2 ? plan_cuts(h->n_layers, key.w, key.h, key.u8) : std::vector<uint32_t>();
+    if (!p.cuts.empty()) {
+        if (!h->copy_stream) LF_HIP(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        while (h->copy_ev.size() < p.cuts.size() + 1) {
+            hipEvent_t e;
+            LF_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            h->copy_ev.push_back(e);
         }
     }
-    if (!stepwise) {
-        // every buffer the recording names, before the upload is queued (growing one waits for the device)
-        const uint64_t cap = top_n ? top_n : h->max_extrema;
-        if (int rc = prepare_pipeline(h, top_n, cap)) return rc;
-        if (int rc = ensure_orient_scratch(h, cap, true, max_out)) return rc;     // d_kps_out, d_det_desc [max_out]
-        if (max_out > h->h_res_cap) {          // the recordings store into it by address
-            retire_graph(h);
-            if (h->h_res_kps) (void)hipHostFree(h->h_res_kps);
-            h->h_res_kps = nullptr;
-            h->h_res_cap = 0;
-            LF_HIP(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_res_kps), max_out * sizeof(lf_mkd_keypoint), hipHostMallocDefault));
-            h->h_res_cap = max_out;
-        }
-        if (!h->d_det_counts) {
-            LF_HIP(h, hipMalloc(reinterpret_cast<void **>(&h->d_det_counts), 8 * sizeof(unsigned long long)));
-            LF_HIP(h, hipMemsetAsync(h->d_det_counts, 0, 8 * sizeof(unsigned long long), s));
-            LF_HIP(h, hipHostMalloc(reinterpret_cast<void **>(&h->h_det_counts), 8 * sizeof(unsigned long long), hipHostMallocDefault));
-            LF_HIP(h, hipStreamSynchronize(s));
-        }
+    RowBands bands{};
+    for (size_t piece = 0; piece <= p.cuts.size(); ++piece) {
+        if (!p.cuts.empty() && !piece_bands(p.cuts, piece, int(key.w), int(key.h), h->n_layers, bands))
+            return fail(h, LF_MKD_ERR_BAD_ARG, "detect: internal error planning the banded upload");
+        Recording r;
+        if (int rc = record_pipeline(h, key.w, key.h, key.top_n, min_size, key.max_out, key.u8 ? nullptr : h->d_image.get(),
+                                     key.u8 ? h->d_image_u8.get() : nullptr, h->d_kps_out, h->d_det_desc, h->d_det_counts,
+                                     h->h_det_counts, h->h_res_kps, r, p.cuts.empty() ? nullptr : &bands))
+            return rc;
+        if (piece == p.cuts.size()) p.graph = std::move(r);
+        else p.heads.push_back(std::move(r));
     }
-    const bool timed = (h->params.flags & LF_MKD_FLAG_KERNEL_TIMING) && !stepwise;
-    if (timed) {
-        for (auto &e : h->det_ev)
-            if (!e) LF_HIP(h, hipEventCreate(&e));
-        LF_HIP(h, hipEventRecord(h->det_ev[0], s));
-    }
-    auto upload_whole = [&]() -> int {
-        if (u8) LF_HIP(h, hipMemcpyAsync(h->d_image_u8, image_u8, size_t(width) * height, hipMemcpyHostToDevice, s));
-        else LF_HIP(h, hipMemcpyAsync(h->d_image, image, size_t(width) * height * 4, hipMemcpyHostToDevice, s));
+    return LF_MKD_OK;
+}
+
+// The frame into d_image / d_image_u8: in one piece, or piece by piece by the plan's cuts (the call has waited for the device
+// at its previous return: nothing still reads the staging frame) -- copy, then the head on the rows it completes, the next
+// piece beside it.  A copy from pageable memory returns when its bytes are on their way, so the host is in the next copy
+// while the device runs a head.
+static int upload_frame(lf_mkd *h, const void *image, bool u8, uint32_t width, uint32_t height, const DetectPlan *plan) {
+    hipStream_t s = h->stream;
+    const size_t row = size_t(width) * (u8 ? 1 : 4);
+    const unsigned char *src = static_cast<const unsigned char *>(image);
+    unsigned char *dst = u8 ? h->d_image_u8.get() : h->d_image.as<unsigned char>();
+    if (!plan || plan->cuts.empty()) {
+        LF_HIP(h, hipMemcpyAsync(dst, src, row * height, hipMemcpyHostToDevice, s));
         return LF_MKD_OK;
-    };
-    if (stepwise) {
-        h->det_upload_ms = h->det_pipeline_ms = h->det_readback_ms = 0;    // lf_mkd_detect_times covers recorded calls only
-        if (int rc = upload_whole()) return rc;
-        return detect_stepwise(h, u8, width, height, top_n, min_size, keypoints, descriptors, max_out, n_out, dropped_blobs,
-                               dropped_features);
     }
-    describe_pyramid(width, height, h->pd);
-    if (direct) {
-        // the first sighting(s) of a request: upload in one piece, the pipeline's launches as they are, then the common tail
-        if (h->pd.levels >= 2)
-            if (int rc = ensure_side_stream(h, 2)) return rc;
-        if (int rc = upload_whole()) return rc;
-        if (timed) LF_HIP(h, hipEventRecord(h->det_ev[1], s));
-        enqueue_pipeline(h, width, height, top_n, min_size, max_out, u8 ? nullptr : h->d_image, u8 ? h->d_image_u8 : nullptr,
-                         reinterpret_cast<lf_mkd_keypoint *>(h->d_kps_out), h->d_det_desc, h->d_det_counts, h->h_det_counts,
-                         h->h_res_kps, nullptr);
-        LF_HIP(h, hipGetLastError());
+    size_t from = 0;
+    for (size_t piece = 0; piece <= plan->cuts.size(); ++piece) {
+        const size_t to = piece < plan->cuts.size() ? plan->cuts[piece] : height;
+        LF_HIP(h, hipMemcpyAsync(dst + row * from, src + row * from, row * (to - from), hipMemcpyHostToDevice, h->copy_stream));
+        LF_HIP(h, hipEventRecord(h->copy_ev[piece], h->copy_stream));
+        LF_HIP(h, hipStreamWaitEvent(s, h->copy_ev[piece], 0));
+        if (piece < plan->cuts.size()) LF_HIP(h, hipGraphLaunch(plan->heads[piece].exec, s));
+        from = to;
     }
-    // (the buffers above may have moved and retired every recording, `plan` among them: look again)
-    plan = nullptr;
-    for (auto &p : h->plans)
-        if (!direct && p.w == width && p.h == height && p.top_n == top_n && p.min_size_bits == ms_bits && p.max_out == max_out && p.u8 == u8)
-            plan = &p;
-    if (!plan && !direct) {
-        if (h->plans.size() >= kMaxPlans) {      // the least recently used recording makes room
-            size_t old = 0;
-            for (size_t i = 1; i < h->plans.size(); ++i)
-                if (h->plans[i].stamp < h->plans[old].stamp) old = i;
-            LF_HIP(h, hipStreamSynchronize(s));
-            destroy_plan(h->plans[old]);
-            h->plans.erase(h->plans.begin() + long(old));
-        }
-        lf_mkd::DetectPlan p;
-        p.w = width; p.h = height; p.top_n = top_n; p.min_size_bits = ms_bits; p.max_out = max_out; p.u8 = u8;
-        p.pd = h->pd;
-        // Large frames go over PCIe in pieces, and the pipeline's front runs on the rows a piece completes while the next one
-        // is on its way (RowBands; plan_cuts chooses the pieces).
-        p.cuts = h->pd.levels >= 2 ? plan_cuts(h->n_layers, width, height, u8) : std::vector<uint32_t>();
-        if (getenv("LF_MKD_BAND_DEBUG")) {
-            std::string line = "lf_mkd: detect " + std::to_string(width) + "x" + std::to_string(height) + (u8 ? " u8" : " f32") +
-                               ", " + std::to_string(h->n_layers) + " layers: cuts";
-            for (uint32_t c : p.cuts) line += " " + std::to_string(c);
-            const FrontModel m;
-            line += p.cuts.empty() ? " (one piece)" : "";
-            line += "; modelled front done at " +
-                    std::to_string(front_finish_us(p.cuts, p.cuts.size() + 1, int(width), int(height), u8 ? 1 : 4, h->n_layers, m)) +
-                    " us, one piece " +
-                    std::to_string(front_finish_us({}, 1, int(width), int(height), u8 ? 1 : 4, h->n_layers, m)) + " us\n";
-            fputs(line.c_str(), stderr);
-        }
-        if (!p.cuts.empty()) {
-            if (!h->copy_stream) LF_HIP(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-            while (h->copy_ev.size() < p.cuts.size() + 1) {
-                hipEvent_t e;
-                LF_HIP(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                h->copy_ev.push_back(e);
-            }
-        }
-        RowBands bands{};
-        for (size_t piece = 0; piece <= p.cuts.size(); ++piece) {
-            const bool last = piece == p.cuts.size();
-            int rc = LF_MKD_OK;
-            if (!p.cuts.empty() && !piece_bands(p.cuts, piece, int(width), int(height), h->n_layers, bands))
-                rc = fail(h, LF_MKD_ERR_BAD_ARG, "detect: internal error planning the banded upload");
-            hipGraph_t g = nullptr;
-            hipGraphExec_t e = nullptr;
-            if (!rc)
-                rc = record_pipeline(h, width, height, top_n, min_size, max_out, u8 ? nullptr : h->d_image,
-                                     u8 ? h->d_image_u8 : nullptr, reinterpret_cast<lf_mkd_keypoint *>(h->d_kps_out),
-                                     h->d_det_desc, h->d_det_counts, h->h_det_counts, h->h_res_kps, &g, &e,
-                                     p.cuts.empty() ? nullptr : &bands);
-            if (rc) {
-                destroy_plan(p);
-                return rc;
-            }
-            if (last) {
-                p.graph = g;
-                p.exec = e;
-            } else {
-                p.head_graphs.push_back(g);
-                p.heads.push_back(e);
-            }
-        }
-        h->plans.push_back(p);
-        plan = &h->plans.back();
-    }
-    if (plan) plan->stamp = ++h->plan_clock;
-    if (direct) {
-        // (already enqueued above)
-    } else if (plan->cuts.empty()) {
-        if (int rc = upload_whole()) return rc;
-        if (timed) LF_HIP(h, hipEventRecord(h->det_ev[1], s));
-    } else {
-        // piece by piece (the call has waited for the device at its previous return: nothing still reads the staging frame):
-        // copy, then the head on the rows it completes, the next piece beside it; after the last piece, the rest.  A copy from
-        // pageable memory returns when its bytes are on their way, so the host is in the next copy while the device runs a head.
-        const size_t bpp = u8 ? 1 : 4, row = size_t(width) * bpp;
-        const unsigned char *src = u8 ? image_u8 : reinterpret_cast<const unsigned char *>(image);
-        unsigned char *dst = u8 ? h->d_image_u8 : reinterpret_cast<unsigned char *>(h->d_image);
-        size_t from = 0;
-        static const bool trace = getenv("LF_MKD_BAND_TRACE") != nullptr;
-        std::vector<double> stamps;
-        const auto t_origin = std::chrono::steady_clock::now();
-        auto stamp = [&] {
-            if (trace) stamps.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_origin).count());
-        };
-        for (size_t piece = 0; piece <= plan->cuts.size(); ++piece) {
-            const size_t to = piece < plan->cuts.size() ? plan->cuts[piece] : height;
-            stamp();
-            LF_HIP(h, hipMemcpyAsync(dst + row * from, src + row * from, row * (to - from), hipMemcpyHostToDevice, h->copy_stream));
-            stamp();
-            LF_HIP(h, hipEventRecord(h->copy_ev[piece], h->copy_stream));
-            LF_HIP(h, hipStreamWaitEvent(s, h->copy_ev[piece], 0));
-            stamp();
-            if (piece < plan->cuts.size()) LF_HIP(h, hipGraphLaunch(plan->heads[piece], s));
-            stamp();
-            from = to;
-        }
-        if (trace) {
-            std::string line = "lf_mkd: band trace (us: copy call begin, end, events done, head launched):";
-            for (size_t i = 0; i < stamps.size(); ++i) line += (i % 4 ? " " : " | ") + std::to_string(int(stamps[i] + 0.5));
-            fputs((line + "\n").c_str(), stderr);
-        }
-        if (timed) LF_HIP(h, hipEventRecord(h->det_ev[1], s));     // (on s behind the last wait: the moment the whole frame is there)
-    }
-    if (!direct) LF_HIP(h, hipGraphLaunch(plan->exec, s));
-    if (timed) LF_HIP(h, hipEventRecord(h->det_ev[2], s));
-    h->n_frames = 1;
-    h->have_image = h->coarse_valid = h->coarse_l1_valid = true;   // the handle holds this frame's pyramid and a-trous stack
-    LF_HIP(h, hipStreamSynchronize(s));
+    return LF_MKD_OK;
+}
+
+// The results of a direct or recorded call, once the stream is through: the counts and the keypoints from the pinned copies
+// the pipeline's last operations made, the descriptors by one copy of the n rows.
+static int read_back(lf_mkd *h, bool timed, lf_mkd_keypoint *keypoints, float *descriptors, uint64_t max_out, uint64_t *n_out,
+                     uint64_t *dropped_blobs, uint64_t *dropped_features) {
+    hipStream_t s = h->stream;
     const auto t_back = std::chrono::steady_clock::now();
     if (timed) {
         float a = 0, b = 0;
@@ -1490,10 +1388,97 @@ static int detect_host(lf_mkd *h, const float *image, const unsigned char *image
     return LF_MKD_OK;
 }
 
+static int detect_host(lf_mkd *h, const float *image, const unsigned char *image_u8, uint32_t width, uint32_t height,
+                       uint32_t top_n, float min_size, lf_mkd_keypoint *keypoints, float *descriptors, uint64_t max_out,
+                       uint64_t *n_out, uint64_t *dropped_blobs, uint64_t *dropped_features) {
+    // validate and clamp
+    if (!h) return LF_MKD_ERR_BAD_ARG;
+    if (!n_out) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: n_out is null");
+    *n_out = 0;
+    if (dropped_blobs) *dropped_blobs = 0;
+    if (dropped_features) *dropped_features = 0;
+    if (max_out && (!keypoints || !descriptors)) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: null output pointer");
+    if (!image && !image_u8) return fail(h, LF_MKD_ERR_BAD_ARG, "detect: null image");
+    if (!h->d_image || !h->d_pyr || width < 2 || height < 2 || width > h->params.max_image_width ||
+        height > h->params.max_image_height)
+        return fail(h, LF_MKD_ERR_BAD_ARG, "detect: image exceeds max_image_width/height given at creation");
+    LF_ENTER(h);
+    hipStream_t s = h->stream;
+    const bool u8 = image_u8 != nullptr;
+    const void *frame = u8 ? static_cast<const void *>(image_u8) : image;
+    if (u8)
+        if (int rc = ensure_u8_staging(h)) return rc;
+    // An extremum yields at most 18 keypoints: a capacity beyond that bound sizes nothing -- not the result staging, not
+    // the pinned keypoint rows a recording copies on every call, not the key of a recording.
+    max_out = std::min<uint64_t>(max_out, std::min<uint64_t>(top_n ? top_n : h->max_extrema, h->max_extrema) *
+                                              LF_MKD_MAX_ANGLES_PER_EXTREMUM);
+    DetectKey key{width, height, top_n, 0, max_out, u8};
+    std::memcpy(&key.min_size_bits, &min_size, 4);
+
+    const DetectForm form = choose_form(h, key);
+    if (form == DetectForm::stepwise) {
+        h->det_upload_ms = h->det_pipeline_ms = h->det_readback_ms = 0;    // lf_mkd_detect_times covers recorded calls only
+        if (int rc = upload_frame(h, frame, u8, width, height, nullptr)) return rc;
+        return detect_stepwise(h, u8, width, height, top_n, min_size, keypoints, descriptors, max_out, n_out, dropped_blobs,
+                               dropped_features);
+    }
+    // every buffer the recording names, before the upload is queued (growing one waits for the device)
+    const uint64_t cap = top_n ? top_n : h->max_extrema;
+    if (int rc = prepare_pipeline(h, top_n, cap)) return rc;
+    if (int rc = ensure_orient_scratch(h, cap, true, max_out)) return rc;     // d_kps_out, d_det_desc [max_out]
+    if (int rc = grow(h, h->h_res_kps, max_out)) return rc;
+    if (!h->d_det_counts) {
+        LF_HIP(h, h->d_det_counts.allocate(8));
+        LF_HIP(h, hipMemsetAsync(h->d_det_counts, 0, 8 * sizeof(unsigned long long), s));
+        LF_HIP(h, h->h_det_counts.allocate(8));
+        LF_HIP(h, hipStreamSynchronize(s));
+    }
+    const bool timed = h->params.flags & LF_MKD_FLAG_KERNEL_TIMING;
+    if (timed) {
+        for (auto &e : h->det_ev)
+            if (!e) LF_HIP(h, hipEventCreate(&e));
+        LF_HIP(h, hipEventRecord(h->det_ev[0], s));
+    }
+    describe_pyramid(width, height, h->pd);
+
+    // the recording (the buffers above may have moved and retired every recording: look again), or the plain launches' stream
+    DetectPlan *plan = nullptr;
+    if (form == DetectForm::recorded && !(plan = h->plans.find(key))) {
+        if (int rc = h->plans.make_room([&] {
+                LF_HIP(h, hipStreamSynchronize(s));
+                return LF_MKD_OK;
+            }))
+            return rc;
+        DetectPlan p;
+        if (int rc = record_plan(h, key, min_size, p)) return rc;
+        plan = &h->plans.add(key, std::move(p));
+    }
+    if (form == DetectForm::direct && h->pd.levels >= 2)
+        if (int rc = ensure_side_stream(h, 2)) return rc;
+
+    // upload, launch
+    if (int rc = upload_frame(h, frame, u8, width, height, plan)) return rc;
+    if (timed) LF_HIP(h, hipEventRecord(h->det_ev[1], s));     // (on s behind the last piece's wait: the whole frame is there)
+    if (plan) {
+        LF_HIP(h, hipGraphLaunch(plan->graph.exec, s));
+    } else {
+        enqueue_pipeline(h, width, height, top_n, min_size, max_out, u8 ? nullptr : h->d_image.get(),
+                         u8 ? h->d_image_u8.get() : nullptr, h->d_kps_out, h->d_det_desc, h->d_det_counts, h->h_det_counts,
+                         h->h_res_kps, nullptr);
+        LF_HIP(h, hipGetLastError());
+    }
+    if (timed) LF_HIP(h, hipEventRecord(h->det_ev[2], s));
+    h->n_frames = 1;
+    h->have_image = h->coarse_valid = h->coarse_l1_valid = true;   // the handle holds this frame's pyramid and a-trous stack
+    LF_HIP(h, hipStreamSynchronize(s));
+
+    return read_back(h, timed, keypoints, descriptors, max_out, n_out, dropped_blobs, dropped_features);
+}
+
 int lf_mkd_detect_recordings(const lf_mkd *h, uint32_t *n_recordings, uint32_t *n_banded, uint32_t *n_sightings) {
     if (!h) return LF_MKD_ERR_BAD_ARG;
     uint32_t banded = 0;
-    for (const auto &p : h->plans) banded += p.cuts.empty() ? 0u : 1u;
+    h->plans.for_each([&](const DetectPlan &p) { banded += p.cuts.empty() ? 0u : 1u; });
     if (n_recordings) *n_recordings = uint32_t(h->plans.size());
     if (n_banded) *n_banded = banded;
     if (n_sightings) *n_sightings = uint32_t(h->sightings.size());
@@ -1545,22 +1530,22 @@ int lf_mkd_detect_frames_device(lf_mkd *h, const float *d_images, uint32_t n_fra
     const uint64_t all_cap = cap_f * n_frames * 2;               // room for frames that exceed their share
     if (int rc = ensure_coarse_stack(h, s)) return rc;
     if (int rc = ensure_detect_scratch(h)) return rc;
-    if (int rc = grow(h, &h->d_det_extrema, &h->det_out_cap, all_cap, sizeof(lf_mkd_extremum), kRecorded)) return rc;
-    if (int rc = grow(h, &h->d_mf_frame_start, &h->mf_start_cap, n_frames, 4)) return rc;
-    if (int rc = grow(h, &h->d_mf_offsets, &h->mf_off_cap, n_frames, 4)) return rc;
-    if (int rc = grow(h, &h->d_mf_padded, &h->mf_padded_cap, keep * n_frames, sizeof(lf_mkd_extremum))) return rc;
-    if (int rc = grow(h, &h->d_mf_list, &h->mf_list_cap, keep * n_frames, sizeof(lf_mkd_extremum))) return rc;
-    if (int rc = grow(h, &h->d_mf_frame_of, &h->mf_fo_cap, keep * n_frames, 4)) return rc;
+    if (int rc = grow(h, h->d_det_extrema, all_cap)) return rc;
+    if (int rc = grow(h, h->d_mf_frame_start, n_frames)) return rc;
+    if (int rc = grow(h, h->d_mf_offsets, n_frames)) return rc;
+    if (int rc = grow(h, h->d_mf_padded, keep * n_frames)) return rc;
+    if (int rc = grow(h, h->d_mf_list, keep * n_frames)) return rc;
+    if (int rc = grow(h, h->d_mf_frame_of, keep * n_frames)) return rc;
     // 1. every frame's extrema, ordered by frame; 2. per-frame selection; 3. one contiguous list + frame ids
     launch_detect_extrema(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse, h->coarse_stride, h->layer_stride,
                           h->n_layers, int(width), int(height), int(n_frames), kBorder, kSkipLayers, kContrastThreshold,
-                          h->d_slots, h->d_cube_counts, h->d_cube_sums, h->d_det_extrema, nullptr, h->d_mf_frame_start,
+                          h->d_slots, h->d_cube_counts, h->d_cube_sums, h->d_det_extrema.as<float>(), nullptr, h->d_mf_frame_start,
                           all_cap, h->d_totals + 0, s);
-    launch_topk_filter(h->d_det_extrema, h->d_mf_frame_start, h->d_totals + 0, 0, n_frames, unsigned(cap_f),
-                       unsigned(keep), top_n ? min_size : -INFINITY, h->d_mf_padded, nullptr, h->d_sel_count, nullptr, 0,
-                       nullptr, s);
-    launch_segments_compact(h->d_mf_padded, h->d_sel_count, h->d_mf_frame_start, h->d_totals + 0, n_frames,
-                            unsigned(cap_f), unsigned(keep), h->d_mf_offsets, h->d_mf_list, h->d_mf_frame_of,
+    launch_topk_filter(h->d_det_extrema.as<float>(), h->d_mf_frame_start, h->d_totals + 0, 0, n_frames, unsigned(cap_f),
+                       unsigned(keep), top_n ? min_size : -INFINITY, h->d_mf_padded.as<float>(), nullptr, h->d_sel_count,
+                       nullptr, 0, nullptr, s);
+    launch_segments_compact(h->d_mf_padded.as<float>(), h->d_sel_count, h->d_mf_frame_start, h->d_totals + 0, n_frames,
+                            unsigned(cap_f), unsigned(keep), h->d_mf_offsets, h->d_mf_list.as<float>(), h->d_mf_frame_of,
                             h->d_totals + 2, s);
     LF_HIP(h, hipGetLastError());
     unsigned long long totals[4] = {0, 0, 0, 0};
@@ -1572,7 +1557,7 @@ int lf_mkd_detect_frames_device(lf_mkd *h, const float *d_images, uint32_t n_fra
     // 4. orientation over the whole list, 5. sampling + description by frame id
     if (int rc = ensure_orient_scratch(h, n_sel, false, 0)) return rc;
     uint64_t n_kp = 0;
-    if (int rc = orient_device(h, h->d_mf_list, h->d_mf_frame_of, n_sel, reinterpret_cast<float *>(d_keypoints),
+    if (int rc = orient_device(h, h->d_mf_list.as<float>(), h->d_mf_frame_of, n_sel, reinterpret_cast<float *>(d_keypoints),
                                d_frame_of_kp, max_out, &n_kp, dropped_features, s))
         return rc;
     *n_out = n_kp;
@@ -1590,12 +1575,9 @@ int lf_mkd_stream_create(lf_mkd *h, uint32_t width, uint32_t height, uint32_t to
     LF_ENTER(h);
     LF_HIP(h, hipStreamSynchronize(h->stream));
     // an earlier recording may still be running on a caller's stream
-    if (h->graph_exec) {
+    if (h->stream_graph) {
         (void)hipDeviceSynchronize();
-        (void)hipGraphExecDestroy(h->graph_exec);
-        (void)hipGraphDestroy(h->graph);
-        h->graph_exec = nullptr;
-        h->graph = nullptr;
+        h->stream_graph.reset();
     }
     // every allocation happens before the capture starts
     describe_pyramid(width, height, h->pd);
@@ -1607,12 +1589,12 @@ int lf_mkd_stream_create(lf_mkd *h, uint32_t width, uint32_t height, uint32_t to
     const uint64_t cap = top_n ? top_n : h->max_extrema;   // extrema that can reach orientation
     if (int rc = prepare_pipeline(h, top_n, cap)) return rc;
     if (!fused_keypoints(h))
-        if (int rc = grow(h, &h->d_stream_patches, &h->stream_patch_cap, max_out * kPx, sizeof(float), kRecorded)) return rc;
+        if (int rc = grow(h, h->d_stream_patches, max_out * kPx)) return rc;
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_counts);
     LF_HIP(h, hipMemsetAsync(cnt, 0, 8 * sizeof(unsigned long long), h->stream));
     LF_HIP(h, hipStreamSynchronize(h->stream));
     if (int rc = record_pipeline(h, width, height, top_n, min_size, max_out, d_image, nullptr, d_keypoints, d_descriptors, cnt,
-                                 nullptr, nullptr, &h->graph, &h->graph_exec))
+                                 nullptr, nullptr, h->stream_graph))
         return rc;
     h->graph_pd = h->pd;
     return LF_MKD_OK;
@@ -1620,11 +1602,11 @@ int lf_mkd_stream_create(lf_mkd *h, uint32_t width, uint32_t height, uint32_t to
 
 int lf_mkd_stream_frame(lf_mkd *h, void *stream) {
     if (!h) return LF_MKD_ERR_BAD_ARG;
-    if (!h->graph_exec)
+    if (!h->stream_graph)
         return fail(h, LF_MKD_ERR_BAD_ARG, "stream_frame: no recorded pipeline (call lf_mkd_stream_create; a call that "
                                            "grew the handle's scratch buffers retires an earlier recording)");
     LF_ENTER(h);
-    LF_HIP(h, hipGraphLaunch(h->graph_exec, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    LF_HIP(h, hipGraphLaunch(h->stream_graph.exec, stream ? static_cast<hipStream_t>(stream) : h->stream));
     // every launch rebuilds the pyramid and the a-trous stack of the frame in d_image: work enqueued behind it on the same
     // stream (describe_keypoints, orientation, the verification taps) sees that frame
     h->pd = h->graph_pd;
@@ -1670,9 +1652,9 @@ static int match_device_impl(lf_mkd *h, const float *d_a, uint64_t na, const flo
     // a goes through in chunks, so that the per-row scratch (2 KiB of candidate records per a row and b split) stays bounded
     const uint64_t chunk = three_term_only ? na : std::min<uint64_t>(na, kMatchChunk);
     const int splits = match_splits(long(chunk), long(nb), h->num_cus);
-    if (int rc = grow(h, &h->d_match_a, &h->match_a_cap, match_tiles_bytes(long(chunk)), 1)) return rc;
-    if (int rc = grow(h, &h->d_match_b, &h->match_b_cap, match_tiles_bytes(long(nb)), 1)) return rc;
-    if (int rc = grow(h, &h->d_match_part, &h->match_part_cap, uint64_t(splits) * chunk * 3, sizeof(float))) return rc;
+    if (int rc = grow(h, h->d_match_a, match_tiles_bytes(long(chunk)))) return rc;
+    if (int rc = grow(h, h->d_match_b, match_tiles_bytes(long(nb)))) return rc;
+    if (int rc = grow(h, h->d_match_part, uint64_t(splits) * chunk * 3)) return rc;
     float *p_best = h->d_match_part, *p_second = p_best + uint64_t(splits) * chunk;
     int *p_index = reinterpret_cast<int *>(p_second + uint64_t(splits) * chunk);
     if (three_term_only) {
@@ -1685,13 +1667,13 @@ static int match_device_impl(lf_mkd *h, const float *d_a, uint64_t na, const flo
         LF_HIP(h, hipGetLastError());
         return LF_MKD_OK;
     }
-    if (int rc = grow(h, &h->d_match_rec, &h->match_rec_cap, match_record_bytes(long(chunk), splits), 1)) return rc;
-    if (int rc = grow(h, &h->d_match_cnt, &h->match_cnt_cap, match_count_bytes(long(chunk), splits), 1)) return rc;
-    if (int rc = grow(h, &h->d_match_norm, &h->match_norm_cap, chunk, sizeof(float))) return rc;
-    if (int rc = grow(h, &h->d_match_floor, &h->match_floor_cap, chunk, sizeof(float))) return rc;   // the splits' shared bounds
+    if (int rc = grow(h, h->d_match_rec, match_record_bytes(long(chunk), splits))) return rc;
+    if (int rc = grow(h, h->d_match_cnt, match_count_bytes(long(chunk), splits))) return rc;
+    if (int rc = grow(h, h->d_match_norm, chunk)) return rc;
+    if (int rc = grow(h, h->d_match_floor, chunk)) return rc;   // the splits' shared bounds
     if (int rc = ensure_match_misc(h, s)) return rc;
-    if (int rc = grow(h, &h->d_match_few_tiles, &h->match_few_tiles_cap, match_few_tiles_bytes(), 1)) return rc;
-    if (int rc = grow(h, &h->d_match_few, &h->match_few_cap, match_few_words(), sizeof(unsigned))) return rc;
+    if (int rc = grow(h, h->d_match_few_tiles, match_few_tiles_bytes())) return rc;
+    if (int rc = grow(h, h->d_match_few, match_few_words())) return rc;
     // misc: [0] largest |b| (float bits), [1] rows of the current chunk whose records overflowed, [2] the same over the call
     LF_HIP(h, hipMemsetAsync(h->d_match_misc, 0, (keep_overflow ? 2 : 3) * sizeof(unsigned), s));
     unsigned *b_max = h->d_match_misc;
@@ -1705,9 +1687,9 @@ static int match_device_impl(lf_mkd *h, const float *d_a, uint64_t na, const flo
         if (at) LF_HIP(h, hipMemsetAsync(n_over, 0, sizeof(int), s));
         launch_match_split(a, n, h->d_match_a, h->d_match_norm, nullptr, s);
         launch_match_screen(h->d_match_a, n, h->d_match_b, long(nb), lo, hi, splits, h->d_match_norm, b_max,
-                            h->d_match_rec, h->d_match_cnt, s, reinterpret_cast<int *>(h->d_match_floor));
+                            h->d_match_rec, h->d_match_cnt, s, h->d_match_floor.as<int>());
         launch_match_verify(a, n, d_b, h->d_match_norm, b_max, h->d_match_rec, h->d_match_cnt, splits, ratio,
-                            d_match + at, best, second, n_over, reinterpret_cast<int *>(h->d_match_few), s);
+                            d_match + at, best, second, n_over, h->d_match_few.as<int>(), s);
         // rows whose records overflowed (more than 64 near-best candidates in one lane's share of b) are redone by the
         // three-term scan: on their own when they are few, else the whole chunk; both are enqueued unconditionally and
         // read the count on the device -- no host round trip, and nothing to do in the ordinary case
@@ -1771,8 +1753,8 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
     if (!a || !b || !match) return fail(h, LF_MKD_ERR_BAD_ARG, "match: null pointer");
     if (nb < 2) return fail(h, LF_MKD_ERR_BAD_ARG, "match: needs at least two candidates in b (main.rs:20)");
     LF_ENTER(h);
-    if (int rc = grow(h, &h->d_match_in, &h->match_in_cap, (na + nb) * kOut, sizeof(float))) return rc;
-    if (int rc = grow(h, &h->d_match_out, &h->match_out_cap, na, sizeof(int))) return rc;
+    if (int rc = grow(h, h->d_match_in, (na + nb) * kOut)) return rc;
+    if (int rc = grow(h, h->d_match_out, na)) return rc;
     LF_HIP(h, hipMemcpyAsync(h->d_match_in, a, na * kOut * 4, hipMemcpyHostToDevice, h->stream));
     LF_HIP(h, hipMemcpyAsync(h->d_match_in + na * kOut, b, nb * kOut * 4, hipMemcpyHostToDevice, h->stream));
     if (int rc = lf_mkd_match_device(h, h->d_match_in, na, h->d_match_in + na * kOut, nb, nullptr, nullptr, ratio,
