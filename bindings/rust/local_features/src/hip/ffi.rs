@@ -159,6 +159,16 @@ extern "C" {
                         matches: *mut i32) -> c_int;
     pub fn lf_mkd_match_overflowed(h: *mut lf_mkd, stream: *mut c_void, n_rows: *mut u64) -> c_int;
 
+    // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
+    pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,
+                                    nb: u64, matches: *const i32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,
+                                    homography: *mut f32, verified: *mut i32, stats: *mut u32) -> c_int;
+    pub fn lf_mkd_verify_homography_device(h: *mut lf_mkd, d_kps_a: *const lf_mkd_keypoint, d_offsets_a: *const u64,
+                                           d_kps_b: *const lf_mkd_keypoint, d_offsets_b: *const u64, d_match: *const i32,
+                                           n_pairs: u32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,
+                                           d_homography: *mut f32, d_verified: *mut i32, d_stats: *mut u32,
+                                           stream: *mut c_void) -> c_int;
+
     // the path's one collective: the all-gather of descriptor shards over RCCL (configs[3])
     pub fn lf_mkd_comm_unique_id(id: *mut u8) -> c_int;
     pub fn lf_mkd_comm_create(h: *mut lf_mkd, id: *const u8, n_ranks: i32, rank: i32, out: *mut *mut lf_mkd_comm) -> c_int;

@@ -67,6 +67,9 @@ fn check(h: *const ffi::lf_mkd, rc: i32) -> Result<(), Error> {
 const _: () = assert!(std::mem::size_of::<Keypoint>() == std::mem::size_of::<ffi::lf_mkd_keypoint>());
 const _: () = assert!(std::mem::align_of::<Keypoint>() == std::mem::align_of::<ffi::lf_mkd_keypoint>());
 
+/// `flags` of `lf_mkd_verify_homography*` (`include/lf_mkd.h`): the best RANSAC hypothesis as is, no least-squares refit.
+pub const VERIFY_NO_REFINE: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,

@@ -360,6 +360,66 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
  * case).  Waits for that call to finish (synchronises `stream`, NULL = the handle's own). */
 int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows);
 
+/* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
+ * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
+ * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the
+ * matcher's int32 match array (index into b, or -1).
+ *   Pair p uses a rows [offsets_a[p], offsets_a[p+1]) and b rows [offsets_b[p], offsets_b[p+1]); match is indexed like a and
+ *   its values are local to the pair's b rows (as lf_mkd_match_device writes them for that pair).  At most 2^31 - 1 rows per
+ *   side of a pair.
+ * Outputs: H [n_pairs][9] row-major, pixel coordinates, scaled so that H[8] = 1; verified (indexed like a) = match with every
+ * non-inlier set to -1; stats [n_pairs][4] = {final inlier count, best hypothesis' inlier count, best hypothesis' index k
+ * (0xFFFFFFFF: no valid hypothesis), M = matches considered}.
+ * The algorithm, exactly (a CPU restatement reproduces every hypothesis: tests/homography_ref.py):
+ *   1. Considered matches: i with 0 <= match[i] < nb_pair (anything else counts as -1); positions 0 .. M-1 list them by
+ *      ascending i.  Both point sets are normalised over the considered matches: centroid at the origin, scale s such that
+ *      the RMS distance from it is sqrt(2) (s = sqrt(2 M / sum of squared distances), 1 if that sum is 0).
+ *   2. Sampler: hypothesis k takes draws t = 0..31, r = splitmix64(((uint64)(seed + p) << 32) ^ ((uint64)k << 5) ^ t),
+ *      pos = ((r >> 32) * M) >> 32, and keeps the first 4 distinct positions (fewer: the hypothesis is invalid).  splitmix64
+ *      is the standard finaliser with the 0x9E3779B97F4A7C15 pre-increment.  A single-pair call with seed s + p therefore
+ *      equals pair p of a batched call with seed s.
+ *   3. Minimal solver, f32 on the normalised coordinates: invalid if either 4-point set has three points with
+ *      |(p1 - p0) x (p2 - p0)| < 1e-4 (twice a triangle's area, for the four triples).  Else Heckbert's square -> quad maps A
+ *      (samples in a) and B (samples in b), multiplied through by their denominators, and H = B adj(A), divided by its
+ *      largest |entry|; invalid if that is not finite and positive, or if the samples' w = h3 . [x y 1] differ in sign.
+ *      H is negated if they are negative (so that w > 0 for the samples), then taken to pixel coordinates (invalid if a
+ *      value is not finite).
+ *   4. Score: point i is an inlier of H if w > 0 and (bx - u/w)^2 + (by - v/w)^2 < threshold^2 (the forward transfer error;
+ *      evaluated as (bx w - u)^2 + (by w - v)^2 < threshold^2 w^2).  The best hypothesis has the largest count; ties go to
+ *      the smallest k.
+ *   5. Refit (unless LF_MKD_VERIFY_NO_REFINE): least squares with h8 = 1 over the current H's inliers in the normalised
+ *      coordinates of step 1 (the normal equations accumulated in f64 in a fixed order, solved by an 8x8 Cholesky
+ *      factorisation; a pivot at or below 1e-12 of the largest diagonal element fails the refit), rescored as in step 4 (w > 0).
+ *      A refit is judged by its truncated quadratic cost over the considered matches (MSAC: an inlier adds its squared
+ *      transfer error, any other match threshold^2; summed in f64 in a fixed order) and kept if that cost is not above the
+ *      current H's -- so a refit that fits the inliers better may give up a few matches that only the 4-point hypothesis
+ *      admitted.  At most 3 rounds, stopping when the inlier set stops changing; a failed or rejected refit keeps the current H.
+ *   6. M < 4, or no valid hypothesis: H all zero, verified all -1, final count 0; the status is LF_MKD_OK.
+ * The bits of every output depend on the pair's inputs, seed + p, n_hypotheses, threshold and flags alone (not on n_pairs or
+ * on the run).  Null pointers, n_hypotheses of 0 or above 65536 and a threshold that is not finite and positive are
+ * LF_MKD_ERR_BAD_ARG; n_pairs == 0 is LF_MKD_OK and writes nothing.  flags: LF_MKD_VERIFY_NO_REFINE (below). */
+
+/* Host pointers, one pair, synchronous. */
+int lf_mkd_verify_homography(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na,
+                             const lf_mkd_keypoint *kps_b, uint64_t nb, const int32_t *match,
+                             uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                             float *H, int32_t *verified, uint32_t *stats);
+
+/* Device pointers, n_pairs independent problems in one call, asynchronous on `stream` (NULL: the handle's own).  Both offset
+ * arrays have n_pairs + 1 entries and live on the device.  Three launches, no host synchronisation, and no allocation once the
+ * handle's scratch has grown to the largest n_pairs x n_hypotheses seen: a warmed-up call can be captured in a hipGraph.
+ * The scratch belongs to the handle, so calls of one handle must be stream-ordered (one stream, or the caller orders them).
+ * d_verified also holds each pair's list of considered rows between the call's launches: it must not overlap d_match or
+ * either keypoint array (an in-place call with d_verified == d_match would overwrite its own input; the identical pointers
+ * are refused with LF_MKD_ERR_BAD_ARG).  A call needs n_pairs x ceil(n_hypotheses / 256) x (its row slices, at most 16)
+ * < 2^24 scoring workgroups; a larger one is LF_MKD_ERR_BAD_ARG. */
+int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                    const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b,
+                                    const int32_t *d_match, uint32_t n_pairs, uint32_t n_hypotheses,
+                                    float threshold_px, uint32_t seed, uint32_t flags,
+                                    float *d_H, int32_t *d_verified, uint32_t *d_stats, void *stream);
+#define LF_MKD_VERIFY_NO_REFINE 1u   /* report the best RANSAC hypothesis as is: no least-squares refit */
+
 /* ---- multi-GPU: the path's ONE collective (BASELINE configs[3]) -------------------------------------------------
  * Keypoint batches shard by image, one process and one handle per GPU, and nothing is exchanged while describing.  The
  * cross-image match stage needs every rank's descriptors on every rank: an all-gather of the descriptor shards over RCCL

@@ -167,6 +167,28 @@ public:
         return res;
     }
 
+    // Geometric verification of matches (lf_mkd_verify_homography): RANSAC over 4-point homographies, then a least-squares
+    // refit on the inliers.  Returns true and sets H (row-major, b ~ H a, H[8] = 1) if a valid hypothesis was found; `inliers`
+    // receives the matches that agree with H within threshold_px.
+    bool verify_homography(const std::vector<Keypoint> &kps_a, const std::vector<Keypoint> &kps_b,
+                           const std::vector<std::pair<std::size_t, std::size_t>> &matches, float H[9],
+                           std::vector<std::pair<std::size_t, std::size_t>> &inliers, float threshold_px = 3.0f,
+                           std::uint32_t n_hypotheses = 2048, std::uint32_t seed = 0) {
+        std::vector<std::int32_t> m(kps_a.size(), -1), ver(kps_a.size(), -1);
+        for (const auto &ij : matches) {
+            if (ij.first >= kps_a.size() || ij.second >= kps_b.size())
+                throw LocalFeaturesError(LocalFeaturesError::Kind::InvalidParameters, "verify_homography: match outside the keypoints");
+            m[ij.first] = std::int32_t(ij.second);
+        }
+        std::uint32_t stats[4];
+        check(lf_mkd_verify_homography(h_, kps_a.data(), kps_a.size(), kps_b.data(), kps_b.size(), m.data(), n_hypotheses,
+                                       threshold_px, seed, 0, H, ver.data(), stats));
+        inliers.clear();
+        for (std::size_t i = 0; i < ver.size(); ++i)
+            if (ver[i] >= 0) inliers.emplace_back(i, std::size_t(ver[i]));
+        return stats[2] != 0xFFFFFFFFu;
+    }
+
     lf_mkd *handle() { return h_; }
 
 private:

@@ -233,6 +233,12 @@ struct lf_mkd {
     HipArray<unsigned> d_match_misc;
     HipArray<unsigned char> d_match_few_tiles;   // the overflowed rows' own tiles; their indices, exclusion ranges, partials
     HipArray<unsigned> d_match_few;
+    // RANSAC verification scratch (lf_mkd_verify_homography*): per-pair normalisation, per-hypothesis partial counts, and the
+    // host form's staging.  No recording names them; they grow only when a call asks for more, so the device form's launches
+    // can be captured once warmed up.  Calls of one handle are stream-ordered (lf_mkd.h).
+    HipArray<VerifyPair> d_ver_pairs;
+    HipArray<unsigned> d_ver_counts;
+    HipArray<unsigned char> d_ver_io;
     int num_cus = 256;
     // LF_MKD_FLAG_KERNEL_TIMING: (start, end) of the describe kernel per batch
     std::vector<hipEvent_t> ev_pending, ev_free;
@@ -1761,6 +1767,78 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
                                      h->d_match_out, nullptr, nullptr, h->stream))
         return rc;
     LF_HIP(h, hipMemcpyAsync(match, h->d_match_out, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// The arguments of both verification entry points, checked before the handle so that every bad argument is reported without
+// a device: the message goes to the handle, or to lf_mkd_last_error(NULL) when there is none.
+static int verify_args(lf_mkd *h, bool null_pointer, uint32_t n_hypotheses, float threshold_px, const char *what) {
+    std::string msg;
+    if (null_pointer) msg = ": null pointer";
+    else if (n_hypotheses == 0 || n_hypotheses > 65536) msg = ": n_hypotheses must be 1 .. 65536";
+    else if (!std::isfinite(threshold_px) || !(threshold_px > 0.f)) msg = ": threshold_px must be finite and positive";
+    else if (!h) msg = ": null handle";
+    if (msg.empty()) return LF_MKD_OK;
+    (h ? h->err : g_create_error) = what + msg;
+    return LF_MKD_ERR_BAD_ARG;
+}
+
+int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                    const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, const int32_t *d_match,
+                                    uint32_t n_pairs, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                                    float *d_H, int32_t *d_verified, uint32_t *d_stats, void *stream) {
+    const bool null = !d_kps_a || !d_offsets_a || !d_kps_b || !d_offsets_b || !d_match || !d_H || !d_verified || !d_stats;
+    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, "verify_homography_device")) return rc;
+    if (n_pairs == 0) return LF_MKD_OK;
+    if (static_cast<const void *>(d_verified) == d_match || static_cast<const void *>(d_verified) == d_kps_a ||
+        static_cast<const void *>(d_verified) == d_kps_b)
+        return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography_device: d_verified must not alias d_match or the keypoints");
+    // a launch's grid holds fewer than 2^24 workgroups of 256 threads (its work-items are counted in 32 bits)
+    const unsigned slices = verify_slices(n_pairs, n_hypotheses, h->num_cus);
+    if (uint64_t(n_pairs) * ((n_hypotheses + 255) / 256) * slices >= (1ull << 24))
+        return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography_device: too many pairs x hypotheses for one call (the scoring grid "
+                                           "needs n_pairs x ceil(n_hypotheses / 256) x row slices < 2^24 workgroups)");
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_ver_pairs, n_pairs)) return rc;
+    if (int rc = grow(h, h->d_ver_counts, uint64_t(n_pairs) * slices * n_hypotheses)) return rc;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    launch_verify(reinterpret_cast<const float *>(d_kps_a), d_offsets_a, reinterpret_cast<const float *>(d_kps_b), d_offsets_b,
+                  d_match, n_pairs, n_hypotheses, threshold_px, seed, flags, slices, h->d_ver_pairs, h->d_ver_counts, d_H,
+                  d_verified, d_stats, s);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_verify_homography(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na, const lf_mkd_keypoint *kps_b, uint64_t nb,
+                             const int32_t *match, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                             float *H, int32_t *verified, uint32_t *stats) {
+    const bool null = (na && (!kps_a || !match || !verified)) || (nb && !kps_b) || !H || !stats;
+    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, "verify_homography")) return rc;
+    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography: more than 2^31 - 1 rows");
+    LF_ENTER(h);
+    // one staging array, every part 16-byte aligned: offsets, keypoints of a and b, match, then the outputs
+    auto up16 = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 15) / 16 * 16; };   // (empty parts do not share an address)
+    const uint64_t o_off = 0, o_ka = 64, o_kb = o_ka + up16(na * sizeof(lf_mkd_keypoint)),
+                   o_m = o_kb + up16(nb * sizeof(lf_mkd_keypoint)), o_v = o_m + up16(na * 4), o_h = o_v + up16(na * 4),
+                   o_st = o_h + 48, total = o_st + 16;
+    if (int rc = grow(h, h->d_ver_io, total)) return rc;
+    unsigned char *io = h->d_ver_io;
+    const uint64_t offs[4] = {0, na, 0, nb};
+    LF_HIP(h, hipMemcpyAsync(io + o_off, offs, sizeof(offs), hipMemcpyHostToDevice, h->stream));
+    if (na) LF_HIP(h, hipMemcpyAsync(io + o_ka, kps_a, na * sizeof(lf_mkd_keypoint), hipMemcpyHostToDevice, h->stream));
+    if (nb) LF_HIP(h, hipMemcpyAsync(io + o_kb, kps_b, nb * sizeof(lf_mkd_keypoint), hipMemcpyHostToDevice, h->stream));
+    if (na) LF_HIP(h, hipMemcpyAsync(io + o_m, match, na * 4, hipMemcpyHostToDevice, h->stream));
+    const uint64_t *d_offs = reinterpret_cast<const uint64_t *>(io + o_off);
+    if (int rc = lf_mkd_verify_homography_device(h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_ka), d_offs,
+                                                 reinterpret_cast<const lf_mkd_keypoint *>(io + o_kb), d_offs + 2,
+                                                 reinterpret_cast<const int32_t *>(io + o_m), 1, n_hypotheses, threshold_px, seed,
+                                                 flags, reinterpret_cast<float *>(io + o_h), reinterpret_cast<int32_t *>(io + o_v),
+                                                 reinterpret_cast<uint32_t *>(io + o_st), h->stream))
+        return rc;
+    LF_HIP(h, hipMemcpyAsync(H, io + o_h, 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipMemcpyAsync(stats, io + o_st, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (na) LF_HIP(h, hipMemcpyAsync(verified, io + o_v, na * 4, hipMemcpyDeviceToHost, h->stream));
     LF_HIP(h, hipStreamSynchronize(h->stream));
     return LF_MKD_OK;
 }

@@ -1,5 +1,5 @@
 // Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip).
+// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -171,6 +171,20 @@ void launch_match_screen(const unsigned char *a_tiles, long na, const unsigned c
 void launch_match_verify(const float *a, long na, const float *b, const float *a_norms, const unsigned *b_max_norm_bits,
                          const void *rec, const void *rec_info, int splits, float ratio, int *match, float *best,
                          float *second, int *n_over, int *over_rows, hipStream_t stream);
+
+// RANSAC homography verification (mkd_verify.hip; algorithm: include/lf_mkd.h).  Keypoints are read as rows of 5 floats
+// (lf_mkd_keypoint).  Scratch the caller owns: pairs [n_pairs], counts [n_pairs][slices][n_hyp]; `verified` also holds each
+// pair's list of considered rows between the first and the last of the call's three launches.
+struct VerifyPair {
+    float ca[2], sa;   // a: centroid, scale (RMS distance from the centroid becomes sqrt(2))
+    float cb[2], sb;   // b: the same
+    unsigned m, pad;   // considered matches
+};
+// row slices per (pair, hypothesis block) of the scoring launch: enough workgroups to fill the chip for few pairs
+unsigned verify_slices(unsigned n_pairs, unsigned n_hyp, int num_cus);
+void launch_verify(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
+                   unsigned n_pairs, unsigned n_hyp, float threshold, unsigned seed, unsigned flags, unsigned slices,
+                   VerifyPair *pairs, unsigned *counts, float *H, int *verified, unsigned *stats, hipStream_t stream);
 
 #ifdef __HIPCC__
 // Which tile a workgroup takes, for the row-tiled pyramid and a-trous kernels: workgroups are dealt to the 8 XCDs round-robin by their

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""match_images IMAGE_1 IMAGE_2 IMAGE_OUT -- the reference's example (examples/match_images/src/main.rs) on the
+"""match_images [--homography] IMAGE_1 IMAGE_2 IMAGE_OUT -- the reference's example (examples/match_images/src/main.rs) on the
 MI355X path: load two images, detect_top_n(2000, min_size 0) on each, brute-force match 1->2 and 2->1 with the
-0.8 ratio test, draw keypoints and the 1->2 matches side by side.
+0.8 ratio test, draw keypoints and the 1->2 matches side by side.  With --homography the 1->2 matches are verified on the
+device first (RANSAC homography, 3 px: LocalFeatures.verify_homography) and only the inliers are drawn.
 
 Image decoding follows main.rs:44-60: 8-bit luma, then f32 / 255 (Pillow's "L" conversion stands in for the `image`
 crate's grayscale(); they may differ by one LSB).  Needs Pillow."""
@@ -19,14 +20,23 @@ def load_gray(path):
     return np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
 
 
-def match_images(img1, img2, top_n=2000, min_size=0.0):
-    """Returns (keypoints1, keypoints2, matches 1->2, matches 2->1) as the example computes them (main.rs:62-121)."""
-    feats = lfp.LocalFeatures(max(img1.shape[1], img2.shape[1]), max(img1.shape[0], img2.shape[0]), 3000,
-                              max_blobs=8000, n_scales=5, pca="liberty", pool_mode=lfp.POOL_F16X3)
+def features(img1, img2):
+    """The example's LocalFeatures handle for two images (main.rs:62-76)."""
+    return lfp.LocalFeatures(max(img1.shape[1], img2.shape[1]), max(img1.shape[0], img2.shape[0]), 3000,
+                             max_blobs=8000, n_scales=5, pca="liberty", pool_mode=lfp.POOL_F16X3)
+
+
+def match_images(img1, img2, top_n=2000, min_size=0.0, feats=None):
+    """Returns (keypoints1, keypoints2, matches 1->2, matches 2->1) as the example computes them (main.rs:62-121), with
+    `feats` (default: a new handle from `features`)."""
+    if feats is None:
+        feats = features(img1, img2)
     kp1, d1 = feats.detect_top_n(img1, top_n, min_size)
     kp2, d2 = feats.detect_top_n(img2, top_n, min_size)
     m12, m21 = feats.match_both(d1, d2)        # main.rs:113-116: both directions, one launch on the device
     return kp1, kp2, d1, d2, m12, m21
+
+
 
 
 def draw(img1, img2, kp1, kp2, matches, out_path):
@@ -47,15 +57,22 @@ def draw(img1, img2, kp1, kp2, matches, out_path):
 
 
 def main():
-    if len(sys.argv) != 4:
-        print("Required arguments: IMAGE_1 IMAGE_2 IMAGE_OUT", file=sys.stderr)
+    args = sys.argv[1:]
+    homography = "--homography" in args
+    args = [a for a in args if a != "--homography"]
+    if len(args) != 3:
+        print("Required arguments: [--homography] IMAGE_1 IMAGE_2 IMAGE_OUT", file=sys.stderr)
         return 1
-    img1, img2 = load_gray(sys.argv[1]), load_gray(sys.argv[2])
-    kp1, kp2, _, _, m12, m21 = match_images(img1, img2)
+    img1, img2 = load_gray(args[0]), load_gray(args[1])
+    feats = features(img1, img2)
+    kp1, kp2, _, _, m12, m21 = match_images(img1, img2, feats=feats)
     print(f"Extracted {len(kp1)} and {len(kp2)} keypoints")
     print(f"Matching 1 -> 2: {len(m12)} matches")
     print(f"Matching 2 -> 1: {len(m21)} matches")
-    draw(img1, img2, kp1, kp2, m12, sys.argv[3])
+    if homography:
+        _, m12 = feats.verify_homography(kp1, kp2, m12, 3.0)   # on the device that detected and matched them
+        print(f"Verified 1 -> 2: {len(m12)} matches agree with one homography")
+    draw(img1, img2, kp1, kp2, m12, args[2])
     return 0
 
 

@@ -14,12 +14,13 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, Comm, MkdHandle,
-                   comm_unique_id, load_library, model_path, plan_upload)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, comm_unique_id, load_library, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
-           "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING"]
+           "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
+           "VERIFY_NO_REFINE"]
 
 
 class Keypoint:
@@ -162,6 +163,57 @@ class LocalFeatures:
             keep = (1.0 - d_1) < (1.0 - d_2) * factor
             m, keep = d_m.cpu().numpy(), keep.cpu().numpy()
         return [(int(i), int(m[i])) for i in np.flatnonzero(keep)]
+
+    def verify_homography(self, kp_a, kp_b, matches, threshold=3.0, n_hypotheses=2048, seed=0, flags=0):
+        """Geometric verification of matches (lf_mkd_verify_homography): RANSAC over 4-point homographies on the GPU, then a
+        least-squares refit on the inliers (include/lf_mkd.h states the algorithm).  kp_a / kp_b: the keypoint lists (or
+        [n,4|5] arrays) the matches index; matches: the (i, j) list `match` / `match_both` return.  Returns (H, inliers):
+        H ndarray[3,3] with b ~ H a in pixels and H[2,2] = 1, or None if no hypothesis was valid; inliers the (i, j) pairs
+        that agree with H within `threshold` pixels.  Per-call numbers (inlier counts, best hypothesis) are kept in
+        `verify_stats`."""
+        a, b = _keypoints_to_array(kp_a), _keypoints_to_array(kp_b)
+        m = np.full(len(a), -1, np.int32)
+        for i, j in matches:
+            if not (0 <= i < len(a) and 0 <= j < len(b)):
+                raise RuntimeError("verify_homography: match (%d, %d) outside the keypoint lists" % (i, j))
+            m[i] = j
+        with self._lock:
+            H, ver, st = self._inner.verify_homography(a.view(np.float32).reshape(-1, 5), b.view(np.float32).reshape(-1, 5), m,
+                                                       n_hypotheses, threshold, seed, flags)
+        self.verify_stats = {"inliers": int(st[0]), "best_hypothesis_inliers": int(st[1]), "best_hypothesis": int(st[2]),
+                             "considered": int(st[3])}
+        if st[2] == 0xFFFFFFFF:
+            return None, []
+        return H.astype(np.float64), [(int(i), int(j)) for i, j in enumerate(ver) if j >= 0]
+
+    def verify_homography_batch(self, kps_a, offsets_a, kps_b, offsets_b, match, threshold=3.0, n_hypotheses=2048, seed=0,
+                                flags=0, stream=None):
+        """Many image pairs in one call (lf_mkd_verify_homography_device), on torch device tensors -- e.g. the keypoints of
+        detect_top_n_batch frames and a matcher's output per pair.  kps_a [Na,5] / kps_b [Nb,5] float32, offsets_a /
+        offsets_b int64 [n_pairs + 1] (pair p: a rows offsets_a[p]..offsets_a[p+1], likewise b), match int32 [Na] with values
+        local to the pair's b rows.  Pair p is seeded with seed + p.  Returns device tensors (H [n_pairs,3,3], verified [Na]
+        int32, stats [n_pairs,4] int64: final inliers, best hypothesis' inliers, best hypothesis (-1: none), considered).
+        Enqueued on `stream` (default: torch's current stream on the handle's device), asynchronously."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError("verify_homography_batch: offsets_a and offsets_b need n_pairs + 1 entries each")
+        ka = kps_a.to(dev, torch.float32).reshape(-1, 5).contiguous()
+        kb = kps_b.to(dev, torch.float32).reshape(-1, 5).contiguous()
+        oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+        mt = match.to(dev, torch.int32).contiguous()
+        if mt.numel() != ka.shape[0]:
+            raise RuntimeError("verify_homography_batch: match must have one entry per row of kps_a")
+        H = torch.empty((max(n_pairs, 1), 3, 3), dtype=torch.float32, device=dev)
+        ver = torch.empty((max(ka.shape[0], 1),), dtype=torch.int32, device=dev)
+        st = torch.empty((max(n_pairs, 1), 4), dtype=torch.int32, device=dev)
+        with self._lock, torch.cuda.device(dev):
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            self._inner.verify_homography_device(ka.data_ptr(), oa.data_ptr(), kb.data_ptr(), ob.data_ptr(), mt.data_ptr(),
+                                                 n_pairs, H.data_ptr(), ver.data_ptr(), st.data_ptr(), n_hypotheses, threshold,
+                                                 seed, flags, s.cuda_stream)
+        return H[:n_pairs], ver[:ka.shape[0]], st[:n_pairs].to(torch.int64)
 
     def describe_patches(self, patches):
         """patches: [n,32,32] float32 -> ndarray[n,128] (the CPU twin's Mkd::patch, mkd_ref.rs:57-77)."""

@@ -13,6 +13,7 @@ MODEL_DIR = os.path.join(_ROOT, "models", "mkd")
 FLAG_KERNEL_TIMING = 1
 FLAG_UNFUSED_KEYPOINTS = 2
 FLAG_DETECT_STEPWISE = 4
+VERIFY_NO_REFINE = 1     # lf_mkd_verify_homography*: the best RANSAC hypothesis as is, no least-squares refit
 ANGLE_SHADER, ANGLE_EXACT, ANGLE_EXACT_ZERO = 0, 1, 2
 POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6 = 0, 1, 2, 3   # lf_mkd_pool_mode; the default is the f16x3 split
 PCA_NAMES = ("liberty", "notredame", "yosemite")   # enum MKDPCA, lib.rs:26-32
@@ -33,6 +34,7 @@ SYMBOLS = (
     "lf_mkd_detect_frames_device", "lf_mkd_orient_keypoints_blocked",
     "lf_mkd_comm_unique_id", "lf_mkd_comm_create", "lf_mkd_comm_destroy", "lf_mkd_comm_info", "lf_mkd_allgather_descriptors",
     "lf_mkd_comm_loopback", "lf_mkd_comm_last_form", "lf_mkd_plan_upload", "lf_mkd_detect_recordings",
+    "lf_mkd_verify_homography", "lf_mkd_verify_homography_device",
 )
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
@@ -115,6 +117,8 @@ def load_library():
     L.lf_mkd_match.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp]
     L.lf_mkd_match_both_device.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp, vp, vp]
     L.lf_mkd_match_overflowed.argtypes = [vp, vp, ctypes.POINTER(u64)]
+    L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
+    L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_stream_create.argtypes = [vp, u32, u32, u32, ctypes.c_float, u64, vp, vp, vp, vp]
     L.lf_mkd_stream_frame.argtypes = [vp, vp]
     L.lf_mkd_orient_keypoints_blocked.argtypes = [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64, pu64, pu64]
@@ -343,6 +347,22 @@ class MkdHandle:
                     "lf_mkd_match")
         return out
 
+    def verify_homography(self, kps_a, kps_b, match, n_hypotheses=2048, threshold=3.0, seed=0, flags=0):
+        """lf_mkd_verify_homography: kps_a [na,5], kps_b [nb,5] f32 rows, match int32 [na] (index into b or -1) ->
+        (H [3,3] f32, verified int32 [na], stats uint32 [4])."""
+        a = np.ascontiguousarray(kps_a, np.float32).reshape(-1, 5)
+        b = np.ascontiguousarray(kps_b, np.float32).reshape(-1, 5)
+        m = np.ascontiguousarray(match, np.int32).reshape(-1)
+        if len(m) != len(a):
+            raise RuntimeError("verify_homography: match must have one entry per row of kps_a")
+        H = np.empty(9, np.float32)
+        ver = np.empty(max(len(a), 1), np.int32)
+        st = np.empty(4, np.uint32)
+        self._check(self.L.lf_mkd_verify_homography(self._h, a.ctypes.data, len(a), b.ctypes.data, len(b), m.ctypes.data,
+                                                     n_hypotheses, threshold, seed, flags, H.ctypes.data, ver.ctypes.data,
+                                                     st.ctypes.data), "lf_mkd_verify_homography")
+        return H.reshape(3, 3), ver[:len(a)].copy(), st
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -458,6 +478,13 @@ class MkdHandle:
         """both directions in one call: match_ab [na] = match(a, b), match_ba [nb] = match(b, a)"""
         self._device_call(stream, lambda s: self.L.lf_mkd_match_both_device(self._h, d_a, na, d_b, nb, ratio, d_match_ab,
                                                                              d_match_ba, s), "lf_mkd_match_both_device")
+
+    def verify_homography_device(self, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, d_H, d_verified, d_stats,
+                                 n_hypotheses=2048, threshold=3.0, seed=0, flags=0, stream=None):
+        """lf_mkd_verify_homography_device: n_pairs problems in one call (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_verify_homography_device(
+            self._h, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, n_hypotheses, threshold, seed, flags, d_H,
+            d_verified, d_stats, s), "lf_mkd_verify_homography_device")
 
     def match_overflowed(self, stream=None):
         """Rows of the latest match call that were redone by the full scan (diagnostic; waits for the call)."""
