@@ -370,10 +370,13 @@ int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows);
  * Outputs: H [n_pairs][9] row-major, pixel coordinates, scaled so that H[8] = 1; verified (indexed like a) = match with every
  * non-inlier set to -1; stats [n_pairs][4] = {final inlier count, best hypothesis' inlier count, best hypothesis' index k
  * (0xFFFFFFFF: no valid hypothesis), M = matches considered}.
- * The algorithm, exactly (a CPU restatement reproduces every hypothesis: tests/homography_ref.py):
+ * The algorithm, exactly (a CPU restatement reproduces every hypothesis: tests/homography_ref.py; an f32 twin of the kernel
+ * reproduces every output bit: tests/homography_f32.py):
  *   1. Considered matches: i with 0 <= match[i] < nb_pair (anything else counts as -1); positions 0 .. M-1 list them by
  *      ascending i.  Both point sets are normalised over the considered matches: centroid at the origin, scale s such that
- *      the RMS distance from it is sqrt(2) (s = sqrt(2 M / sum of squared distances), 1 if that sum is 0).
+ *      the RMS distance from it is sqrt(2) (s = sqrt(2 M / sum of squared distances), 1 if that sum is 0).  Rows that are
+ *      not considered are never read; a NaN or infinite coordinate in a considered row leaves the pair without a valid
+ *      hypothesis (its normalised coordinates on that axis are all non-finite), so its outputs are those of step 6.
  *   2. Sampler: hypothesis k takes draws t = 0..31, r = splitmix64(((uint64)(seed + p) << 32) ^ ((uint64)k << 5) ^ t),
  *      pos = ((r >> 32) * M) >> 32, and keeps the first 4 distinct positions (fewer: the hypothesis is invalid).  splitmix64
  *      is the standard finaliser with the 0x9E3779B97F4A7C15 pre-increment.  A single-pair call with seed s + p therefore
@@ -396,7 +399,8 @@ int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows);
  *      admitted.  At most 3 rounds, stopping when the inlier set stops changing; a failed or rejected refit keeps the current H.
  *   6. M < 4, or no valid hypothesis: H all zero, verified all -1, final count 0; the status is LF_MKD_OK.
  * The bits of every output depend on the pair's inputs, seed + p, n_hypotheses, threshold and flags alone (not on n_pairs or
- * on the run).  Null pointers, n_hypotheses of 0 or above 65536 and a threshold that is not finite and positive are
+ * on the run).  Null pointers, n_hypotheses of 0 or above 65536 and a threshold that is not positive or whose f32 square
+ * threshold * threshold is not a finite normal number (so 1.0842022e-19 <= threshold <= 1.8446743e19 as f32 values) are
  * LF_MKD_ERR_BAD_ARG; n_pairs == 0 is LF_MKD_OK and writes nothing.  flags: LF_MKD_VERIFY_NO_REFINE (below). */
 
 /* Host pointers, one pair, synchronous. */

@@ -1777,7 +1777,10 @@ static int verify_args(lf_mkd *h, bool null_pointer, uint32_t n_hypotheses, floa
     std::string msg;
     if (null_pointer) msg = ": null pointer";
     else if (n_hypotheses == 0 || n_hypotheses > 65536) msg = ": n_hypotheses must be 1 .. 65536";
-    else if (!std::isfinite(threshold_px) || !(threshold_px > 0.f)) msg = ": threshold_px must be finite and positive";
+    // the kernels compare against thr^2 in f32: it must be a normal number (thr of about 1.09e-19 .. 1.84e19), else an exact
+    // match is no inlier (thr^2 = 0) or every refit is kept (thr^2 = inf)
+    else if (!(threshold_px > 0.f) || !std::isnormal(threshold_px * threshold_px))
+        msg = ": threshold_px must be positive, with a finite normal f32 square (about 1.09e-19 .. 1.84e19)";
     else if (!h) msg = ": null handle";
     if (msg.empty()) return LF_MKD_OK;
     (h ? h->err : g_create_error) = what + msg;

@@ -7,39 +7,18 @@ import numpy as np
 import pytest
 
 import homography_ref as ref
+from homography_cases import CORNERS, H_TRUE, THR, band, planted
+from homography_cases import pairs as _pairs
 from conftest import GOLDEN
 
 import local_features_python as lfp
 
 pytestmark = pytest.mark.gpu
 
-THR = 3.0
-H_TRUE = np.array([[0.92, -0.18, 60.0], [0.12, 1.05, -30.0], [1.2e-4, -1.5e-4, 1.0]])
-CORNERS = np.array([[0.0, 0.0], [1000.0, 0.0], [1000.0, 1000.0], [0.0, 1000.0]])
-
 
 @pytest.fixture(scope="module")
 def handle():
     return lfp.MkdHandle(max_features=64)
-
-
-def planted(m, frac, seed, sigma=0.5, h=H_TRUE):
-    """m matches (kps as [m,5] f32, identity match array): a fraction `frac` maps by h plus noise, the rest is random."""
-    g = np.random.default_rng(seed)
-    a = g.uniform(0, 1000, (m, 2))
-    b = ref.map_points(h, a) + g.normal(0, sigma, (m, 2))
-    out = g.random(m) >= frac
-    b[out] = g.uniform(0, 1000, (int(out.sum()), 2))
-    ka, kb = np.zeros((m, 5), np.float32), np.zeros((m, 5), np.float32)
-    ka[:, :2], kb[:, :2] = a, b
-    ka[:, 2] = kb[:, 2] = 4.0
-    return ka, kb, np.arange(m, dtype=np.int32)
-
-
-def band(prob, h, thr=THR):
-    """Considered matches whose squared residual under h lies within 5 % of thr^2 (where f32 and f64 may disagree)."""
-    w, e2 = prob.residuals(h)
-    return np.abs(e2 - thr * thr) <= 0.05 * thr * thr
 
 
 @pytest.mark.parametrize("m,n_hyp", [(4, 256), (50, 2048), (1000, 2048), (20000, 256)])
@@ -85,39 +64,6 @@ def test_refit_matches_the_restatement(handle, m, frac):
     assert np.abs(ref.map_points(H, CORNERS) - ref.map_points(want["H"], CORNERS)).max() < 0.05
     # against the planted map: 1 px on the corners of the square the points fill (25 noisy inliers extrapolate less well)
     assert np.abs(ref.map_points(H, CORNERS) - ref.map_points(H_TRUE, CORNERS)).max() < (1.0 if m >= 1000 else 2.0)
-
-
-def _pairs(n_pairs=64):
-    """Pairs of differing sizes: empty ones, M < 4, all-collinear ones, and ordinary planted problems (with rows that do
-    not count: -1 and out-of-range matches)."""
-    g = np.random.default_rng(3)
-    pairs = []
-    for p in range(n_pairs):
-        kind = p % 8
-        if kind == 0:
-            ka, kb, mt = np.zeros((0, 5), np.float32), np.zeros((0, 5), np.float32), np.zeros(0, np.int32)
-        elif kind == 1:
-            ka, kb, mt = planted(3, 1.0, p)
-        elif kind == 2:
-            n = 40
-            ka, kb = np.zeros((n, 5), np.float32), np.zeros((n, 5), np.float32)
-            ka[:, 0] = np.arange(n) * 9.0
-            ka[:, 1] = 5.0 + 0.5 * ka[:, 0]
-            kb[:, :2] = ka[:, :2] + 20.0
-            mt = np.arange(n, dtype=np.int32)
-        else:
-            n = int(g.integers(20, 1500))
-            ka, kb, mt = planted(n, float(g.uniform(0.2, 0.9)), 1000 + p)
-            extra = g.uniform(0, 1000, (n // 3, 5)).astype(np.float32)   # b rows nobody matches
-            kb = np.concatenate([kb, extra])
-            perm = g.permutation(len(kb))
-            inv = np.argsort(perm)
-            kb, mt = kb[perm], inv[mt].astype(np.int32)
-            drop = g.random(n) < 0.3
-            mt[drop] = -1
-            mt[g.random(n) < 0.02] = len(kb) + 5                           # out of range: counts as -1
-        pairs.append((ka, kb, mt))
-    return pairs
 
 
 def _batch_call(handle, pairs, n_hyp, seed, flags=0, stream=None, out=None):

@@ -97,3 +97,34 @@ def test_restatement_edge_cases():
     line[:, 1] = 3.0 + 2.0 * line[:, 0]
     out = ref.verify(line, line, np.arange(20), n_hyp=64)     # all collinear: every quad is degenerate
     assert out["stats"][2] == ref.INVALID and out["stats"][3] == 20
+
+
+def test_threshold_square_must_be_a_finite_normal_f32():
+    """The kernels compare against thr^2 in f32: below ~1.08e-19 it is subnormal or 0 (an exact match would be no inlier),
+    above ~1.84e19 it is inf (every refit would be kept).  Both entry points refuse those thresholds and accept the f32
+    values just inside; without a handle, an accepted threshold is then refused for the missing handle."""
+    L = lfp.load_library()
+    f32 = np.float32
+    lo, hi = f32(1.0842022e-19), f32(1.8446743e19)
+    assert np.isfinite(lo * lo) and lo * lo >= np.finfo(f32).tiny
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.nextafter(hi, f32(np.inf)) ** 2) and np.isfinite(hi * hi)
+    assert np.nextafter(lo, f32(0)) ** 2 < np.finfo(f32).tiny
+    kp = np.zeros((8, 5), np.float32)
+    m = np.zeros(8, np.int32)
+    H, ver, st = np.zeros(9, np.float32), np.zeros(8, np.int32), np.zeros(4, np.uint32)
+    p = ctypes.c_void_p(16)   # never dereferenced: the arguments are refused first
+    calls = [lambda t: L.lf_mkd_verify_homography(None, kp.ctypes.data, 8, kp.ctypes.data, 8, m.ctypes.data, 64, t, 0, 0,
+                                                  H.ctypes.data, ver.ctypes.data, st.ctypes.data),
+             lambda t: L.lf_mkd_verify_homography_device(None, p, p, p, p, p, 4, 64, t, 0, 0, p, p, p, None)]
+    refused = [np.nextafter(lo, f32(0)), f32(1e-20), f32(1e-30), np.finfo(f32).tiny, f32(1.4e-45),
+               np.nextafter(hi, f32(np.inf)), f32(1e20), np.finfo(f32).max]
+    accepted = [lo, np.nextafter(lo, f32(1)), f32(1e-3), f32(1.0), f32(3.0), f32(3.5), f32(8.0), f32(1e10),
+                np.nextafter(hi, f32(0)), hi]
+    for call in calls:
+        for t in refused:
+            assert call(float(t)) == -1, t
+            assert b"threshold" in L.lf_mkd_last_error(None), (t, L.lf_mkd_last_error(None))
+        for t in accepted:
+            assert call(float(t)) == -1, t
+            assert b"null handle" in L.lf_mkd_last_error(None), (t, L.lf_mkd_last_error(None))
