@@ -168,6 +168,15 @@ extern "C" {
                                            n_pairs: u32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,
                                            d_homography: *mut f32, d_verified: *mut i32, d_stats: *mut u32,
                                            stream: *mut c_void) -> c_int;
+    // RANSAC fundamental-matrix verification (7-point samples, Sampson distance): the same two faces
+    pub fn lf_mkd_verify_fundamental(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,
+                                     nb: u64, matches: *const i32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,
+                                     fundamental: *mut f32, verified: *mut i32, stats: *mut u32) -> c_int;
+    pub fn lf_mkd_verify_fundamental_device(h: *mut lf_mkd, d_kps_a: *const lf_mkd_keypoint, d_offsets_a: *const u64,
+                                            d_kps_b: *const lf_mkd_keypoint, d_offsets_b: *const u64, d_match: *const i32,
+                                            n_pairs: u32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,
+                                            d_fundamental: *mut f32, d_verified: *mut i32, d_stats: *mut u32,
+                                            stream: *mut c_void) -> c_int;
 
     // the path's one collective: the all-gather of descriptor shards over RCCL (configs[3])
     pub fn lf_mkd_comm_unique_id(id: *mut u8) -> c_int;

@@ -67,7 +67,8 @@ fn check(h: *const ffi::lf_mkd, rc: i32) -> Result<(), Error> {
 const _: () = assert!(std::mem::size_of::<Keypoint>() == std::mem::size_of::<ffi::lf_mkd_keypoint>());
 const _: () = assert!(std::mem::align_of::<Keypoint>() == std::mem::align_of::<ffi::lf_mkd_keypoint>());
 
-/// `flags` of `lf_mkd_verify_homography*` (`include/lf_mkd.h`): the best RANSAC hypothesis as is, no least-squares refit.
+/// `flags` of `lf_mkd_verify_homography*` and `lf_mkd_verify_fundamental*` (`include/lf_mkd.h`): the best RANSAC
+/// candidate as is, no least-squares refit.
 pub const VERIFY_NO_REFINE: u32 = 1;
 
 pub struct LocalFeaturesHip {
@@ -264,6 +265,34 @@ impl LocalFeaturesHip {
                                             m.as_mut_ptr()))?;
         }
         Ok(m.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect())
+    }
+
+    /// RANSAC fundamental-matrix verification of matches (`lf_mkd_verify_fundamental`, `include/lf_mkd.h` states the
+    /// algorithm): 7-point samples scored by Sampson distance on the GPU, then a rank-2 least-squares refit.  `matches` are
+    /// (row of `kps_a`, row of `kps_b`) pairs as `match_features` returns them.  Returns F (row-major, b^T F a = 0 in pixels,
+    /// its largest entry +1) and the matches within `threshold_px` of Sampson distance; `None` if no sample was valid.
+    pub fn verify_fundamental(&mut self, kps_a: &[Keypoint], kps_b: &[Keypoint], matches: &[(usize, usize)],
+                              threshold_px: f32, n_hypotheses: u32, seed: u32)
+        -> Result<(Option<[f32; 9]>, Vec<(usize, usize)>), Error> {
+        let mut m = vec![-1i32; kps_a.len()];
+        for &(i, j) in matches {
+            if i >= kps_a.len() || j >= kps_b.len() {
+                return Err(Error::BadArgument("verify_fundamental: match outside the keypoints".into()));
+            }
+            m[i] = j as i32;
+        }
+        let mut f = [0f32; 9];
+        let mut ver = vec![-1i32; kps_a.len()];
+        let mut stats = [0u32; 4];
+        // SAFETY: Keypoint and lf_mkd_keypoint share their layout (asserted above); every array has the length passed
+        unsafe {
+            check(self.h, ffi::lf_mkd_verify_fundamental(self.h, kps_a.as_ptr() as *const ffi::lf_mkd_keypoint,
+                                                         kps_a.len() as u64, kps_b.as_ptr() as *const ffi::lf_mkd_keypoint,
+                                                         kps_b.len() as u64, m.as_ptr(), n_hypotheses, threshold_px, seed, 0,
+                                                         f.as_mut_ptr(), ver.as_mut_ptr(), stats.as_mut_ptr()))?;
+        }
+        let inliers = ver.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect();
+        Ok((if stats[2] == u32::MAX { None } else { Some(f) }, inliers))
     }
 
     /// The match stage of a job sharded by image over the GPUs of a node (one process and one `LocalFeaturesHip` per GPU;

@@ -422,7 +422,67 @@ int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, c
                                     const int32_t *d_match, uint32_t n_pairs, uint32_t n_hypotheses,
                                     float threshold_px, uint32_t seed, uint32_t flags,
                                     float *d_H, int32_t *d_verified, uint32_t *d_stats, void *stream);
-#define LF_MKD_VERIFY_NO_REFINE 1u   /* report the best RANSAC hypothesis as is: no least-squares refit */
+/* ---- geometric verification: RANSAC fundamental matrix of matched keypoints --------------------------------------
+ * The general two-view constraint b^T F a = 0 (a = (x, y, 1) in image a, b = (u, v, 1) in image b, pixels), fitted robustly
+ * by 7-point RANSAC: for pairs with parallax (a 3-D scene seen from two places), where a homography keeps only the dominant
+ * plane.  A scene that is (nearly) one plane leaves F underdetermined -- any F = [e]x H fits it -- so use the homography
+ * for such pairs.  Inputs, pair layout, argument checks, n_pairs == 0, the 2^24-workgroup limit and the stream rules are
+ * those of lf_mkd_verify_homography*; F and H verification share the handle's scratch, so calls of one handle (of either
+ * kind) must be stream-ordered.  d_verified must not overlap d_match or the keypoints (d_verified == d_match is refused).
+ * Outputs: F [n_pairs][9] row-major, pixel coordinates, divided by its entry of largest magnitude (the first in row-major
+ * order on a tie), which is therefore exactly +1; verified = match with every non-inlier set to -1; stats [n_pairs][4] =
+ * {final inlier count, best candidate's inlier count, best candidate's index c = 3 k + j (k the sample, j the candidate's
+ * place among that sample's real roots; 0xFFFFFFFF: none), M = matches considered}.
+ * The algorithm, exactly (a CPU restatement reproduces every sample: tests/fundamental_ref.py):
+ *   1. Considered matches and normalisation: homography step 1, unchanged (the same launch computes them).
+ *   2. Sampler: sample k takes draws t = 0..63, r = splitmix64(((uint64)(seed + p) << 32) ^ ((uint64)k << 6) ^ t),
+ *      pos = ((r >> 32) * M) >> 32, and keeps the first 7 distinct positions (fewer: the sample is invalid).
+ *   3. Minimal solver, f32 on the normalised coordinates, using only correctly rounded operations (+ - * /, sqrt, fma) with
+ *      fixed iteration counts.  Sampled match i gives the row [u x, u y, u, v x, v y, v, x, y, 1] (a = (x, y), b = (u, v)).
+ *      Gauss-Jordan elimination with full pivoting: at each of the 7 steps the pivot is the largest |entry| among the rows and
+ *      columns not used yet (the first in row-major order on a tie); the sample is invalid if it is not above 1e-5 times the
+ *      first pivot.  Every other row r gets row_r + (-(a_r * (1 / pivot))) * pivot row as fma, its pivot-column entry set to 0.
+ *      F1, F2 = the null vectors with 1 in the first, resp. second, unused column and 0 in the other (the rest: -(a * (1 / d))
+ *      from each pivot row).  With G = F2, D = F1 - F2 and Cof() the cofactor matrix: det(l F1 + (1 - l) F2) = c3 l^3 + c2 l^2
+ *      + c1 l + c0, c0 = det G, c1 = sum Cof(G) .* D, c2 = sum Cof(D) .* G, c3 = det D.  No candidate if a coefficient is not
+ *      finite or |c3| <= 2^-20 max(|c0|, |c1|, |c2|) (a vanishing leading coefficient: its root near infinity, F = D, is not
+ *      sought).  Otherwise the roots lie in [-R, R], R = 1 + max(|c0|, |c1|, |c2|) / |c3|; the derivative's real roots (the
+ *      cancellation-free quadratic formula, clamped to [-R, R]) cut it into three monotone pieces; a piece [lo, hi] holds a
+ *      root iff (p(lo) < 0) != (p(hi) < 0), found by 40 bisection steps and then 4 Newton steps (a step that leaves the
+ *      bracket is not taken).  Each real root l, in ascending order, is candidate j = 0, 1, 2: G + l D, divided by its largest
+ *      |entry|, then taken to pixel coordinates F = Tb^T Fn Ta (invalid if that largest |entry| is not finite and positive,
+ *      or a value is not finite).
+ *   4. Score (Sampson distance, pixels): with l = F a and l' = F^T b, point i is an inlier iff
+ *      (b . l)^2 < threshold^2 (l0^2 + l1^2 + l'0^2 + l'1^2).  The best candidate has the largest count; ties go to the
+ *      smallest c.
+ *   5. Refit (unless LF_MKD_VERIFY_NO_REFINE): least squares sum (r_i . f)^2 over the current F's inliers in the normalised
+ *      coordinates of step 1, with f_c = 1 for c the index of the current normalised F's largest |entry| (F33 is not pinned:
+ *      it vanishes for sideways camera motion).  The 8x8 normal equations come from the 36 distinct moments
+ *      b~_i b~_j a~_k a~_l accumulated in f64 in a fixed order and are solved by the homography's Cholesky and pivot rule.
+ *      Rank 2: F <- F (I - v v^T), v the eigenvector of F^T F of the smallest eigenvalue from 6 sweeps of cyclic Jacobi in f64.
+ *      The result, divided by its largest |entry|, is rounded to f32, taken to pixels and rescored as in step 4.  It is kept
+ *      if its MSAC cost (an inlier adds its Sampson error, any other considered match threshold^2; summed in f64 in a fixed
+ *      order) is not above the current F's.  At most 3 rounds, stopping when the inlier set stops changing.
+ *   6. M < 7, or no valid candidate: F all zero, verified all -1, final count 0, stats[2] = 0xFFFFFFFF; status LF_MKD_OK.
+ * The bits of every output depend on the pair's inputs, seed + p, n_hypotheses, threshold and flags alone: pair p of a
+ * batched call equals a single-pair call with seed + p, and a captured call replays to the same bits. */
+
+/* Host pointers, one pair, synchronous. */
+int lf_mkd_verify_fundamental(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na,
+                              const lf_mkd_keypoint *kps_b, uint64_t nb, const int32_t *match,
+                              uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                              float *F, int32_t *verified, uint32_t *stats);
+
+/* Device pointers, n_pairs independent problems in one call, asynchronous on `stream` (NULL: the handle's own); three
+ * launches, no host synchronisation, no allocation once the handle's scratch has grown (capturable), as
+ * lf_mkd_verify_homography_device. */
+int lf_mkd_verify_fundamental_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                     const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b,
+                                     const int32_t *d_match, uint32_t n_pairs, uint32_t n_hypotheses,
+                                     float threshold_px, uint32_t seed, uint32_t flags,
+                                     float *d_F, int32_t *d_verified, uint32_t *d_stats, void *stream);
+
+#define LF_MKD_VERIFY_NO_REFINE 1u   /* report the best RANSAC candidate as is: no least-squares refit (both verifiers) */
 
 /* ---- multi-GPU: the path's ONE collective (BASELINE configs[3]) -------------------------------------------------
  * Keypoint batches shard by image, one process and one handle per GPU, and nothing is exchanged while describing.  The

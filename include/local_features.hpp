@@ -189,6 +189,28 @@ public:
         return stats[2] != 0xFFFFFFFFu;
     }
 
+    // RANSAC fundamental-matrix verification of matches (lf_mkd_verify_fundamental): 7-point samples scored by Sampson
+    // distance, then a rank-2 least-squares refit.  Returns true and sets F (row-major, b^T F a = 0 in pixels, its largest
+    // entry +1) if a valid sample was found; `inliers` receives the matches within threshold_px of Sampson distance.
+    bool verify_fundamental(const std::vector<Keypoint> &kps_a, const std::vector<Keypoint> &kps_b,
+                            const std::vector<std::pair<std::size_t, std::size_t>> &matches, float F[9],
+                            std::vector<std::pair<std::size_t, std::size_t>> &inliers, float threshold_px = 1.5f,
+                            std::uint32_t n_hypotheses = 2048, std::uint32_t seed = 0) {
+        std::vector<std::int32_t> m(kps_a.size(), -1), ver(kps_a.size(), -1);
+        for (const auto &ij : matches) {
+            if (ij.first >= kps_a.size() || ij.second >= kps_b.size())
+                throw LocalFeaturesError(LocalFeaturesError::Kind::InvalidParameters, "verify_fundamental: match outside the keypoints");
+            m[ij.first] = std::int32_t(ij.second);
+        }
+        std::uint32_t stats[4];
+        check(lf_mkd_verify_fundamental(h_, kps_a.data(), kps_a.size(), kps_b.data(), kps_b.size(), m.data(), n_hypotheses,
+                                        threshold_px, seed, 0, F, ver.data(), stats));
+        inliers.clear();
+        for (std::size_t i = 0; i < ver.size(); ++i)
+            if (ver[i] >= 0) inliers.emplace_back(i, std::size_t(ver[i]));
+        return stats[2] != 0xFFFFFFFFu;
+    }
+
     lf_mkd *handle() { return h_; }
 
 private:

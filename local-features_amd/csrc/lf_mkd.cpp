@@ -233,8 +233,8 @@ struct lf_mkd {
     HipArray<unsigned> d_match_misc;
     HipArray<unsigned char> d_match_few_tiles;   // the overflowed rows' own tiles; their indices, exclusion ranges, partials
     HipArray<unsigned> d_match_few;
-    // RANSAC verification scratch (lf_mkd_verify_homography*): per-pair normalisation, per-hypothesis partial counts, and the
-    // host form's staging.  No recording names them; they grow only when a call asks for more, so the device form's launches
+    // RANSAC verification scratch (lf_mkd_verify_homography*, lf_mkd_verify_fundamental*, which share it): per-pair
+    // normalisation, per-candidate partial counts, and the host form's staging.  No recording names them; they grow only when a call asks for more, so the device form's launches
     // can be captured once warmed up.  Calls of one handle are stream-ordered (lf_mkd.h).
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
@@ -1787,38 +1787,64 @@ static int verify_args(lf_mkd *h, bool null_pointer, uint32_t n_hypotheses, floa
     return LF_MKD_ERR_BAD_ARG;
 }
 
-int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
-                                    const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, const int32_t *d_match,
-                                    uint32_t n_pairs, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
-                                    float *d_H, int32_t *d_verified, uint32_t *d_stats, void *stream) {
-    const bool null = !d_kps_a || !d_offsets_a || !d_kps_b || !d_offsets_b || !d_match || !d_H || !d_verified || !d_stats;
-    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, "verify_homography_device")) return rc;
+// The device form of both verifiers: the same checks, scratch and grid; `launch` is launch_verify or launch_fundamental.
+// Both count one partial per scoring candidate in d_ver_counts: a homography hypothesis has one, a 7-point sample three.
+typedef void (*VerifyLaunch)(const float *, const uint64_t *, const float *, const uint64_t *, const int *, unsigned, unsigned,
+                             float, unsigned, unsigned, unsigned, VerifyPair *, unsigned *, float *, int *, unsigned *,
+                             hipStream_t);
+static int verify_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a, const lf_mkd_keypoint *d_kps_b,
+                         const uint64_t *d_offsets_b, const int32_t *d_match, uint32_t n_pairs, uint32_t n_hypotheses,
+                         float threshold_px, uint32_t seed, uint32_t flags, float *d_model, int32_t *d_verified,
+                         uint32_t *d_stats, void *stream, VerifyLaunch launch, unsigned per_hypothesis, const char *what) {
+    const bool null = !d_kps_a || !d_offsets_a || !d_kps_b || !d_offsets_b || !d_match || !d_model || !d_verified || !d_stats;
+    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, what)) return rc;
     if (n_pairs == 0) return LF_MKD_OK;
     if (static_cast<const void *>(d_verified) == d_match || static_cast<const void *>(d_verified) == d_kps_a ||
         static_cast<const void *>(d_verified) == d_kps_b)
-        return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography_device: d_verified must not alias d_match or the keypoints");
+        return fail(h, LF_MKD_ERR_BAD_ARG, std::string(what) + ": d_verified must not alias d_match or the keypoints");
     // a launch's grid holds fewer than 2^24 workgroups of 256 threads (its work-items are counted in 32 bits)
     const unsigned slices = verify_slices(n_pairs, n_hypotheses, h->num_cus);
     if (uint64_t(n_pairs) * ((n_hypotheses + 255) / 256) * slices >= (1ull << 24))
-        return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography_device: too many pairs x hypotheses for one call (the scoring grid "
-                                           "needs n_pairs x ceil(n_hypotheses / 256) x row slices < 2^24 workgroups)");
+        return fail(h, LF_MKD_ERR_BAD_ARG, std::string(what) + ": too many pairs x hypotheses for one call (the scoring grid "
+                                                               "needs n_pairs x ceil(n_hypotheses / 256) x row slices < 2^24 "
+                                                               "workgroups)");
     LF_ENTER(h);
     if (int rc = grow(h, h->d_ver_pairs, n_pairs)) return rc;
-    if (int rc = grow(h, h->d_ver_counts, uint64_t(n_pairs) * slices * n_hypotheses)) return rc;
+    if (int rc = grow(h, h->d_ver_counts, uint64_t(n_pairs) * slices * n_hypotheses * per_hypothesis)) return rc;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    launch_verify(reinterpret_cast<const float *>(d_kps_a), d_offsets_a, reinterpret_cast<const float *>(d_kps_b), d_offsets_b,
-                  d_match, n_pairs, n_hypotheses, threshold_px, seed, flags, slices, h->d_ver_pairs, h->d_ver_counts, d_H,
-                  d_verified, d_stats, s);
+    launch(reinterpret_cast<const float *>(d_kps_a), d_offsets_a, reinterpret_cast<const float *>(d_kps_b), d_offsets_b, d_match,
+           n_pairs, n_hypotheses, threshold_px, seed, flags, slices, h->d_ver_pairs, h->d_ver_counts, d_model, d_verified,
+           d_stats, s);
     LF_HIP(h, hipGetLastError());
     return LF_MKD_OK;
 }
 
-int lf_mkd_verify_homography(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na, const lf_mkd_keypoint *kps_b, uint64_t nb,
-                             const int32_t *match, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
-                             float *H, int32_t *verified, uint32_t *stats) {
-    const bool null = (na && (!kps_a || !match || !verified)) || (nb && !kps_b) || !H || !stats;
-    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, "verify_homography")) return rc;
-    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return fail(h, LF_MKD_ERR_BAD_ARG, "verify_homography: more than 2^31 - 1 rows");
+int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                    const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, const int32_t *d_match,
+                                    uint32_t n_pairs, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                                    float *d_H, int32_t *d_verified, uint32_t *d_stats, void *stream) {
+    return verify_device(h, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, n_hypotheses, threshold_px, seed,
+                         flags, d_H, d_verified, d_stats, stream, launch_verify, 1, "verify_homography_device");
+}
+
+int lf_mkd_verify_fundamental_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                     const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, const int32_t *d_match,
+                                     uint32_t n_pairs, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                                     float *d_F, int32_t *d_verified, uint32_t *d_stats, void *stream) {
+    return verify_device(h, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, n_hypotheses, threshold_px, seed,
+                         flags, d_F, d_verified, d_stats, stream, launch_fundamental, 3, "verify_fundamental_device");
+}
+
+// The host form of both verifiers: one pair staged through the handle's d_ver_io, the device form, and the outputs back.
+typedef int (*VerifyDevice)(lf_mkd *, const lf_mkd_keypoint *, const uint64_t *, const lf_mkd_keypoint *, const uint64_t *,
+                            const int32_t *, uint32_t, uint32_t, float, uint32_t, uint32_t, float *, int32_t *, uint32_t *,
+                            void *);
+static int verify_host(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na, const lf_mkd_keypoint *kps_b, uint64_t nb,
+                       const int32_t *match, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                       float *model, int32_t *verified, uint32_t *stats, VerifyDevice device, const char *what) {
+    const bool null = (na && (!kps_a || !match || !verified)) || (nb && !kps_b) || !model || !stats;
+    if (int rc = verify_args(h, null, n_hypotheses, threshold_px, what)) return rc;
+    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return fail(h, LF_MKD_ERR_BAD_ARG, std::string(what) + ": more than 2^31 - 1 rows");
     LF_ENTER(h);
     // one staging array, every part 16-byte aligned: offsets, keypoints of a and b, match, then the outputs
     auto up16 = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 15) / 16 * 16; };   // (empty parts do not share an address)
@@ -1833,17 +1859,30 @@ int lf_mkd_verify_homography(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t n
     if (nb) LF_HIP(h, hipMemcpyAsync(io + o_kb, kps_b, nb * sizeof(lf_mkd_keypoint), hipMemcpyHostToDevice, h->stream));
     if (na) LF_HIP(h, hipMemcpyAsync(io + o_m, match, na * 4, hipMemcpyHostToDevice, h->stream));
     const uint64_t *d_offs = reinterpret_cast<const uint64_t *>(io + o_off);
-    if (int rc = lf_mkd_verify_homography_device(h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_ka), d_offs,
-                                                 reinterpret_cast<const lf_mkd_keypoint *>(io + o_kb), d_offs + 2,
-                                                 reinterpret_cast<const int32_t *>(io + o_m), 1, n_hypotheses, threshold_px, seed,
-                                                 flags, reinterpret_cast<float *>(io + o_h), reinterpret_cast<int32_t *>(io + o_v),
-                                                 reinterpret_cast<uint32_t *>(io + o_st), h->stream))
+    if (int rc = device(h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_ka), d_offs,
+                        reinterpret_cast<const lf_mkd_keypoint *>(io + o_kb), d_offs + 2, reinterpret_cast<const int32_t *>(io + o_m),
+                        1, n_hypotheses, threshold_px, seed, flags, reinterpret_cast<float *>(io + o_h),
+                        reinterpret_cast<int32_t *>(io + o_v), reinterpret_cast<uint32_t *>(io + o_st), h->stream))
         return rc;
-    LF_HIP(h, hipMemcpyAsync(H, io + o_h, 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipMemcpyAsync(model, io + o_h, 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     LF_HIP(h, hipMemcpyAsync(stats, io + o_st, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     if (na) LF_HIP(h, hipMemcpyAsync(verified, io + o_v, na * 4, hipMemcpyDeviceToHost, h->stream));
     LF_HIP(h, hipStreamSynchronize(h->stream));
     return LF_MKD_OK;
+}
+
+int lf_mkd_verify_homography(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na, const lf_mkd_keypoint *kps_b, uint64_t nb,
+                             const int32_t *match, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                             float *H, int32_t *verified, uint32_t *stats) {
+    return verify_host(h, kps_a, na, kps_b, nb, match, n_hypotheses, threshold_px, seed, flags, H, verified, stats,
+                       lf_mkd_verify_homography_device, "verify_homography");
+}
+
+int lf_mkd_verify_fundamental(lf_mkd *h, const lf_mkd_keypoint *kps_a, uint64_t na, const lf_mkd_keypoint *kps_b, uint64_t nb,
+                              const int32_t *match, uint32_t n_hypotheses, float threshold_px, uint32_t seed, uint32_t flags,
+                              float *F, int32_t *verified, uint32_t *stats) {
+    return verify_host(h, kps_a, na, kps_b, nb, match, n_hypotheses, threshold_px, seed, flags, F, verified, stats,
+                       lf_mkd_verify_fundamental_device, "verify_fundamental");
 }
 
 int lf_mkd_orient_keypoints_blocked(lf_mkd *h, const float *extremum_data, uint64_t n_extrema, uint32_t block_len,

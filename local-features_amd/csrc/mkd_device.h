@@ -1,5 +1,5 @@
 // Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_verify.hip).
+// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_verify.hip, mkd_fundamental.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -185,6 +185,16 @@ unsigned verify_slices(unsigned n_pairs, unsigned n_hyp, int num_cus);
 void launch_verify(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
                    unsigned n_pairs, unsigned n_hyp, float threshold, unsigned seed, unsigned flags, unsigned slices,
                    VerifyPair *pairs, unsigned *counts, float *H, int *verified, unsigned *stats, hipStream_t stream);
+// launch 1 of both verifiers alone (include/lf_mkd.h, step 1): each pair's considered rows by ascending row into `list`
+// (indexed like match), and its normalisation into pairs[p]
+void launch_verify_prepare(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
+                           unsigned n_pairs, VerifyPair *pairs, int *list, hipStream_t stream);
+// RANSAC fundamental matrix (mkd_fundamental.hip; algorithm: include/lf_mkd.h).  Scratch: pairs [n_pairs], counts
+// [n_pairs][slices][n_hyp][3] (one count per candidate of a sample; slices from verify_slices, the same grid shape);
+// `verified` holds the considered rows as above.
+void launch_fundamental(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
+                        unsigned n_pairs, unsigned n_hyp, float threshold, unsigned seed, unsigned flags, unsigned slices,
+                        VerifyPair *pairs, unsigned *counts, float *F, int *verified, unsigned *stats, hipStream_t stream);
 
 #ifdef __HIPCC__
 // Which tile a workgroup takes, for the row-tiled pyramid and a-trous kernels: workgroups are dealt to the 8 XCDs round-robin by their

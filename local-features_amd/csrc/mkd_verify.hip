@@ -24,48 +24,15 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "mkd_device.h"
+#include "mkd_verify_common.h"
 
 #pragma clang fp contract(off)
 
 namespace lfmkd {
 namespace {
 
-constexpr int kThreads = 256;                  // every kernel here: 4 waves
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxDraws = 32;                  // sampler draws per hypothesis
 constexpr float kDegenerate = 1e-4f;           // |twice a triangle's area| below this in normalised coordinates
-constexpr unsigned kInvalid = 0xFFFFFFFFu;
-constexpr unsigned kMaxSlices = 16;            // row slices per (pair, hypothesis block) of verify_score
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// rows [lo, hi) of a pair, as the offsets give them (a pair whose offsets decrease is empty)
-__device__ __forceinline__ uint64_t pair_rows(const uint64_t *off, unsigned p, uint64_t &lo) {
-    lo = off[p];
-    const uint64_t hi = off[p + 1];
-    return hi > lo ? hi - lo : 0;
-}
-
-struct Pt {
-    float ax, ay, bx, by;
-};
-
-// row r of a pair: considered if its match indexes the pair's b rows; then its two points
-__device__ __forceinline__ bool load_row(const float *ka, const float *kb, const int *match, uint64_t r, uint64_t nb, Pt &q) {
-    const int m = match[r];
-    if (m < 0 || uint64_t(m) >= nb) return false;
-    q.ax = ka[5 * r];
-    q.ay = ka[5 * r + 1];
-    q.bx = kb[5 * uint64_t(m)];
-    q.by = kb[5 * uint64_t(m) + 1];
-    return true;
-}
 
 // Inlier test of one point under H (pixel coordinates, oriented so that the hypothesis' samples have w > 0):
 // w > 0 and (bx w - u)^2 + (by w - v)^2 < thr^2 w^2, i.e. the forward transfer error below thr, without a division.
@@ -203,32 +170,6 @@ __device__ bool hypothesis(const float *ka, const float *kb, const int *match, c
 #pragma unroll
         for (int i = 0; i < 9; ++i) n[i] = -n[i];
     return denormalise(n, P, h);
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Workgroup sum of N values per thread, in a fixed order (butterfly within a wave, then the waves in order); every thread
-// gets the totals.  `red` holds kWaves * N values.
-template <typename T, int N>
-__device__ __forceinline__ void block_sum(T *v, T *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const T s = wave_sum(v[i]);
-        if (lane == 0) red[wave * N + i] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        T s = red[i];
-        for (int w = 1; w < kWaves; ++w) s += red[w * N + i];
-        v[i] = s;
-    }
-    __syncthreads();
 }
 
 // ---- launch 1: considered matches + normalisation ---------------------------------------------------------------------
@@ -378,43 +319,7 @@ __device__ bool solve_refit(const double *m, float *n) {
     N[3][6] = -m[11]; N[3][7] = -m[12]; N[4][6] = -m[12]; N[4][7] = -m[13]; N[5][6] = -m[14]; N[5][7] = -m[15];
     N[6][6] = m[16]; N[6][7] = m[17]; N[7][7] = m[18];
     r[0] = m[9]; r[1] = m[10]; r[2] = m[19]; r[3] = m[14]; r[4] = m[15]; r[5] = m[20]; r[6] = -m[21]; r[7] = -m[22];
-    double dmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dmax = fmax(dmax, N[i][i]);
-    const double floor = 1e-12 * dmax;
-    bool ok = dmax > 0.0;
-    // N = L L^T in the upper triangle read as L^T (row i of L^T = column i of L)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        double d = N[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= N[k][j] * N[k][j];
-        ok = ok && d > floor;
-        const double l = sqrt(fmax(d, floor));
-        N[j][j] = l;
-#pragma unroll
-        for (int i = j + 1; i < 8; ++i) {
-            double s = N[j][i];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= N[k][j] * N[k][i];
-            N[j][i] = s / l;
-        }
-    }
-    // L y = r, then L^T h = y
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= N[k][i] * r[k];
-        r[i] = s / N[i][i];
-    }
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = i + 1; k < 8; ++k) s -= N[i][k] * r[k];
-        r[i] = s / N[i][i];
-    }
+    bool ok = cholesky8(N, r);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         n[i] = float(r[i]);
@@ -548,14 +453,19 @@ unsigned verify_slices(unsigned n_pairs, unsigned n_hyp, int num_cus) {
     return unsigned(want < 1 ? 1 : want > kMaxSlices ? kMaxSlices : want);
 }
 
+void launch_verify_prepare(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
+                           unsigned n_pairs, VerifyPair *pairs, int *list, hipStream_t stream) {
+    if (n_pairs == 0) return;
+    hipLaunchKernelGGL(verify_prepare, dim3(n_pairs), dim3(kThreads), 0, stream, kps_a, off_a, kps_b, off_b, match, list, pairs);
+}
+
 void launch_verify(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
                    unsigned n_pairs, unsigned n_hyp, float threshold, unsigned seed, unsigned flags, unsigned slices,
                    VerifyPair *pairs, unsigned *counts, float *H, int *verified, unsigned *stats, hipStream_t stream) {
     if (n_pairs == 0) return;
     const float thr2 = threshold * threshold;
     const unsigned hyp_blocks = (n_hyp + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(verify_prepare, dim3(n_pairs), dim3(kThreads), 0, stream, kps_a, off_a, kps_b, off_b, match, verified,
-                       pairs);
+    launch_verify_prepare(kps_a, off_a, kps_b, off_b, match, n_pairs, pairs, verified, stream);
     hipLaunchKernelGGL(verify_score, dim3(n_pairs * hyp_blocks * slices), dim3(kThreads), 0, stream, kps_a, off_a, kps_b,
                        off_b, match, verified, pairs, n_hyp, hyp_blocks, slices, thr2, seed, counts);
     hipLaunchKernelGGL(verify_select, dim3(n_pairs), dim3(kThreads), 0, stream, kps_a, off_a, kps_b, off_b, match, verified,

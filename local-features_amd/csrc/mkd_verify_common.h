@@ -1,0 +1,120 @@
+// Device helpers the two RANSAC verifiers share (mkd_verify.hip: homography, mkd_fundamental.hip: fundamental matrix).
+// Each source is its own translation unit and includes this header: no device code crosses a translation unit.  Everything
+// here is a fixed sequence of IEEE operations under contraction OFF, so both files get the same bits from it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "mkd_device.h"
+
+#pragma clang fp contract(off)
+
+namespace lfmkd {
+namespace {
+
+constexpr int kThreads = 256;                  // every verification kernel: 4 waves
+constexpr int kWaves = kThreads / 64;
+constexpr unsigned kInvalid = 0xFFFFFFFFu;
+constexpr unsigned kMaxSlices = 16;            // row slices per (pair, hypothesis block) of a scoring launch
+
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// rows [lo, hi) of a pair, as the offsets give them (a pair whose offsets decrease is empty)
+__device__ __forceinline__ uint64_t pair_rows(const uint64_t *off, unsigned p, uint64_t &lo) {
+    lo = off[p];
+    const uint64_t hi = off[p + 1];
+    return hi > lo ? hi - lo : 0;
+}
+
+struct Pt {
+    float ax, ay, bx, by;
+};
+
+// row r of a pair: considered if its match indexes the pair's b rows; then its two points
+__device__ __forceinline__ bool load_row(const float *ka, const float *kb, const int *match, uint64_t r, uint64_t nb, Pt &q) {
+    const int m = match[r];
+    if (m < 0 || uint64_t(m) >= nb) return false;
+    q.ax = ka[5 * r];
+    q.ay = ka[5 * r + 1];
+    q.bx = kb[5 * uint64_t(m)];
+    q.by = kb[5 * uint64_t(m) + 1];
+    return true;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Workgroup sum of N values per thread, in a fixed order (butterfly within a wave, then the waves in order); every thread
+// gets the totals.  `red` holds kWaves * N values.
+template <typename T, int N>
+__device__ __forceinline__ void block_sum(T *v, T *red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const T s = wave_sum(v[i]);
+        if (lane == 0) red[wave * N + i] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        T s = red[i];
+        for (int w = 1; w < kWaves; ++w) s += red[w * N + i];
+        v[i] = s;
+    }
+    __syncthreads();
+}
+
+// Solves N x = r in place (x returned in r) for a symmetric 8x8 N by Cholesky; false if a pivot is at or below 1e-12 of N's
+// largest diagonal element (or that element is not positive).  Every loop has constant bounds: the matrix stays in registers.
+__host__ __device__ __forceinline__ bool cholesky8(double (&N)[8][8], double (&r)[8]) {
+    double dmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dmax = fmax(dmax, N[i][i]);
+    const double floor = 1e-12 * dmax;
+    bool ok = dmax > 0.0;
+    // N = L L^T in the upper triangle read as L^T (row i of L^T = column i of L)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        double d = N[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= N[k][j] * N[k][j];
+        ok = ok && d > floor;
+        const double l = sqrt(fmax(d, floor));
+        N[j][j] = l;
+#pragma unroll
+        for (int i = j + 1; i < 8; ++i) {
+            double s = N[j][i];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= N[k][j] * N[k][i];
+            N[j][i] = s / l;
+        }
+    }
+    // L y = r, then L^T x = y
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        double s = r[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= N[k][i] * r[k];
+        r[i] = s / N[i][i];
+    }
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {
+        double s = r[i];
+#pragma unroll
+        for (int k = i + 1; k < 8; ++k) s -= N[i][k] * r[k];
+        r[i] = s / N[i][i];
+    }
+    return ok;
+}
+
+}  // namespace
+}  // namespace lfmkd

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""match_images [--homography] IMAGE_1 IMAGE_2 IMAGE_OUT -- the reference's example (examples/match_images/src/main.rs) on the
+"""match_images [--homography | --fundamental] IMAGE_1 IMAGE_2 IMAGE_OUT -- the reference's example (examples/match_images/src/main.rs) on the
 MI355X path: load two images, detect_top_n(2000, min_size 0) on each, brute-force match 1->2 and 2->1 with the
 0.8 ratio test, draw keypoints and the 1->2 matches side by side.  With --homography the 1->2 matches are verified on the
-device first (RANSAC homography, 3 px: LocalFeatures.verify_homography) and only the inliers are drawn.
+device first (RANSAC homography, 3 px: LocalFeatures.verify_homography) and only the inliers are drawn; with --fundamental
+they are verified by epipolar geometry instead (7-point RANSAC, 1.5 px Sampson distance: LocalFeatures.verify_fundamental),
+which keeps the correct matches of a 3-D scene seen from two places, not only those of its dominant plane.
 
 Image decoding follows main.rs:44-60: 8-bit luma, then f32 / 255 (Pillow's "L" conversion stands in for the `image`
 crate's grayscale(); they may differ by one LSB).  Needs Pillow."""
@@ -58,10 +60,10 @@ def draw(img1, img2, kp1, kp2, matches, out_path):
 
 def main():
     args = sys.argv[1:]
-    homography = "--homography" in args
-    args = [a for a in args if a != "--homography"]
-    if len(args) != 3:
-        print("Required arguments: [--homography] IMAGE_1 IMAGE_2 IMAGE_OUT", file=sys.stderr)
+    homography, fundamental = "--homography" in args, "--fundamental" in args
+    args = [a for a in args if a not in ("--homography", "--fundamental")]
+    if len(args) != 3 or (homography and fundamental):
+        print("Required arguments: [--homography | --fundamental] IMAGE_1 IMAGE_2 IMAGE_OUT", file=sys.stderr)
         return 1
     img1, img2 = load_gray(args[0]), load_gray(args[1])
     feats = features(img1, img2)
@@ -72,6 +74,9 @@ def main():
     if homography:
         _, m12 = feats.verify_homography(kp1, kp2, m12, 3.0)   # on the device that detected and matched them
         print(f"Verified 1 -> 2: {len(m12)} matches agree with one homography")
+    if fundamental:
+        _, m12 = feats.verify_fundamental(kp1, kp2, m12, 1.5)
+        print(f"Verified 1 -> 2: {len(m12)} matches agree with one epipolar geometry")
     draw(img1, img2, kp1, kp2, m12, args[2])
     return 0
 

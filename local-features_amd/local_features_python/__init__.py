@@ -215,6 +215,58 @@ class LocalFeatures:
                                                  seed, flags, s.cuda_stream)
         return H[:n_pairs], ver[:ka.shape[0]], st[:n_pairs].to(torch.int64)
 
+    def verify_fundamental(self, kp_a, kp_b, matches, threshold=1.5, n_hypotheses=2048, seed=0, flags=0):
+        """Geometric verification of matches by epipolar geometry (lf_mkd_verify_fundamental): 7-point RANSAC on the GPU,
+        scored by Sampson distance, then a rank-2 least-squares refit (include/lf_mkd.h states the algorithm).  For pairs with
+        parallax, where a homography keeps only one plane; a (nearly) planar scene leaves F underdetermined.  Arguments as
+        verify_homography.  Returns (F, inliers): F ndarray[3,3] with b^T F a = 0 in pixels and its largest entry +1, or
+        None if no sample was valid; inliers the (i, j) pairs within `threshold` px of Sampson distance.  Per-call numbers
+        are kept in `verify_stats` (best_candidate = 3 k + j: sample k, root j)."""
+        a, b = _keypoints_to_array(kp_a), _keypoints_to_array(kp_b)
+        m = np.full(len(a), -1, np.int32)
+        for i, j in matches:
+            if not (0 <= i < len(a) and 0 <= j < len(b)):
+                raise RuntimeError("verify_fundamental: match (%d, %d) outside the keypoint lists" % (i, j))
+            m[i] = j
+        with self._lock:
+            F, ver, st = self._inner.verify_fundamental(a.view(np.float32).reshape(-1, 5), b.view(np.float32).reshape(-1, 5), m,
+                                                        n_hypotheses, threshold, seed, flags)
+        self.verify_stats = {"inliers": int(st[0]), "best_candidate_inliers": int(st[1]), "best_candidate": int(st[2]),
+                             "considered": int(st[3])}
+        if st[2] == 0xFFFFFFFF:
+            return None, []
+        return F.astype(np.float64), [(int(i), int(j)) for i, j in enumerate(ver) if j >= 0]
+
+    def verify_fundamental_batch(self, kps_a, offsets_a, kps_b, offsets_b, match, threshold=1.5, n_hypotheses=2048, seed=0,
+                                 flags=0, stream=None):
+        """Many image pairs in one call (lf_mkd_verify_fundamental_device) on torch device tensors, laid out as for
+        verify_homography_batch.  Returns device tensors (F [n_pairs,3,3], verified [Na] int32, stats [n_pairs,4] int64:
+        final inliers, best candidate's inliers, best candidate 3 k + j (-1: none), considered)."""
+        return self._verify_batch(self._inner.verify_fundamental_device, "verify_fundamental_batch", kps_a, offsets_a, kps_b,
+                                  offsets_b, match, threshold, n_hypotheses, seed, flags, stream)
+
+    def _verify_batch(self, device_call, what, kps_a, offsets_a, kps_b, offsets_b, match, threshold, n_hypotheses, seed, flags,
+                      stream):
+        import torch
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError(what + ": offsets_a and offsets_b need n_pairs + 1 entries each")
+        ka = kps_a.to(dev, torch.float32).reshape(-1, 5).contiguous()
+        kb = kps_b.to(dev, torch.float32).reshape(-1, 5).contiguous()
+        oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+        mt = match.to(dev, torch.int32).contiguous()
+        if mt.numel() != ka.shape[0]:
+            raise RuntimeError(what + ": match must have one entry per row of kps_a")
+        M = torch.empty((max(n_pairs, 1), 3, 3), dtype=torch.float32, device=dev)
+        ver = torch.empty((max(ka.shape[0], 1),), dtype=torch.int32, device=dev)
+        st = torch.empty((max(n_pairs, 1), 4), dtype=torch.int32, device=dev)
+        with self._lock, torch.cuda.device(dev):
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            device_call(ka.data_ptr(), oa.data_ptr(), kb.data_ptr(), ob.data_ptr(), mt.data_ptr(), n_pairs, M.data_ptr(),
+                        ver.data_ptr(), st.data_ptr(), n_hypotheses, threshold, seed, flags, s.cuda_stream)
+        return M[:n_pairs], ver[:ka.shape[0]], st[:n_pairs].to(torch.int64)
+
     def describe_patches(self, patches):
         """patches: [n,32,32] float32 -> ndarray[n,128] (the CPU twin's Mkd::patch, mkd_ref.rs:57-77)."""
         with self._lock:

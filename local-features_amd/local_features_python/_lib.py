@@ -13,7 +13,7 @@ MODEL_DIR = os.path.join(_ROOT, "models", "mkd")
 FLAG_KERNEL_TIMING = 1
 FLAG_UNFUSED_KEYPOINTS = 2
 FLAG_DETECT_STEPWISE = 4
-VERIFY_NO_REFINE = 1     # lf_mkd_verify_homography*: the best RANSAC hypothesis as is, no least-squares refit
+VERIFY_NO_REFINE = 1     # lf_mkd_verify_homography* / _fundamental*: the best RANSAC candidate as is, no least-squares refit
 ANGLE_SHADER, ANGLE_EXACT, ANGLE_EXACT_ZERO = 0, 1, 2
 POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6 = 0, 1, 2, 3   # lf_mkd_pool_mode; the default is the f16x3 split
 PCA_NAMES = ("liberty", "notredame", "yosemite")   # enum MKDPCA, lib.rs:26-32
@@ -35,6 +35,7 @@ SYMBOLS = (
     "lf_mkd_comm_unique_id", "lf_mkd_comm_create", "lf_mkd_comm_destroy", "lf_mkd_comm_info", "lf_mkd_allgather_descriptors",
     "lf_mkd_comm_loopback", "lf_mkd_comm_last_form", "lf_mkd_plan_upload", "lf_mkd_detect_recordings",
     "lf_mkd_verify_homography", "lf_mkd_verify_homography_device",
+    "lf_mkd_verify_fundamental", "lf_mkd_verify_fundamental_device",
 )
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
@@ -119,6 +120,8 @@ def load_library():
     L.lf_mkd_match_overflowed.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
+    L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
+    L.lf_mkd_verify_fundamental_device.argtypes = L.lf_mkd_verify_homography_device.argtypes
     L.lf_mkd_stream_create.argtypes = [vp, u32, u32, u32, ctypes.c_float, u64, vp, vp, vp, vp]
     L.lf_mkd_stream_frame.argtypes = [vp, vp]
     L.lf_mkd_orient_keypoints_blocked.argtypes = [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64, pu64, pu64]
@@ -363,6 +366,21 @@ class MkdHandle:
                                                      st.ctypes.data), "lf_mkd_verify_homography")
         return H.reshape(3, 3), ver[:len(a)].copy(), st
 
+    def verify_fundamental(self, kps_a, kps_b, match, n_hypotheses=2048, threshold=1.5, seed=0, flags=0):
+        """lf_mkd_verify_fundamental: as verify_homography -> (F [3,3] f32, verified int32 [na], stats uint32 [4])."""
+        a = np.ascontiguousarray(kps_a, np.float32).reshape(-1, 5)
+        b = np.ascontiguousarray(kps_b, np.float32).reshape(-1, 5)
+        m = np.ascontiguousarray(match, np.int32).reshape(-1)
+        if len(m) != len(a):
+            raise RuntimeError("verify_fundamental: match must have one entry per row of kps_a")
+        F = np.empty(9, np.float32)
+        ver = np.empty(max(len(a), 1), np.int32)
+        st = np.empty(4, np.uint32)
+        self._check(self.L.lf_mkd_verify_fundamental(self._h, a.ctypes.data, len(a), b.ctypes.data, len(b), m.ctypes.data,
+                                                      n_hypotheses, threshold, seed, flags, F.ctypes.data, ver.ctypes.data,
+                                                      st.ctypes.data), "lf_mkd_verify_fundamental")
+        return F.reshape(3, 3), ver[:len(a)].copy(), st
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -485,6 +503,13 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_verify_homography_device(
             self._h, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, n_hypotheses, threshold, seed, flags, d_H,
             d_verified, d_stats, s), "lf_mkd_verify_homography_device")
+
+    def verify_fundamental_device(self, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, d_F, d_verified, d_stats,
+                                  n_hypotheses=2048, threshold=1.5, seed=0, flags=0, stream=None):
+        """lf_mkd_verify_fundamental_device: n_pairs problems in one call (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_verify_fundamental_device(
+            self._h, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, n_hypotheses, threshold, seed, flags, d_F,
+            d_verified, d_stats, s), "lf_mkd_verify_fundamental_device")
 
     def match_overflowed(self, stream=None):
         """Rows of the latest match call that were redone by the full scan (diagnostic; waits for the call)."""
