@@ -155,6 +155,11 @@ extern "C" {
                                d_best: *mut f32, d_second: *mut f32, stream: *mut c_void) -> c_int;
     pub fn lf_mkd_match_both_device(h: *mut lf_mkd, d_a: *const f32, na: u64, d_b: *const f32, nb: u64, ratio: f32,
                                     d_match_ab: *mut i32, d_match_ba: *mut i32, stream: *mut c_void) -> c_int;
+    // n_pairs match problems in one launch, in the batched verifiers' layout (offsets on the device); flags: LF_MKD_MATCH_MUTUAL
+    pub fn lf_mkd_match_pairs_device(h: *mut lf_mkd, d_a: *const f32, d_offsets_a: *const u64, na_total: u64,
+                                     d_b: *const f32, d_offsets_b: *const u64, nb_total: u64, n_pairs: u32, ratio: f32,
+                                     flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut f32,
+                                     d_second: *mut f32, stream: *mut c_void) -> c_int;
     pub fn lf_mkd_match(h: *mut lf_mkd, a: *const f32, na: u64, b: *const f32, nb: u64, ratio: f32,
                         matches: *mut i32) -> c_int;
     pub fn lf_mkd_match_overflowed(h: *mut lf_mkd, stream: *mut c_void, n_rows: *mut u64) -> c_int;

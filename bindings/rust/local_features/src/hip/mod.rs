@@ -71,6 +71,10 @@ const _: () = assert!(std::mem::align_of::<Keypoint>() == std::mem::align_of::<f
 /// candidate as is, no least-squares refit.
 pub const VERIFY_NO_REFINE: u32 = 1;
 
+/// `flags` of `lf_mkd_match_pairs_device` (`include/lf_mkd.h`, `LF_MKD_MATCH_MUTUAL`): both directions are matched and a
+/// match is kept only if the other direction agrees.
+pub const MATCH_MUTUAL: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,

@@ -353,6 +353,40 @@ int lf_mkd_match_device(lf_mkd *h, const float *d_a, uint64_t na, const float *d
  * na == 0; otherwise na, nb >= 2.  lf_mkd_match_overflowed afterwards reports the rows redone over BOTH directions. */
 int lf_mkd_match_both_device(lf_mkd *h, const float *d_a, uint64_t na, const float *d_b, uint64_t nb, float ratio,
                              int32_t *d_match_ab, int32_t *d_match_ba, void *stream);
+/* Many image pairs in one call: n_pairs independent match_features problems (examples/match_images/src/main.rs:8-27) in the
+ * layout of the batched verifiers below, so that the outputs go into lf_mkd_verify_homography_device /
+ * lf_mkd_verify_fundamental_device unchanged.
+ *   Pair p is a rows [offsets_a[p], offsets_a[p+1]) against b rows [offsets_b[p], offsets_b[p+1]).  Both offset arrays hold
+ *   n_pairs + 1 uint64 entries, live on the device and are non-decreasing.  na_total / nb_total are the numbers of
+ *   addressable rows of d_a / d_b (each at most 2^31 - 1): the host sizes the grid from them, never reads the offsets and
+ *   never waits.  Rows outside [offsets[0], offsets[n_pairs]) are neither read nor written; whatever the offsets hold, no row
+ *   at or beyond a total is touched (an offset beyond the total is read as the total; an inverted pair is an empty one).
+ * Outputs: d_match_ab [na_total]: for row i of pair p the index LOCAL to the pair's b rows, or -1.  d_match_ba [nb_total]
+ * (may be NULL unless LF_MKD_MATCH_MUTUAL): the other direction, indices local to the pair's a rows.  d_best / d_second
+ * [na_total] (may be NULL): the two similarities of the a -> b direction.
+ * Per pair: with nb_p >= 2 (and na_p >= 2 for the reverse direction) every output of pair p equals, bit for bit,
+ * lf_mkd_match_device on that pair's rows in its one-launch ("small") form -- the same three terms in the same order, best *
+ * ratio > second (main.rs:22), ties to the highest index, ratio <= 0: no test.  A side the single-pair call refuses (nb_p < 2,
+ * or na_p < 2 for the reverse direction; main.rs:20) yields -1 for every row of that direction and -inf in best / second,
+ * whatever the ratio: a batch survives an empty frame.  The result of a pair depends neither on n_pairs, nor on the other
+ * pairs, nor on the run.
+ * flags: LF_MKD_MATCH_MUTUAL -- both directions are decided with the ratio test; then match_ab[i] = j survives iff
+ * match_ba[j] == i, and match_ba[j] = i survives iff match_ab[i] == j (both evaluated on the unfiltered arrays); everything
+ * else becomes -1.  d_best / d_second are not filtered.
+ * Sizes: any pair size is correct, but every workgroup (16 a rows) converts its pair's whole b side, as the small form does:
+ * the call is meant for pairs of up to about 4096 rows per side.  One large pair belongs to lf_mkd_match_device, which picks
+ * the scan or screen form for it.
+ * One launch (three with LF_MKD_MATCH_MUTUAL), no scratch and no allocation, asynchronous on `stream` (NULL: the handle's
+ * own): capturable in a hipGraph.  n_pairs == 0 is LF_MKD_OK and writes nothing.  LF_MKD_ERR_BAD_ARG, reported before any
+ * device is touched (the message starts with "match_pairs_device" and is reachable through lf_mkd_last_error(NULL) when h is
+ * NULL): a null handle; null d_a, d_b, offsets or d_match_ab; LF_MKD_MATCH_MUTUAL without d_match_ba; unknown flag bits; d_a
+ * or d_b not 16-byte aligned; a total above 2^31 - 1; floor(na_total / 16) + n_pairs (plus the same over b when d_match_ba
+ * is given) above 2^31 - 1 workgroups.  lf_mkd_match_overflowed afterwards reports 0: this form redoes nothing.
+ * (LF_MKD_MATCH_MUTUAL is defined with the verifiers' flag, below their prototypes.) */
+int lf_mkd_match_pairs_device(lf_mkd *h, const float *d_a, const uint64_t *d_offsets_a, uint64_t na_total,
+                              const float *d_b, const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs,
+                              float ratio, uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba, float *d_best,
+                              float *d_second, void *stream);
 /* Host pointers, synchronous. */
 int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_t nb, float ratio,
                  int32_t *match);
@@ -483,6 +517,7 @@ int lf_mkd_verify_fundamental_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, 
                                      float *d_F, int32_t *d_verified, uint32_t *d_stats, void *stream);
 
 #define LF_MKD_VERIFY_NO_REFINE 1u   /* report the best RANSAC candidate as is: no least-squares refit (both verifiers) */
+#define LF_MKD_MATCH_MUTUAL 1u       /* lf_mkd_match_pairs_device: keep a match only if the other direction agrees */
 
 /* ---- multi-GPU: the path's ONE collective (BASELINE configs[3]) -------------------------------------------------
  * Keypoint batches shard by image, one process and one handle per GPU, and nothing is exchanged while describing.  The

@@ -1739,6 +1739,35 @@ int lf_mkd_match_both_device(lf_mkd *h, const float *d_a, uint64_t na, const flo
     return match_device_impl(h, d_b, nb, d_a, na, nullptr, nullptr, ratio, d_match_ba, nullptr, nullptr, s, true);
 }
 
+// Many pairs in one call.  Like the verifiers it feeds, it checks its arguments before the handle, so that every bad
+// argument is reported without a device: the message goes to the handle, or to lf_mkd_last_error(NULL) when there is none.
+int lf_mkd_match_pairs_device(lf_mkd *h, const float *d_a, const uint64_t *d_offsets_a, uint64_t na_total, const float *d_b,
+                              const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs, float ratio, uint32_t flags,
+                              int32_t *d_match_ab, int32_t *d_match_ba, float *d_best, float *d_second, void *stream) {
+    const bool mutual = flags & LF_MKD_MATCH_MUTUAL;
+    const char *msg = nullptr;
+    if (!d_a || !d_b || !d_offsets_a || !d_offsets_b || !d_match_ab) msg = "null pointer";
+    else if (flags & ~LF_MKD_MATCH_MUTUAL) msg = "unknown flag bits";
+    else if (mutual && !d_match_ba) msg = "LF_MKD_MATCH_MUTUAL needs d_match_ba";
+    else if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 15) msg = "d_a and d_b must be 16-byte aligned";
+    else if (na_total > 0x7FFFFFFFull || nb_total > 0x7FFFFFFFull) msg = "more than 2^31 - 1 rows on a side";
+    else if (match_pairs_slots(na_total, n_pairs) + (d_match_ba ? match_pairs_slots(nb_total, n_pairs) : 0) > 0x7FFFFFFFull)
+        msg = "too many rows and pairs for one call (the grid needs floor(rows / 16) + n_pairs workgroups per direction, "
+              "at most 2^31 - 1 in all)";
+    else if (!h) msg = "null handle";
+    if (msg) {
+        (h ? h->err : g_create_error) = std::string("match_pairs_device: ") + msg;
+        return LF_MKD_ERR_BAD_ARG;
+    }
+    if (n_pairs == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    launch_match_small_pairs(d_a, d_offsets_a, na_total, d_b, d_offsets_b, nb_total, n_pairs, ratio, mutual, d_match_ab,
+                             d_match_ba, d_best, d_second, h->d_match_misc ? h->d_match_misc + 2 : nullptr, s);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows) {
     if (!h) return LF_MKD_ERR_BAD_ARG;
     if (!n_rows) return fail(h, LF_MKD_ERR_BAD_ARG, "match_overflowed: null pointer");

@@ -153,6 +153,14 @@ void launch_match_small(const float *a, long na, const float *b, long nb, const 
 // both directions (a's rows against b, b's rows against a) in one launch; both must fit match_small_fits
 void launch_match_small_both(const float *a, long na, const float *b, long nb, float ratio, int *match_ab, int *match_ba,
                              unsigned *overflowed_word, hipStream_t stream);
+// n_pairs problems in one launch (lf_mkd_match_pairs_device): pair p = a rows [off_a[p], off_a[p+1]) against b rows
+// [off_b[p], off_b[p+1]), offsets on the device and never read by the host; each pair decided by match_small's body.
+// match_ba (nullable): the other direction from the same launch; mutual: two more element-wise launches keep only the
+// matches both directions agree on.  match_pairs_slots: workgroups one direction over n_total rows takes.
+uint64_t match_pairs_slots(uint64_t n_total, unsigned n_pairs);
+void launch_match_small_pairs(const float *a, const uint64_t *off_a, uint64_t na_total, const float *b, const uint64_t *off_b,
+                              uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab, int *match_ba,
+                              float *best, float *second, unsigned *overflowed_word, hipStream_t stream);
 // the same scan over the overflowed rows alone (few_words: their indices first, written by launch_match_verify)
 size_t match_few_tiles_bytes();
 size_t match_few_words();

@@ -450,6 +450,100 @@ __global__ __launch_bounds__(64 * kSmallWaves) void match_small_both(const float
         match_small_block(b, nb, a, na, nullptr, nullptr, ratio, match_ba, nullptr, nullptr, (long)blockIdx.x - blocks_ab);
 }
 
+// ---- many pairs in ONE launch ----------------------------------------------------------------------------------------
+// lf_mkd_match_pairs_device: pair p is rows [off_a[p], off_a[p + 1]) of a against rows [off_b[p], off_b[p + 1]) of b, the
+// layout of the batched verifiers.  The host never reads the offsets, so the grid is sized from the totals alone and every
+// workgroup finds its own pair: pair p owns the slots from floor(off[p] / 16) + p on.  That start is strictly increasing in p
+// (the offsets are non-decreasing), and the next pair's start is at least ceil(n_p / 16) further on, because
+// ceil(n / 16) <= floor((o + n) / 16) - floor(o / 16) + 1; the last pair ends at or before floor(n_total / 16) + n_pairs, the
+// grid of one direction.  No prefix launch, no scratch; at most one idle slot per pair and sixteenth of a row.
+// An offset beyond the total is read as the total and an inverted pair as empty: whatever the offsets hold, no row at or
+// beyond a total is touched.
+
+// the first row and the number of rows of a pair whose two offsets are first and next
+__device__ __forceinline__ void pair_rows(uint64_t first, uint64_t next, uint64_t total, long &lo, long &n) {
+    const uint64_t o0 = first < total ? first : total, o1 = next < total ? next : total;
+    lo = (long)o0;
+    n = o1 > o0 ? (long)(o1 - o0) : 0;
+}
+
+// the largest p of [0, n_pairs) with key(p) <= v, for a strictly or weakly increasing key; n_pairs > 0 (the caller checks
+// key(p) <= v itself: v may lie in front of pair 0)
+template <typename Key>
+__device__ __forceinline__ unsigned last_pair_at_or_before(unsigned n_pairs, uint64_t v, Key key) {
+    unsigned lo = 0, hi = n_pairs;
+    while (hi - lo > 1) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if (key(mid) <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// One direction (slots_ab workgroups, match_ba == nullptr) or both (the slots of b's rows follow): the body is
+// match_small_block, given the pair's rows as its whole problem, so every output of a pair is what match_small writes for
+// that pair alone -- bit for bit.  best / second belong to the a -> b direction.  A side the single-pair call refuses (fewer
+// than two candidates) gives -1 and -inf.  The search is the same for a whole workgroup: scalar loads, no divergence.
+__global__ __launch_bounds__(64 * kSmallWaves) void match_small_pairs(const float *__restrict__ a,
+                                                                      const uint64_t *__restrict__ off_a, uint64_t na_total,
+                                                                      const float *__restrict__ b,
+                                                                      const uint64_t *__restrict__ off_b, uint64_t nb_total,
+                                                                      unsigned n_pairs, unsigned slots_ab, float ratio,
+                                                                      int *__restrict__ match_ab, int *__restrict__ match_ba,
+                                                                      float *__restrict__ best_out,
+                                                                      float *__restrict__ second_out,
+                                                                      unsigned *__restrict__ overflowed_word) {
+    if (overflowed_word && blockIdx.x == 0 && threadIdx.x == 0) *overflowed_word = 0u;   // this form redoes nothing
+    const bool rev = blockIdx.x >= slots_ab;
+    const uint64_t slot = rev ? blockIdx.x - slots_ab : blockIdx.x;
+    const uint64_t *off_x = rev ? off_b : off_a, *off_y = rev ? off_a : off_b;
+    const uint64_t x_total = rev ? nb_total : na_total, y_total = rev ? na_total : nb_total;
+    auto start = [&](unsigned p) { return (off_x[p] < x_total ? off_x[p] : x_total) / 16 + p; };
+    const unsigned p = last_pair_at_or_before(n_pairs, slot, start);
+    // the pair's four offsets are requested together, in front of the tests that may end the workgroup: one round trip to
+    // memory between the search and the body's first rows, not three (left alone, the compiler sinks each load behind the
+    // branch in front of its first use)
+    uint64_t x0 = off_x[p], x1 = off_x[p + 1], y0 = off_y[p], y1 = off_y[p + 1];
+    asm volatile("" : "+s"(x0), "+s"(x1), "+s"(y0), "+s"(y1));
+    long x_lo, nx, y_lo, ny;
+    pair_rows(x0, x1, x_total, x_lo, nx);
+    pair_rows(y0, y1, y_total, y_lo, ny);
+    const long block = (long)slot - (x_lo / 16 + (long)p);   // slot - start(p)
+    if (block < 0) return;                             // rows in front of the first pair
+    if (block * 16 >= nx) return;                      // the pair's idle slot(s)
+    int *match = (rev ? match_ba : match_ab) + x_lo;
+    float *best = rev || !best_out ? nullptr : best_out + x_lo, *second = rev || !second_out ? nullptr : second_out + x_lo;
+    if (ny < 2) {
+        const long row = block * 16 + threadIdx.x;
+        if (threadIdx.x < 16 && row < nx) {
+            match[row] = -1;
+            if (best) best[row] = -INFINITY;
+            if (second) second[row] = -INFINITY;
+        }
+        return;
+    }
+    match_small_block((rev ? b : a) + x_lo * 128, nx, (rev ? a : b) + y_lo * 128, ny, nullptr, nullptr, ratio, match, best,
+                      second, block);
+}
+
+// LF_MKD_MATCH_MUTUAL, one of its two element-wise launches: x[i] = j (local to the pair's y rows) survives iff y[j] == i
+// (local to the pair's x rows).  First ab against the untouched ba, then ba against the filtered ab: ab_filtered[i] == j iff
+// ab[i] == j and ba[j] == i, so the second launch applies the same rule to the unfiltered arrays.
+__global__ __launch_bounds__(256) void match_mutual_filter(int *__restrict__ x, const uint64_t *__restrict__ off_x,
+                                                           uint64_t x_total, const int *__restrict__ y,
+                                                           const uint64_t *__restrict__ off_y, uint64_t y_total,
+                                                           unsigned n_pairs) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= x_total) return;
+    const unsigned p = last_pair_at_or_before(n_pairs, i, [&](unsigned q) { return off_x[q]; });
+    long x_lo, nx, y_lo, ny;
+    pair_rows(off_x[p], off_x[p + 1], x_total, x_lo, nx);
+    pair_rows(off_y[p], off_y[p + 1], y_total, y_lo, ny);
+    if ((long)i < x_lo || (long)i >= x_lo + nx) return;   // outside every pair
+    const int j = x[i];
+    if (j < 0) return;
+    if (j >= ny || y[y_lo + j] != (int)((long)i - x_lo)) x[i] = -1;
+}
+
 // ---- two-pass form ----------------------------------------------------------------------------------------------
 // Screen: s~ = <hi(a), hi(b)> on the matrix cores.  With a = hi(a) + da, |da_k| <= 2^-11 |a_k| (f16 round to nearest;
 // below 2^-14 the f16 grid is 2^-24 wide, the MFMA does not flush) and the same for b,
@@ -861,6 +955,25 @@ void launch_match_small_both(const float *a, long na, const float *b, long nb, f
     if (na <= 0 || nb <= 0) return;
     hipLaunchKernelGGL(match_small_both, dim3((unsigned)((na + 15) / 16 + (nb + 15) / 16)), dim3(64 * kSmallWaves), 0, stream, a,
                        na, b, nb, ratio, match_ab, match_ba, overflowed_word);
+}
+
+uint64_t match_pairs_slots(uint64_t n_total, unsigned n_pairs) { return n_total / 16 + n_pairs; }
+
+void launch_match_small_pairs(const float *a, const uint64_t *off_a, uint64_t na_total, const float *b, const uint64_t *off_b,
+                              uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab, int *match_ba,
+                              float *best, float *second, unsigned *overflowed_word, hipStream_t stream) {
+    if (n_pairs == 0) return;
+    const uint64_t slots_ab = match_pairs_slots(na_total, n_pairs);
+    const uint64_t slots = slots_ab + (match_ba ? match_pairs_slots(nb_total, n_pairs) : 0);
+    hipLaunchKernelGGL(match_small_pairs, dim3((unsigned)slots), dim3(64 * kSmallWaves), 0, stream, a, off_a, na_total, b,
+                       off_b, nb_total, n_pairs, (unsigned)slots_ab, ratio, match_ab, match_ba, best, second, overflowed_word);
+    if (!mutual) return;
+    if (na_total)
+        hipLaunchKernelGGL(match_mutual_filter, dim3((unsigned)((na_total + 255) / 256)), dim3(256), 0, stream, match_ab, off_a,
+                           na_total, (const int *)match_ba, off_b, nb_total, n_pairs);
+    if (nb_total)
+        hipLaunchKernelGGL(match_mutual_filter, dim3((unsigned)((nb_total + 255) / 256)), dim3(256), 0, stream, match_ba, off_b,
+                           nb_total, (const int *)match_ab, off_a, na_total, n_pairs);
 }
 
 size_t match_few_tiles_bytes() { return match_tiles_bytes(kOverRows); }

@@ -14,13 +14,13 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, VERIFY_NO_REFINE, Comm,
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
                    MkdHandle, comm_unique_id, load_library, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
-           "VERIFY_NO_REFINE"]
+           "VERIFY_NO_REFINE", "MATCH_MUTUAL"]
 
 
 class Keypoint:
@@ -139,6 +139,45 @@ class LocalFeatures:
             self._inner.synchronize()       # (torch's default stream is handle 0 = "the library's own stream" to the ABI)
             m_ab, m_ba = m_ab.cpu().numpy(), m_ba.cpu().numpy()
         return ([(int(i), int(j)) for i, j in enumerate(m_ab) if j >= 0], [(int(i), int(j)) for i, j in enumerate(m_ba) if j >= 0])
+
+    def match_batch(self, desc_a, offsets_a, desc_b, offsets_b, ratio=0.8, mutual=False, both=False, stream=None):
+        """Many image pairs in one call (lf_mkd_match_pairs_device: one launch, three with `mutual`) on torch tensors, which
+        are moved to the handle's device if they are elsewhere.  desc_a [Na,128] / desc_b [Nb,128] (any float dtype),
+        offsets_a / offsets_b [n_pairs + 1] (any integer dtype, non-decreasing): pair p matches a rows
+        offsets_a[p]..offsets_a[p+1] against b rows offsets_b[p]..offsets_b[p+1], each pair exactly as `match` decides it alone.
+        Two layouts:
+          * the verifiers' own -- the pairs' rows back to back on either side, offsets = the running sums of the pairs' sizes;
+            the result goes into verify_homography_batch / verify_fundamental_batch with the same offsets;
+          * a sequence without a copied row -- one array `desc` of F frames with frame offsets o [F + 1]: desc_a = desc with
+            offsets_a = o[0:F], desc_b = desc[o[1]:] (a view) with offsets_b = o[1:F+1] - o[1]; pair t is then frame t against
+            frame t + 1.  (desc_b = desc itself with offsets_b = o[1:F+1] says the same without reading o[1] on the host.)
+        Returns device tensors (match_ab [Na] int32, match_ba [Nb] int32 or None, best [Na], second [Na]): match_ab[i] is
+        the index local to the pair's b rows or -1, match_ba (with `both` or `mutual`) the other direction, local to the
+        pair's a rows; rows outside every pair hold -1 / -inf.  `mutual` keeps a match only if both directions agree (best /
+        second stay as the a -> b direction found them).  Enqueued on `stream` (default: torch's current stream on the
+        handle's device), asynchronously."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError("match_batch: offsets_a and offsets_b need n_pairs + 1 entries each")
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):      # the copies and the fills below are ordered with the call
+            a = desc_a.to(dev, torch.float32).reshape(-1, 128).contiguous()
+            b = desc_b.to(dev, torch.float32).reshape(-1, 128).contiguous()
+            oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+            na, nb = a.shape[0], b.shape[0]
+            m_ab = torch.full((na,), -1, dtype=torch.int32, device=dev)
+            m_ba = torch.full((nb,), -1, dtype=torch.int32, device=dev) if (both or mutual) else None
+            best = torch.full((na,), float("-inf"), dtype=torch.float32, device=dev)
+            second = torch.full((na,), float("-inf"), dtype=torch.float32, device=dev)
+            if n_pairs and na and nb:       # (an empty side: every pair is refused, the fills above are the answer)
+                with self._lock:
+                    self._inner.match_pairs_device(a.data_ptr(), oa.data_ptr(), na, b.data_ptr(), ob.data_ptr(), nb, n_pairs,
+                                                   m_ab.data_ptr(), m_ba.data_ptr() if m_ba is not None else None, ratio,
+                                                   MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
+                                                   s.cuda_stream)
+        return m_ab, m_ba, best, second
 
     def match_ip_distance(self, desc_a, desc_b, factor=0.75):
         """The webcam example's acceptance rule (examples/webcam/src/main.rs:97-104,261-265): nearest and second-nearest
