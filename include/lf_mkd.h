@@ -68,10 +68,11 @@ typedef enum { LF_MKD_ANGLE_SHADER = 0, LF_MKD_ANGLE_EXACT = 1, LF_MKD_ANGLE_EXA
  *           rate at ~117 M descriptors/s (2.1x slower).
  * F16_FP6 : an experiment kept as a mode (round 4, NOTEBOOK.md section 11): hi*hi in f16 as above, the two cross terms of the
  *           harmonics' streams in ONE block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 per accumulator tile with e2m3
- *           operands (51 instead of 81 matrix instructions per wave-row).  e2m3 carries three bits below its block's
+ *           operands (51 instead of the 81 matrix instructions per wave-row of the unfolded three-term form it was built on and
+ *           keeps; the default has since folded its rows to 63 and is the faster of the two).  e2m3 carries three bits below its block's
  *           maximum: descriptors within 3e-5 of the oracle (measured worst 2.95e-5, mean 2.0e-5, over the goldens and 4099
  *           patches x 3 angle modes x both kernel forms; F16X3: 4.2e-6 / 3.1e-6 -- seven times the error, inside the gate; the
- *           -m gpu test holds it below 4e-5) for +2 % of speed -- NOT the default, not used for any reported parity figure.  Patch mode only: keypoint
+ *           -m gpu test holds it below 4e-5) for +2 % of speed over the unfolded F16X3 of its time -- NOT the default, not used for any reported parity figure.  Patch mode only: keypoint
  *           entry points take the two-launch form in this mode. */
 typedef enum { LF_MKD_POOL_DEFAULT = 0, LF_MKD_POOL_F16X3 = 1, LF_MKD_POOL_F32 = 2, LF_MKD_POOL_F16_FP6 = 3 } lf_mkd_pool_mode;
 

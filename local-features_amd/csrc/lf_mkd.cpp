@@ -159,9 +159,9 @@ struct lf_mkd {
     hipStream_t side_stream = nullptr;   // lf_mkd_detect / the recorded pipeline: pyramid levels >= 1 are built here beside the detector
     std::vector<hipEvent_t> side_events;
     struct {                             // the model's constants, uploaded at creation ...
-        HipArray<short> colmap;
+        HipArray<short> colmap, colmap_unfolded;
         HipArray<float> pool_b_f32, white_a_f32, white_bias;
-        HipArray<uint16_t> pool_b_f16, pool_b_fp6, white_a_f16;
+        HipArray<uint16_t> pool_b_f16, pool_b_fp6, white_a_f16, white_a_f16_unfolded;
     } consts;
     DeviceConsts dc;                     // ... as the launchers take them
     uint64_t batch = 0;                  // descriptors per internal batch (multiple of 64)
@@ -370,11 +370,16 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
     LF_CREATE_HIP(upload(c.colmap, hc.colmap));
     LF_CREATE_HIP(upload(c.pool_b_f32, hc.pool_b_f32));
     LF_CREATE_HIP(upload(c.pool_b_f16, hc.pool_b_f16));
-    if (h->params.pool_mode == LF_MKD_POOL_F16_FP6) LF_CREATE_HIP(upload(c.pool_b_fp6, hc.pool_b_fp6));
+    if (h->params.pool_mode == LF_MKD_POOL_F16_FP6) {   // the unfolded row form's own tables
+        LF_CREATE_HIP(upload(c.pool_b_fp6, hc.pool_b_fp6));
+        LF_CREATE_HIP(upload(c.colmap_unfolded, hc.colmap_unfolded));
+        LF_CREATE_HIP(upload(c.white_a_f16_unfolded, hc.white_a_f16_unfolded));
+    }
     LF_CREATE_HIP(upload(c.white_a_f16, hc.white_a_f16));
     LF_CREATE_HIP(upload(c.white_a_f32, hc.white_a_f32));
     LF_CREATE_HIP(upload(c.white_bias, hc.white_bias));
-    h->dc = DeviceConsts{c.colmap, c.pool_b_f32, c.pool_b_f16, c.pool_b_fp6, c.white_a_f16, c.white_a_f32, c.white_bias};
+    h->dc = DeviceConsts{c.colmap, c.pool_b_f32, c.pool_b_f16, c.white_a_f16, c.white_a_f32, c.colmap_unfolded, c.pool_b_fp6,
+                         c.white_a_f16_unfolded, c.white_bias};
     // (the staging buffers of the host-pointer and keypoint entry points -- 4.6 KiB per descriptor of the internal batch --
     // are allocated on first use: a caller of the device-pointer patch API never needs them)
     LF_CREATE_HIP(h->d_totals.allocate(8));
@@ -766,6 +771,25 @@ int lf_mkd_build_constants(const float *mean, const float *eigvals, const float 
     if (embedding_cartesian)
         std::memcpy(embedding_cartesian, hc.embedding_cartesian.data(), hc.embedding_cartesian.size() * 4);
     if (w_t) std::memcpy(w_t, hc.w_t.data(), hc.w_t.size() * 4);
+    return LF_MKD_OK;
+}
+
+// Test-only tap (not part of include/lf_mkd.h): the folded pooling tables as the handle would upload them.
+//   pool_b_f32 [32][12][2][64][4], colmap [336], parity_defect [1]; any of them may be null
+int lfmkd_test_pool_tables(const float *mean, const float *eigvals, const float *eigvecs, float *pool_b_f32, int16_t *colmap, float *parity_defect) {
+    if (!mean || !eigvals || !eigvecs) return LF_MKD_ERR_BAD_ARG;
+    PcaModel pca;
+    pca.mean.assign(mean, mean + kRaw);
+    pca.eigvals.assign(eigvals, eigvals + kRaw);
+    pca.eigvecs.assign(eigvecs, eigvecs + size_t(kRaw) * kRaw);
+    HostConsts hc;
+    if (const std::string e = build_host_consts(pca, hc); !e.empty()) {
+        g_create_error = e;
+        return LF_MKD_ERR_BAD_ARG;
+    }
+    if (pool_b_f32) std::memcpy(pool_b_f32, hc.pool_b_f32.data(), hc.pool_b_f32.size() * 4);
+    if (colmap) std::memcpy(colmap, hc.colmap.data(), hc.colmap.size() * 2);
+    if (parity_defect) *parity_defect = hc.lut_parity_defect;
     return LF_MKD_OK;
 }
 

@@ -64,7 +64,7 @@ uint32_t e2m3_bits(float v) {
     return uint32_t(best) | (v < 0.f ? 32u : 0u);
 }
 
-// One column of a LUT tile: which spatial kernel, rotated by which harmonic of phi.
+// One column of the LUT: which spatial kernel, rotated by which harmonic of phi.
 struct LutColumn {
     bool used;
     bool polar;     // EP or EC
@@ -73,7 +73,8 @@ struct LutColumn {
     int rot;        // 0: as is, 1: times cos(k phi), 2: times sin(k phi)
 };
 
-LutColumn lut_column(int ut, int c) {
+// ---- the unfolded row form (LF_MKD_POOL_F16_FP6 alone): 15 LUT tiles over a row's 32 pixels ----
+LutColumn unfolded_lut_column(int ut, int c) {
     LutColumn z{false, false, 0, 0, 0};
     if (ut == 0) return {true, true, c, 0, 0};                                        // m: EP 0..15
     if (ut == 1) return c < 9 ? LutColumn{true, true, 16 + c, 0, 0} : LutColumn{true, false, c - 9, 0, 0};   // EP 16..24 | EC 0..6
@@ -89,7 +90,7 @@ LutColumn lut_column(int ut, int c) {
 // Packed output column (tile after the epilogue's combine step, slot) -> descriptor index, or -1.
 // Descriptor order (shaders/common.glsl:114-139): polar block [in-dim i][kernel j] (175), then cartesian [i][j] (63);
 // in-dims: 0 = m, k = cos k, k + 3 = sin k.
-int packed_desc(int tile, int c) {
+int unfolded_packed_desc(int tile, int c) {
     const int cart0 = kDimsIn * kPolar;
     if (tile == 0) return c;
     if (tile == 1) return c < 9 ? 16 + c : cart0 + (c - 9);
@@ -104,6 +105,87 @@ int packed_desc(int tile, int c) {
         case 4: return (c == 9 || c == 10) ? cart0 + ic * kCart + 7 + (c - 9) : -1;
         default: return (c == 9 || c == 10) ? cart0 + is * kCart + 7 + (c - 9) : -1;
     }
+}
+
+// ---- the folded row form (LF_MKD_POOL_F16X3, LF_MKD_POOL_F32; mkd_consts.hpp) ----
+// One column of a folded LUT tile: what its two K halves hold and which descriptor entries its products are.
+struct FoldColumn {
+    LutColumn first{false, false, 0, 0, 0}, second{false, false, 0, 0, 0};   // (.used == false: zeros)
+    int sign_second = 1;              // the second half is stored times this
+    int desc_u = -1, desc_v = -1;     // entry under the operand M or U / under V
+    int sign_v = 1;                   // the V product is sign_v x its entry
+};
+struct FoldLayout {
+    FoldColumn col[kUniqueTiles][kTileCols];
+};
+
+// parity(col) = +1 / -1: the column is even / odd under x -> 31 - x.  Returns "" or why the layout does not fit.
+template <class Parity>
+std::string build_fold_layout(Parity parity, FoldLayout &fl) {
+    const int cart0 = kDimsIn * kPolar;
+    auto place_cart = [&](int ut0, int k, int dc, int ds) -> std::string {   // even EC -> tile 1 slots 10.., odd EC -> tile 2
+        int n_even = 0, n_odd = 0;
+        for (int i = 0; i < kCart; ++i) {
+            const LutColumn ec{true, false, i, k, 0};
+            FoldColumn fc;
+            if (parity(ec) > 0) {
+                if (kPolarSlots + n_even >= kTileCols) return "internal: too many even cartesian kernels for a mixed tile";
+                fc.first = ec;
+                fc.desc_u = cart0 + dc * kCart + i;
+                if (k) fc.desc_v = cart0 + ds * kCart + i;
+                fl.col[ut0 + 1][kPolarSlots + n_even++] = fc;
+            } else {
+                if (n_odd >= kTileCols) return "internal: too many odd cartesian kernels for a tile";
+                fc.second = ec;
+                fc.desc_u = cart0 + (k ? ds : dc) * kCart + i;   // U's second half is sin_o, M's is m_o
+                if (k) { fc.desc_v = cart0 + dc * kCart + i; fc.sign_v = -1; }   // V's is -cos_o
+                fl.col[ut0 + 2][n_odd++] = fc;
+            }
+        }
+        return "";
+    };
+    // m stream: EP 0-15 | EP 16-24 and even EC | odd EC
+    for (int j = 0; j < kPolar; ++j) {
+        const LutColumn ep{true, true, j, 0, 0};
+        FoldColumn fc;
+        (parity(ep) > 0 ? fc.first : fc.second) = ep;
+        fc.desc_u = j;
+        if (j >= kTileCols + kPolarSlots) return "internal: the m stream's polar kernels do not fit two tiles";
+        fl.col[j / kTileCols][j % kTileCols] = fc;
+    }
+    if (const std::string e = place_cart(0, 0, 0, 0); !e.empty()) return e;
+    for (int k = 1; k <= 3; ++k) {
+        const int ut0 = 3 + 3 * (k - 1), ic = k, is = k + 3;
+        FoldColumn cls[2][kPolar];   // [0]: EPc even, [1]: EPc odd
+        int n[2] = {0, 0};
+        for (int j = 0; j < kPolar; ++j) {
+            const LutColumn pc{true, true, j, k, 1}, ps{true, true, j, k, 2};
+            if (parity(pc) == parity(ps)) return "internal: EP cos and EP sin columns of equal parity";
+            FoldColumn fc;
+            if (parity(pc) > 0) {
+                fc.first = pc; fc.second = ps; fc.sign_second = -1;
+                fc.desc_u = ic * kPolar + j; fc.desc_v = is * kPolar + j;
+            } else {
+                fc.first = ps; fc.second = pc;
+                fc.desc_u = is * kPolar + j; fc.desc_v = ic * kPolar + j; fc.sign_v = -1;
+            }
+            cls[parity(pc) > 0 ? 0 : 1][n[parity(pc) > 0 ? 0 : 1]++] = fc;
+        }
+        const int big = n[0] >= n[1] ? 0 : 1;
+        if (n[big] > kTileCols || n[big ^ 1] > kPolarSlots) return "internal: the polar parity classes do not fit their tiles";
+        for (int i = 0; i < n[big]; ++i) fl.col[ut0][i] = cls[big][i];
+        for (int i = 0; i < n[big ^ 1]; ++i) fl.col[ut0 + 1][i] = cls[big ^ 1][i];
+        if (const std::string e = place_cart(ut0, k, ic, is); !e.empty()) return e;
+    }
+    return "";
+}
+
+// accumulator tile -> (LUT tile, 0: operand M / U, 1: operand V)
+void acc_tile_source(int t, int &ut, int &v) {
+    if (t < 3) { ut = t; v = 0; return; }
+    const int h = (t - 3) / 6, r = (t - 3) % 6;
+    ut = 3 + 3 * h + r / 2;
+    v = r & 1;
 }
 
 }  // namespace
@@ -198,37 +280,70 @@ std::string build_host_consts(const PcaModel &pca, HostConsts &hc) {
     }
 
     // ---- device layouts ----
-    hc.colmap.assign(kPackedCols, -1);
-    {
-        std::vector<int> seen(kRaw, 0);
-        for (int t = 0; t < kTiles; ++t)
-            for (int c = 0; c < kTileCols; ++c) {
-                const int d = packed_desc(t, c);
-                hc.colmap[t * kTileCols + c] = int16_t(d);
-                if (d >= 0) ++seen[d];
-            }
-        for (int d = 0; d < kRaw; ++d)
-            if (seen[d] != 1)   // every descriptor entry has exactly one packed column (a property of packed_desc alone)
-                return "internal: descriptor entry " + std::to_string(d) + " has " + std::to_string(seen[d]) + " packed columns";
-    }
-    auto lut_value = [&](const LutColumn &col, int px) -> float {
-        if (!col.used) return 0.f;
+    auto lut_value_d = [&](const LutColumn &col, int px) -> double {
+        if (!col.used) return 0.0;
         const double e = col.polar ? hc.embedding_polar[size_t(col.j) * kPx + px]
                                    : hc.embedding_cartesian[size_t(col.j) * kPx + px];
         const double ph = double(col.k) * double(hc.gradient_angle[px]);
         const double rot = col.rot == 1 ? std::cos(ph) : (col.rot == 2 ? std::sin(ph) : 1.0);
-        return float(double(kVmN3K8[col.k]) * e * rot);
+        return double(kVmN3K8[col.k]) * e * rot;
     };
+    auto lut_value = [&](const LutColumn &col, int px) -> float { return float(lut_value_d(col, px)); };
+    // the x-parity of a column, and how far the column is from having one
+    float defect = 0.f;
+    int known[2][kPolar][4][3] = {};
+    auto parity = [&](const LutColumn &col) -> int {
+        int &memo = known[col.polar ? 1 : 0][col.j][col.k][col.rot];
+        if (memo) return memo;
+        double even_err = 0.0, odd_err = 0.0, mx = 0.0;
+        for (int y = 0; y < kPatch; ++y)
+            for (int x = 0; x < kPatch / 2; ++x) {
+                const double a = lut_value(col, y * kPatch + x), b = lut_value(col, y * kPatch + kPatch - 1 - x);
+                even_err = std::fmax(even_err, std::fabs(a - b));
+                odd_err = std::fmax(odd_err, std::fabs(a + b));
+                mx = std::fmax(mx, std::fmax(std::fabs(a), std::fabs(b)));
+            }
+        defect = std::fmax(defect, float(std::fmin(even_err, odd_err) / mx));
+        return memo = even_err <= odd_err ? 1 : -1;
+    };
+    FoldLayout fl;
+    if (const std::string e = build_fold_layout(parity, fl); !e.empty()) return e;
+    hc.lut_parity_defect = defect;
+    if (!(defect < 1e-4f))   // (f32 rounding of the grid and of atan2 leaves a few 1e-6)
+        return "internal: a pooling LUT column is neither even nor odd in x (defect " + std::to_string(defect) + ")";
+    hc.colmap.assign(kPackedCols, -1);
+    {
+        std::vector<int> seen(kRaw, 0);
+        for (int t = 0; t < kTiles; ++t) {
+            int ut, v;
+            acc_tile_source(t, ut, v);
+            for (int c = 0; c < kTileCols; ++c) {
+                const FoldColumn &fc = fl.col[ut][c];
+                const int d = v ? fc.desc_v : fc.desc_u;
+                if (d < 0) continue;
+                hc.colmap[t * kTileCols + c] = int16_t(v && fc.sign_v < 0 ? -2 - d : d);
+                ++seen[d];
+            }
+        }
+        for (int d = 0; d < kRaw; ++d)
+            if (seen[d] != 1)   // every descriptor entry has exactly one packed column
+                return "internal: descriptor entry " + std::to_string(d) + " has " + std::to_string(seen[d]) + " packed columns";
+    }
     hc.pool_b_f32.assign(size_t(kPatch) * kUniqueTiles * 2 * 64 * 4, 0.f);
     hc.pool_b_f16.assign(size_t(kPatch) * kUniqueTiles * 2 * 64 * 8, 0);
     for (int y = 0; y < kPatch; ++y)
         for (int ut = 0; ut < kUniqueTiles; ++ut)
             for (int lane = 0; lane < 64; ++lane) {
-                const LutColumn col = lut_column(ut, lane & 15);
+                const FoldColumn &fc = fl.col[ut][lane & 15];
                 const int q = lane >> 4;
                 for (int e = 0; e < 8; ++e) {
-                    const int px = y * kPatch + 8 * q + e;
-                    const float v = lut_value(col, px);
+                    const LutColumn &col = e < 4 ? fc.first : fc.second;
+                    float v = 0.f;
+                    if (col.used) {   // the mean of the two mirror values, in f64
+                        const int x = 4 * q + (e & 3);
+                        const double a = lut_value_d(col, y * kPatch + x), b = lut_value_d(col, y * kPatch + kPatch - 1 - x);
+                        v = float(0.5 * (a + double(parity(col)) * b) * double(e < 4 ? 1 : fc.sign_second));
+                    }
                     hc.pool_b_f32[(((size_t(y) * kUniqueTiles + ut) * 2 + (e >> 2)) * 64 + lane) * 4 + (e & 3)] = v;
                     const uint16_t hi = f16_bits(v);
                     const uint16_t lo = f16_bits(v - f16_value(hi));  // f16 subnormals survive the MFMA (tools/micro)
@@ -236,12 +351,27 @@ std::string build_host_consts(const PcaModel &pca, HostConsts &hc) {
                     hc.pool_b_f16[(((size_t(y) * kUniqueTiles + ut) * 2 + 1) * 64 + lane) * 8 + e] = lo;
                 }
             }
-    // LF_MKD_POOL_F16_FP6: the cross-term operands of the harmonics' tiles (see mkd_consts.hpp)
-    hc.pool_b_fp6 = hc.pool_b_f16;
+    // LF_MKD_POOL_F16_FP6: the unfolded row images, with the cross-term operands of the harmonics' tiles (see mkd_consts.hpp)
+    hc.colmap_unfolded.assign(kPackedCols, -1);
+    for (int t = 0; t < kTiles; ++t)
+        for (int c = 0; c < kTileCols; ++c) hc.colmap_unfolded[t * kTileCols + c] = int16_t(unfolded_packed_desc(t, c));
+    hc.pool_b_fp6.assign(size_t(kPatch) * kUnfUniqueTiles * 2 * 64 * 8, 0);
+    for (int y = 0; y < kPatch; ++y)
+        for (int ut = 0; ut < kUnfUniqueTiles; ++ut)
+            for (int lane = 0; lane < 64; ++lane) {
+                const LutColumn col = unfolded_lut_column(ut, lane & 15);
+                const int q = lane >> 4;
+                for (int e = 0; e < 8; ++e) {
+                    const float v = lut_value(col, y * kPatch + 8 * q + e);
+                    const uint16_t hi = f16_bits(v);
+                    hc.pool_b_fp6[(((size_t(y) * kUnfUniqueTiles + ut) * 2 + 0) * 64 + lane) * 8 + e] = hi;
+                    hc.pool_b_fp6[(((size_t(y) * kUnfUniqueTiles + ut) * 2 + 1) * 64 + lane) * 8 + e] = f16_bits(v - f16_value(hi));
+                }
+            }
     {
         const float kX = 2048.f;      // the residuals' common factor (the kernel scales its stream residuals by the same)
         auto slot_values = [&](int y, int ut, int lane, float (&sv)[16]) {
-            const LutColumn col = lut_column(ut, lane & 15);
+            const LutColumn col = unfolded_lut_column(ut, lane & 15);
             const int q = lane >> 4;
             for (int e = 0; e < 8; ++e) {
                 const float v = lut_value(col, y * kPatch + 8 * q + e);
@@ -251,7 +381,7 @@ std::string build_host_consts(const PcaModel &pca, HostConsts &hc) {
             }
         };
         for (int y = 0; y < kPatch; ++y)
-            for (int ut = 3; ut < kUniqueTiles; ++ut)
+            for (int ut = 3; ut < kUnfUniqueTiles; ++ut)
                 for (int lane = 0; lane < 64; ++lane) {
                     float sv[16], other[16];
                     slot_values(y, ut, lane, sv);
@@ -271,29 +401,39 @@ std::string build_host_consts(const PcaModel &pca, HostConsts &hc) {
                         w[(6 * f) / 32] |= uint32_t(bits);
                         if ((6 * f) / 32 + 1 < 3) w[(6 * f) / 32 + 1] |= uint32_t(bits >> 32);
                     }
-                    uint16_t *dst = &hc.pool_b_fp6[(((size_t(y) * kUniqueTiles + ut) * 2 + 1) * 64 + lane) * 8];
+                    uint16_t *dst = &hc.pool_b_fp6[(((size_t(y) * kUnfUniqueTiles + ut) * 2 + 1) * 64 + lane) * 8];
                     std::memcpy(dst, w, 16);
                 }
     }
-    auto w_packed = [&](int n, int packed_col) -> float {
-        const int d = packed_col < kPackedCols ? hc.colmap[packed_col] : -1;
-        return d < 0 ? 0.f : hc.w_t[size_t(n) * kRaw + d];
+    // whitening fragments in a packed order (colmap: the folded forms; colmap_unfolded: LF_MKD_POOL_F16_FP6)
+    auto w_packed = [&](const std::vector<int16_t> &cm, int n, int packed_col) -> float {
+        const int d = packed_col < kPackedCols ? cm[packed_col] : -1;
+        if (d == -1) return 0.f;
+        return d >= 0 ? hc.w_t[size_t(n) * kRaw + d] : -hc.w_t[size_t(n) * kRaw + (-2 - d)];
     };
-    hc.white_a_f16.assign(size_t(11) * 8 * 2 * 64 * 8, 0);
+    auto white_f16 = [&](const std::vector<int16_t> &cm, std::vector<uint16_t> &dst) {
+        dst.assign(size_t(11) * 8 * 2 * 64 * 8, 0);
+        for (int r = 0; r < 8; ++r)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int n = 16 * r + (lane & 15), q = lane >> 4;
+                for (int s = 0; s < 11; ++s)
+                    for (int j = 0; j < 8; ++j) {
+                        const float v = w_packed(cm, n, 16 * (2 * s + (j >> 2)) + 4 * q + (j & 3));
+                        const uint16_t hi = f16_bits(v);
+                        dst[(((size_t(s) * 8 + r) * 2 + 0) * 64 + lane) * 8 + j] = hi;
+                        dst[(((size_t(s) * 8 + r) * 2 + 1) * 64 + lane) * 8 + j] = f16_bits(v - f16_value(hi));
+                    }
+            }
+    };
+    white_f16(hc.colmap, hc.white_a_f16);
+    white_f16(hc.colmap_unfolded, hc.white_a_f16_unfolded);
     hc.white_a_f32.assign(size_t(kTiles) * 4 * 8 * 64, 0.f);
     for (int r = 0; r < 8; ++r)
         for (int lane = 0; lane < 64; ++lane) {
             const int n = 16 * r + (lane & 15), q = lane >> 4;
-            for (int s = 0; s < 11; ++s)
-                for (int j = 0; j < 8; ++j) {
-                    const float v = w_packed(n, 16 * (2 * s + (j >> 2)) + 4 * q + (j & 3));
-                    const uint16_t hi = f16_bits(v);
-                    hc.white_a_f16[(((size_t(s) * 8 + r) * 2 + 0) * 64 + lane) * 8 + j] = hi;
-                    hc.white_a_f16[(((size_t(s) * 8 + r) * 2 + 1) * 64 + lane) * 8 + j] = f16_bits(v - f16_value(hi));
-                }
             for (int t = 0; t < kTiles; ++t)
                 for (int i = 0; i < 4; ++i)
-                    hc.white_a_f32[((size_t(t) * 4 + i) * 8 + r) * 64 + lane] = w_packed(n, 16 * t + 4 * q + i);
+                    hc.white_a_f32[((size_t(t) * 4 + i) * 8 + r) * 64 + lane] = w_packed(hc.colmap, n, 16 * t + 4 * q + i);
         }
     hc.white_bias.assign(kOut, 0.f);
     for (int n = 0; n < kOut; ++n) {

@@ -25,21 +25,41 @@ constexpr int kOut = 128;       // shaders/common.glsl:20
 // pixel only, so its rotation is folded into the LUT instead of into six more streams:
 //   sum_px m cos(k(t+phi)) EP_j = sum_px [m cos kt] (EP_j cos k phi) - [m sin kt] (EP_j sin k phi)
 //   sum_px m sin(k(t+phi)) EP_j = sum_px [m sin kt] (EP_j cos k phi) + [m cos kt] (EP_j sin k phi)
-// Per harmonic k both streams meet the same four LUT tiles of 16 columns:
-//   P0 = EPc[0:16] | Q0 = EPs[0:16] | R = EPc[16:25], EC[0:7] | S = EPs[16:25], EC[7:9], 5 unused
-// (EPc_j = c_k EP_j cos k phi, EPs_j = c_k EP_j sin k phi, EC_j scaled by c_k; c_k the von-Mises coefficient), into 8
-// products; the m stream keeps its 3 tiles.  24 accumulator tiles in the row loop (the two products of relsin[0:16] share
-// one); the epilogue adds / subtracts
-// them into the 21 tiles of packed output columns the whitening consumes.
+// A patch row is then FOLDED about its middle (the pixel grid's x -> -x): every LUT column L is even or odd in x (to f32
+// rounding; build_host_consts checks it), so with e(x) = s(x) + s(31-x), o(x) = s(x) - s(31-x) for x < 16
+//   sum_{x<32} L(x) s(x) = sum_{x<16} L(x) e(x)  (L even)   or   sum_{x<16} L(x) o(x)  (L odd),
+// and EPc_j = c_k EP_j cos k phi, EPs_j = c_k EP_j sin k phi (c_k the von-Mises coefficient) always have OPPOSITE parity.
+// One K = 32 operand therefore holds the even half of one stream beside the odd half of the other:
+//   M = [m_e | m_o]      U_k = [cos_e | sin_o]      V_k = [sin_e | -cos_o]
+// (K slot of a lane (patch, q): 0-3 = the first half at x = 4q + i, 4-7 = the second half at the same x) and per harmonic
+// both operands meet the SAME three LUT tiles, whose columns are one of
+//   EPc_j even: [EPc_j | -EPs_j]   U -> relcos_j,  V -> relsin_j
+//   EPc_j odd:  [EPs_j |  EPc_j]   U -> relsin_j,  V -> -relcos_j
+//   EC_i even:  [EC_i | 0]         U -> abscos_i,  V -> abssin_i
+//   EC_i odd:   [0 | EC_i]         U -> abssin_i,  V -> -abscos_i
+// The minus signs of the V products are carried by the whitening fragments (and by `colmap` for the raw tap).
+// Tiles of a harmonic: 0 = the larger polar class (15 columns) | 1 = the smaller (10, slots 0-9), even EC (6, slots 10-15) |
+// 2 = odd EC (3).  The m stream's three tiles have the same shape: EP 0-15 | EP 16-24, even EC in slots 10-15 | odd EC; a
+// column fills the half its parity selects.  The LUT is symmetrised: a folded value is the f64 mean of the two mirror values.
+// 12 LUT tiles and 21 accumulator tiles per row, 6 products per harmonic; the accumulators are the packed output columns.
 constexpr int kStreams = 7;
-constexpr int kAccTiles = 24;     // row loop: 0-2 m | per harmonic h = k-1, base 3 + 7h: cos x P0, sin x Q0, sin x P0 + cos x Q0,
-                                  //           cos x R, sin x R, cos x S, sin x S
-constexpr int kTiles = 21;        // after the epilogue's combine step (what `colmap` and the whitening fragments index):
-                                  // 0-2 m | per harmonic, base 3 + 6h: relcos[0:16] | relsin[0:16] | relcos[16:25],abscos[0:7]
-                                  //        | relsin[16:25],abssin[0:7] | abscos[7:9] in slots 9,10 | abssin[7:9] in slots 9,10
+constexpr int kTiles = 21;        // accumulator tiles = packed output tiles (what `colmap` and the whitening fragments index):
+                                  // 0-2 m | per harmonic h = k-1, 3 + 6h + 2 (LUT tile 0..2) + (0: U, 1: V)
+constexpr int kAccTiles = kTiles;
 constexpr int kTileCols = 16;
+constexpr int kPolarSlots = 10;   // a mixed tile (LUT tile 1 of a group): slots below it are polar, the others cartesian
 constexpr int kPackedCols = kTiles * kTileCols;  // 336
-constexpr int kUniqueTiles = 15;  // LUT tiles per patch row: 0-2 m | 3 + 4h + {0: P0, 1: Q0, 2: R, 3: S}
+constexpr int kUniqueTiles = 12;  // LUT tiles per patch row: 0-2 m | 3 + 3h + {0, 1, 2}
+
+// The UNFOLDED row form, kept for LF_MKD_POOL_F16_FP6 alone (an experiment frozen as a mode): a lane holds the 8 pixels
+// x in [8q, 8q+8) of the row and per harmonic k both streams meet four LUT tiles of 16 columns:
+//   P0 = EPc[0:16] | Q0 = EPs[0:16] | R = EPc[16:25], EC[0:7] | S = EPs[16:25], EC[7:9], 5 unused
+// into 8 products; the m stream keeps 3 tiles.  24 accumulator tiles in the row loop (the two products of relsin[0:16]
+// share one); the epilogue adds / subtracts them into 21 tiles of packed output columns:
+//   0-2 m | per harmonic, base 3 + 6h: relcos[0:16] | relsin[0:16] | relcos[16:25],abscos[0:7]
+//        | relsin[16:25],abssin[0:7] | abscos[7:9] in slots 9,10 | abssin[7:9] in slots 9,10
+constexpr int kUnfAccTiles = 24;
+constexpr int kUnfUniqueTiles = 15;
 
 struct PcaModel {
     std::vector<float> mean, eigvals, eigvecs;  // [238], [238], [238*238] row-major
@@ -57,26 +77,33 @@ struct HostConsts {
     std::vector<float> w_t;                  // [128][238]  scaled eigenvectors, transposed
 
     // device layouts
-    std::vector<int16_t> colmap;    // [336] packed column (after the combine step) -> descriptor index (0..237) or -1
+    // [336] packed column -> descriptor index d (0..237); -1: unused; -2 - d: the column holds MINUS entry d
+    std::vector<int16_t> colmap;
     // f32 pooling fragments for v_mfma_f32_16x16x4_f32:
-    //   [row y 32][unique tile 15][jg 2][lane 64][e 4] = LUT_col(lane&15)[y][8*(lane>>4) + 4*jg + e]
+    //   [row y 32][unique tile 12][half 2][lane 64][i 4] = the column's (lane & 15) half at x = 4 (lane >> 4) + i
     std::vector<float> pool_b_f32;
-    // f16 hi/lo pooling fragments for v_mfma_f32_16x16x32_f16 (B[k][col], k = 8*(lane>>4)+e):
-    //   [row y 32][unique tile 15][hi|lo 2][lane 64][e 8] (uint16 bit patterns); v = hi + lo, both f16
+    // f16 hi/lo pooling fragments for v_mfma_f32_16x16x32_f16 (B[k][col], k = 8*(lane>>4)+e, e = 4 half + i):
+    //   [row y 32][unique tile 12][hi|lo 2][lane 64][e 8] (uint16 bit patterns); v = hi + lo, both f16
     std::vector<uint16_t> pool_b_f16;
-    // The same row images for LF_MKD_POOL_F16_FP6: the hi pieces (and the m stream's three tiles) as above; for the tiles of
+    // Whitening as out^T = W_T x raw with the pooling accumulators as B operand: a lane (patch p, q) holds
+    // packed columns 16t + 4q + i in accumulator (t, i).  A fragments = rows of W_T, K ordered to match:
+    //   f16 (16x16x32): [step 11][row tile 8][hi|lo 2][lane 64][j 8], lane = (row n = lane&15, q = lane>>4),
+    //        value +-W_T[16r + n][desc(16*(2s + (j>>2)) + 4q + (j&3))], 0 for padding columns
+    //   f32 (16x16x4):  [tile 21][i 4][row tile 8][lane 64] = +-W_T[16r + n][desc(16t + 4q + i)]
+    std::vector<uint16_t> white_a_f16;
+    std::vector<float> white_a_f32;
+    // LF_MKD_POOL_F16_FP6 (the unfolded row form): its own packed order, whitening fragments and row images
+    //   [row y 32][unique tile 15][hi|lo 2][lane 64][e 8], pixel 8 (lane >> 4) + e.  The hi pieces, and both pieces of the m
+    // stream's three tiles, are f16 as above; for the tiles of
     // the harmonics the lo piece is replaced by the lane's operand of v_mfma_scale_f32_16x16x128_f8f6f4 that carries BOTH
     // cross terms of the split: 16 e2m3 fields (12 bytes) -- field 2e = 2048 (v - hi) / T, field 2e + 1 = hi / T for the
     // lane's pixel e -- and a word with the lane's block scale T as an E8M0 byte (tiles P0 and Q0 of a harmonic share T:
     // they meet in one instruction).
+    std::vector<int16_t> colmap_unfolded;       // [336], entries >= -1
     std::vector<uint16_t> pool_b_fp6;
-    // Whitening as out^T = W_T x raw with the pooling accumulators as B operand: a lane (patch p, q) holds
-    // packed columns 16t + 4q + i in accumulator (t, i).  A fragments = rows of W_T, K ordered to match:
-    //   f16 (16x16x32): [step 11][row tile 8][hi|lo 2][lane 64][j 8], lane = (row n = lane&15, q = lane>>4),
-    //        value W_T[16r + n][desc(16*(2s + (j>>2)) + 4q + (j&3))], 0 for padding columns
-    //   f32 (16x16x4):  [tile 21][i 4][row tile 8][lane 64] = W_T[16r + n][desc(16t + 4q + i)]
-    std::vector<uint16_t> white_a_f16;
-    std::vector<float> white_a_f32;
+    std::vector<uint16_t> white_a_f16_unfolded;
+    // largest |L(x) -+ L(31-x)| of a LUT column relative to the column's largest value: what the fold assumes to be zero
+    float lut_parity_defect = 0.f;
     std::vector<float> white_bias;  // [128] = -sum_d W_T[n][d] mean[d]  (whitening.glsl subtracts the mean first)
 };
 

@@ -6,12 +6,14 @@
 //  sampling --, mkd_orient.hip, mkd_detect.hip and mkd_match.hip)
 //
 // Pooling is a GEMM with M = patches, K = pixels, N = (stream, spatial kernel) columns.  One wave
-// owns 16 patches; lane l = (patch p = l & 15, segment q = l >> 4) holds the 8 pixels
-// x in [8q, 8q+8) of the current patch row, which is exactly the A-operand lane map of the
-// 16x16 MFMAs (row = l & 15, k-group = l >> 4).  So blur, gradients and the von-Mises
+// owns 16 patches; lane l = (patch p = l & 15, segment q = l >> 4) holds 8 pixels of the current patch row: the block
+// x in [4q, 4q+4) and its mirror image [28-4q, 32-4q), so that the row can be FOLDED about its middle inside the lane (every
+// LUT column is even or odd in x: mkd_consts.hpp) -- the folded values' K slots are exactly the operand lane map of the
+// 16x16 MFMAs (column = l & 15, k-group = l >> 4).  So blur, gradients and the von-Mises
 // embedding are computed in the registers that feed the matrix cores; nothing but the final
 // sums leaves the wave.  Horizontal neighbours come from lanes l -/+ 16 via ds_bpermute; vertical
 // neighbours from a ring of raw patch rows that LDS-DMA keeps filled.
+// (LF_POOL_F16_FP6, an experiment frozen as a mode, keeps the earlier unfolded form: x in [8q, 8q+8) per lane.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,29 +41,35 @@ __device__ __forceinline__ f32x2 pk_set(float v) { return f32x2{v, v}; }
 __device__ __host__ constexpr bool f16_family(int pool) { return pool == LF_POOL_F16X3 || pool == LF_POOL_F16_FP6; }
 
 // Seven per-pixel streams -- m, and m cos / sin (k theta) for k = 1..3 -- are pooled; the rotation by gradient_angle(px)
-// that the polar kernels' streams carry (embedding.glsl:70-72) is folded into the LUT (mkd_consts.hpp):
+// that the polar kernels' streams carry (embedding.glsl:70-72) is folded into the LUT (mkd_consts.hpp).
+// The folded forms (fold_form(POOL)): 12 LUT tiles per patch row -- 0-2 m | 3 + 3h + {0, 1, 2} for harmonic h = k-1 -- and 21
+// accumulator tiles, which are the packed output tiles themselves: 0-2 m | 3 + 6h + 2 (LUT tile) + (0: operand U, 1: V).
+// The unfolded form (LF_POOL_F16_FP6):
 //   LUT tiles of a patch row: 0-2 m | per harmonic h = k-1, 3 + 4h + {0: P0 = EPc[0:16], 1: Q0 = EPs[0:16],
 //                                      2: R = EPc[16:25] | EC[0:7], 3: S = EPs[16:25] | EC[7:9]}
 //   accumulator tiles of the row loop: 0-2 m | base 3 + 7h: cos x P0 | sin x Q0 | sin x P0 + cos x Q0 (one tile: both
 //                                      products of relsin[0:16]) | cos x R | sin x R | cos x S | sin x S
 //   packed output tiles after the epilogue's combine step (colmap, whitening fragments): 21, see combine_tiles.
-constexpr int kAccTiles = 24;
+__device__ __host__ constexpr bool fold_form(int pool) { return pool != LF_POOL_F16_FP6; }
 constexpr int kTiles = 21;
-constexpr int kUniqueTiles = 15;
-constexpr int kLutPieces = 2 * kUniqueTiles;   // 1 KiB pieces per LUT row
+constexpr int kAccTiles = 21, kUnfAccTiles = 24;
+__device__ __host__ constexpr int acc_tiles(bool fold) { return fold ? kAccTiles : kUnfAccTiles; }
+__device__ __host__ constexpr int lut_pieces(bool fold) { return fold ? 24 : 30; }   // 1 KiB pieces per LUT row: 2 per tile
+constexpr int kPolarSlots = 10;   // folded mixed tiles: slots below it hold polar kernels, the others cartesian ones
 
 // 5-tap sigma=0.7 kernel, patch_gradients.glsl:22-28
 constexpr float kB0 = 0.0096f, kB1 = 0.2054f, kB2 = 0.5699f;
 
 // LDS map of the pooling kernel (bytes)
-constexpr int kRowBytes = kLutPieces * 1024;          // 30720: one LUT row image, 2 x 1 KiB pieces per tile
-constexpr int kRingOff = 2 * kRowBytes;              // raw patch rows: [wave 8][slot 6][2 KiB]
+__device__ __host__ constexpr int row_bytes(bool fold) { return lut_pieces(fold) * 1024; }   // one LUT row image: 24576 (30720)
+__device__ __host__ constexpr int ring_off(bool fold) { return 2 * row_bytes(fold); }         // raw patch rows: [wave 8][slot 6][2 KiB]
+constexpr int kRowBytes = row_bytes(true), kRingOff = ring_off(true);                         // the folded forms'
 constexpr int kRingSlots = 6;
-// total: kRingOff + waves * kRingSlots * 2048 = 159744 B for 8 waves, 110592 B for 4
+// total: ring_off + waves * kRingSlots * 2048 = 147456 B for 8 waves, 98304 B for 4
 // Keypoint mode (SRC = kSrcKeypoints): the ring of a describe wave is filled by a producer wave of the same workgroup, four
 // patch rows at a time (a group), so it holds 12 rows: the 8 a describe wave reads while a group is being written + that
 // group.  Raw row r of the workgroup's it-th batch lives in slot (8 it + r) mod 12 (32 mod 12 = 8: the numbering simply
-// runs on across batches).  4 describe waves: kRingOff + 4 * 12 * 2048 = 159744 B, plus the level table.
+// runs on across batches).  4 describe waves: kRingOff + 4 * 12 * 2048 = 147456 B, plus the level table.
 // SRC = kSrcKeypointsSplit (round 6; requests of at most 4096 keypoints): the 32 rows of a batch's patches are divided among
 // R = 2 or 4 WORKGROUPS (row-split form, see mkd_pool) whose partial pooled sums meet in global memory.
 [[maybe_unused]] constexpr int kSrcPatches = 0, kSrcKeypoints = 1, kSrcKeypointsSplit = 2;
@@ -90,15 +98,16 @@ __device__ __forceinline__ void lds_dma16_sv(const unsigned char *uniform_base, 
 // hipcc then selects the SGPR-base form `global_load_lds_dwordx4 v_off, s[base:base+1]`, which costs no 64-bit VALU add and
 // no VGPR pair per request (written as per-lane pointer + uniform offset, every request carried its own v_lshl_add_u64
 // and the hoisted address pairs were spilled).
-// one LUT row (30 pieces) into an LDS row buffer, piece p by wave p mod W (the first waves take one piece more)
-template <int W>
+// one LUT row (24 pieces; 30 unfolded) into an LDS row buffer, piece p by wave p mod W (the first waves take one piece more)
+template <int W, bool FOLD = true>
 __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ lut_rows, int row,
                                               unsigned char *lds_row, int wave, int lane) {
+    constexpr int kPieces = lut_pieces(FOLD);
     const unsigned lane16 = (unsigned)lane * 16u;
 #pragma unroll
-    for (int j = 0; j < (kLutPieces + W - 1) / W; ++j) {
-        if (wave + W * j < kLutPieces) {   // uniform
-            const unsigned char *g = lut_rows + ((size_t)row * kRowBytes + (size_t)(wave + W * j) * 1024);   // uniform
+    for (int j = 0; j < (kPieces + W - 1) / W; ++j) {
+        if (wave + W * j < kPieces) {   // uniform
+            const unsigned char *g = lut_rows + ((size_t)row * row_bytes(FOLD) + (size_t)(wave + W * j) * 1024);   // uniform
             lds_dma16_sv(g, lane16, lds_row + (wave + W * j) * 1024);
         }
     }
@@ -110,7 +119,8 @@ __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ 
 // can be requested into buffer 0 while the last step is still being consumed).
 constexpr int kWStepBytes = 16384;
 __device__ __forceinline__ constexpr int wstage_slot(int step) { return step % 3 == 0 ? 0 : (step % 3 == 1 ? 32768 : 16384); }
-static_assert(wstage_slot(0) + kWStepBytes <= kRowBytes && wstage_slot(10) >= kRowBytes && wstage_slot(10) + kWStepBytes <= 2 * kRowBytes, "");
+static_assert(wstage_slot(0) + kWStepBytes <= row_bytes(true) && wstage_slot(10) >= row_bytes(false) &&
+              wstage_slot(10) + kWStepBytes <= 2 * row_bytes(true), "both forms' row buffers");
 
 template <int W>
 __device__ __forceinline__ void issue_w_step(const unsigned char *__restrict__ wfrag, int step, unsigned char *lds,
@@ -449,33 +459,116 @@ __device__ __forceinline__ void blur_row_impl(const unsigned char *ring_lane, Sl
     out_r = has_r ? hr : out[7];
 }
 
-__device__ __forceinline__ void blur_row(const unsigned char *ring_lane, int s0, int addr_l, int addr_r, bool has_l,
-                                         bool has_r, float (&out)[8], float &out_l, float &out_r) {
-    blur_row_impl(ring_lane, [s0](int i) { const int sl = s0 + i; return sl >= kRingSlots ? sl - kRingSlots : sl; }, addr_l,
-                  addr_r, has_l, has_r, out, out_l, out_r);
+// The same for the folded forms' lane map.  The lane's two blocks of the raw row come from ring_a (x in [4q, 4q+4)) and
+// ring_b (x in [28-4q, 32-4q)).  out[0..3] = the first block in ascending x, out[4..7] = the second in DESCENDING x: out[4 + i]
+// is the mirror pixel of out[i].  Each block needs two neighbours a side of the vertically blurred row and one of the
+// blurred row: the first block's from the first blocks of lanes -/+16, the second block's from the second blocks of
+// lanes +/-16; where the two blocks touch (q == 3) they are the lane's own values, at the patch's edges (q == 0) they replicate.
+// nb = the blurred row at x = 4q-1, 4q+4, 27-4q, 32-4q.  Per pixel the arithmetic and its order are blur_row_impl's.
+template <class SlotOfTap>
+__device__ __forceinline__ void blur_row_fold_impl(const unsigned char *ring_a, const unsigned char *ring_b, SlotOfTap slot_of_tap,
+                                                   int addr_l, int addr_r, bool has_l, bool has_r, float (&out)[8],
+                                                   float (&nb)[4]) {
+    if constexpr (ablate::kNoFrontEnd) {   // no blur: the first tap's raw row as it is
+        const int sl = slot_of_tap(0);
+        const f32x4 a_ = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
+        const f32x4 b_ = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) { out[x] = a_[x]; out[4 + x] = b_[3 - x]; }
+        nb[0] = out[0]; nb[1] = out[3]; nb[2] = out[7]; nb[3] = out[4];
+        return;
+    }
+    float va[4], vb[4];   // vertically blurred, both blocks in ascending x
+    {
+        const float kk[5] = {kB0, kB1, kB2, kB1, kB0};
+        f32x2 v2[4];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int sl = slot_of_tap(i);
+            const f32x4 lo = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
+            const f32x4 hi = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
+            const f32x2 r[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v2[e] = i == 0 ? pk_set(kk[0]) * r[e] : pk_fma(pk_set(kk[i]), r[e], v2[e]);
+        }
+        va[0] = v2[0].x; va[1] = v2[0].y; va[2] = v2[1].x; va[3] = v2[1].y;
+        vb[0] = v2[2].x; vb[1] = v2[2].y; vb[2] = v2[3].x; vb[3] = v2[3].y;
+    }
+    float ea[8], eb[8];
+    {
+        const float la0 = lane_fetch(addr_l, va[2]), la1 = lane_fetch(addr_l, va[3]);   // x = 4q-2, 4q-1
+        const float rb0 = lane_fetch(addr_l, vb[0]), rb1 = lane_fetch(addr_l, vb[1]);   // x = 32-4q, 33-4q
+        const float ra0 = lane_fetch(addr_r, va[0]), ra1 = lane_fetch(addr_r, va[1]);   // x = 4q+4, 4q+5
+        const float lb0 = lane_fetch(addr_r, vb[2]), lb1 = lane_fetch(addr_r, vb[3]);   // x = 26-4q, 27-4q
+        ea[0] = has_l ? la0 : va[0];
+        ea[1] = has_l ? la1 : va[0];
+        ea[6] = has_r ? ra0 : vb[0];
+        ea[7] = has_r ? ra1 : vb[1];
+        eb[0] = has_r ? lb0 : va[2];
+        eb[1] = has_r ? lb1 : va[3];
+        eb[6] = has_l ? rb0 : vb[3];
+        eb[7] = has_l ? rb1 : vb[3];
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { ea[2 + x] = va[x]; eb[2 + x] = vb[x]; }
+    float ob[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {   // (the first tap as an fma onto +0.0: see blur_row_impl)
+        float s = ablate::kMulFirstTap ? kB0 * ea[x] : fmaf(kB0, ea[x], 0.0f);
+        s = fmaf(kB1, ea[x + 1], s);
+        s = fmaf(kB2, ea[x + 2], s);
+        s = fmaf(kB1, ea[x + 3], s);
+        s = fmaf(kB0, ea[x + 4], s);
+        out[x] = s;
+        float t = ablate::kMulFirstTap ? kB0 * eb[x] : fmaf(kB0, eb[x], 0.0f);
+        t = fmaf(kB1, eb[x + 1], t);
+        t = fmaf(kB2, eb[x + 2], t);
+        t = fmaf(kB1, eb[x + 3], t);
+        t = fmaf(kB0, eb[x + 4], t);
+        ob[x] = t;
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) out[4 + x] = ob[3 - x];
+    const float hal = lane_fetch(addr_l, out[3]), hbr = lane_fetch(addr_l, ob[0]);
+    const float har = lane_fetch(addr_r, out[0]), hbl = lane_fetch(addr_r, ob[3]);
+    nb[0] = has_l ? hal : out[0];
+    nb[1] = has_r ? har : ob[0];
+    nb[2] = has_r ? hbl : out[3];
+    nb[3] = has_l ? hbr : ob[3];
 }
 
-// Harmonics k = 1..3 of the gradient angle by angle addition, each stream pair against its four LUT tiles.  The 21 matrix
-// instructions of a harmonic (7 accumulators x 3 terms) are issued term by term across the accumulators, so dependent
-// ones are seven apart; `g` holds the fragments of P0 on entry (prefetched by the caller) and P0 of the next harmonic on
-// exit.
+// Folds a stream about the row's middle: s[0], s[1] = the lane's first block, s[2], s[3] = the mirror pixels of the same.
+__device__ __forceinline__ void fold_sum(const f32x2 (&s)[4], f32x2 &e0, f32x2 &e1) { e0 = s[0] + s[2]; e1 = s[1] + s[3]; }
+__device__ __forceinline__ void fold_diff(const f32x2 (&s)[4], f32x2 &o0, f32x2 &o1) { o0 = s[0] - s[2]; o1 = s[1] - s[3]; }
+__device__ __forceinline__ void fold_diff_rev(const f32x2 (&s)[4], f32x2 &o0, f32x2 &o1) { o0 = s[2] - s[0]; o1 = s[3] - s[1]; }
+
+// Harmonics k = 1..3 of the gradient angle (the folded forms).  The recurrence runs on the products themselves,
+// (pk, qk) = m (cos, sin)(k theta), as a three-term (Chebyshev) recurrence x_{k+1} = 2 c1 x_k - x_{k-1} with x_0 = (m, 0): one
+// instruction per stream and harmonic instead of a rotation of the unit vector (two) plus a product.  After each step the pair is
+// folded into the two operands U = [cos_e | sin_o] and V = [sin_e | -cos_o] (mkd_consts.hpp), which meet the SAME three LUT
+// tiles: 6 products (18 matrix instructions, f16x3) per harmonic, issued term by term across the six accumulators.  `g` holds
+// the fragments of the harmonic's first tile on entry (prefetched by the caller) and the next harmonic's on exit.
 template <int POOL>
 __device__ __forceinline__ void pool_harmonics(const f32x2 (&m)[4], const f32x2 (&c1)[4], const f32x2 (&s1)[4],
                                                const unsigned char *brow, BFrag &g, f32x4 (&acc)[kAccTiles]) {
-    // The recurrence runs on the products themselves, (pk, qk) = m (cos, sin)(k theta), as a three-term (Chebyshev)
-    // recurrence x_{k+1} = 2 c1 x_k - x_{k-1} with x_0 = (m, 0): one instruction per stream and harmonic instead of a
-    // rotation of the unit vector (two) plus a product.
     f32x2 pk[4], qk[4], pp[4], qp[4], tc[4];
-    AFrag<POOL> ac, as;
+    AFrag<POOL> au, av;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { pk[e] = m[e] * c1[e]; qk[e] = m[e] * s1[e]; tc[e] = c1[e] + c1[e]; }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        if constexpr (POOL == LF_POOL_F16X3) {
-            AFrag<POOL>::set2(ac, pk, as, qk);
-        } else {
-            ac.set(pk);
-            as.set(qk);
+        {
+            f32x2 u[4], v[4];
+            fold_sum(pk, u[0], u[1]);
+            fold_diff(qk, u[2], u[3]);
+            fold_sum(qk, v[0], v[1]);
+            fold_diff_rev(pk, v[2], v[3]);
+            if constexpr (POOL == LF_POOL_F16X3) {
+                AFrag<POOL>::set2(au, u, av, v);
+            } else {
+                au.set(u);
+                av.set(v);
+            }
         }
         if (k < 2) {
 #pragma unroll
@@ -486,21 +579,15 @@ __device__ __forceinline__ void pool_harmonics(const f32x2 (&m)[4], const f32x2 
                 pk[e] = pn; qk[e] = qn;
             }
         }
-        const int a0 = 3 + 7 * k, u0 = 3 + 4 * k;
-        const BFrag p0 = g, q0 = load_b(brow, u0 + 1), r = load_b(brow, u0 + 2), sf = load_b(brow, u0 + 3);
-        if (k < 2) g = load_b(brow, u0 + 4);
-        // cos x P0 -> a0 | sin x P0 -> a0+2 | sin x Q0 -> a0+1 | cos x R, sin x R -> a0+3, a0+4 | cos x S, sin x S -> a0+5, a0+6
-        mma_part<POOL, 0>(ac, p0, acc[a0 + 0]); mma_part<POOL, 0>(as, p0, acc[a0 + 2]); mma_part<POOL, 0>(as, q0, acc[a0 + 1]);
-        mma_part<POOL, 0>(ac, r, acc[a0 + 3]); mma_part<POOL, 0>(as, r, acc[a0 + 4]);
-        mma_part<POOL, 0>(ac, sf, acc[a0 + 5]); mma_part<POOL, 0>(as, sf, acc[a0 + 6]);
-        mma_part<POOL, 1>(ac, p0, acc[a0 + 0]); mma_part<POOL, 1>(as, p0, acc[a0 + 2]); mma_part<POOL, 1>(as, q0, acc[a0 + 1]);
-        mma_part<POOL, 1>(ac, r, acc[a0 + 3]); mma_part<POOL, 1>(as, r, acc[a0 + 4]);
-        mma_part<POOL, 1>(ac, sf, acc[a0 + 5]); mma_part<POOL, 1>(as, sf, acc[a0 + 6]);
-        mma_part<POOL, 2>(ac, p0, acc[a0 + 0]); mma_part<POOL, 2>(as, p0, acc[a0 + 2]); mma_part<POOL, 2>(as, q0, acc[a0 + 1]);
-        mma_part<POOL, 2>(ac, r, acc[a0 + 3]); mma_part<POOL, 2>(as, r, acc[a0 + 4]);
-        mma_part<POOL, 2>(ac, sf, acc[a0 + 5]); mma_part<POOL, 2>(as, sf, acc[a0 + 6]);
-        // cos x Q0: the second product of relsin[0:16], into the accumulator of the first
-        mma_part<POOL, 0>(ac, q0, acc[a0 + 2]); mma_part<POOL, 1>(ac, q0, acc[a0 + 2]); mma_part<POOL, 2>(ac, q0, acc[a0 + 2]);
+        const int a0 = 3 + 6 * k, u0 = 3 + 3 * k;
+        const BFrag t0 = g, t1 = load_b(brow, u0 + 1), t2 = load_b(brow, u0 + 2);
+        if (k < 2) g = load_b(brow, u0 + 3);
+        mma_part<POOL, 0>(au, t0, acc[a0 + 0]); mma_part<POOL, 0>(av, t0, acc[a0 + 1]); mma_part<POOL, 0>(au, t1, acc[a0 + 2]);
+        mma_part<POOL, 0>(av, t1, acc[a0 + 3]); mma_part<POOL, 0>(au, t2, acc[a0 + 4]); mma_part<POOL, 0>(av, t2, acc[a0 + 5]);
+        mma_part<POOL, 1>(au, t0, acc[a0 + 0]); mma_part<POOL, 1>(av, t0, acc[a0 + 1]); mma_part<POOL, 1>(au, t1, acc[a0 + 2]);
+        mma_part<POOL, 1>(av, t1, acc[a0 + 3]); mma_part<POOL, 1>(au, t2, acc[a0 + 4]); mma_part<POOL, 1>(av, t2, acc[a0 + 5]);
+        mma_part<POOL, 2>(au, t0, acc[a0 + 0]); mma_part<POOL, 2>(av, t0, acc[a0 + 1]); mma_part<POOL, 2>(au, t1, acc[a0 + 2]);
+        mma_part<POOL, 2>(av, t1, acc[a0 + 3]); mma_part<POOL, 2>(au, t2, acc[a0 + 4]); mma_part<POOL, 2>(av, t2, acc[a0 + 5]);
     }
 }
 
@@ -517,7 +604,7 @@ typedef unsigned v6u __attribute__((ext_vector_type(6)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void pool_harmonics_fp6(const f32x2 (&m)[4], const f32x2 (&c1)[4], const f32x2 (&s1)[4],
-                                                   const unsigned char *brow, BFrag &g, f32x4 (&acc)[kAccTiles]) {
+                                                   const unsigned char *brow, BFrag &g, f32x4 (&acc)[kUnfAccTiles]) {
     // the harmonic's two streams live in the conversion's first source, aq = (pk[0..3], qk[0..3]): the recurrence writes the
     // next harmonic into a fresh one (the k loop is unrolled: renaming, no copies)
     v16f aq, ap;
@@ -609,11 +696,11 @@ __device__ __forceinline__ void pool_harmonics_fp6(const f32x2 (&m)[4], const f3
     }
 }
 
-// The 24 accumulator tiles of the row loop -> the 21 tiles of packed output columns (mkd_consts.hpp, packed_desc):
+// Unfolded form: the 24 accumulator tiles of the row loop -> the 21 tiles of packed output columns (mkd_consts.hpp):
 //   relcos_k = cos x EPc - sin x EPs, relsin_k = sin x EPc + cos x EPs (columns 0-15 in P0 / Q0, 16-24 in slots 0-8 of R / S),
 //   abscos_k / abssin_k = the EC columns: 0-6 in slots 9-15 of R, 7-8 in slots 9-10 of S.
 // Slot of (lane, i) in a tile: 4 (lane >> 4) + i.  Unused slots are set to zero (the norms run over whole tiles).
-__device__ __forceinline__ void combine_tiles(const f32x4 (&a)[kAccTiles], int q, f32x4 (&o)[kTiles]) {
+__device__ __forceinline__ void combine_tiles(const f32x4 (&a)[kUnfAccTiles], int q, f32x4 (&o)[kTiles]) {
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
 #pragma unroll
     for (int h = 0; h < 3; ++h) {
@@ -633,7 +720,8 @@ __device__ __forceinline__ void combine_tiles(const f32x4 (&a)[kAccTiles], int q
 }
 
 // which block of the raw descriptor a packed tile's slots belong to (normalize.glsl: polar | cartesian):
-// 0 = all polar, 1 = all cartesian (or unused = 0), 2 = slots 0-8 polar, 9-15 cartesian
+// 0 = all polar, 1 = all cartesian (or unused = 0), 2 = mixed: the first slots polar (folded: 10, unfolded: 9), the others cartesian
+// (one rule for both forms: folded tile 3 + 6h + 2 (LUT tile) + (U | V), unfolded tile 3 + 6h + part)
 __device__ __forceinline__ constexpr int tile_block(int t) {
     if (t < 3) return t == 0 ? 0 : (t == 1 ? 2 : 1);
     const int part = (t - 3) % 6;
@@ -648,24 +736,30 @@ __device__ __forceinline__ constexpr int tile_block(int t) {
 // f16 path: on entry step 0 of the fragments is on its way into its slot (requested by the caller during patch row 31);
 // on exit LUT row 0 of the next batch is on its way into row buffer 0 if `more`.  Every wave of the workgroup must call.
 template <int POOL, int W>
-__device__ __forceinline__ void finish_descriptors(const f32x4 (&acc_row)[kAccTiles], int lane, int wave, bool valid, long patch,
-                                                   const short *__restrict__ colmap,
+__device__ __forceinline__ void finish_descriptors(const f32x4 (&acc_row)[acc_tiles(fold_form(POOL))], int lane, int wave, bool valid,
+                                                   long patch, const short *__restrict__ colmap,
                                                    const unsigned char *__restrict__ wfrag,
                                                    const float *__restrict__ bias, float *__restrict__ out,
                                                    float *__restrict__ raw_out, unsigned char *s_mem,
                                                    const unsigned char *__restrict__ lut_rows, bool more) {
+    constexpr bool kFold = fold_form(POOL);
     const int q = lane >> 4;
     f32x4 acc[kTiles];
-    combine_tiles(acc_row, q, acc);
+    if constexpr (kFold) {   // the accumulators are the packed tiles
+#pragma unroll
+        for (int t = 0; t < kTiles; ++t) acc[t] = acc_row[t];
+    } else {
+        combine_tiles(acc_row, q, acc);
+    }
     if constexpr (f16_family(POOL)) {
         __syncthreads();   // every wave has left patch row 31: row buffer 1 is free too
         issue_w_step<W>(wfrag, 1, s_mem, wave, lane);
         issue_w_step<W>(wfrag, 2, s_mem, wave, lane);
     }
-    // mixed tiles hold polar kernels in packed columns 0-8 and cartesian ones in 9-15
+    // mixed tiles hold polar kernels in their first packed columns (0-9; unfolded: 0-8) and cartesian ones in the others
     bool lo9[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) lo9[i] = 4 * q + i < 9;
+    for (int i = 0; i < 4; ++i) lo9[i] = 4 * q + i < (kFold ? kPolarSlots : 9);
     float sp = 0.f, sc = 0.f;
 #pragma unroll
     for (int t = 0; t < kTiles; ++t)
@@ -702,8 +796,8 @@ __device__ __forceinline__ void finish_descriptors(const f32x4 (&acc_row)[kAccTi
         for (int t = 0; t < kTiles; ++t)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int d = colmap[t * 16 + 4 * q + i];
-                if (valid && d >= 0) raw_out[patch * 238 + d] = acc[t][i];
+                const int d = colmap[t * 16 + 4 * q + i];   // (-2 - d: the column holds minus entry d -- the folded forms)
+                if (valid && d != -1) raw_out[patch * 238 + (d >= 0 ? d : -2 - d)] = d >= 0 ? acc[t][i] : -acc[t][i];
             }
     }
     f32x4 o[8];
@@ -747,7 +841,7 @@ __device__ __forceinline__ void finish_descriptors(const f32x4 (&acc_row)[kAccTi
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __syncthreads();
             if (s >= 1 && s + 2 < 11) issue_w_step<W>(wfrag, s + 2, s_mem, wave, lane);
-            if (s == 10 && more) issue_lut_row<W>(lut_rows, 0, s_mem, wave, lane);
+            if (s == 10 && more) issue_lut_row<W, kFold>(lut_rows, 0, s_mem, wave, lane);
             read_unit(2 * s, wbuf[0]);
             __builtin_amdgcn_sched_barrier(0);
             if (s > 0) mma_unit(2 * s - 1, wbuf[1]);
@@ -819,7 +913,7 @@ struct KpSource {
     float psf;                   // patch_scale_factor
     PyramidDesc pd;
     // row-split form only: workgroups per batch (2 or 4), the partial sums' exchange buffer
-    // [batch][role R-1][wave W][tile 24][half 2][lane 64] 2 x f32, its arrival counters [batch][wave] and an error word
+    // [batch][role R-1][wave W][tile 21][half 2][lane 64] 2 x f32, its arrival counters [batch][wave] and an error word
     int split;
     float *xchg;
     unsigned *xchg_cnt;
@@ -1136,7 +1230,7 @@ constexpr int kSplitSpinMax = 1 << 21;   // polls of a consumer wave for its par
 // form above is a wave walking 32 rows for its 16 patches whatever the request's size -- ~70 us of latency at the reference's
 // own 2000-3000 keypoints, on a quarter of the chip.  Here R = 2 or 4 workgroups share a batch of 32 keypoints by ROWS:
 // workgroup `role` samples and pools rows [32 role / R, 32 (role + 1) / R) only (pooling is a sum over pixels), the first
-// R - 1 leave their 24 accumulator tiles in global memory and count themselves in, the last one -- the highest workgroup id of
+// R - 1 leave their 21 accumulator tiles in global memory and count themselves in, the last one -- the highest workgroup id of
 // the batch, so that those it waits for were dispatched before it -- adds them to its own in a fixed order and runs the
 // epilogue.  A descriptor's sum is then R partial chains instead of one: bit-identical within the form, ~1e-7 relative
 // from the whole-patch forms.  Same sampling, blur, gradient and MFMA arithmetic per row.
@@ -1158,7 +1252,10 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     constexpr int kSlots = kKp ? kRingSlotsKp : kRingSlots;
     static_assert(!kKp || POOL == LF_POOL_F16X3, "keypoint mode pools in f16x3");
     constexpr int kMPool = POOL == LF_POOL_F16_FP6 ? LF_POOL_F16X3 : POOL;   // the m stream keeps the three-term form
-    __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRingOff + W * kSlots * 2048 +
+    constexpr bool kFold = fold_form(POOL);
+    static_assert(!kKp || kFold, "the producers write the folded forms' LDS map");
+    constexpr int kNAcc = acc_tiles(kFold), kRowB = row_bytes(kFold), kRingO = ring_off(kFold);
+    __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRingO + W * kSlots * 2048 +
                                                                 (kKp ? kLevelTableBytes + kMaxPyrLevels * 8 : 0)];
     // number of patches: given by the host, or (graph-captured pipelines) left on the device by the previous stage
     const long n = n_dev ? (long)*n_dev : n_host;
@@ -1168,7 +1265,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     const int addr_l = ((lane - 16) & 63) * 4, addr_r = ((lane + 16) & 63) * 4;
     const bool has_l = q > 0, has_r = q < 3;
     const long nbatch = (n + 16 * W - 1) / (16 * W);
-    unsigned char *ring = s_mem + kRingOff + wave * (kSlots * 2048);
+    unsigned char *ring = s_mem + kRingO + wave * (kSlots * 2048);
     BatchWalk walk{(long)blockIdx.x, nbatch, (long)gridDim.x};
     [[maybe_unused]] RowSpan span{0, 32, 0, 32, 7, true};
     [[maybe_unused]] int role = 0, n_roles = 1;
@@ -1188,7 +1285,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         }
         if (walk.cur >= walk.end) return;
         // per-level geometry into LDS (lanes look up different levels: see LevelTable)
-        int *lv = reinterpret_cast<int *>(s_mem + kRingOff + W * kSlots * 2048);
+        int *lv = reinterpret_cast<int *>(s_mem + kRingO + W * kSlots * 2048);
         long *lv_off = reinterpret_cast<long *>(lv + 5 * kMaxPyrLevels);
         if (threadIdx.x < kMaxPyrLevels) {
             const int l = threadIdx.x;
@@ -1211,8 +1308,10 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         if constexpr (ablate::kConsumerPrio >= 0) __builtin_amdgcn_s_setprio(ablate::kConsumerPrio);
     }
     // DMA writes are lane-linear (lane l -> bytes [16l, 16l+16) of a 1 KiB piece): lane (p, q) moves the 16-B
-    // chunk q of its patch's half-row; the reader (p, q) needs chunks 2(q&1), 2(q&1)+1 of half q>>1.
-    const unsigned char *ring_lane = ring + (q >> 1) * 1024 + ((2 * (q & 1)) * 16 + p) * 16;
+    // chunk q of its patch's half-row; the reader (p, q) needs chunk q of half 0 and its mirror, chunk 3 - q of half 1
+    // (unfolded: chunks 2(q&1), 2(q&1)+1 of half q>>1, 256 bytes apart).
+    const unsigned char *ring_lane = kFold ? ring + (q * 16 + p) * 16 : ring + (q >> 1) * 1024 + ((2 * (q & 1)) * 16 + p) * 16;
+    [[maybe_unused]] const unsigned char *ring_mirror = ring + 1024 + ((3 - q) * 16 + p) * 16;
 
     long batch = walk.cur;
     if (batch >= walk.end) return;
@@ -1229,7 +1328,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 #pragma unroll
             for (int r = -2; r <= 3; ++r) issue_raw_row(src, r, ring, r + 2);
         }
-        issue_lut_row<W>(lut_rows, kSplit ? span.lo : 0, s_mem, wave, lane);
+        issue_lut_row<W, kFold>(lut_rows, kSplit ? span.lo : 0, s_mem, wave, lane);
     }
     int slot0 = 0;   // keypoint mode: ring slot of raw row 0 of the current batch
     unsigned par = 0;  // LUT row buffer holding the row about to be consumed
@@ -1254,10 +1353,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         const RawSrc src = kKp ? RawSrc{nullptr, 0u} : raw_src(pt, batch);
         const RawSrc src_next = !kKp && more ? raw_src(pt, batch + walk.step) : src;
 
-        f32x4 acc[kAccTiles];
+        f32x4 acc[kNAcc];
 #pragma unroll
-        for (int t = 0; t < kAccTiles; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float cur[8], prv[8], cur_l = 0.f, cur_r = 0.f;  // blurred rows g and g-1 (row -1 replicates row 0)
+        for (int t = 0; t < kNAcc; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // blurred rows g and g-1 (row -1 replicates row 0) in the lane's pixel order, and row g just outside the lane's
+        // pixels: folded (blur_row_fold_impl) x = 4q-1, 4q+4, 27-4q, 32-4q; unfolded x = 8q-1, 8q+8
+        float cur[8], prv[8], cur_nb[4] = {0.f, 0.f, 0.f, 0.f};
         int s0 = 1;                                      // ring slot of raw row g-1 (rows g-1..g+3 feed hb(g+1))
 
         // The first and the last row of a batch differ from the 30 between them (two blurs and a later ring request /
@@ -1275,12 +1376,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 __syncthreads();
             }
             phase.mark(0);
-            const unsigned char *brow = s_mem + par * kRowBytes + lane * 16;
+            const unsigned char *brow = s_mem + par * kRowB + lane * 16;
             // row buffer par ^ 1 is free: next LUT row; during row 31 the f16 epilogue's first whitening step instead
             // (keypoint mode: the producer waves request LUT rows 1..31 -- an LDS-DMA request stalls its issuer for 60-180
             // cycles, which a producer can afford -- so a describe wave issues no memory instruction in the row loop)
             if (f16_family(POOL) ? !kLast : (!kLast || more)) {
-                if constexpr (!kKp) issue_lut_row<W>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowBytes, wave, lane);
+                if constexpr (!kKp) issue_lut_row<W, kFold>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowB, wave, lane);
             } else if (f16_family(POOL)) {
                 issue_w_step<W>(wf, 0, s_mem, wave, lane);
             }
@@ -1299,30 +1400,34 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 r_ = r_ < 0 ? 0 : (r_ > 31 ? 31 : r_);
                 return (slot0 + r_) % kRingSlotsKp;
             };
+            // one blurred row, by either lane map; tap(i) = ring slot of the i-th of its five raw rows
+            auto blur = [&](auto tap, float (&o)[8], float (&o_nb)[4]) __attribute__((always_inline)) {
+                if constexpr (kFold) blur_row_fold_impl(ring_lane, ring_mirror, tap, addr_l, addr_r, has_l, has_r, o, o_nb);
+                else blur_row_impl(ring_lane, tap, addr_l, addr_r, has_l, has_r, o, o_nb[0], o_nb[1]);
+            };
+            auto ring_tap = [](int first) {   // patch mode: consecutive slots of the 6-slot ring from `first`
+                return [first](int i) { const int sl = first + i; return sl >= kRingSlots ? sl - kRingSlots : sl; };
+            };
             if (kFirst) {  // first blurred row of the batch: rows -2..2 sit in slots 0..4
-                if constexpr (kKp)
-                    blur_row_impl(ring_lane, [&](int i) { return kp_slot(0, i); }, addr_l, addr_r, has_l, has_r, cur, cur_l, cur_r);
-                else
-                    blur_row(ring_lane, 0, addr_l, addr_r, has_l, has_r, cur, cur_l, cur_r);
+                if constexpr (kKp) blur([&](int i) { return kp_slot(0, i); }, cur, cur_nb);
+                else blur(ring_tap(0), cur, cur_nb);
 #pragma unroll
                 for (int x = 0; x < 8; ++x) prv[x] = cur[x];
             }
             if constexpr (kFirstInner) {   // blurred rows g - 1 and g themselves: nothing replicates
-                float edge_l, edge_r;
-                blur_row_impl(ring_lane, [&](int i) { return kp_slot(g - 1, i); }, addr_l, addr_r, has_l, has_r, prv, edge_l, edge_r);
-                blur_row_impl(ring_lane, [&](int i) { return kp_slot(g, i); }, addr_l, addr_r, has_l, has_r, cur, cur_l, cur_r);
+                float edge[4];
+                blur([&](int i) { return kp_slot(g - 1, i); }, prv, edge);
+                blur([&](int i) { return kp_slot(g, i); }, cur, cur_nb);
             }
-            float nxt[8], nxt_l, nxt_r;
+            float nxt[8], nxt_nb[4] = {0.f, 0.f, 0.f, 0.f};
             if (!kLast) {  // hb(g+1) from raw rows g-1..g+3 = slots s0..s0+4
-                if constexpr (kKp)
-                    blur_row_impl(ring_lane, [&](int i) { return kp_slot(g + 1, i); }, addr_l, addr_r, has_l, has_r, nxt, nxt_l, nxt_r);
-                else
-                    blur_row(ring_lane, s0, addr_l, addr_r, has_l, has_r, nxt, nxt_l, nxt_r);
+                if constexpr (kKp) blur([&](int i) { return kp_slot(g + 1, i); }, nxt, nxt_nb);
+                else blur(ring_tap(s0), nxt, nxt_nb);
             } else {  // row 32 replicates row 31
 #pragma unroll
                 for (int x = 0; x < 8; ++x) nxt[x] = cur[x];
-                nxt_l = cur_l;
-                nxt_r = cur_r;
+#pragma unroll
+                for (int x = 0; x < 4; ++x) nxt_nb[x] = cur_nb[x];
             }
             // the slot of raw row g-2 is free now (its last reader was the blur above when g == 0)
             asm volatile("" ::: "memory");
@@ -1343,8 +1448,16 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {  // patch_gradients.glsl:94-100, two pixels at a time
                     const int x = 2 * e;
-                    const f32x2 left = {x == 0 ? cur_l : cur[x - 1], cur[x]};
-                    const f32x2 right = {cur[x + 1], x == 6 ? cur_r : cur[x + 2]};
+                    f32x2 left, right;
+                    if constexpr (kFold) {   // cur[0..3] ascending in x, cur[4..7] descending (blur_row_fold_impl)
+                        left = e == 0 ? f32x2{cur_nb[0], cur[0]} : e == 1 ? f32x2{cur[1], cur[2]}
+                               : e == 2 ? f32x2{cur[5], cur[6]} : f32x2{cur[7], cur_nb[2]};
+                        right = e == 0 ? f32x2{cur[1], cur[2]} : e == 1 ? f32x2{cur[3], cur_nb[1]}
+                                : e == 2 ? f32x2{cur_nb[3], cur[4]} : f32x2{cur[5], cur[6]};
+                    } else {
+                        left = f32x2{x == 0 ? cur_nb[0] : cur[x - 1], cur[x]};
+                        right = f32x2{cur[x + 1], x == 6 ? cur_nb[1] : cur[x + 2]};
+                    }
                     // left - right, plus +0.0: the value unchanged, but -0.0 (a blurred -0.0 on the left of a +0.0 -- the blur of
                     // negative denormals underflows to it, fma or not) becomes +0.0, so that the sign bit gradient_direction
                     // takes from gx is never the sign of a zero: the shader's (cos, sin) = (1, 0) at gx == -0.0, atan2.glsl:29-45
@@ -1367,15 +1480,22 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 prv[x] = cur[x];
                 cur[x] = nxt[x];
             }
-            cur_l = nxt_l;
-            cur_r = nxt_r;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) cur_nb[x] = nxt_nb[x];
             phase.mark(2);
 
             // m stream x (polar | cartesian) kernels: accumulator tiles 0-2
             BFrag gfrag = load_b(brow, 3);   // first harmonic: P0
             {
                 AFrag<kMPool> am;
-                am.set(m);
+                if constexpr (kFold) {   // [m_e | m_o]
+                    f32x2 mf[4];
+                    fold_sum(m, mf[0], mf[1]);
+                    fold_diff(m, mf[2], mf[3]);
+                    am.set(mf);
+                } else {
+                    am.set(m);
+                }
 #pragma unroll
                 for (int t = 0; t < 3; ++t) mma_part<kMPool, 0>(am, bm[t], acc[t]);
 #pragma unroll
@@ -1384,7 +1504,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 for (int t = 0; t < 3; ++t) mma_part<kMPool, 2>(am, bm[t], acc[t]);
             }
             phase.mark(3);
-            // cos / sin streams of the three harmonics x their four LUT tiles: accumulator tiles 3-23
+            // cos / sin streams of the three harmonics x their LUT tiles: accumulator tiles 3-20 (unfolded: 3-23)
             if constexpr (POOL == LF_POOL_F16_FP6) pool_harmonics_fp6(m, c1, s1, brow, gfrag, acc);
             else pool_harmonics<POOL>(m, c1, s1, brow, gfrag, acc);
             phase.mark(4);
@@ -1432,7 +1552,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 #pragma unroll 1
             for (int r = 0; r + 1 < n_roles; ++r) {
                 const u64 *srcp = reinterpret_cast<const u64 *>(ks.xchg + ((((long)batch * (n_roles - 1) + r) * W + wave) * kAccTiles) * 256) + lane;
-                // a partner's 24 tiles are requested in one go (48 loads in flight: one trip to memory per partner, not per
+                // a partner's 21 tiles are requested in one go (42 loads in flight: one trip to memory per partner, not per
                 // tile -- a workgroup of this form has a SIMD's 512 registers per wave) and added in tile order
                 u64 v[2 * kAccTiles];
 #pragma unroll
@@ -1455,11 +1575,11 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         }
         if constexpr (ablate::kNoEpilogue) {
             f32x4 sum = acc[0];
-            for (int t = 1; t < kAccTiles; ++t) sum += acc[t];
+            for (int t = 1; t < kNAcc; ++t) sum += acc[t];
             if (base + p < n) *reinterpret_cast<f32x4 *>(out + (base + p) * 128 + 4 * q) = sum;
             if (f16_family(POOL)) {
                 __syncthreads();
-                if (more) issue_lut_row<W>(lr, 0, s_mem, wave, lane);
+                if (more) issue_lut_row<W, kFold>(lr, 0, s_mem, wave, lane);
             }
         } else {
             finish_descriptors<POOL, W>(acc, lane, wave, base + p < n, base + p, cm, wf, bs, o, ro, s_mem, lr, more);
@@ -1495,11 +1615,14 @@ void launch_describe(const float *patches, long n, const unsigned long long *n_d
     const unsigned char *lut = pool_mode == LF_POOL_F16_FP6 ? reinterpret_cast<const unsigned char *>(dc.pool_b_fp6)
                                : f16                        ? reinterpret_cast<const unsigned char *>(dc.pool_b_f16)
                                                             : reinterpret_cast<const unsigned char *>(dc.pool_b_f32);
-    const unsigned char *wf = f16 ? reinterpret_cast<const unsigned char *>(dc.white_a_f16)
-                                  : reinterpret_cast<const unsigned char *>(dc.white_a_f32);
+    const bool unfolded = !fold_form(pool_mode);   // LF_POOL_F16_FP6: its own packed order and whitening fragments
+    const unsigned char *wf = unfolded ? reinterpret_cast<const unsigned char *>(dc.white_a_f16_unfolded)
+                              : f16    ? reinterpret_cast<const unsigned char *>(dc.white_a_f16)
+                                       : reinterpret_cast<const unsigned char *>(dc.white_a_f32);
+    const short *colmap = unfolded ? dc.colmap_unfolded : dc.colmap;
 #define LF_LAUNCH_W(A, P, WV)                                                                                          \
     hipLaunchKernelGGL((mkd_pool<A, P, WV, kSrcPatches>), dim3(grid), dim3(64 * WV), 0, stream, patches, n, n_dev, lut, \
-                       dc.colmap, wf, dc.white_bias, out, raw_out, 0, clk)
+                       colmap, wf, dc.white_bias, out, raw_out, 0, clk)
 #define LF_LAUNCH(A, P)            \
     do {                           \
         if (small) LF_LAUNCH_W(A, P, 4); \
@@ -1524,10 +1647,10 @@ void launch_describe(const float *patches, long n, const unsigned long long *n_d
 
 #else   // LF_DESCRIBE_KP
 // Keypoint mode in one launch: 4 describe waves + 4 producer waves per workgroup, 64 keypoints per batch, one workgroup
-// per CU (160 KB of LDS), persistent; requests of at most 8192 keypoints: 2 + 2 waves, 32 keypoints per workgroup (below).
+// per CU (144 KiB of LDS), persistent; requests of at most 8192 keypoints: 2 + 2 waves, 32 keypoints per workgroup (below).
 static long nbatch32(long n) { return (n + 31) / 32; }
 size_t kp_split_exchange_bytes(int num_cus) {
-    // R = 4: num_cus / 4 batches x 3 partial roles; R = 2: num_cus / 2 x 1 -- the larger of the two, x 2 waves x 24 tiles x 1 KiB
+    // R = 4: num_cus / 4 batches x 3 partial roles; R = 2: num_cus / 2 x 1 -- the larger of the two, x 2 waves x 21 tiles x 1 KiB
     return size_t(num_cus / 4 + 8) * 3 * 2 * kAccTiles * 1024;
 }
 size_t kp_split_counter_words(int num_cus) { return 1 + size_t(num_cus / 2 + 8) * 2; }   // the error word, then [batch][wave]

@@ -54,11 +54,14 @@ bool plan_row_bands(int raw_rows, int w, int h, int n_layers, int border, RowBan
 // Device copies of HostConsts' device layouts (mkd_consts.hpp).
 struct DeviceConsts {
     short *colmap = nullptr;        // [336]
-    float *pool_b_f32 = nullptr;    // [32][15][2][64][4]
-    uint16_t *pool_b_f16 = nullptr; // [32][15][2][64][8]
-    uint16_t *pool_b_fp6 = nullptr; // the same row images with fp6 cross-term operands for the harmonics' tiles (mkd_consts.hpp)
+    float *pool_b_f32 = nullptr;    // [32][12][2][64][4]
+    uint16_t *pool_b_f16 = nullptr; // [32][12][2][64][8]
     uint16_t *white_a_f16 = nullptr; // [11][8][2][64][8]
     float *white_a_f32 = nullptr;    // [21][4][8][64]
+    // LF_MKD_POOL_F16_FP6 alone (the unfolded row form; null in the other modes)
+    short *colmap_unfolded = nullptr;         // [336]
+    uint16_t *pool_b_fp6 = nullptr;           // [32][15][2][64][8]
+    uint16_t *white_a_f16_unfolded = nullptr; // [11][8][2][64][8]
     float *white_bias = nullptr;     // [128]  -W mean
 };
 

@@ -7,9 +7,11 @@ import torch
 import local_features_python as lfp
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 18
+# optional second argument: the angle modes to time, e.g. "2" (exact_zero) or "0,1,2"
+angles = [int(a) for a in sys.argv[2].split(",")] if len(sys.argv) > 2 else (lfp.ANGLE_SHADER, lfp.ANGLE_EXACT)
 p = torch.rand((n, 32, 32), device="cuda")
 out = torch.empty((n, 128), device="cuda")
-for angle in (lfp.ANGLE_SHADER, lfp.ANGLE_EXACT):
+for angle in angles:
     for pool in (lfp.POOL_F32, lfp.POOL_F16X3, lfp.POOL_F16_FP6):
         h = lfp.MkdHandle(max_features=n, angle_mode=angle, pool_mode=pool)
         s = torch.cuda.current_stream().cuda_stream
