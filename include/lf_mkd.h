@@ -468,8 +468,11 @@ int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, c
  * order on a tie), which is therefore exactly +1; verified = match with every non-inlier set to -1; stats [n_pairs][4] =
  * {final inlier count, best candidate's inlier count, best candidate's index c = 3 k + j (k the sample, j the candidate's
  * place among that sample's real roots; 0xFFFFFFFF: none), M = matches considered}.
- * The algorithm, exactly (a CPU restatement reproduces every sample: tests/fundamental_ref.py):
- *   1. Considered matches and normalisation: homography step 1, unchanged (the same launch computes them).
+ * The algorithm, exactly (a CPU restatement reproduces every sample: tests/fundamental_ref.py; the kernels' own arithmetic,
+ * built for the host, reproduces every output bit: tests/cpp/fundamental_twin.cpp):
+ *   1. Considered matches and normalisation: homography step 1, unchanged (the same launch computes them).  As there, a NaN
+ *      or infinite coordinate in a considered row leaves the pair without a valid candidate (step 6), and rows that are not
+ *      considered are never read.
  *   2. Sampler: sample k takes draws t = 0..63, r = splitmix64(((uint64)(seed + p) << 32) ^ ((uint64)k << 6) ^ t),
  *      pos = ((r >> 32) * M) >> 32, and keeps the first 7 distinct positions (fewer: the sample is invalid).
  *   3. Minimal solver, f32 on the normalised coordinates, using only correctly rounded operations (+ - * /, sqrt, fma) with
@@ -499,6 +502,16 @@ int lf_mkd_verify_homography_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, c
  *      if its MSAC cost (an inlier adds its Sampson error, any other considered match threshold^2; summed in f64 in a fixed
  *      order) is not above the current F's.  At most 3 rounds, stopping when the inlier set stops changing.
  *   6. M < 7, or no valid candidate: F all zero, verified all -1, final count 0, stats[2] = 0xFFFFFFFF; status LF_MKD_OK.
+ *      That is the outcome whenever every sample's 7 x 9 system is rank deficient: all rows identical, fewer than 7 distinct
+ *      matches, all points of one image on a line.  Matches that satisfy one homography (a plane, a camera that only turns)
+ *      leave a one-parameter family of F: samples whose last pivot is rounding noise above 1e-5 of the first still give
+ *      candidates, and every one of them fits the matches; which is returned carries no information about the scene.
+ *   Precision.  Steps 2, 3 and 5 work in the normalised coordinates and do not depend on where the origin is.  Step 4 and
+ *   the returned F do: in pixel coordinates F's constant entry is of the order of C^2 times its leading ones for points at a
+ *   distance C from the origin, and every f32 rounding of it moves the epipolar lines by about C^2 2^-24 / (image extent)
+ *   pixels -- 0.001 px for a 1000 px frame at the origin, a pixel at C = 1e5.  Translate coordinates that far away first.
+ *   The threshold's smallest accepted values are below what step 4 resolves: a match whose f32 Sampson numerator does not
+ *   round to less than threshold^2 times the denominator is not an inlier, be it one of the sample's own seven.
  * The bits of every output depend on the pair's inputs, seed + p, n_hypotheses, threshold and flags alone: pair p of a
  * batched call equals a single-pair call with seed + p, and a captured call replays to the same bits. */
 

@@ -6,6 +6,8 @@
 #include <functional>
 #include <stdint.h>
 
+#include "mkd_verify_pair.h"
+
 #define LF_ANGLE_SHADER 0
 #define LF_ANGLE_EXACT 1
 #define LF_ANGLE_EXACT_ZERO 2   // exact direction, but angle 0 where gx == 0 like the shader
@@ -186,11 +188,7 @@ void launch_match_verify(const float *a, long na, const float *b, const float *a
 // RANSAC homography verification (mkd_verify.hip; algorithm: include/lf_mkd.h).  Keypoints are read as rows of 5 floats
 // (lf_mkd_keypoint).  Scratch the caller owns: pairs [n_pairs], counts [n_pairs][slices][n_hyp]; `verified` also holds each
 // pair's list of considered rows between the first and the last of the call's three launches.
-struct VerifyPair {
-    float ca[2], sa;   // a: centroid, scale (RMS distance from the centroid becomes sqrt(2))
-    float cb[2], sb;   // b: the same
-    unsigned m, pad;   // considered matches
-};
+// (VerifyPair, a pair's normalisation: mkd_verify_pair.h)
 // row slices per (pair, hypothesis block) of the scoring launch: enough workgroups to fill the chip for few pairs
 unsigned verify_slices(unsigned n_pairs, unsigned n_hyp, int num_cus);
 void launch_verify(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
+#include "mkd_verify_host.h"   // kInvalid, splitmix64, cholesky8: what a host compiler shares with the kernels
 
 #pragma clang fp contract(off)
 
@@ -15,15 +16,7 @@ namespace {
 
 constexpr int kThreads = 256;                  // every verification kernel: 4 waves
 constexpr int kWaves = kThreads / 64;
-constexpr unsigned kInvalid = 0xFFFFFFFFu;
 constexpr unsigned kMaxSlices = 16;            // row slices per (pair, hypothesis block) of a scoring launch
-
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // rows [lo, hi) of a pair, as the offsets give them (a pair whose offsets decrease is empty)
 __device__ __forceinline__ uint64_t pair_rows(const uint64_t *off, unsigned p, uint64_t &lo) {
@@ -71,49 +64,6 @@ __device__ __forceinline__ void block_sum(T *v, T *red) {
         v[i] = s;
     }
     __syncthreads();
-}
-
-// Solves N x = r in place (x returned in r) for a symmetric 8x8 N by Cholesky; false if a pivot is at or below 1e-12 of N's
-// largest diagonal element (or that element is not positive).  Every loop has constant bounds: the matrix stays in registers.
-__host__ __device__ __forceinline__ bool cholesky8(double (&N)[8][8], double (&r)[8]) {
-    double dmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dmax = fmax(dmax, N[i][i]);
-    const double floor = 1e-12 * dmax;
-    bool ok = dmax > 0.0;
-    // N = L L^T in the upper triangle read as L^T (row i of L^T = column i of L)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        double d = N[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= N[k][j] * N[k][j];
-        ok = ok && d > floor;
-        const double l = sqrt(fmax(d, floor));
-        N[j][j] = l;
-#pragma unroll
-        for (int i = j + 1; i < 8; ++i) {
-            double s = N[j][i];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= N[k][j] * N[k][i];
-            N[j][i] = s / l;
-        }
-    }
-    // L y = r, then L^T x = y
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= N[k][i] * r[k];
-        r[i] = s / N[i][i];
-    }
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = i + 1; k < 8; ++k) s -= N[i][k] * r[k];
-        r[i] = s / N[i][i];
-    }
-    return ok;
 }
 
 }  // namespace

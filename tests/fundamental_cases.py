@@ -1,5 +1,6 @@
 """Synthetic two-view problems the fundamental-matrix tests share (tests/test_fundamental_api.py,
-tests/test_gpu_fundamental.py): random 3-D points seen by two cameras with known K, R and t, so that
+tests/test_gpu_fundamental.py, tests/test_fundamental_twin.py, tests/test_gpu_fundamental_exact.py): random 3-D points
+seen by two cameras with known K, R and t, so that
 F_true = K^-T [t]x R K^-1 (b^T F a = 0 for a in view 1 and b in view 2), with 0.5 px noise and planted outliers."""
 import numpy as np
 
@@ -94,6 +95,29 @@ def band(prob, f, thr=THR, rel=0.05):
     return ~np.isfinite(e) | (np.abs(e - thr * thr) <= rel * thr * thr)
 
 
+def f32_band(prob, f, thr=THR, roundings=16):
+    """Considered matches that f32 arithmetic in pixel coordinates cannot decide under f: e = b . F a is a sum of nine
+    products b_j F_jk a_k, and F's entries (after the denormalisation: up to 6 roundings on the constant entry) and the
+    Sampson test's fused steps (2 per line coefficient, 3 for e) each round at 2^-24 of a partial sum no larger than
+    T = sum |b_j F_jk a_k|.  So the computed |e| is off by at most roundings * 2^-24 * T with roundings = 16, and a match is
+    undecided when | |e| - thr sqrt(l0^2 + l1^2 + l'0^2 + l'1^2) | is within that.  For coordinates within a frame at the
+    origin this is a fraction of the 5 % band; at an offset C it grows with C^2, and at a threshold below f32's
+    resolution it is what remains."""
+    f = np.asarray(f, np.float64).reshape(3, 3)
+    ah = np.concatenate([prob.a, np.ones((prob.m, 1))], axis=1)
+    bh = np.concatenate([prob.b, np.ones((prob.m, 1))], axis=1)
+    with np.errstate(all="ignore"):
+        t = np.einsum("ij,jk,ik->i", np.abs(bh), np.abs(f), np.abs(ah))
+        num, den = prob.sampson(f)
+        gap = np.abs(np.sqrt(num) - thr * np.sqrt(den))
+        return ~np.isfinite(gap) | (gap <= roundings * 2.0 ** -24 * t)
+
+
+def undecided(prob, f, thr=THR):
+    """band() or f32_band(): the matches on which an f32 and an f64 evaluation of the Sampson test under f may differ."""
+    return band(prob, f, thr) | f32_band(prob, f, thr)
+
+
 def pairs(n_pairs=48):
     """A ragged batch: empty pairs, M < 7, M = 7 exactly, and ordinary problems of every family with rows that do not
     count (-1 and out-of-range matches) and b rows nobody matches."""
@@ -118,4 +142,72 @@ def pairs(n_pairs=48):
             mt[g.random(n) < 0.25] = -1
             mt[g.random(n) < 0.02] = len(kb) + 3
         out.append((ka, kb, mt))
+    return out
+
+
+# ---- edge cases (tests/test_fundamental_twin.py: twin against the restatement; tests/test_gpu_fundamental_exact.py: device
+# against the twin).  What include/lf_mkd.h promises of each is asserted by those tests. -------------------------------
+THR_MIN, THR_MAX = 1.0842022e-19, 1.8446743e19   # the smallest and the largest threshold the entry points accept
+
+
+def _with_outliers(g, a, b, outliers, sigma):
+    m = len(a)
+    bn = b + g.normal(0, sigma, b.shape)
+    out = g.random(m) < outliers
+    bn[out] = g.uniform([0, 0], [WIDTH, HEIGHT], (int(out.sum()), 2))
+    ka, kb = _rows(a, bn)
+    return ka, kb, np.arange(m, dtype=np.int32)
+
+
+def _plane_points(g, m):
+    """m points of the plane Z = 8 + 0.3 (x - W/2) / W seen by the near_planar cameras: b is a homography of a."""
+    r, t = MOTIONS["near_planar"]
+    uv = g.uniform([0, 0], [WIDTH, HEIGHT], (m, 2))
+    z = 8.0 + 0.3 * (uv[:, 0] - WIDTH / 2) / WIDTH
+    x = np.concatenate([(uv - K[:2, 2]) / K[0, 0] * z[:, None], z[:, None]], axis=1)
+    return _project(K, x), _project(K, x @ r.T + t)
+
+
+def edge_cases(m=200):
+    """[(name, ka, kb, match, threshold)]: degenerate geometry, repeated rows, a large coordinate offset and the two ends of
+    the threshold's range."""
+    g = np.random.default_rng(23)
+    out = []
+    a, b = _plane_points(g, m)
+    out.append(("plane_exact", *_with_outliers(g, a, b, 0.0, 0.0), THR))
+    out.append(("plane_noisy", *_with_outliers(g, a, b, 0.3, 0.5), THR))
+    ka, kb, mt, _ = two_view(m, 0.3, 31)
+    ka[:, 1] = np.float32(0.3) * ka[:, 0] + np.float32(100.0)          # every a point on one line
+    out.append(("collinear_a", ka, kb, mt, THR))
+    ka, kb = _rows(np.tile([[100.0, 200.0]], (50, 1)), np.tile([[300.0, 250.0]], (50, 1)))
+    out.append(("identical_rows", ka, kb, np.arange(50, dtype=np.int32), THR))
+    a8 = np.tile([[400.0, 300.0]], (8, 1))
+    b8 = np.tile([[420.0, 310.0]], (8, 1))
+    a8[7], b8[7] = (100.0, 50.0), (140.0, 90.0)
+    out.append(("seven_repeated", *_rows(a8, b8), np.arange(8, dtype=np.int32), THR))
+    rot = K @ rotation(2.0, -4.0, 3.0) @ np.linalg.inv(K)               # t = 0: b = K R K^-1 a, a homography
+    a = g.uniform([0, 0], [WIDTH, HEIGHT], (m, 2))
+    bh = np.concatenate([a, np.ones((m, 1))], axis=1) @ rot.T
+    out.append(("pure_rotation", *_with_outliers(g, a, bh[:, :2] / bh[:, 2:], 0.3, 0.5), THR))
+    ka, kb, mt, _ = two_view(m, 0.4, 37)
+    ka[:, :2] += np.float32(1e5)
+    kb[:, :2] += np.float32(1e5)
+    out.append(("large_offset", ka, kb, mt, THR))
+    ka, kb, mt, _ = two_view(m, 0.4, 41)
+    out.append(("threshold_min", ka, kb, mt, THR_MIN))
+    out.append(("threshold_max", ka, kb, mt, THR_MAX))
+    return out
+
+
+BAD_ROW = 5
+
+
+def non_finite(bad, m=300):
+    """Four copies of one problem with `bad` (NaN, +Inf or -Inf) in considered row BAD_ROW: a.x, a.y, b.x, b.y."""
+    ka, kb, mt, _ = two_view(m, 0.4, 43)
+    out = []
+    for which, col in ((0, 0), (0, 1), (1, 0), (1, 1)):
+        a, b = ka.copy(), kb.copy()
+        (a if which == 0 else b)[BAD_ROW, col] = bad
+        out.append((a, b, mt))
     return out

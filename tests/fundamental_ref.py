@@ -37,12 +37,16 @@ def design_rows(an, bn):
     return np.stack([u * x, u * y, u, v * x, v * y, v, x, y, np.ones_like(x)], axis=1)
 
 
-def null_space(a):
+def null_space(a, info=None):
     """(F1, F2) of the 7 x 9 system by Gauss-Jordan with full pivoting (the kernel's rule), or None if a pivot is not above
-    PIVOT_REL times the first."""
+    PIVOT_REL times the first.  `info` (a dict) receives how close the decisions were: pivot_ratio = the smallest
+    pivot / first pivot seen, pivot_tie = the smallest (pivot - runner-up) / pivot over the steps, the runner-up being the
+    largest eligible |entry| strictly below the pivot (1 if there is none)."""
     a = np.array(a, np.float64)
     used_r, used_c, piv = set(), set(), {}
     first = None
+    if info is not None:
+        info.update(pivot_ratio=1.0, pivot_tie=1.0)
     for _ in range(7):
         best, pr, pc = -1.0, 0, 0
         for r in range(7):
@@ -50,6 +54,12 @@ def null_space(a):
                 if r not in used_r and c not in used_c and abs(a[r, c]) > best:
                     best, pr, pc = abs(a[r, c]), r, c
         first = best if first is None else first
+        if info is not None and np.isfinite(best) and best > 0 and first > 0:
+            free = np.abs(a[np.ix_([r for r in range(7) if r not in used_r], [c for c in range(9) if c not in used_c])])
+            below = free[free < best]
+            info["pivot_ratio"] = min(info["pivot_ratio"], best / first)
+            if below.size:
+                info["pivot_tie"] = min(info["pivot_tie"], (best - below.max()) / best)
         if not (best > PIVOT_REL * first) or not np.isfinite(best):
             return None
         prow = a[pr].copy()
@@ -83,9 +93,14 @@ def cubic_coefficients(f1, f2):
     return float(g[:3] @ cg[:3]), float(cg @ d), float(cd @ g), float(d[:3] @ cd[:3])
 
 
-def cubic_roots(c0, c1, c2, c3, bisect=80, newton=4):
-    """Real roots, ascending, by the kernel's bracketing (three monotone pieces of [-R, R]), bisection and Newton."""
+def cubic_roots(c0, c1, c2, c3, bisect=80, newton=4, info=None):
+    """Real roots, ascending, by the kernel's bracketing (three monotone pieces of [-R, R]), bisection and Newton.  `info`
+    (a dict) receives how close the decisions were: lead = |c3| / max(|c0|, |c1|, |c2|), and end_value = the smallest
+    |p(e)| / (|c3 e^3| + |c2 e^2| + |c1 e| + |c0|) over the derivative's roots e that cut the bracket (1 if there are none)."""
     big = max(abs(c0), abs(c1), abs(c2))
+    if info is not None:
+        with np.errstate(all="ignore"):
+            info.update(lead=abs(c3) / big if big > 0 and np.isfinite(big) else np.inf, end_value=1.0)
     if not all(np.isfinite([c0, c1, c2, c3])) or not abs(c3) > LEAD_REL * big:
         return []
     p = lambda x: ((c3 * x + c2) * x + c1) * x + c0
@@ -99,6 +114,10 @@ def cubic_roots(c0, c1, c2, c3, bisect=80, newton=4):
         r1, r2 = q / t, c1 / q
         e1 = min(max(min(r1, r2), -r_bound), r_bound)
         e2 = min(max(max(r1, r2), -r_bound), r_bound)
+        if info is not None:
+            for e in (e1, e2):
+                scale = abs(c3 * e ** 3) + abs(c2 * e * e) + abs(c1 * e) + abs(c0)
+                info["end_value"] = min(info["end_value"], abs(p(e)) / scale if scale > 0 else 0.0)
     ends = [-r_bound, e1, e2, r_bound]
     roots = []
     for lo, hi in zip(ends[:-1], ends[1:]):
@@ -175,18 +194,19 @@ class Problem:
         pos = sample(seed_p, k, self.m)
         return None if pos is None else design_rows(self.an[pos], self.bn[pos])
 
-    def candidates(self, seed_p, k):
-        """[3] list of (F pixels, Fn normalised scaled by its largest |entry|) or None, in the kernel's slot order."""
+    def candidates(self, seed_p, k, info=None):
+        """[3] list of (F pixels, Fn normalised scaled by its largest |entry|) or None, in the kernel's slot order.  `info`:
+        as null_space's and cubic_roots', for this sample."""
         out = [None, None, None]
         a = self.sample_rows(seed_p, k)
         if a is None:
             return out
-        ns = null_space(a)
+        ns = null_space(a, info)
         if ns is None:
             return out
         f1, f2 = ns
         d = f1 - f2
-        for j, lam in enumerate(cubic_roots(*cubic_coefficients(f1, f2))):
+        for j, lam in enumerate(cubic_roots(*cubic_coefficients(f1, f2), info=info)):
             g = f2 + lam * d
             big = np.abs(g).max()
             if not (np.isfinite(big) and big > 0):
