@@ -335,10 +335,16 @@ int lf_mkd_stream_frame(lf_mkd *h, void *stream);
  *              used for mid-sized problems;
  *   screen  -- two passes, for na >= 16384 and na * nb >= 2^29: every pair is screened with the f16 roundings of both sides
  *              (one term; error bounded by ~1e-3 |a||b|, from the rows' norms), every candidate within that bound of a row's
- *              second best is re-scored as an f32 dot product, and the decision is taken on the re-scored values, i.e. the
- *              result of an exhaustive f32 scan; ~5.9e12 pairs/s.  A row with more than 64 such candidates in one lane's
- *              share of b (hundreds of near-duplicates of its best match) is redone by the scan form inside the same call,
- *              decided on the device.
+ *              second best is re-scored as an f32 dot product, and the decision is taken on the re-scored values: for every
+ *              row that is not redone (below), best, second and match are those of an exhaustive scan of b with that dot
+ *              product, bit for bit -- 16 partial sums, partial l being a[8l] * b[8l] followed by fmaf(a[8l+j], b[8l+j], .)
+ *              for j = 1 .. 7, added as p[l] += p[l ^ 8], then ^ 4, ^ 2, ^ 1, all in f32; the higher index wins among equal
+ *              similarities (tests/cpp/match_twin.cpp is that scan on the host); ~5.9e12 pairs/s.  A row with more than 64
+ *              such candidates in one lane's share of b (hundreds of near-duplicates of its best match) is redone by the scan
+ *              form inside the same call, decided on the device, and carries that form's ~2^-21 instead;
+ *              lf_mkd_match_overflowed counts those rows.  (Experiments: LF_MKD_MATCH_SPLITS = b splits;
+ *              LF_MKD_MATCH_SHARE = stages between two exchanges of the splits' shared bounds, 0 = none -- 1 publishes the
+ *              bounds and never takes them, since a bound is taken one stage after it was asked for.)
  * LF_MKD_MATCH=small, =scan or =screen in the environment forces a form (small: where it fits -- also nb >= 128 or na <= 4096 --
  * else scan).  Elements must be finite and below 65504 in magnitude (f16 range).
  * Device pointers, asynchronous on `stream`.  d_a and d_b must be 16-byte aligned (rows are read as 16-byte vectors; any
