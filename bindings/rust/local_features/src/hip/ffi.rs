@@ -160,6 +160,14 @@ extern "C" {
                                      d_b: *const f32, d_offsets_b: *const u64, nb_total: u64, n_pairs: u32, ratio: f32,
                                      flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut f32,
                                      d_second: *mut f32, stream: *mut c_void) -> c_int;
+    // the same batch under each pair's verified model (d_model [n_pairs][9], kind: GUIDE_HOMOGRAPHY / GUIDE_FUNDAMENTAL of
+    // mod.rs): a row's candidates are the rows that pass the verifier's inlier test with it
+    pub fn lf_mkd_match_guided_pairs_device(h: *mut lf_mkd, d_a: *const f32, d_kps_a: *const lf_mkd_keypoint,
+                                            d_offsets_a: *const u64, na_total: u64, d_b: *const f32,
+                                            d_kps_b: *const lf_mkd_keypoint, d_offsets_b: *const u64, nb_total: u64,
+                                            d_model: *const f32, n_pairs: u32, kind: u32, threshold_px: f32, ratio: f32,
+                                            flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut f32,
+                                            d_second: *mut f32, stream: *mut c_void) -> c_int;
     pub fn lf_mkd_match(h: *mut lf_mkd, a: *const f32, na: u64, b: *const f32, nb: u64, ratio: f32,
                         matches: *mut i32) -> c_int;
     pub fn lf_mkd_match_overflowed(h: *mut lf_mkd, stream: *mut c_void, n_rows: *mut u64) -> c_int;

@@ -75,6 +75,11 @@ pub const VERIFY_NO_REFINE: u32 = 1;
 /// match is kept only if the other direction agrees.
 pub const MATCH_MUTUAL: u32 = 1;
 
+/// `kind` of `lf_mkd_match_guided_pairs_device` (`include/lf_mkd.h`, `LF_MKD_GUIDE_HOMOGRAPHY` / `LF_MKD_GUIDE_FUNDAMENTAL`):
+/// what a pair's nine model floats are -- the H or the F its verifier wrote.
+pub const GUIDE_HOMOGRAPHY: u32 = 0;
+pub const GUIDE_FUNDAMENTAL: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,

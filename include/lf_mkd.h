@@ -394,6 +394,50 @@ int lf_mkd_match_pairs_device(lf_mkd *h, const float *d_a, const uint64_t *d_off
                               const float *d_b, const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs,
                               float ratio, uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba, float *d_best,
                               float *d_second, void *stream);
+/* Guided matching: lf_mkd_match_pairs_device once more, under each pair's verified model.  Once lf_mkd_verify_homography_device
+ * or lf_mkd_verify_fundamental_device has given pair p its H or F, the ratio test is run again over only the candidates the
+ * geometry allows: the rows of the other side inside a transfer disc (H) or an epipolar band (F).  That recovers matches which
+ * the unrelated rows of a whole frame suppressed, and the second best is then a competitor in the same place.
+ *   Layout, offset rules, outputs and LF_MKD_MATCH_MUTUAL are exactly those of lf_mkd_match_pairs_device: offsets on the device
+ *   and never read by the host; an offset beyond a total is read as the total, an inverted pair is empty; match values are
+ *   local to the pair; rows outside the pairs are untouched.  d_kps_a [na_total] / d_kps_b [nb_total] are indexed like the
+ *   descriptor rows; only x and y are read.  d_model is [n_pairs][9] floats, exactly what the verifiers write as d_H / d_F.
+ * Candidates: row j of pair p's b side is admissible for row i of its a side iff the verifier's own step-4 test (below) holds
+ * for the point pair (a_i, b_j) with thr2 = threshold_px * threshold_px formed as the verifiers form it -- the same correctly
+ * rounded operations in the same order:
+ *   LF_MKD_GUIDE_HOMOGRAPHY   u, v, w = H a;  w > 0  and  fmaf(ex, ex, ey * ey) < thr2 * (w * w),  ex = fmaf(bx, w, -u), ey likewise
+ *   LF_MKD_GUIDE_FUNDAMENTAL  the Sampson test  e^2 < thr2 * (l0^2 + l1^2 + l'0^2 + l'1^2),  l = F a, l' = F^T b, e = b . l
+ * Both directions use the SAME relation: the candidates of b row j in the b -> a direction are the a rows i with
+ * admissible(a_i, b_j); no inverse model is formed, so the relation is symmetric by construction and the mutual rule
+ * meaningful.  An all-zero model (what verification writes when it found nothing), a NaN anywhere in the model and a NaN
+ * coordinate need no special case: the comparison is false, the row has no candidate.
+ * Decision, per row: best and second are the largest and the next similarity over the admissible rows ONLY -- the one-launch
+ * form's similarity, the same three terms in the same order, ties to the highest index; match = the best's index if
+ * ratio <= 0 or best * ratio > second, else -1.  A row with one candidate has second = -inf and is accepted; a row with none
+ * gets -1 and -inf in both scores.  There is no refusal of a small side here (nb_p < 2 is fine): one row is a legitimate
+ * candidate set.  The result of a pair depends neither on n_pairs, nor on the other pairs, nor on the run.
+ * Superset property: take `verified` from lf_mkd_verify_*_device run on the LF_MKD_MATCH_MUTUAL output of
+ * lf_mkd_match_pairs_device; run this call with that model, the same kind, the same ratio, LF_MKD_MATCH_MUTUAL and a
+ * threshold not below the verifier's.  Then every verified[i] = j >= 0 has match_ab[i] == j and match_ba[j] == i: j was i's
+ * best over a superset of the admissible rows, with ties to the highest index, so it is the best of the subset; the subset's
+ * second is not above the superset's, so the ratio test still passes; the reverse direction likewise; and thr2 * den is
+ * monotone in thr2, so an inlier of the verifier is admissible here.  Guided matching never loses a verified match.
+ * Cost: a 16 x 16 tile of candidates is tested on 8 bytes per row before any of its descriptors is requested, and a tile
+ * without an admissible pair is skipped whole -- under a homography, almost every tile.
+ * One launch (three with LF_MKD_MATCH_MUTUAL), no scratch and no allocation, asynchronous on `stream` (NULL: the handle's own):
+ * capturable in a hipGraph.  n_pairs == 0 is LF_MKD_OK and writes nothing.  LF_MKD_ERR_BAD_ARG, reported before any device is
+ * touched (the message starts with "match_guided_pairs_device" and is reachable through lf_mkd_last_error(NULL) when h is
+ * NULL): a null handle; null d_a, d_b, d_kps_a, d_kps_b, offsets, d_model or d_match_ab; LF_MKD_MATCH_MUTUAL without
+ * d_match_ba; unknown flag bits; kind > 1; threshold_px not positive or its f32 square not a finite normal number (the
+ * verifiers' rule); d_a or d_b not 16-byte aligned; a total above 2^31 - 1; floor(na_total / 16) + n_pairs (plus the same
+ * over b when d_match_ba is given) above 2^31 - 1 workgroups.
+ * (LF_MKD_GUIDE_* and LF_MKD_MATCH_MUTUAL are defined with the verifiers' flag, below their prototypes.) */
+int lf_mkd_match_guided_pairs_device(lf_mkd *h, const float *d_a, const lf_mkd_keypoint *d_kps_a,
+                                     const uint64_t *d_offsets_a, uint64_t na_total, const float *d_b,
+                                     const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, uint64_t nb_total,
+                                     const float *d_model, uint32_t n_pairs, uint32_t kind, float threshold_px, float ratio,
+                                     uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba, float *d_best,
+                                     float *d_second, void *stream);
 /* Host pointers, synchronous. */
 int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_t nb, float ratio,
                  int32_t *match);
@@ -538,6 +582,8 @@ int lf_mkd_verify_fundamental_device(lf_mkd *h, const lf_mkd_keypoint *d_kps_a, 
 
 #define LF_MKD_VERIFY_NO_REFINE 1u   /* report the best RANSAC candidate as is: no least-squares refit (both verifiers) */
 #define LF_MKD_MATCH_MUTUAL 1u       /* lf_mkd_match_pairs_device: keep a match only if the other direction agrees */
+#define LF_MKD_GUIDE_HOMOGRAPHY 0u   /* lf_mkd_match_guided_pairs_device, kind: d_model holds the pairs' H (b ~ H a) */
+#define LF_MKD_GUIDE_FUNDAMENTAL 1u  /* ... the pairs' F (b^T F a = 0) */
 
 /* ---- multi-GPU: the path's ONE collective (BASELINE configs[3]) -------------------------------------------------
  * Keypoint batches shard by image, one process and one handle per GPU, and nothing is exchanged while describing.  The

@@ -1792,6 +1792,41 @@ int lf_mkd_match_pairs_device(lf_mkd *h, const float *d_a, const uint64_t *d_off
     return LF_MKD_OK;
 }
 
+// Guided matching: the same batch under each pair's verified model.  Arguments are checked as above, before the handle.
+int lf_mkd_match_guided_pairs_device(lf_mkd *h, const float *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                     uint64_t na_total, const float *d_b, const lf_mkd_keypoint *d_kps_b,
+                                     const uint64_t *d_offsets_b, uint64_t nb_total, const float *d_model, uint32_t n_pairs,
+                                     uint32_t kind, float threshold_px, float ratio, uint32_t flags, int32_t *d_match_ab,
+                                     int32_t *d_match_ba, float *d_best, float *d_second, void *stream) {
+    const bool mutual = flags & LF_MKD_MATCH_MUTUAL;
+    const char *msg = nullptr;
+    if (!d_a || !d_b || !d_kps_a || !d_kps_b || !d_offsets_a || !d_offsets_b || !d_model || !d_match_ab) msg = "null pointer";
+    else if (flags & ~LF_MKD_MATCH_MUTUAL) msg = "unknown flag bits";
+    else if (mutual && !d_match_ba) msg = "LF_MKD_MATCH_MUTUAL needs d_match_ba";
+    else if (kind > LF_MKD_GUIDE_FUNDAMENTAL) msg = "kind must be LF_MKD_GUIDE_HOMOGRAPHY or LF_MKD_GUIDE_FUNDAMENTAL";
+    // (the verifiers' rule, verify_args below: the kernel compares against thr^2 in f32)
+    else if (!(threshold_px > 0.f) || !std::isnormal(threshold_px * threshold_px))
+        msg = "threshold_px must be positive, with a finite normal f32 square (about 1.09e-19 .. 1.84e19)";
+    else if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 15) msg = "d_a and d_b must be 16-byte aligned";
+    else if (na_total > 0x7FFFFFFFull || nb_total > 0x7FFFFFFFull) msg = "more than 2^31 - 1 rows on a side";
+    else if (match_pairs_slots(na_total, n_pairs) + (d_match_ba ? match_pairs_slots(nb_total, n_pairs) : 0) > 0x7FFFFFFFull)
+        msg = "too many rows and pairs for one call (the grid needs floor(rows / 16) + n_pairs workgroups per direction, "
+              "at most 2^31 - 1 in all)";
+    else if (!h) msg = "null handle";
+    if (msg) {
+        (h ? h->err : g_create_error) = std::string("match_guided_pairs_device: ") + msg;
+        return LF_MKD_ERR_BAD_ARG;
+    }
+    if (n_pairs == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    launch_match_guided_pairs(d_a, reinterpret_cast<const float *>(d_kps_a), d_offsets_a, na_total, d_b,
+                              reinterpret_cast<const float *>(d_kps_b), d_offsets_b, nb_total, d_model, n_pairs, kind,
+                              threshold_px, ratio, mutual, d_match_ab, d_match_ba, d_best, d_second, s);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows) {
     if (!h) return LF_MKD_ERR_BAD_ARG;
     if (!n_rows) return fail(h, LF_MKD_ERR_BAD_ARG, "match_overflowed: null pointer");

@@ -1,5 +1,5 @@
 // Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_verify.hip, mkd_fundamental.hip).
+// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_guided.hip, mkd_verify.hip, mkd_fundamental.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -166,6 +166,16 @@ uint64_t match_pairs_slots(uint64_t n_total, unsigned n_pairs);
 void launch_match_small_pairs(const float *a, const uint64_t *off_a, uint64_t na_total, const float *b, const uint64_t *off_b,
                               uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab, int *match_ba,
                               float *best, float *second, unsigned *overflowed_word, hipStream_t stream);
+// LF_MKD_MATCH_MUTUAL's two element-wise launches over both match arrays of such a batch (the guided call's as well)
+void launch_match_mutual(const uint64_t *off_a, uint64_t na_total, const uint64_t *off_b, uint64_t nb_total, unsigned n_pairs,
+                         int *match_ab, int *match_ba, hipStream_t stream);
+// guided matching (csrc/mkd_match_guided.hip, lf_mkd_match_guided_pairs_device): the same batch, the same slot map and
+// workgroup body, but a row's candidates are the rows of the other side that pass the verifier's inlier test with it under
+// the pair's model [n_pairs][9] (kind 0: homography, 1: fundamental matrix); kps_a / kps_b rows of 5 floats (x, y read)
+void launch_match_guided_pairs(const float *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total, const float *b,
+                               const float *kps_b, const uint64_t *off_b, uint64_t nb_total, const float *model,
+                               unsigned n_pairs, unsigned kind, float threshold, float ratio, bool mutual, int *match_ab,
+                               int *match_ba, float *best, float *second, hipStream_t stream);
 // the same scan over the overflowed rows alone (few_words: their indices first, written by launch_match_verify)
 size_t match_few_tiles_bytes();
 size_t match_few_words();

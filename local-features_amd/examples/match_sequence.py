@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_sequence [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
+"""match_sequence [--fundamental] [--guided] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
 device, every stage launched once for all of them and nothing copied to the host in between:
 
   detect_top_n(2000, min_size 0) on all frames      lf_mkd_detect_frames_device
@@ -8,8 +8,11 @@ device, every stage launched once for all of them and nothing copied to the host
   0.8 ratio test, cross-check                        filter launches for all pairs (lf_mkd_match_pairs_device)
   RANSAC homography (3 px) per pair, or with         LocalFeatures.verify_homography_batch / verify_fundamental_batch
   --fundamental epipolar geometry (1.5 px)
+  with --guided: every pair matched again under its   LocalFeatures.match_guided_batch (lf_mkd_match_guided_pairs_device):
+  model, then verified once more with the same seed   candidates restricted to the model's transfer disc / epipolar band
 
-and prints one line per pair: ratio-test matches t -> t + 1, those the other direction confirms, those the geometry keeps.
+and prints one line per pair: ratio-test matches t -> t + 1, those the other direction confirms, those the geometry keeps
+(and with --guided: the guided mutual matches -- never fewer than the geometry kept -- and those the second verification keeps).
 The frames are ONE descriptor array; the matcher is given it twice -- with the offsets of frames 0 .. N-2 as the a side and
 with the offsets of frames 1 .. N-1 as the b side -- so no row is duplicated.
 
@@ -28,10 +31,11 @@ def load_gray(path):
     return np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
 
 
-def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None):
+def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None, guided=False):
     """frames [n, h, w] float32 in [0, 1].  Returns device tensors (keypoints [m,5], descriptors [m,128], frame offsets
     [n + 1], mutual matches t -> t + 1 [m] local to frame t + 1, verified matches [m], model [n - 1,3,3], per pair
-    [n - 1, 3]: ratio-test matches, mutual matches, verified inliers)."""
+    [n - 1, 3]: ratio-test matches, mutual matches, verified inliers).  guided: the matches, the verified matches and the
+    model are those of the guided second pass, and per pair has two more columns: guided mutual matches, verified again."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -58,27 +62,35 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
         # cross-check leaves as the a -> b direction found them
         in_pair = frame_of < n - 1
         count = lambda mask: torch.bincount(frame_of[mask & in_pair], minlength=n)[:n - 1]
-        per_pair = torch.stack([count(best * ratio > second), count(m_ab >= 0), count(ver >= 0)], dim=1)
+        columns = [count(best * ratio > second), count(m_ab >= 0), count(ver >= 0)]
+        if guided:
+            # the verifier's model, threshold (the defaults of both calls) and ratio: every verified match is found again
+            m_ab, _, _, _ = feats.match_guided_batch(desc, kps, oa, desc, kps, ob, model,
+                                                     kind="fundamental" if fundamental else "homography", ratio=ratio, mutual=True)
+            model, ver, stats = verify(kps, oa, kps, ob, m_ab, seed=seed)
+            columns += [count(m_ab >= 0), count(ver >= 0)]
+        per_pair = torch.stack(columns, dim=1)
     return kps, desc, o, m_ab, ver, model, per_pair
 
 
 def main():
     args = sys.argv[1:]
-    fundamental = "--fundamental" in args
-    args = [a for a in args if a != "--fundamental"]
+    fundamental, guided = "--fundamental" in args, "--guided" in args
+    args = [a for a in args if a not in ("--fundamental", "--guided")]
     if len(args) < 2:
-        print("Required arguments: [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
+        print("Required arguments: [--fundamental] [--guided] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
         return 1
     imgs = [load_gray(a) for a in args]
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental)
+    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental, guided=guided)
     o, per_pair = o.cpu().tolist(), per_pair.cpu().tolist()
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
-    for t, (raw, mutual, inl) in enumerate(per_pair):
-        print(f"Pair {t + 1} -> {t + 2}: {raw} matches, {mutual} mutual, {inl} agree with {what}")
+    for t, (raw, mutual, inl, *again) in enumerate(per_pair):
+        more = f", {again[0]} guided, {again[1]} agree after re-verification" if guided else ""
+        print(f"Pair {t + 1} -> {t + 2}: {raw} matches, {mutual} mutual, {inl} agree with {what}{more}")
     return 0
 
 

@@ -14,13 +14,13 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
                    MkdHandle, comm_unique_id, load_library, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
-           "VERIFY_NO_REFINE", "MATCH_MUTUAL"]
+           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL"]
 
 
 class Keypoint:
@@ -178,6 +178,64 @@ class LocalFeatures:
                                                    MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
                                                    s.cuda_stream)
         return m_ab, m_ba, best, second
+
+    def match_guided_batch(self, desc_a, kps_a, offsets_a, desc_b, kps_b, offsets_b, model, kind="homography", threshold=None,
+                           ratio=0.8, mutual=True, stream=None):
+        """Guided matching of many image pairs in one call (lf_mkd_match_guided_pairs_device: one launch, three with
+        `mutual`): match_batch once more, with the candidates of every row restricted to the rows of the other side that pass
+        the verifier's inlier test with it under the pair's model -- a transfer disc under H, an epipolar band under F.
+        Tensors as match_batch takes them (moved to the handle's device, any float / integer dtype), plus kps_a [Na,5] /
+        kps_b [Nb,5] (indexed like the descriptor rows; x and y are read) and model [n_pairs,3,3] (or [n_pairs,9]), e.g. what
+        verify_homography_batch / verify_fundamental_batch return.  kind: "homography" or "fundamental" (or GUIDE_*);
+        threshold in pixels, default the verifier's own (3.0 for H, 1.5 for F).  Returns device tensors (match_ab [Na] int32,
+        match_ba [Nb] int32, best [Na], second [Na]) as match_batch does; rows outside every pair hold -1 / -inf.  With the
+        verifier's model, threshold and ratio and `mutual`, every verified match is found again (include/lf_mkd.h).
+        Enqueued on `stream` (default: torch's current stream on the handle's device), asynchronously."""
+        import torch
+        kinds = {"homography": GUIDE_HOMOGRAPHY, "fundamental": GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY: GUIDE_HOMOGRAPHY,
+                 GUIDE_FUNDAMENTAL: GUIDE_FUNDAMENTAL}
+        if kind not in kinds:
+            raise RuntimeError('match_guided_batch: kind must be "homography" or "fundamental"')
+        kind = kinds[kind]
+        if threshold is None:
+            threshold = 3.0 if kind == GUIDE_HOMOGRAPHY else 1.5
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError("match_guided_batch: offsets_a and offsets_b need n_pairs + 1 entries each")
+        if int(model.numel()) != 9 * n_pairs:
+            raise RuntimeError("match_guided_batch: model needs 9 entries per pair")
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):      # the copies and the fills below are ordered with the call
+            a = desc_a.to(dev, torch.float32).reshape(-1, 128).contiguous()
+            b = desc_b.to(dev, torch.float32).reshape(-1, 128).contiguous()
+            ka = kps_a.to(dev, torch.float32).reshape(-1, 5).contiguous()
+            kb = kps_b.to(dev, torch.float32).reshape(-1, 5).contiguous()
+            oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+            md = model.to(dev, torch.float32).reshape(-1, 9).contiguous()
+            na, nb = a.shape[0], b.shape[0]
+            if ka.shape[0] != na or kb.shape[0] != nb:
+                raise RuntimeError("match_guided_batch: one keypoint per descriptor row on either side")
+            m_ab = torch.full((na,), -1, dtype=torch.int32, device=dev)
+            m_ba = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+            best = torch.full((na,), float("-inf"), dtype=torch.float32, device=dev)
+            second = torch.full((na,), float("-inf"), dtype=torch.float32, device=dev)
+            if n_pairs and na and nb:       # (an empty side: no row has a candidate, the fills above are the answer)
+                with self._lock:
+                    self._inner.match_guided_pairs_device(a.data_ptr(), ka.data_ptr(), oa.data_ptr(), na, b.data_ptr(),
+                                                          kb.data_ptr(), ob.data_ptr(), nb, md.data_ptr(), n_pairs,
+                                                          m_ab.data_ptr(), m_ba.data_ptr(), kind, threshold, ratio,
+                                                          MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
+                                                          s.cuda_stream)
+        return m_ab, m_ba, best, second
+
+    def match_guided(self, desc_a, kps_a, desc_b, kps_b, model, kind="homography", threshold=None, ratio=0.8, mutual=True,
+                     stream=None):
+        """match_guided_batch for one pair (n_pairs = 1: all of desc_a against all of desc_b under `model` [3,3])."""
+        import torch
+        na, nb = int(desc_a.numel()) // 128, int(desc_b.numel()) // 128
+        return self.match_guided_batch(desc_a, kps_a, torch.tensor([0, na]), desc_b, kps_b, torch.tensor([0, nb]), model, kind,
+                                       threshold, ratio, mutual, stream)
 
     def match_ip_distance(self, desc_a, desc_b, factor=0.75):
         """The webcam example's acceptance rule (examples/webcam/src/main.rs:97-104,261-265): nearest and second-nearest

@@ -15,6 +15,7 @@ FLAG_UNFUSED_KEYPOINTS = 2
 FLAG_DETECT_STEPWISE = 4
 VERIFY_NO_REFINE = 1     # lf_mkd_verify_homography* / _fundamental*: the best RANSAC candidate as is, no least-squares refit
 MATCH_MUTUAL = 1         # lf_mkd_match_pairs_device: keep a match only if the other direction agrees
+GUIDE_HOMOGRAPHY, GUIDE_FUNDAMENTAL = 0, 1   # lf_mkd_match_guided_pairs_device: what the pair's nine model floats are
 ANGLE_SHADER, ANGLE_EXACT, ANGLE_EXACT_ZERO = 0, 1, 2
 POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6 = 0, 1, 2, 3   # lf_mkd_pool_mode; the default is the f16x3 split
 PCA_NAMES = ("liberty", "notredame", "yosemite")   # enum MKDPCA, lib.rs:26-32
@@ -31,7 +32,7 @@ SYMBOLS = (
     "lf_mkd_build_constants", "lf_mkd_kernel_times", "lf_mkd_kernel_clock", "lf_mkd_synchronize", "lf_mkd_version",
     "lf_mkd_orient_keypoints", "lf_mkd_orient_keypoints_device", "lf_mkd_get_coarse_layer",
     "lf_mkd_detect_extrema", "lf_mkd_detect_extrema_device", "lf_mkd_filter_extrema_device", "lf_mkd_detect",
-    "lf_mkd_match", "lf_mkd_match_device", "lf_mkd_match_both_device", "lf_mkd_match_pairs_device", "lf_mkd_match_overflowed", "lf_mkd_stream_create", "lf_mkd_stream_frame",
+    "lf_mkd_match", "lf_mkd_match_device", "lf_mkd_match_both_device", "lf_mkd_match_pairs_device", "lf_mkd_match_guided_pairs_device", "lf_mkd_match_overflowed", "lf_mkd_stream_create", "lf_mkd_stream_frame",
     "lf_mkd_detect_frames_device", "lf_mkd_orient_keypoints_blocked",
     "lf_mkd_comm_unique_id", "lf_mkd_comm_create", "lf_mkd_comm_destroy", "lf_mkd_comm_info", "lf_mkd_allgather_descriptors",
     "lf_mkd_comm_loopback", "lf_mkd_comm_last_form", "lf_mkd_plan_upload", "lf_mkd_detect_recordings",
@@ -119,6 +120,8 @@ def load_library():
     L.lf_mkd_match.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp]
     L.lf_mkd_match_both_device.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp, vp, vp]
     L.lf_mkd_match_pairs_device.argtypes = [vp, vp, vp, u64, vp, vp, u64, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_match_guided_pairs_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, ctypes.c_float,
+                                                   ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_match_overflowed.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
@@ -506,6 +509,16 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_match_pairs_device(
             self._h, d_a, d_offsets_a, na_total, d_b, d_offsets_b, nb_total, n_pairs, ratio, flags, d_match_ab, d_match_ba,
             d_best, d_second, s), "lf_mkd_match_pairs_device")
+
+    def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
+                                  d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
+                                  d_best=None, d_second=None, stream=None):
+        """lf_mkd_match_guided_pairs_device: match_pairs_device with every row's candidates restricted to the rows that pass
+        the verifier's inlier test with it under the pair's model d_model [n_pairs][9] (device pointers; see
+        include/lf_mkd.h).  kind: GUIDE_HOMOGRAPHY / GUIDE_FUNDAMENTAL; flags: MATCH_MUTUAL."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_match_guided_pairs_device(
+            self._h, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs, kind, threshold,
+            ratio, flags, d_match_ab, d_match_ba, d_best, d_second, s), "lf_mkd_match_guided_pairs_device")
 
     def verify_homography_device(self, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, d_H, d_verified, d_stats,
                                  n_hypotheses=2048, threshold=3.0, seed=0, flags=0, stream=None):
