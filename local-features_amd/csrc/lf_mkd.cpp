@@ -160,7 +160,7 @@ struct lf_mkd {
     std::vector<hipEvent_t> side_events;
     struct {                             // the model's constants, uploaded at creation ...
         HipArray<short> colmap, colmap_unfolded;
-        HipArray<float> pool_b_f32, white_a_f32, white_bias;
+        HipArray<float> pool_b_f32, white_a_f32, white_bias, odd_cart;
         HipArray<uint16_t> pool_b_f16, pool_b_fp6, white_a_f16, white_a_f16_unfolded;
     } consts;
     DeviceConsts dc;                     // ... as the launchers take them
@@ -378,8 +378,13 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
     LF_CREATE_HIP(upload(c.white_a_f16, hc.white_a_f16));
     LF_CREATE_HIP(upload(c.white_a_f32, hc.white_a_f32));
     LF_CREATE_HIP(upload(c.white_bias, hc.white_bias));
+    {
+        std::vector<float> oc(hc.odd_cart_fx, hc.odd_cart_fx + 16);
+        oc.insert(oc.end(), &hc.odd_cart_gy[0][0], &hc.odd_cart_gy[0][0] + 32 * 4);
+        LF_CREATE_HIP(upload(c.odd_cart, oc));
+    }
     h->dc = DeviceConsts{c.colmap, c.pool_b_f32, c.pool_b_f16, c.white_a_f16, c.white_a_f32, c.colmap_unfolded, c.pool_b_fp6,
-                         c.white_a_f16_unfolded, c.white_bias};
+                         c.white_a_f16_unfolded, c.white_bias, c.odd_cart};
     // (the staging buffers of the host-pointer and keypoint entry points -- 4.6 KiB per descriptor of the internal batch --
     // are allocated on first use: a caller of the device-pointer patch API never needs them)
     LF_CREATE_HIP(h->d_totals.allocate(8));
@@ -790,6 +795,25 @@ int lfmkd_test_pool_tables(const float *mean, const float *eigvals, const float 
     if (pool_b_f32) std::memcpy(pool_b_f32, hc.pool_b_f32.data(), hc.pool_b_f32.size() * 4);
     if (colmap) std::memcpy(colmap, hc.colmap.data(), hc.colmap.size() * 2);
     if (parity_defect) *parity_defect = hc.lut_parity_defect;
+    return LF_MKD_OK;
+}
+
+// Test-only tap (not part of include/lf_mkd.h): the factors LF_MKD_POOL_F16X3 pools the x-odd cartesian kernels with.
+//   fx [16], gy [32][4], defect [1] (HostConsts::odd_cart_*); any of them may be null
+int lfmkd_test_pool_factors(const float *mean, const float *eigvals, const float *eigvecs, float *fx, float *gy, float *defect) {
+    if (!mean || !eigvals || !eigvecs) return LF_MKD_ERR_BAD_ARG;
+    PcaModel pca;
+    pca.mean.assign(mean, mean + kRaw);
+    pca.eigvals.assign(eigvals, eigvals + kRaw);
+    pca.eigvecs.assign(eigvecs, eigvecs + size_t(kRaw) * kRaw);
+    HostConsts hc;
+    if (const std::string e = build_host_consts(pca, hc); !e.empty()) {
+        g_create_error = e;
+        return LF_MKD_ERR_BAD_ARG;
+    }
+    if (fx) std::memcpy(fx, hc.odd_cart_fx, sizeof hc.odd_cart_fx);
+    if (gy) std::memcpy(gy, hc.odd_cart_gy, sizeof hc.odd_cart_gy);
+    if (defect) *defect = hc.odd_cart_defect;
     return LF_MKD_OK;
 }
 

@@ -311,6 +311,46 @@ std::string build_host_consts(const PcaModel &pca, HostConsts &hc) {
     hc.lut_parity_defect = defect;
     if (!(defect < 1e-4f))   // (f32 rounding of the grid and of atan2 leaves a few 1e-6)
         return "internal: a pooling LUT column is neither even nor odd in x (defect " + std::to_string(defect) + ")";
+    // The x-odd Cartesian kernels as c_k fx(x) gy_b(y) (mkd_consts.hpp): LF_MKD_POOL_F16X3 pools them on the vector ALU.
+    // f32 rounding of the builder's three factors and of `gauss` leaves a few ulp between the product and the LUT.
+    {
+        for (int k = 0; k <= 3; ++k)
+            for (int i = 0; i < kCart; ++i)
+                if ((parity(LutColumn{true, false, i, k, 0}) < 0) != (i >= 6))
+                    return "internal: the x-odd cartesian kernels are not EC 6, 7, 8";
+        const double half_pi = 3.14159265358979323846 / 2.0, mn2 = double(max_norm) * double(max_norm);
+        auto vm1 = [&](int a, double t) {
+            return a == 0 ? double(kVmN1K1[0]) : (a == 1 ? std::cos(t) : std::sin(t)) * double(kVmN1K1[1]);
+        };
+        auto fx = [&](int x) {
+            const double g = grid.x[x];
+            return vm1(2, g * half_pi) * std::exp(-(g * g) / mn2);
+        };
+        for (int x = 0; x < kPatch / 2; ++x) hc.odd_cart_fx[x] = float(0.5 * (fx(x) - fx(kPatch - 1 - x)));
+        for (int y = 0; y < kPatch; ++y) {
+            const double g = grid.y[y * kPatch];
+            for (int b = 0; b < 3; ++b) hc.odd_cart_gy[y][b] = float(vm1(b, g * half_pi) * std::exp(-(g * g) / mn2));
+            hc.odd_cart_gy[y][3] = 0.f;
+        }
+        double worst = 0.0;
+        for (int k = 0; k <= 3; ++k)
+            for (int b = 0; b < 3; ++b) {
+                const LutColumn col{true, false, 6 + b, k, 0};
+                double err = 0.0, mx = 0.0;
+                for (int y = 0; y < kPatch; ++y)
+                    for (int x = 0; x < kPatch; ++x) {
+                        const double f = x < kPatch / 2 ? hc.odd_cart_fx[x] : -double(hc.odd_cart_fx[kPatch - 1 - x]);
+                        const double v = lut_value_d(col, y * kPatch + x);
+                        err = std::fmax(err, std::fabs(double(kVmN3K8[k]) * f * double(hc.odd_cart_gy[y][b]) - v));
+                        mx = std::fmax(mx, std::fabs(v));
+                    }
+                worst = std::fmax(worst, err / mx);
+            }
+        hc.odd_cart_defect = float(worst);
+        if (!(hc.odd_cart_defect < 1e-6f))
+            return "internal: the x-odd cartesian kernels are not a product of an x- and a y-profile (defect " +
+                   std::to_string(hc.odd_cart_defect) + ")";
+    }
     hc.colmap.assign(kPackedCols, -1);
     {
         std::vector<int> seen(kRaw, 0);

@@ -42,6 +42,11 @@ constexpr int kOut = 128;       // shaders/common.glsl:20
 // 2 = odd EC (3).  The m stream's three tiles have the same shape: EP 0-15 | EP 16-24, even EC in slots 10-15 | odd EC; a
 // column fills the half its parity selects.  The LUT is symmetrised: a folded value is the f64 mean of the two mirror values.
 // 12 LUT tiles and 21 accumulator tiles per row, 6 products per harmonic; the accumulators are the packed output columns.
+// LF_MKD_POOL_F16X3 does not spend matrix instructions on tile 2 of a group ([0 | EC_i], 3 of 16 columns, half of every K
+// zero): the x-odd Cartesian kernels are EC 6, 7, 8 = vM1(x pi/2)[2] vM1(y pi/2)[b] G, G factors in x and y and a Cartesian
+// column carries no rotation, so c_k EC_{6+b}(x, y) = c_k fx(x) gy_b(y) with ONE x-profile for all 21 columns (HostConsts::
+// odd_cart_*).  Its row loop sums gy_b(y) * sum_{x<16} fx(x) s_o(x, y) in f32 on the vector ALU and rebuilds accumulator
+// tiles 2, 7, 8, 13, 14, 19, 20 once per batch; the tables, `colmap` and the whitening fragments are the same in every mode.
 constexpr int kStreams = 7;
 constexpr int kTiles = 21;        // accumulator tiles = packed output tiles (what `colmap` and the whitening fragments index):
                                   // 0-2 m | per harmonic h = k-1, 3 + 6h + 2 (LUT tile 0..2) + (0: U, 1: V)
@@ -104,6 +109,13 @@ struct HostConsts {
     std::vector<uint16_t> white_a_f16_unfolded;
     // largest |L(x) -+ L(31-x)| of a LUT column relative to the column's largest value: what the fold assumes to be zero
     float lut_parity_defect = 0.f;
+    // The x-odd Cartesian kernels EC 6, 7, 8 as a product (see above), built in f64 from the grid and coefficients of the
+    // LUT and rounded to f32: fx at the folded x < 16, symmetrised like the LUT, (f(x) - f(31-x)) / 2; gy_0..2(y) and a pad
+    // (0).  odd_cart_defect: the largest |c_k fx(x) gy_b(y) - lut value of (EC_{6+b}, c_k)| over all 32 x 32 pixels and
+    // k = 0..3, relative to the column's largest value -- what LF_MKD_POOL_F16X3's row loop assumes to be zero.
+    float odd_cart_fx[16] = {};
+    float odd_cart_gy[32][4] = {};
+    float odd_cart_defect = 0.f;
     std::vector<float> white_bias;  // [128] = -sum_d W_T[n][d] mean[d]  (whitening.glsl subtracts the mean first)
 };
 

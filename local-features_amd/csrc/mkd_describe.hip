@@ -14,6 +14,8 @@
 // sums leaves the wave.  Horizontal neighbours come from lanes l -/+ 16 via ds_bpermute; vertical
 // neighbours from a ring of raw patch rows that LDS-DMA keeps filled.
 // (LF_POOL_F16_FP6, an experiment frozen as a mode, keeps the earlier unfolded form: x in [8q, 8q+8) per lane.)
+// LF_POOL_F16X3 leaves three of the 211 LUT columns to the vector ALU: the x-odd cartesian kernels are a product fx(x) gy_b(y),
+// so their 21 packed columns cost ~40 f32 instructions per row instead of 21 matrix instructions (valu_odd_cart below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,6 +46,8 @@ __device__ __host__ constexpr bool f16_family(int pool) { return pool == LF_POOL
 // that the polar kernels' streams carry (embedding.glsl:70-72) is folded into the LUT (mkd_consts.hpp).
 // The folded forms (fold_form(POOL)): 12 LUT tiles per patch row -- 0-2 m | 3 + 3h + {0, 1, 2} for harmonic h = k-1 -- and 21
 // accumulator tiles, which are the packed output tiles themselves: 0-2 m | 3 + 6h + 2 (LUT tile) + (0: operand U, 1: V).
+// (LF_POOL_F16X3 meets LUT tiles 0 and 1 of each group only -- 42 matrix instructions per row -- and fills the accumulator
+//  tiles of LUT tile 2 after the last row: valu_odd_cart.)
 // The unfolded form (LF_POOL_F16_FP6):
 //   LUT tiles of a patch row: 0-2 m | per harmonic h = k-1, 3 + 4h + {0: P0 = EPc[0:16], 1: Q0 = EPs[0:16],
 //                                      2: R = EPc[16:25] | EC[0:7], 3: S = EPs[16:25] | EC[7:9]}
@@ -55,6 +59,13 @@ constexpr int kTiles = 21;
 constexpr int kAccTiles = 21, kUnfAccTiles = 24;
 __device__ __host__ constexpr int acc_tiles(bool fold) { return fold ? kAccTiles : kUnfAccTiles; }
 __device__ __host__ constexpr int lut_pieces(bool fold) { return fold ? 24 : 30; }   // 1 KiB pieces per LUT row: 2 per tile
+// LF_POOL_F16X3 pools the x-odd cartesian kernels -- LUT tile 2 of each group, [0 | EC_6..8]: 3 columns of 16, half of every
+// K zero -- on the vector ALU instead of the matrix cores: c_k EC_{6+b}(x, y) = c_k fx(x) gy_b(y) (mkd_consts.hpp), so per
+// row and stream a lane adds gy_b(y) * sum_i fx(4q + i) s_o(4q + i) to three f32 sums, and accumulator tiles 2, 7, 8, 13, 14,
+// 19, 20 are rebuilt from them once per batch (rebuild_odd_cart).  The tiles' LUT pieces are then neither moved into LDS
+// nor read; every piece keeps its place in the row image and in the row buffers (the holes are simply not filled).
+__device__ __host__ constexpr bool valu_odd_cart(int pool) { return pool == LF_POOL_F16X3; }
+constexpr int kOddCartSums = 7;   // m | per harmonic: sin_o (operand U), -cos_o (operand V)
 constexpr int kPolarSlots = 10;   // folded mixed tiles: slots below it hold polar kernels, the others cartesian ones
 
 // 5-tap sigma=0.7 kernel, patch_gradients.glsl:22-28
@@ -98,17 +109,20 @@ __device__ __forceinline__ void lds_dma16_sv(const unsigned char *uniform_base, 
 // hipcc then selects the SGPR-base form `global_load_lds_dwordx4 v_off, s[base:base+1]`, which costs no 64-bit VALU add and
 // no VGPR pair per request (written as per-lane pointer + uniform offset, every request carried its own v_lshl_add_u64
 // and the hoisted address pairs were spilled).
-// one LUT row (24 pieces; 30 unfolded) into an LDS row buffer, piece p by wave p mod W (the first waves take one piece more)
-template <int W, bool FOLD = true>
+// one LUT row (24 pieces; 30 unfolded) into an LDS row buffer, piece p by wave p mod W (the first waves take one piece more).
+// ODDV (valu_odd_cart): the two pieces of tile 2 of each group stay behind -- 16 pieces, the i-th of them piece i + 2 (i / 4).
+template <int W, bool FOLD, bool ODDV>
 __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ lut_rows, int row,
                                               unsigned char *lds_row, int wave, int lane) {
-    constexpr int kPieces = lut_pieces(FOLD);
+    static_assert(!ODDV || FOLD, "the folded forms' tiles");
+    constexpr int kPieces = ODDV ? lut_pieces(FOLD) - 8 : lut_pieces(FOLD);
     const unsigned lane16 = (unsigned)lane * 16u;
 #pragma unroll
     for (int j = 0; j < (kPieces + W - 1) / W; ++j) {
         if (wave + W * j < kPieces) {   // uniform
-            const unsigned char *g = lut_rows + ((size_t)row * row_bytes(FOLD) + (size_t)(wave + W * j) * 1024);   // uniform
-            lds_dma16_sv(g, lane16, lds_row + (wave + W * j) * 1024);
+            const int i = wave + W * j, piece = ODDV ? i + 2 * (i >> 2) : i;
+            const unsigned char *g = lut_rows + ((size_t)row * row_bytes(FOLD) + (size_t)piece * 1024);   // uniform
+            lds_dma16_sv(g, lane16, lds_row + piece * 1024);
         }
     }
 }
@@ -542,15 +556,44 @@ __device__ __forceinline__ void fold_sum(const f32x2 (&s)[4], f32x2 &e0, f32x2 &
 __device__ __forceinline__ void fold_diff(const f32x2 (&s)[4], f32x2 &o0, f32x2 &o1) { o0 = s[0] - s[2]; o1 = s[1] - s[3]; }
 __device__ __forceinline__ void fold_diff_rev(const f32x2 (&s)[4], f32x2 &o0, f32x2 &o1) { o0 = s[2] - s[0]; o1 = s[3] - s[1]; }
 
+// The x-odd cartesian kernels' share of one patch row for one stream (valu_odd_cart): h0, h1 = the stream's odd half at
+// x = 4q .. 4q+3, fx = the x-profile at the same x, gy = gy_0..2 of the row (wave-uniform).  Six instructions.
+__device__ __forceinline__ void odd_cart_row(const f32x2 (&fx)[2], const f32x4 &gy, f32x2 h0, f32x2 h1, float (&oc)[3]) {
+    const f32x2 r = pk_fma(fx[1], h1, fx[0] * h0);
+    const float t = r.x + r.y;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) oc[b] = __builtin_fmaf(gy[b], t, oc[b]);
+}
+
+// ... and once per batch: accumulator tiles 2 | 3 + 6h + 4 (U), 3 + 6h + 5 (V) from the sums.  Column b of such a tile is c_k
+// times the sum over the patch's four lanes; every other column is zero.  As three 16x16x4 f32 matrix instructions per tile
+// with A[i][k] = (i == b ? c_k : 0) and B[k][patch] = the sum of lane (patch, q = k): a k-ordered f32 fma chain that lands in the
+// packed tiles' own layout (column 4 (lane >> 4) + register of patch lane & 15), with no lane exchange.
+__device__ __forceinline__ void rebuild_odd_cart(const float (&oc)[kOddCartSums][3], int lane, f32x4 (&acc)[kAccTiles]) {
+    constexpr float kVm[4] = {0.37872374f, 0.51796234f, 0.46882015f, 0.39798096f};   // c_k: kVmN3K8 of mkd_consts.cpp
+#pragma unroll
+    for (int s = 0; s < kOddCartSums; ++s) {
+        const int k = (s + 1) / 2, t = s == 0 ? 2 : 3 + 6 * (k - 1) + 4 + ((s - 1) & 1);
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32((lane & 15) == b ? kVm[k] : 0.f, oc[s][b], d, 0, 0, 0);
+        acc[t] = d;
+    }
+}
+
 // Harmonics k = 1..3 of the gradient angle (the folded forms).  The recurrence runs on the products themselves,
 // (pk, qk) = m (cos, sin)(k theta), as a three-term (Chebyshev) recurrence x_{k+1} = 2 c1 x_k - x_{k-1} with x_0 = (m, 0): one
 // instruction per stream and harmonic instead of a rotation of the unit vector (two) plus a product.  After each step the pair is
 // folded into the two operands U = [cos_e | sin_o] and V = [sin_e | -cos_o] (mkd_consts.hpp), which meet the SAME three LUT
 // tiles: 6 products (18 matrix instructions, f16x3) per harmonic, issued term by term across the six accumulators.  `g` holds
 // the fragments of the harmonic's first tile on entry (prefetched by the caller) and the next harmonic's on exit.
+// valu_odd_cart(POOL): tile 2 is not met -- 4 products (12 matrix instructions) per harmonic -- and the second halves of U and
+// V, sin_o and -cos_o, go through odd_cart_row before the f16 split (fx, gy: see there; oc: the batch's 7 x 3 sums).
 template <int POOL>
 __device__ __forceinline__ void pool_harmonics(const f32x2 (&m)[4], const f32x2 (&c1)[4], const f32x2 (&s1)[4],
-                                               const unsigned char *brow, BFrag &g, f32x4 (&acc)[kAccTiles]) {
+                                               const unsigned char *brow, BFrag &g, f32x4 (&acc)[kAccTiles],
+                                               const f32x2 (&fx)[2], const f32x4 &gy, float (&oc)[kOddCartSums][3]) {
     f32x2 pk[4], qk[4], pp[4], qp[4], tc[4];
     AFrag<POOL> au, av;
 #pragma unroll
@@ -563,6 +606,10 @@ __device__ __forceinline__ void pool_harmonics(const f32x2 (&m)[4], const f32x2 
             fold_diff(qk, u[2], u[3]);
             fold_sum(qk, v[0], v[1]);
             fold_diff_rev(pk, v[2], v[3]);
+            if constexpr (valu_odd_cart(POOL)) {
+                odd_cart_row(fx, gy, u[2], u[3], oc[1 + 2 * k]);
+                odd_cart_row(fx, gy, v[2], v[3], oc[2 + 2 * k]);
+            }
             if constexpr (POOL == LF_POOL_F16X3) {
                 AFrag<POOL>::set2(au, u, av, v);
             } else {
@@ -580,7 +627,18 @@ __device__ __forceinline__ void pool_harmonics(const f32x2 (&m)[4], const f32x2 
             }
         }
         const int a0 = 3 + 6 * k, u0 = 3 + 3 * k;
-        const BFrag t0 = g, t1 = load_b(brow, u0 + 1), t2 = load_b(brow, u0 + 2);
+        const BFrag t0 = g, t1 = load_b(brow, u0 + 1);
+        if constexpr (valu_odd_cart(POOL)) {
+            if (k < 2) g = load_b(brow, u0 + 3);
+            mma_part<POOL, 0>(au, t0, acc[a0 + 0]); mma_part<POOL, 0>(av, t0, acc[a0 + 1]); mma_part<POOL, 0>(au, t1, acc[a0 + 2]);
+            mma_part<POOL, 0>(av, t1, acc[a0 + 3]);
+            mma_part<POOL, 1>(au, t0, acc[a0 + 0]); mma_part<POOL, 1>(av, t0, acc[a0 + 1]); mma_part<POOL, 1>(au, t1, acc[a0 + 2]);
+            mma_part<POOL, 1>(av, t1, acc[a0 + 3]);
+            mma_part<POOL, 2>(au, t0, acc[a0 + 0]); mma_part<POOL, 2>(av, t0, acc[a0 + 1]); mma_part<POOL, 2>(au, t1, acc[a0 + 2]);
+            mma_part<POOL, 2>(av, t1, acc[a0 + 3]);
+            continue;
+        }
+        const BFrag t2 = load_b(brow, u0 + 2);
         if (k < 2) g = load_b(brow, u0 + 3);
         mma_part<POOL, 0>(au, t0, acc[a0 + 0]); mma_part<POOL, 0>(av, t0, acc[a0 + 1]); mma_part<POOL, 0>(au, t1, acc[a0 + 2]);
         mma_part<POOL, 0>(av, t1, acc[a0 + 3]); mma_part<POOL, 0>(au, t2, acc[a0 + 4]); mma_part<POOL, 0>(av, t2, acc[a0 + 5]);
@@ -841,7 +899,7 @@ __device__ __forceinline__ void finish_descriptors(const f32x4 (&acc_row)[acc_ti
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __syncthreads();
             if (s >= 1 && s + 2 < 11) issue_w_step<W>(wfrag, s + 2, s_mem, wave, lane);
-            if (s == 10 && more) issue_lut_row<W, kFold>(lut_rows, 0, s_mem, wave, lane);
+            if (s == 10 && more) issue_lut_row<W, kFold, valu_odd_cart(POOL)>(lut_rows, 0, s_mem, wave, lane);
             read_unit(2 * s, wbuf[0]);
             __builtin_amdgcn_sched_barrier(0);
             if (s > 0) mma_unit(2 * s - 1, wbuf[1]);
@@ -1120,7 +1178,7 @@ __device__ __forceinline__ void kp_produce(const KpSource &ks, const LevelTable 
         auto step = [&](int g, KpTaps &cur, KpTaps &nxt) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // ring writes, LUT pieces and taps have landed
             __syncthreads();
-            if (g < 31) issue_lut_row<W>(lut_rows, g + 1, s_mem + ((g + 1) & 1) * kRowBytes, pw, lane);
+            if (g < 31) issue_lut_row<W, true, true>(lut_rows, g + 1, s_mem + ((g + 1) & 1) * kRowBytes, pw, lane);
             const int qn = g + 8;    // the quarter of step g + 1
             if (qn < 32) sm.request(qn, set, nxt);
             else if (more) sm.request(qn - 32, set ^ 1, nxt);   // (g = 31: quarter 7 of the next batch)
@@ -1193,7 +1251,7 @@ __device__ __forceinline__ void kp_produce_split(const KpSource &ks, const Level
         __syncthreads();
         // LUT row lo + st + 1 into the buffer the describe waves have just left (never beyond the span: during the last
         // step of the consumer workgroup buffer 0 takes the epilogue's first whitening step)
-        if (sp.lo + st + 1 < sp.hi) issue_lut_row<W>(lut_rows, sp.lo + st + 1, s_mem + ((st + 1) & 1) * kRowBytes, pw, lane);
+        if (sp.lo + st + 1 < sp.hi) issue_lut_row<W, true, true>(lut_rows, sp.lo + st + 1, s_mem + ((st + 1) & 1) * kRowBytes, pw, lane);
         if (q_step0 + st + 1 < sp.q_end) sm.request(q_step0 + st + 1, 0, nxt);
         __builtin_amdgcn_sched_barrier(0);
         if (q_step0 + st < sp.q_end) sm.finish(q_step0 + st, 0, 0, cur);
@@ -1238,7 +1296,7 @@ template <int ANGLE, int POOL, int W, int SRC>
 __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_pool(
     const float *__restrict__ patches, long n_host, const unsigned long long *__restrict__ n_dev,
     const unsigned char *__restrict__ lut_rows, const short *__restrict__ colmap, const unsigned char *__restrict__ wfrag,
-    const float *__restrict__ bias, float *__restrict__ out, float *__restrict__ raw_out,
+    const float *__restrict__ bias, const float *__restrict__ odd_cart, float *__restrict__ out, float *__restrict__ raw_out,
     std::conditional_t<SRC != kSrcPatches, KpSource, int> ks, unsigned long long *__restrict__ clk) {
     constexpr bool kKp = SRC != kSrcPatches, kSplit = SRC == kSrcKeypointsSplit;
     static_assert(!kSplit || W == 2, "the row-split form is the narrow (2 + 2 wave) form");
@@ -1252,8 +1310,8 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     constexpr int kSlots = kKp ? kRingSlotsKp : kRingSlots;
     static_assert(!kKp || POOL == LF_POOL_F16X3, "keypoint mode pools in f16x3");
     constexpr int kMPool = POOL == LF_POOL_F16_FP6 ? LF_POOL_F16X3 : POOL;   // the m stream keeps the three-term form
-    constexpr bool kFold = fold_form(POOL);
-    static_assert(!kKp || kFold, "the producers write the folded forms' LDS map");
+    constexpr bool kFold = fold_form(POOL), kOddV = valu_odd_cart(POOL);
+    static_assert(!kKp || (kFold && kOddV), "the producers write the folded forms' LDS map and request f16x3's LUT pieces");
     constexpr int kNAcc = acc_tiles(kFold), kRowB = row_bytes(kFold), kRingO = ring_off(kFold);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRingO + W * kSlots * 2048 +
                                                                 (kKp ? kLevelTableBytes + kMaxPyrLevels * 8 : 0)];
@@ -1315,6 +1373,15 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 
     long batch = walk.cur;
     if (batch >= walk.end) return;
+    // the x-odd cartesian kernels' x-profile at the lane's folded pixels 4q .. 4q+3 (valu_odd_cart): loaded once, and landed
+    // before the first LDS-DMA request -- the row loop itself issues no vector load (see wait_vmcnt)
+    [[maybe_unused]] f32x2 oc_fx[2] = {pk_set(0.f), pk_set(0.f)};
+    if constexpr (kOddV) {
+        const f32x4 f = *reinterpret_cast<const f32x4 *>(odd_cart + 4 * q);
+        oc_fx[0] = f32x2{f[0], f[1]};
+        oc_fx[1] = f32x2{f[2], f[3]};
+        asm volatile("" : "+v"(oc_fx[0]), "+v"(oc_fx[1]));
+    }
     // lanes beyond the last patch recompute it: the wave's base is clamped the same way, so lane offsets stay >= 0
     auto raw_src = [&](const float *pt, long b) {
         const long b0 = b * (16 * W) + wave * 16;
@@ -1328,7 +1395,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 #pragma unroll
             for (int r = -2; r <= 3; ++r) issue_raw_row(src, r, ring, r + 2);
         }
-        issue_lut_row<W, kFold>(lut_rows, kSplit ? span.lo : 0, s_mem, wave, lane);
+        issue_lut_row<W, kFold, kOddV>(lut_rows, kSplit ? span.lo : 0, s_mem, wave, lane);
     }
     int slot0 = 0;   // keypoint mode: ring slot of raw row 0 of the current batch
     unsigned par = 0;  // LUT row buffer holding the row about to be consumed
@@ -1347,6 +1414,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         float *o = out, *ro = raw_out;
         const short *cm = colmap;
         asm volatile("" : "+s"(wf), "+s"(bs), "+s"(lr), "+s"(o), "+s"(ro), "+s"(cm), "+s"(pt));
+        const float *oc_tab = odd_cart;
         const long base = batch * (16 * W) + wave * 16;
         const bool more = batch + walk.step < walk.end;
         // (keypoint mode: pt is null and these stay unused)
@@ -1356,6 +1424,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         f32x4 acc[kNAcc];
 #pragma unroll
         for (int t = 0; t < kNAcc; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // valu_odd_cart: the batch's sums for the x-odd cartesian columns -- [m | sin_o, -cos_o of k = 1..3][gy_b]
+        [[maybe_unused]] float oc[kOddCartSums][3];
+#pragma unroll
+        for (int s = 0; s < kOddCartSums; ++s)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) oc[s][b] = 0.f;
         // blurred rows g and g-1 (row -1 replicates row 0) in the lane's pixel order, and row g just outside the lane's
         // pixels: folded (blur_row_fold_impl) x = 4q-1, 4q+4, 27-4q, 32-4q; unfolded x = 8q-1, 8q+8
         float cur[8], prv[8], cur_nb[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1381,12 +1455,18 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             // (keypoint mode: the producer waves request LUT rows 1..31 -- an LDS-DMA request stalls its issuer for 60-180
             // cycles, which a producer can afford -- so a describe wave issues no memory instruction in the row loop)
             if (f16_family(POOL) ? !kLast : (!kLast || more)) {
-                if constexpr (!kKp) issue_lut_row<W, kFold>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowB, wave, lane);
+                if constexpr (!kKp) issue_lut_row<W, kFold, kOddV>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowB, wave, lane);
             } else if (f16_family(POOL)) {
                 issue_w_step<W>(wf, 0, s_mem, wave, lane);
             }
             par ^= 1;
-            BFrag bm[3] = {load_b(brow, 0), load_b(brow, 1), load_b(brow, 2)};   // m-stream fragments
+            constexpr int kMTiles = kOddV ? 2 : 3;   // m-stream fragments
+            BFrag bm[kMTiles];
+#pragma unroll
+            for (int t = 0; t < kMTiles; ++t) bm[t] = load_b(brow, t);
+            // gy_0..2 of row g for the x-odd cartesian columns: a wave-uniform address -- a scalar load, not a vector one
+            [[maybe_unused]] f32x4 oc_gy = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (kOddV) oc_gy = *reinterpret_cast<const f32x4 *>(oc_tab + 16 + 4 * g);
 
             // Raw row g+4 goes into the slot of row g-2, whose last reader was the blur of the previous iteration: for
             // g >= 1 it is requested here, a whole row before the vmcnt(0) that waits for it (counters: the waves spend
@@ -1492,21 +1572,22 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                     f32x2 mf[4];
                     fold_sum(m, mf[0], mf[1]);
                     fold_diff(m, mf[2], mf[3]);
+                    if constexpr (kOddV) odd_cart_row(oc_fx, oc_gy, mf[2], mf[3], oc[0]);
                     am.set(mf);
                 } else {
                     am.set(m);
                 }
 #pragma unroll
-                for (int t = 0; t < 3; ++t) mma_part<kMPool, 0>(am, bm[t], acc[t]);
+                for (int t = 0; t < kMTiles; ++t) mma_part<kMPool, 0>(am, bm[t], acc[t]);
 #pragma unroll
-                for (int t = 0; t < 3; ++t) mma_part<kMPool, 1>(am, bm[t], acc[t]);
+                for (int t = 0; t < kMTiles; ++t) mma_part<kMPool, 1>(am, bm[t], acc[t]);
 #pragma unroll
-                for (int t = 0; t < 3; ++t) mma_part<kMPool, 2>(am, bm[t], acc[t]);
+                for (int t = 0; t < kMTiles; ++t) mma_part<kMPool, 2>(am, bm[t], acc[t]);
             }
             phase.mark(3);
             // cos / sin streams of the three harmonics x their LUT tiles: accumulator tiles 3-20 (unfolded: 3-23)
             if constexpr (POOL == LF_POOL_F16_FP6) pool_harmonics_fp6(m, c1, s1, brow, gfrag, acc);
-            else pool_harmonics<POOL>(m, c1, s1, brow, gfrag, acc);
+            else pool_harmonics<POOL>(m, c1, s1, brow, gfrag, acc, oc_fx, oc_gy, oc);
             phase.mark(4);
             phase.mark(5);
         };
@@ -1517,6 +1598,8 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             for (int g = span.lo + 1; g < span.hi - 1; ++g) patch_row(std::integral_constant<int, 1>(), g);
             if (span.consumer) patch_row(std::integral_constant<int, 2>(), span.hi - 1);
             else patch_row(std::integral_constant<int, 1>(), span.hi - 1);
+            // (before the partial sums are published: sums over row subsets add, and the exchange keeps its 21 tiles)
+            if constexpr (kOddV) rebuild_odd_cart(oc, lane, acc);
             // the partial sums meet: [batch][role][wave][tile][lane] f32x4, one counter per (batch, wave)
             unsigned *cnt = ks.xchg_cnt + batch * W + wave;
             // Every access to the exchange buffer and its counters is a relaxed atomic of agent scope: such a store is
@@ -1572,6 +1655,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 #pragma unroll 1
             for (int g = 1; g < ablate::kRows - 1; ++g) patch_row(std::integral_constant<int, 1>(), g);
             patch_row(std::integral_constant<int, 2>(), ablate::kRows - 1);
+            if constexpr (kOddV) rebuild_odd_cart(oc, lane, acc);
         }
         if constexpr (ablate::kNoEpilogue) {
             f32x4 sum = acc[0];
@@ -1579,7 +1663,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             if (base + p < n) *reinterpret_cast<f32x4 *>(out + (base + p) * 128 + 4 * q) = sum;
             if (f16_family(POOL)) {
                 __syncthreads();
-                if (more) issue_lut_row<W, kFold>(lr, 0, s_mem, wave, lane);
+                if (more) issue_lut_row<W, kFold, kOddV>(lr, 0, s_mem, wave, lane);
             }
         } else {
             finish_descriptors<POOL, W>(acc, lane, wave, base + p < n, base + p, cm, wf, bs, o, ro, s_mem, lr, more);
@@ -1622,7 +1706,7 @@ void launch_describe(const float *patches, long n, const unsigned long long *n_d
     const short *colmap = unfolded ? dc.colmap_unfolded : dc.colmap;
 #define LF_LAUNCH_W(A, P, WV)                                                                                          \
     hipLaunchKernelGGL((mkd_pool<A, P, WV, kSrcPatches>), dim3(grid), dim3(64 * WV), 0, stream, patches, n, n_dev, lut, \
-                       colmap, wf, dc.white_bias, out, raw_out, 0, clk)
+                       colmap, wf, dc.white_bias, dc.odd_cart, out, raw_out, 0, clk)
 #define LF_LAUNCH(A, P)            \
     do {                           \
         if (small) LF_LAUNCH_W(A, P, 4); \
@@ -1692,7 +1776,7 @@ void launch_describe_keypoints(const float *pyr, long pyr_stride, const PyramidD
             const unsigned sgrid = (unsigned)(nb8 * r);
 #define LF_LAUNCH_KP_SPLIT(A)                                                                                                  \
     hipLaunchKernelGGL((mkd_pool<A, LF_POOL_F16X3, 2, kSrcKeypointsSplit>), dim3(sgrid), dim3(256), 0, stream,                    \
-                       (const float *)nullptr, n, n_dev, lut, dc.colmap, wf, dc.white_bias, out, (float *)nullptr, ks, clk)
+                       (const float *)nullptr, n, n_dev, lut, dc.colmap, wf, dc.white_bias, dc.odd_cart, out, (float *)nullptr, ks, clk)
             if (angle_mode == LF_ANGLE_EXACT) LF_LAUNCH_KP_SPLIT(LF_ANGLE_EXACT);
             else if (angle_mode == LF_ANGLE_EXACT_ZERO) LF_LAUNCH_KP_SPLIT(LF_ANGLE_EXACT_ZERO);
             else LF_LAUNCH_KP_SPLIT(LF_ANGLE_SHADER);
@@ -1702,7 +1786,7 @@ void launch_describe_keypoints(const float *pyr, long pyr_stride, const PyramidD
     }
 #define LF_LAUNCH_KP_W(A, WV)                                                                                          \
     hipLaunchKernelGGL((mkd_pool<A, LF_POOL_F16X3, WV, kSrcKeypoints>), dim3(grid), dim3(128 * WV), 0, stream,          \
-                       (const float *)nullptr, n, n_dev, lut, dc.colmap, wf, dc.white_bias, out, (float *)nullptr, ks, clk)
+                       (const float *)nullptr, n, n_dev, lut, dc.colmap, wf, dc.white_bias, dc.odd_cart, out, (float *)nullptr, ks, clk)
 #define LF_LAUNCH_KP(A)                 \
     do {                                \
         if (narrow) LF_LAUNCH_KP_W(A, 2); \

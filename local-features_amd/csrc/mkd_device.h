@@ -65,6 +65,7 @@ struct DeviceConsts {
     uint16_t *pool_b_fp6 = nullptr;           // [32][15][2][64][8]
     uint16_t *white_a_f16_unfolded = nullptr; // [11][8][2][64][8]
     float *white_bias = nullptr;     // [128]  -W mean
+    float *odd_cart = nullptr;       // [16] odd_cart_fx, then [32][4] odd_cart_gy (LF_MKD_POOL_F16X3's x-odd cartesian columns)
 };
 
 // patches [n][32][32] -> out [n][128] (and, when raw_out != nullptr, the un-whitened [n][238])
