@@ -1,5 +1,5 @@
 // Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_guided.hip, mkd_verify.hip, mkd_fundamental.hip).
+// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_guided.hip, mkd_verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -209,7 +209,7 @@ void launch_verify(const float *kps_a, const uint64_t *off_a, const float *kps_b
 // (indexed like match), and its normalisation into pairs[p]
 void launch_verify_prepare(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,
                            unsigned n_pairs, VerifyPair *pairs, int *list, hipStream_t stream);
-// RANSAC fundamental matrix (mkd_fundamental.hip; algorithm: include/lf_mkd.h).  Scratch: pairs [n_pairs], counts
+// RANSAC fundamental matrix (mkd_verify.hip as well; algorithm: include/lf_mkd.h).  Scratch: pairs [n_pairs], counts
 // [n_pairs][slices][n_hyp][3] (one count per candidate of a sample; slices from verify_slices, the same grid shape);
 // `verified` holds the considered rows as above.
 void launch_fundamental(const float *kps_a, const uint64_t *off_a, const float *kps_b, const uint64_t *off_b, const int *match,

@@ -1,7 +1,7 @@
-// The arithmetic of the RANSAC fundamental-matrix verifier (mkd_fundamental.hip; algorithm: include/lf_mkd.h): the sampler,
-// the 7-point solver, the Sampson test and the refit's solve, every one __host__ __device__.  mkd_fundamental.hip includes
-// this header for its two kernels; tests/cpp/fundamental_twin.cpp includes it under a plain C++ compiler (with
-// -ffp-contract=off) and restates only the kernels' orchestration, so the host twin the device is held to bit for bit
+// The arithmetic of the RANSAC fundamental-matrix verifier (mkd_verify.hip; algorithm: include/lf_mkd.h): the sampler,
+// the 7-point solver, the Sampson test and the refit's solve, every one __host__ __device__, and FundamentalModel, what
+// ransac_score / ransac_select of mkd_verify.hip are instantiated with.  tests/cpp/fundamental_twin.cpp includes it under a
+// plain C++ compiler (with -ffp-contract=off) and restates only the kernels' orchestration, so the host twin the device is held to bit for bit
 // (tests/test_gpu_fundamental_exact.py) is this code and no transcription of it.  Needs <math.h> and <stdint.h> alone.
 #pragma once
 #include <math.h>
@@ -447,6 +447,41 @@ __host__ __device__ __forceinline__ bool refit_solve(const double *m, int c, flo
     }
     return ok;
 }
+
+// What ransac_score / ransac_select (mkd_verify.hip) take from a model: see the list above them.
+struct FundamentalModel {
+    static constexpr int kCand = 3;        // a sample's cubic has up to three real roots
+    static constexpr int kMoments = lfmkd::kMoments;
+    static constexpr int kRows = 1;        // rows per unrolled scoring step
+    __host__ __device__ static __forceinline__ unsigned candidates(const float *ka, const float *kb, const int *match,
+                                                                   const int *list, const VerifyPair &P, unsigned seed_p,
+                                                                   unsigned k, float (&f)[3][9], float (&fn)[3][9]) {
+        return lfmkd::candidates(ka, kb, match, list, P, seed_p, k, f, fn);
+    }
+    __host__ __device__ static __forceinline__ bool inlier(const float *f, float ax, float ay, float bx, float by, float thr2) {
+        return f_inlier(f, ax, ay, bx, by, thr2);
+    }
+    __host__ __device__ static __forceinline__ bool inlier_cost(const float *f, float ax, float ay, float bx, float by,
+                                                                float thr2, float &cost) {
+        return f_inlier_cost(f, ax, ay, bx, by, thr2, cost);
+    }
+    __host__ __device__ static __forceinline__ void add_moments(double *m, double x, double y, double u, double v) {
+        add_moments36(m, x, y, u, v);
+    }
+    // (the current model's largest entry is the one the refit pins to 1)
+    __host__ __device__ static __forceinline__ bool refit(const double *m, const float *fn, const VerifyPair &P, float (&fn2)[9],
+                                                          float *f2) {
+        return refit_solve(m, argmax_abs9(fn), fn2) && f_denormalise(fn2, P, f2);
+    }
+    // the entry the output is divided by: the one of largest magnitude
+    __host__ __device__ static __forceinline__ float pivot(const float *f) {
+        const int c = argmax_abs9(f);
+        float piv = f[0];
+#pragma unroll
+        for (int i = 1; i < 9; ++i) piv = i == c ? f[i] : piv;
+        return piv;
+    }
+};
 
 }  // namespace
 }  // namespace lfmkd

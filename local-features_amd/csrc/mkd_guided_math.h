@@ -1,12 +1,12 @@
 // The admissibility tests of guided matching (mkd_match_guided.hip; contract: include/lf_mkd.h): the two verifiers' step-4
-// inlier tests -- inlier() of mkd_verify.hip under a homography, f_inlier() / sampson() of mkd_fundamental_math.h under a
-// fundamental matrix -- in HOISTED form, every one __host__ __device__.  A matcher's workgroup tests one fixed point
+// inlier tests -- h_inlier() of mkd_homography_math.h under a homography, f_inlier() / sampson() of mkd_fundamental_math.h
+// under a fundamental matrix -- in HOISTED form, every one __host__ __device__.  A matcher's workgroup tests one fixed point
 // against many: what depends on one point alone is computed once for it and kept, the rest per pair of points.  Hoisting
 // moves operations, it neither reorders nor re-associates one: each test below is the verifier's sequence of correctly
 // rounded operations, operand for operand (the Sampson test's denominator stays ONE nested fma chain whose innermost two
 // links depend on b alone), so a pair of points is admissible exactly when the verifier calls it an inlier, bit for bit.
 // tests/cpp/guided_twin.cpp includes this header under a plain C++ compiler (with -ffp-contract=off) and is held to
-// f_inlier() itself and to a restatement of inlier().  Needs <math.h> and <stdint.h> alone.
+// h_inlier() and f_inlier() themselves.  Needs <math.h> and <stdint.h> alone.
 #pragma once
 #include <math.h>
 #include <stdint.h>

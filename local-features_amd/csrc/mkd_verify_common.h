@@ -1,6 +1,5 @@
-// Device helpers the two RANSAC verifiers share (mkd_verify.hip: homography, mkd_fundamental.hip: fundamental matrix).
-// Each source is its own translation unit and includes this header: no device code crosses a translation unit.  Everything
-// here is a fixed sequence of IEEE operations under contraction OFF, so both files get the same bits from it.
+// Device helpers of the RANSAC verifiers' kernels (mkd_verify.hip: verify_prepare, ransac_score, ransac_select), whatever
+// the model.  Everything here is a fixed sequence of IEEE operations under contraction OFF.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -1,6 +1,7 @@
 // The pieces of the two RANSAC verifiers that a plain C++ compiler can read as well as hipcc: the sampler's hash and the
 // refit's Cholesky solve (the per-pair record is mkd_verify_pair.h).  mkd_verify_common.h includes it for the device build
-// and mkd_fundamental_math.h for both, so that a host program (tests/cpp/fundamental_twin.cpp) is built from the very code
+// and the two models' math headers (mkd_homography_math.h, mkd_fundamental_math.h) for both, so that a host program
+// (tests/cpp/fundamental_twin.cpp, tests/cpp/guided_twin.cpp) is built from the very code
 // the kernels run; mkd_device.h must not: the pragma below holds for the rest of any file that includes this one.  Only
 // <math.h> / <stdint.h> are needed.  Everything here is a fixed sequence of IEEE operations under contraction OFF (a host
 // build passes -ffp-contract=off as well: the pragma is clang's).

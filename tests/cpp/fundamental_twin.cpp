@@ -1,6 +1,6 @@
-// Host twin of local-features_amd/csrc/mkd_fundamental.hip: the kernels' own arithmetic (csrc/mkd_fundamental_math.h, compiled
-// here by a plain C++ compiler with -ffp-contract=off) under a serial restatement of what fundamental_score and
-// fundamental_select do with it -- every sample's candidates and counts, the selection on (count, -c), and the refit with the
+// Host twin of the fundamental-matrix verifier of local-features_amd/csrc/mkd_verify.hip: the kernels' own arithmetic
+// (csrc/mkd_fundamental_math.h, compiled here by a plain C++ compiler with -ffp-contract=off) under a serial restatement of
+// what ransac_score and ransac_select do with FundamentalModel -- every sample's candidates and counts, the selection on (count, -c), and the refit with the
 // workgroup's summation order (thread tid adds rows tid, tid + 256, ...; an xor butterfly 32 .. 1 within each wave of 64;
 // then waves 0 .. 3 in order).  No arithmetic of its own beyond those sums.  tests/fundamental_twin.py drives it:
 //
@@ -86,7 +86,7 @@ void run(const Problem &q, unsigned seed_p, bool want_records, FILE *out) {
     const int *mt = q.match.data(), *list = q.list.data();
     const unsigned na = q.na;
     const float thr2 = q.thr2;
-    // fundamental_score, summed over the slices; fundamental_select's argmax on (count, -c), an invalid candidate skipped
+    // ransac_score, summed over the slices; ransac_select's argmax on (count, -c), an invalid candidate skipped
     std::vector<Record> recs(want_records ? q.n_hyp : 0);
     unsigned long long best = 0;
     for (unsigned k = 0; k < q.n_hyp; ++k) {

@@ -7,8 +7,8 @@
 // f32 a[na][2], f32 b[nb][2].  <out>, per problem, three byte masks:
 //   fwd [na][nb]   the a -> b direction as the kernel hoists it: what depends on a_i once per i, then every b_j
 //   rev [nb][na]   the b -> a direction: what depends on b_j once per j, then every a_i -- the same relation, (a_i, b_j)
-//   ref [na][nb]   the verifier's own test, not hoisted: f_inlier() of mkd_fundamental_math.h called directly, and inlier()
-//                  of mkd_verify.hip (a .hip file no host compiler reads) restated here op for op
+//   ref [na][nb]   the verifier's own test, not hoisted: h_inlier() of mkd_homography_math.h and f_inlier() of
+//                  mkd_fundamental_math.h, called directly
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -17,18 +17,9 @@
 
 #include "mkd_fundamental_math.h"
 #include "mkd_guided_math.h"
+#include "mkd_homography_math.h"
 
 using namespace lfmkd;
-
-// inlier() of csrc/mkd_verify.hip
-static bool h_inlier(const float *h, float ax, float ay, float bx, float by, float thr2) {
-    const float u = fmaf(h[0], ax, fmaf(h[1], ay, h[2]));
-    const float v = fmaf(h[3], ax, fmaf(h[4], ay, h[5]));
-    const float w = fmaf(h[6], ax, fmaf(h[7], ay, h[8]));
-    const float ex = fmaf(bx, w, -u), ey = fmaf(by, w, -v);
-    const float num = fmaf(ex, ex, ey * ey), den = w * w;
-    return w > 0.f && num < thr2 * den;
-}
 
 int main(int argc, char **argv) {
     if (argc != 3) {
@@ -53,7 +44,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "guided_twin: truncated problem\n");
             return 1;
         }
-        const float thr2 = thr * thr;   // as launch_verify / launch_fundamental form it
+        const float thr2 = thr * thr;   // as launch_ransac (mkd_verify.hip) forms it
         std::vector<uint8_t> fwd(size_t(na) * nb), rev(size_t(na) * nb), ref(size_t(na) * nb);
         for (uint32_t i = 0; i < na; ++i) {
             const float ax = a[2 * i], ay = a[2 * i + 1];

@@ -1,4 +1,4 @@
-"""f32 twin of local-features_amd/csrc/mkd_verify.hip: the kernel's own operations in its own order, on the CPU.
+"""f32 twin of the homography verifier (csrc/mkd_verify.hip with mkd_homography_math.h): its operations in its order, on the CPU.
 
 homography_ref.py restates the algorithm (include/lf_mkd.h, steps 1-6) in float64; this file transcribes the device code
 instead, so that it gives the device's bits:
@@ -203,7 +203,7 @@ class Pair:
         return inlier_cost(h, self.ax, self.ay, self.bx, self.by, thr2)
 
     def counts(self, seed_p, n_hyp, thr2, chunk=1 << 22):
-        """verify_score summed over the slices: (counts int64 [n_hyp], -1 for an invalid hypothesis; valid; H)."""
+        """ransac_score<HomographyModel> summed over the slices: (counts int64 [n_hyp], -1 for an invalid hypothesis; valid; H)."""
         valid, h = self.hypotheses(seed_p, np.arange(n_hyp))
         counts = np.full(n_hyp, -1, np.int64)
         step = max(1, chunk // max(self.m, 1))
