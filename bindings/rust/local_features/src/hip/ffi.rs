@@ -172,6 +172,20 @@ extern "C" {
                         matches: *mut i32) -> c_int;
     pub fn lf_mkd_match_overflowed(h: *mut lf_mkd, stream: *mut c_void, n_rows: *mut u64) -> c_int;
 
+    // 8-bit descriptors: byte = clamp(rint(x * scale), -127, 127) + 128 (scale 0.0: the default, 256), and the matcher
+    // over such rows, decided on exact integer similarities (d_best / d_second are i32)
+    pub fn lf_mkd_quantize_descriptors_device(h: *mut lf_mkd, d_desc: *const f32, n: u64, scale: f32, d_q: *mut u8,
+                                              stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_quantize_descriptors(h: *mut lf_mkd, desc: *const f32, n: u64, scale: f32, q: *mut u8) -> c_int;
+    pub fn lf_mkd_match_q8_device(h: *mut lf_mkd, d_a: *const u8, na: u64, d_b: *const u8, nb: u64,
+                                  d_exclude_lo: *const u32, d_exclude_hi: *const u32, ratio: f32, d_match: *mut i32,
+                                  d_best: *mut i32, d_second: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_match_q8(h: *mut lf_mkd, a: *const u8, na: u64, b: *const u8, nb: u64, ratio: f32,
+                           matches: *mut i32) -> c_int;
+    // the grid (a blocks x b splits) and the scratch lf_mkd_match_q8_device takes for a size; host only, no handle
+    pub fn lf_mkd_match_q8_plan(na: u64, nb: u64, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
+                                scratch_bytes: *mut u64) -> c_int;
+
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,
                                     nb: u64, matches: *const i32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,

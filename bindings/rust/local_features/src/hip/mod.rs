@@ -276,6 +276,33 @@ impl LocalFeaturesHip {
         Ok(m.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect())
     }
 
+    /// 8-bit descriptors (`lf_mkd_quantize_descriptors`, `include/lf_mkd.h`): byte = clamp(rint(x * 256), -127, 127) + 128,
+    /// a quarter of the bytes of the f32 rows.
+    pub fn quantize(&mut self, desc: &ArrayView2<f32>) -> Result<Array2<u8>, Error> {
+        assert_eq!(desc.ncols(), DESCRIPTOR_LEN);
+        let desc = desc.as_standard_layout();
+        let mut q = Array2::<u8>::zeros((desc.nrows(), DESCRIPTOR_LEN));
+        // SAFETY: desc is contiguous [n][128]; `q` is standard layout with as many rows
+        unsafe {
+            check(self.h, ffi::lf_mkd_quantize_descriptors(self.h, desc.as_ptr(), desc.nrows() as u64, 0.0, q.as_mut_ptr()))?;
+        }
+        Ok(q)
+    }
+
+    /// `match_features` over 8-bit descriptors (`lf_mkd_match_q8`): exact integer similarities, Lowe's ratio 0.8.
+    pub fn match_q8(&mut self, a: &ArrayView2<u8>, b: &ArrayView2<u8>) -> Result<Vec<(usize, usize)>, Error> {
+        assert_eq!(a.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(b.ncols(), DESCRIPTOR_LEN);
+        let (a, b) = (a.as_standard_layout(), b.as_standard_layout());
+        let mut m = vec![-1i32; a.nrows()];
+        // SAFETY: a, b are contiguous [n][128]; `m` has a.nrows() entries
+        unsafe {
+            check(self.h, ffi::lf_mkd_match_q8(self.h, a.as_ptr(), a.nrows() as u64, b.as_ptr(), b.nrows() as u64, 0.8,
+                                               m.as_mut_ptr()))?;
+        }
+        Ok(m.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect())
+    }
+
     /// RANSAC fundamental-matrix verification of matches (`lf_mkd_verify_fundamental`, `include/lf_mkd.h` states the
     /// algorithm): 7-point samples scored by Sampson distance on the GPU, then a rank-2 least-squares refit.  `matches` are
     /// (row of `kps_a`, row of `kps_b`) pairs as `match_features` returns them.  Returns F (row-major, b^T F a = 0 in pixels,

@@ -445,6 +445,68 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
  * case).  Waits for that call to finish (synchronises `stream`, NULL = the handle's own). */
 int lf_mkd_match_overflowed(lf_mkd *h, void *stream, uint64_t *n_rows);
 
+/* ---- 8-bit descriptors: the quantiser and the exact int8 matcher -------------------------------------------------
+ * The format.  A quantised descriptor is 128 uint8_t (128 bytes a row instead of 512), offset-binary: byte = q + 128 with
+ * q in [-127, 127], so bytes are 1 .. 255 and 0 never occurs.  q = clamp(rint(x * scale), -127, 127): x * scale is one
+ * correctly rounded f32 multiplication, rint rounds to nearest with ties to even, a NaN product gives q = 0, +-inf
+ * saturates.  `scale` is a call argument, a positive, finite, normal f32; 0 means the default, 256.  The descriptors are
+ * L2-normalised, so |x| <= 1 and in practice far below it: at 256 nothing below |x| = 0.496 saturates.  Unsigned on the
+ * boundary because uint8 is what every binding has; the matcher turns a dword of it into two's complement with one xor
+ * 0x80808080.  One global scale, not one per row: the rows have unit norm, and a per-row scale would make the similarities
+ * of one a row against different b rows incomparable as integers.  With s the integer similarity below, s / scale^2
+ * approximates the f32 dot product; for two rows without a saturated element
+ *   |s / scale^2 - <a, b>| <= (|a|_1 + |b|_1) / (2 scale) + 128 / (4 scale^2).
+ *
+ * lf_mkd_quantize_descriptors_device: d_desc [n][128] f32 -> d_q [n][128] bytes, exactly n * 128 bytes written.  Device
+ * pointers (d_desc 16-byte, d_q 4-byte aligned), one launch, asynchronous on `stream` (NULL: the handle's own), no scratch:
+ * capturable in a hipGraph.  n == 0 is LF_MKD_OK and writes nothing.  lf_mkd_quantize_descriptors is the same for host
+ * pointers (any alignment), synchronous, through the handle's staging.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "quantize_descriptors_device" /
+ * "quantize_descriptors" and is reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; with n > 0 a null
+ * or misaligned pointer; n above 2^31 - 1; a scale that is negative, NaN, infinite or subnormal. */
+int lf_mkd_quantize_descriptors_device(lf_mkd *h, const float *d_desc, uint64_t n, float scale, uint8_t *d_q,
+                                       void *stream);
+int lf_mkd_quantize_descriptors(lf_mkd *h, const float *desc, uint64_t n, float scale, uint8_t *q);
+/* The matcher over quantised rows: lf_mkd_match_device's semantics restated for integers, and exact.
+ *   similarity  s(i, j) = sum_k (a[i][k] - 128) * (b[j][k] - 128), an exact int32 (|s| <= 128 * 127^2 = 2 064 512 < 2^24);
+ *   best        the largest s over the candidates; among equal maxima the HIGHEST index wins;
+ *   second      the largest over the remaining candidates (equal to best when the maximum occurs twice);
+ *   exclusion   b rows [lo[i], hi[i]) are not candidates for a row i (both pointers NULL: none; one NULL: refused);
+ *   acceptance  match[i] = the best's index if ratio <= 0 or (float)best * ratio > (float)second -- both conversions are
+ *               exact, one f32 multiplication -- else -1;
+ *   too few     with one candidate second = INT32_MIN and the row is accepted; with none match = -1 and best = second =
+ *               INT32_MIN.
+ * d_best / d_second [na] int32 may be NULL.  nb must be at least 2, as in the f32 call; na == 0 is LF_MKD_OK and writes
+ * nothing.  d_a and d_b must be 16-byte aligned (a row is 128 bytes).  The result depends on the inputs alone: not on the
+ * run, not on the split count, not on the device's CU count -- integer sums have no rounding, every tie rule is by index.
+ * There is one form for every size (v_mfma_i32_32x32x32_i8, 4 matrix instructions per 32 x 32 tile of pairs, b streamed
+ * through LDS straight from the caller's rows): no operand tiles, no margin, no re-score, no fallback, and
+ * lf_mkd_match_overflowed is not affected.  Two launches (scan over a grid of a blocks x b splits, then a merge of the
+ * splits' partial results), one when the plan below has one split.  Asynchronous on `stream` (NULL: the handle's own), no
+ * host synchronisation, no allocation once the handle's scratch (the splits' partials) has grown to the largest plan seen;
+ * a warmed-up call can be captured in a hipGraph.  lf_mkd_match_q8 is the same for host pointers, synchronous, without
+ * exclusion ranges.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "match_q8_device" / "match_q8" and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; with na > 0 a null d_a, d_b or d_match; one
+ * exclusion pointer without the other; d_a or d_b not 16-byte aligned; nb < 2; na or nb above 2^31 - 1. */
+int lf_mkd_match_q8_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                           const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi, float ratio, int32_t *d_match,
+                           int32_t *d_best, int32_t *d_second, void *stream);
+int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb, float ratio,
+                    int32_t *match);
+/* What lf_mkd_match_q8_device launches for a problem size, and the scratch it needs -- host-only, no device, no handle, no
+ * environment variable; the launch path calls this very function.  num_cus: the device's compute units, 0 means 256.
+ * *a_blocks x *b_splits is the scan's grid: an a block is 1024 rows (8 waves x 4 tiles of 32), a split a contiguous range of
+ * 32-row b tiles.  b_splits is 1 when all of b is one LDS stage (nb <= 128); otherwise about two workgroups per CU, at least
+ * 2 and at most one per b tile (and at most 1024) -- a condition on nb alone.  *scratch_bytes is 0 exactly when b_splits == 1
+ * (the scan then writes the result itself) and otherwise 12 bytes per (split, a row), stated as an upper bound that is
+ * non-decreasing in na for a given nb and num_cus and within a factor 2 of b_splits * na * 12:
+ *   12 * 1024 * min(A + max(W, A), A * ceil(nb / 32)),  A = a_blocks, W = 2 * num_cus.
+ * na == 0: (0, 1, 0).  Output pointers may be NULL.  LF_MKD_ERR_BAD_ARG (message "match_q8_plan: ...", through
+ * lf_mkd_last_error(NULL)): nb < 2, na or nb above 2^31 - 1. */
+int lf_mkd_match_q8_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                         uint64_t *scratch_bytes);
+
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
  * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the

@@ -233,6 +233,8 @@ struct lf_mkd {
     HipArray<unsigned> d_match_misc;
     HipArray<unsigned char> d_match_few_tiles;   // the overflowed rows' own tiles; their indices, exclusion ranges, partials
     HipArray<unsigned> d_match_few;
+    // 8-bit descriptors: the int8 matcher's per-split partials (match_q8_plan's scratch_bytes), and the host forms' staging
+    HipArray<unsigned char> d_q8_part, d_q8_io;
     // RANSAC verification scratch (lf_mkd_verify_homography*, lf_mkd_verify_fundamental*, which share it): per-pair
     // normalisation, per-candidate partial counts, and the host form's staging.  No recording names them; they grow only when a call asks for more, so the device form's launches
     // can be captured once warmed up.  Calls of one handle are stream-ordered (lf_mkd.h).
@@ -1877,6 +1879,111 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
     LF_HIP(h, hipMemcpyAsync(h->d_match_in + na * kOut, b, nb * kOut * 4, hipMemcpyHostToDevice, h->stream));
     if (int rc = lf_mkd_match_device(h, h->d_match_in, na, h->d_match_in + na * kOut, nb, nullptr, nullptr, ratio,
                                      h->d_match_out, nullptr, nullptr, h->stream))
+        return rc;
+    LF_HIP(h, hipMemcpyAsync(match, h->d_match_out, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// ---- 8-bit descriptors (csrc/mkd_match_q8.hip) --------------------------------------------------------------------------
+// Like the batched calls above, these check their arguments before the handle, so that every bad argument is reported
+// without a device: the message goes to the handle, or to lf_mkd_last_error(NULL) when there is none.
+static int q8_refuse(lf_mkd *h, const char *who, const char *msg) {
+    (h ? h->err : g_create_error) = std::string(who) + ": " + msg;
+    return LF_MKD_ERR_BAD_ARG;
+}
+
+// 0 -> the default; nullptr: fine
+static const char *q8_scale(float &scale) {
+    if (scale == 0.f) scale = 256.f;
+    return scale > 0.f && std::isnormal(scale) ? nullptr : "scale must be a positive, finite, normal f32 (0: the default, 256)";
+}
+
+static const char *quantize_args(const lf_mkd *h, const void *desc, uint64_t n, float &scale, const void *q, bool device) {
+    if (const char *msg = q8_scale(scale)) return msg;
+    if (n && (!desc || !q)) return "null pointer";
+    if (n > 0x7FFFFFFFull) return "more than 2^31 - 1 rows";
+    if (device && n && ((reinterpret_cast<uintptr_t>(desc) & 15) || (reinterpret_cast<uintptr_t>(q) & 3)))
+        return "d_desc must be 16-byte aligned and d_q 4-byte aligned";
+    return h ? nullptr : "null handle";
+}
+
+int lf_mkd_quantize_descriptors_device(lf_mkd *h, const float *d_desc, uint64_t n, float scale, uint8_t *d_q, void *stream) {
+    if (const char *msg = quantize_args(h, d_desc, n, scale, d_q, true)) return q8_refuse(h, "quantize_descriptors_device", msg);
+    if (n == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_quantize_rows(d_desc, n, scale, d_q, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_quantize_descriptors(lf_mkd *h, const float *desc, uint64_t n, float scale, uint8_t *q) {
+    if (const char *msg = quantize_args(h, desc, n, scale, q, false)) return q8_refuse(h, "quantize_descriptors", msg);
+    if (n == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_match_in, n * kOut)) return rc;
+    if (int rc = grow(h, h->d_q8_io, n * kOut)) return rc;
+    LF_HIP(h, hipMemcpyAsync(h->d_match_in, desc, n * kOut * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    launch_quantize_rows(h->d_match_in, n, scale, h->d_q8_io, h->stream);
+    LF_HIP(h, hipGetLastError());
+    LF_HIP(h, hipMemcpyAsync(q, h->d_q8_io, n * kOut, hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+static const char *match_q8_sizes(uint64_t na, uint64_t nb) {
+    if (nb < 2) return "needs at least two candidates in b";
+    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";
+    return nullptr;
+}
+
+int lf_mkd_match_q8_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                         uint64_t *scratch_bytes) {
+    if (const char *msg = match_q8_sizes(na, nb)) return q8_refuse(nullptr, "match_q8_plan", msg);
+    const Q8Plan p = match_q8_plan(long(na), long(nb), int(std::min<uint32_t>(num_cus, 1u << 20)));
+    if (a_blocks) *a_blocks = p.a_blocks;
+    if (b_splits) *b_splits = p.splits;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+static const char *match_q8_args(const lf_mkd *h, const void *a, uint64_t na, const void *b, uint64_t nb, const void *lo,
+                                 const void *hi, const void *match, bool device) {
+    if (na && (!a || !b || !match)) return "null pointer";
+    if ((lo == nullptr) != (hi == nullptr)) return "exclude_lo and exclude_hi go together";
+    if (device && na && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15))
+        return "d_a and d_b must be 16-byte aligned";
+    if (const char *msg = match_q8_sizes(na, nb)) return msg;
+    return h ? nullptr : "null handle";
+}
+
+int lf_mkd_match_q8_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                           const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi, float ratio, int32_t *d_match,
+                           int32_t *d_best, int32_t *d_second, void *stream) {
+    if (const char *msg = match_q8_args(h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, d_match, true))
+        return q8_refuse(h, "match_q8_device", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const Q8Plan plan = match_q8_plan(long(na), long(nb), h->num_cus);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_q8_part, plan.scratch_bytes)) return rc;
+    launch_match_q8(d_a, long(na), d_b, long(nb), d_exclude_lo, d_exclude_hi, ratio, plan,
+                    plan.scratch_bytes ? h->d_q8_part.get() : nullptr, d_match, d_best, d_second,
+                    stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb, float ratio, int32_t *match) {
+    if (const char *msg = match_q8_args(h, a, na, b, nb, nullptr, nullptr, match, false)) return q8_refuse(h, "match_q8", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_q8_io, (na + nb) * kOut)) return rc;
+    if (int rc = grow(h, h->d_match_out, na)) return rc;
+    LF_HIP(h, hipMemcpyAsync(h->d_q8_io, a, na * kOut, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(h->d_q8_io + na * kOut, b, nb * kOut, hipMemcpyHostToDevice, h->stream));
+    if (int rc = lf_mkd_match_q8_device(h, h->d_q8_io, na, h->d_q8_io + na * kOut, nb, nullptr, nullptr, ratio, h->d_match_out,
+                                        nullptr, nullptr, h->stream))
         return rc;
     LF_HIP(h, hipMemcpyAsync(match, h->d_match_out, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     LF_HIP(h, hipStreamSynchronize(h->stream));

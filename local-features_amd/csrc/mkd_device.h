@@ -1,5 +1,5 @@
 // Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_guided.hip, mkd_verify.hip).
+// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_q8.hip, mkd_match_guided.hip, mkd_verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -195,6 +195,21 @@ void launch_match_screen(const unsigned char *a_tiles, long na, const unsigned c
 void launch_match_verify(const float *a, long na, const float *b, const float *a_norms, const unsigned *b_max_norm_bits,
                          const void *rec, const void *rec_info, int splits, float ratio, int *match, float *best,
                          float *second, int *n_over, int *over_rows, hipStream_t stream);
+
+// 8-bit descriptors (csrc/mkd_match_q8.hip; include/lf_mkd.h): x [n][128] f32 -> q [n][128] offset-binary bytes,
+// byte = clamp(rint(x * scale), -127, 127) + 128 (NaN -> 128)
+void launch_quantize_rows(const float *x, unsigned long long n, float scale, unsigned char *q, hipStream_t stream);
+// the exact int8 matcher's grid and scratch for a problem size: what lf_mkd_match_q8_plan reports and launch_match_q8 launches
+struct Q8Plan {
+    unsigned a_blocks, splits;         // the scan's grid; splits == 1: it writes the result itself, no merge launch
+    long tiles_per_split;              // 32-row b tiles one split scans
+    unsigned long long scratch_bytes;  // partial (best, second, index) per (split, a row); 0 exactly when splits == 1
+};
+Q8Plan match_q8_plan(long na, long nb, int num_cus);
+// a [na][128] against b [nb][128] bytes -> match [na], best / second (nullable) as exact int32 sums; scratch: plan.scratch_bytes
+void launch_match_q8(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *excl_lo,
+                     const unsigned *excl_hi, float ratio, const Q8Plan &plan, void *scratch, int *match, int *best,
+                     int *second, hipStream_t stream);
 
 // RANSAC homography verification (mkd_verify.hip; algorithm: include/lf_mkd.h).  Keypoints are read as rows of 5 floats
 // (lf_mkd_keypoint).  Scratch the caller owns: pairs [n_pairs], counts [n_pairs][slices][n_hyp]; `verified` also holds each

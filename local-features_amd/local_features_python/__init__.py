@@ -15,12 +15,12 @@ import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
                    POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, comm_unique_id, load_library, model_path, plan_upload)
+                   MkdHandle, Q8_SCALE, comm_unique_id, load_library, match_q8_plan, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
-           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL"]
+           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan"]
 
 
 class Keypoint:
@@ -236,6 +236,71 @@ class LocalFeatures:
         na, nb = int(desc_a.numel()) // 128, int(desc_b.numel()) // 128
         return self.match_guided_batch(desc_a, kps_a, torch.tensor([0, na]), desc_b, kps_b, torch.tensor([0, nb]), model, kind,
                                        threshold, ratio, mutual, stream)
+
+    def quantize(self, desc, scale=Q8_SCALE):
+        """8-bit descriptors (lf_mkd.h): [n,128] f32 -> [n,128] uint8, byte = clamp(rint(x * scale), -127, 127) + 128, a quarter
+        of the bytes.  A numpy array goes through the host form and comes back as numpy; a torch tensor is quantised on the
+        handle's device (moved there if it is elsewhere) on torch's current stream and comes back as a device tensor."""
+        if isinstance(desc, np.ndarray) or not hasattr(desc, "data_ptr"):
+            with self._lock:
+                return self._inner.quantize(desc, scale)
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            d = desc.to(dev, torch.float32).reshape(-1, 128).contiguous()
+            q = torch.empty((d.shape[0], 128), dtype=torch.uint8, device=dev)
+            if d.shape[0]:
+                with self._lock:
+                    self._inner.quantize_descriptors_device(d.data_ptr(), d.shape[0], q.data_ptr(), scale, s.cuda_stream)
+        return q
+
+    @staticmethod
+    def dequantize(q, scale=Q8_SCALE):
+        """The f32 values an 8-bit descriptor stands for: (byte - 128) / scale.  numpy in, numpy out; torch in, torch out."""
+        if isinstance(q, np.ndarray):
+            return (q.astype(np.float32) - np.float32(128)) / np.float32(scale)
+        import torch
+        return (q.to(torch.float32) - 128.0) / float(scale)
+
+    def match_q8(self, qa, qb, ratio=0.8, exclude=None, scores=False):
+        """`match` over 8-bit descriptors (lf_mkd_match_q8_device): every similarity is an exact integer, so the decisions are
+        those of an integer matrix product -- no rounding anywhere, ties to the highest index.  qa [na,128] / qb [nb,128]
+        uint8, numpy arrays or torch tensors; exclude: None or (lo, hi), uint32 [na] each -- b rows lo[i] .. hi[i] - 1 are no
+        candidates for row i.  Returns the list of (i, j) as `match` does; with scores=True (list, best [na] int32,
+        second [na] int32) as numpy arrays."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def rows(x):
+            t = torch.from_numpy(np.ascontiguousarray(x, np.uint8)) if not hasattr(x, "data_ptr") else x
+            return t.to(dev, torch.uint8).reshape(-1, 128).contiguous()
+
+        with self._lock, torch.cuda.device(dev):
+            a, b = rows(qa), rows(qb)
+            na, nb = a.shape[0], b.shape[0]
+            if na == 0:
+                empty = np.zeros(0, np.int32)
+                return ([], empty, empty) if scores else []
+            lo = hi = None
+            if exclude is not None:
+                # (the uint32 bounds travel as their int32 bit patterns: torch's uint32 support is partial)
+                lo, hi = (torch.from_numpy(np.ascontiguousarray(np.asarray(e.cpu() if hasattr(e, "cpu") else e))
+                                           .astype(np.uint32).view(np.int32)).to(dev) for e in exclude)
+                if lo.numel() != na or hi.numel() != na:
+                    raise RuntimeError("match_q8: exclude needs one (lo, hi) per row of qa")
+            m = torch.empty((na,), dtype=torch.int32, device=dev)
+            best = torch.empty((na,), dtype=torch.int32, device=dev)
+            second = torch.empty((na,), dtype=torch.int32, device=dev)
+            s = torch.cuda.current_stream(dev)
+            self._inner.match_q8_device(a.data_ptr(), na, b.data_ptr(), nb, m.data_ptr(), ratio,
+                                        lo.data_ptr() if lo is not None else None, hi.data_ptr() if hi is not None else None,
+                                        best.data_ptr(), second.data_ptr(), s.cuda_stream)
+            s.synchronize()
+            self._inner.synchronize()       # (torch's default stream is handle 0 = "the library's own stream" to the ABI)
+            m, best, second = m.cpu().numpy(), best.cpu().numpy(), second.cpu().numpy()
+        pairs = [(int(i), int(j)) for i, j in enumerate(m) if j >= 0]
+        return (pairs, best, second) if scores else pairs
 
     def match_ip_distance(self, desc_a, desc_b, factor=0.75):
         """The webcam example's acceptance rule (examples/webcam/src/main.rs:97-104,261-265): nearest and second-nearest

@@ -38,7 +38,10 @@ SYMBOLS = (
     "lf_mkd_comm_loopback", "lf_mkd_comm_last_form", "lf_mkd_plan_upload", "lf_mkd_detect_recordings",
     "lf_mkd_verify_homography", "lf_mkd_verify_homography_device",
     "lf_mkd_verify_fundamental", "lf_mkd_verify_fundamental_device",
+    "lf_mkd_quantize_descriptors", "lf_mkd_quantize_descriptors_device", "lf_mkd_match_q8", "lf_mkd_match_q8_device",
+    "lf_mkd_match_q8_plan",
 )
+Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -123,6 +126,11 @@ def load_library():
     L.lf_mkd_match_guided_pairs_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, u32, u32, ctypes.c_float,
                                                    ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_match_overflowed.argtypes = [vp, vp, ctypes.POINTER(u64)]
+    L.lf_mkd_quantize_descriptors_device.argtypes = [vp, vp, u64, ctypes.c_float, vp, vp]
+    L.lf_mkd_quantize_descriptors.argtypes = [vp, vp, u64, ctypes.c_float, vp]
+    L.lf_mkd_match_q8_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, ctypes.c_float, vp, vp, vp, vp]
+    L.lf_mkd_match_q8.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp]
+    L.lf_mkd_match_q8_plan.argtypes = [u64, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -169,6 +177,17 @@ def comm_unique_id():
     if rc != 0:
         raise RuntimeError(f"lf_mkd_comm_unique_id failed ({rc}): RCCL is not loadable")
     return bytes(buf)
+
+
+def match_q8_plan(na, nb, num_cus=0):
+    """(a_blocks, b_splits, scratch_bytes): the grid lf_mkd_match_q8_device launches for this size and the scratch it needs
+    (lf_mkd_match_q8_plan; needs no device).  num_cus 0: 256."""
+    a, s, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_match_q8_plan(na, nb, num_cus, ctypes.byref(a), ctypes.byref(s), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_match_q8_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return a.value, s.value, b.value
 
 
 class Comm:
@@ -355,6 +374,23 @@ class MkdHandle:
                     "lf_mkd_match")
         return out
 
+    def quantize(self, desc, scale=Q8_SCALE):
+        """lf_mkd_quantize_descriptors: [n,128] f32 -> [n,128] uint8, byte = clamp(rint(x * scale), -127, 127) + 128."""
+        d = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+        out = np.empty((len(d), 128), np.uint8)
+        self._check(self.L.lf_mkd_quantize_descriptors(self._h, d.ctypes.data, len(d), scale, out.ctypes.data),
+                    "lf_mkd_quantize_descriptors")
+        return out
+
+    def match_q8(self, qa, qb, ratio=0.8):
+        """lf_mkd_match_q8: `match` over 8-bit descriptors [n,128] uint8, decided on exact integer similarities."""
+        a = np.ascontiguousarray(qa, np.uint8).reshape(-1, 128)
+        b = np.ascontiguousarray(qb, np.uint8).reshape(-1, 128)
+        out = np.empty(len(a), np.int32)
+        self._check(self.L.lf_mkd_match_q8(self._h, a.ctypes.data, len(a), b.ctypes.data, len(b), ratio, out.ctypes.data),
+                    "lf_mkd_match_q8")
+        return out
+
     def verify_homography(self, kps_a, kps_b, match, n_hypotheses=2048, threshold=3.0, seed=0, flags=0):
         """lf_mkd_verify_homography: kps_a [na,5], kps_b [nb,5] f32 rows, match int32 [na] (index into b or -1) ->
         (H [3,3] f32, verified int32 [na], stats uint32 [4])."""
@@ -496,6 +532,17 @@ class MkdHandle:
                      d_second=None, stream=None):
         self._device_call(stream, lambda s: self.L.lf_mkd_match_device(
             self._h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, ratio, d_match, d_best, d_second, s), "lf_mkd_match_device")
+
+    def quantize_descriptors_device(self, d_desc, n, d_q, scale=Q8_SCALE, stream=None):
+        """lf_mkd_quantize_descriptors_device: d_desc [n][128] f32 -> d_q [n][128] uint8"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_quantize_descriptors_device(self._h, d_desc, n, scale, d_q, s),
+                          "lf_mkd_quantize_descriptors_device")
+
+    def match_q8_device(self, d_a, na, d_b, nb, d_match, ratio=0.8, d_exclude_lo=None, d_exclude_hi=None, d_best=None,
+                        d_second=None, stream=None):
+        """lf_mkd_match_q8_device: match_device over 8-bit rows; d_best / d_second are int32 (exact integer similarities)"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_device(
+            self._h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, ratio, d_match, d_best, d_second, s), "lf_mkd_match_q8_device")
 
     def match_both_device(self, d_a, na, d_b, nb, d_match_ab, d_match_ba, ratio=0.8, stream=None):
         """both directions in one call: match_ab [na] = match(a, b), match_ba [nb] = match(b, a)"""
