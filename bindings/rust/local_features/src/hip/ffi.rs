@@ -185,6 +185,15 @@ extern "C" {
     // the grid (a blocks x b splits) and the scratch lf_mkd_match_q8_device takes for a size; host only, no handle
     pub fn lf_mkd_match_q8_plan(na: u64, nb: u64, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
                                 scratch_bytes: *mut u64) -> c_int;
+    // n_pairs match problems over 8-bit rows in one launch: lf_mkd_match_pairs_device's layout (offsets on the device), each
+    // pair decided as lf_mkd_match_q8_device decides it alone; d_best / d_second are i32; flags: LF_MKD_MATCH_MUTUAL
+    pub fn lf_mkd_match_q8_pairs_device(h: *mut lf_mkd, d_a: *const u8, d_offsets_a: *const u64, na_total: u64,
+                                        d_b: *const u8, d_offsets_b: *const u64, nb_total: u64, n_pairs: u32, ratio: f32,
+                                        flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut i32,
+                                        d_second: *mut i32, stream: *mut c_void) -> c_int;
+    // the a rows one workgroup of that launch owns and its grid, floor(rows / block_rows) + n_pairs per direction; host only
+    pub fn lf_mkd_match_q8_pairs_plan(na_total: u64, nb_total: u64, n_pairs: u32, both_directions: u32,
+                                      block_rows: *mut u32, workgroups: *mut u64) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -303,6 +303,45 @@ impl LocalFeaturesHip {
         Ok(m.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect())
     }
 
+    /// Many pairs of 8-bit descriptors in one call (`lf_mkd_match_q8_pairs_device`): pair p is rows
+    /// `offsets_a[p]..offsets_a[p + 1]` of `a` against rows `offsets_b[p]..offsets_b[p + 1]` of `b` (`n_pairs + 1`
+    /// non-decreasing offsets each), every pair decided exactly as `match_q8` decides it alone, Lowe's ratio 0.8.  With
+    /// `mutual` a match is kept only if the other direction agrees (`MATCH_MUTUAL`).  Returns, per pair, the (row of the
+    /// pair's a rows, row of its b rows) matches.  The rows, the offsets and the result cross the bus once; the matcher is
+    /// one launch (three with `mutual`) for all pairs.
+    pub fn match_q8_batch(&mut self, a: &ArrayView2<u8>, offsets_a: &[u64], b: &ArrayView2<u8>, offsets_b: &[u64], mutual: bool)
+        -> Result<Vec<Vec<(usize, usize)>>, Error> {
+        assert_eq!(a.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(b.ncols(), DESCRIPTOR_LEN);
+        if offsets_a.is_empty() || offsets_a.len() != offsets_b.len() {
+            return Err(Error::BadArgument("match_q8_batch: offsets_a and offsets_b need n_pairs + 1 entries each".into()));
+        }
+        let n_pairs = offsets_a.len() - 1;
+        let (a, b) = (a.as_standard_layout(), b.as_standard_layout());
+        let (na, nb) = (a.nrows(), b.nrows());
+        let mut m = vec![-1i32; na];
+        if n_pairs > 0 && na > 0 && nb > 0 {
+            // SAFETY: a, b are contiguous [n][128]; device buffers sized as declared; `m` has na entries
+            unsafe {
+                let (d_a, d_b) = (DeviceBuffer::from_slice(a.as_slice().unwrap())?, DeviceBuffer::from_slice(b.as_slice().unwrap())?);
+                let (d_oa, d_ob) = (DeviceBuffer::from_slice(offsets_a)?, DeviceBuffer::from_slice(offsets_b)?);
+                let d_ab = DeviceBuffer::from_slice(&m)?;                    // rows outside every pair stay -1
+                let d_ba = DeviceBuffer::<i32>::new(if mutual { nb } else { 0 })?;
+                check(self.h, ffi::lf_mkd_match_q8_pairs_device(
+                    self.h, d_a.as_ptr(), d_oa.as_ptr(), na as u64, d_b.as_ptr(), d_ob.as_ptr(), nb as u64, n_pairs as u32, 0.8,
+                    if mutual { MATCH_MUTUAL } else { 0 }, d_ab.as_mut_ptr(),
+                    if mutual { d_ba.as_mut_ptr() } else { std::ptr::null_mut() }, std::ptr::null_mut(), std::ptr::null_mut(),
+                    std::ptr::null_mut()))?;
+                check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+                d_ab.download(&mut m)?;
+            }
+        }
+        Ok((0..n_pairs).map(|p| {
+            let (lo, hi) = ((offsets_a[p] as usize).min(na), (offsets_a[p + 1] as usize).min(na));
+            (lo..hi.max(lo)).filter(|&i| m[i] >= 0).map(|i| (i - lo, m[i] as usize)).collect()
+        }).collect())
+    }
+
     /// RANSAC fundamental-matrix verification of matches (`lf_mkd_verify_fundamental`, `include/lf_mkd.h` states the
     /// algorithm): 7-point samples scored by Sampson distance on the GPU, then a rank-2 least-squares refit.  `matches` are
     /// (row of `kps_a`, row of `kps_b`) pairs as `match_features` returns them.  Returns F (row-major, b^T F a = 0 in pixels,

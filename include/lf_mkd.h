@@ -506,6 +506,42 @@ int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, 
  * lf_mkd_last_error(NULL)): nb < 2, na or nb above 2^31 - 1. */
 int lf_mkd_match_q8_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
                          uint64_t *scratch_bytes);
+/* Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device over the q8 format above, for the multi-frame pipeline.
+ *   Layout and offsets are those of lf_mkd_match_pairs_device, word for word: pair p is a rows [offsets_a[p], offsets_a[p+1])
+ *   against b rows [offsets_b[p], offsets_b[p+1]); both offset arrays hold n_pairs + 1 uint64 entries, live on the device, are
+ *   non-decreasing and are never read by the host.  An offset beyond a total is read as the total; an inverted pair is empty;
+ *   no row at or beyond a total is read or written; rows outside [offsets[0], offsets[n_pairs]) are neither read nor written.
+ *   Rows are 128 offset-binary bytes; d_a and d_b must be 16-byte aligned.
+ * Per pair: with nb_p >= 2 (and na_p >= 2 for the reverse direction) every output of pair p EQUALS what
+ * lf_mkd_match_q8_device writes for that pair's rows alone without exclusion ranges -- exact integer similarity, ties to the
+ * highest index, second == best when the maximum occurs twice, acceptance ratio <= 0 || (float)best * ratio > (float)second.
+ * d_match_ab [na_total] / d_match_ba [nb_total] are local to the pair; d_best / d_second [na_total] are the int32 sums of the
+ * a -> b direction and may be NULL.  A side with too few candidates (nb_p < 2, or na_p < 2 for the reverse direction) yields
+ * -1 for every row of that direction and INT32_MIN in best / second, whatever the ratio: a batch survives an empty frame.
+ * The result of a pair depends neither on n_pairs, nor on the other pairs, nor on the run, nor on the device's CU count.
+ * d_match_ba may be NULL unless LF_MKD_MATCH_MUTUAL is set; when given, both directions are decided in the same matcher
+ * launch.  LF_MKD_MATCH_MUTUAL then keeps match_ab[i] = j iff match_ba[j] == i and match_ba[j] = i iff match_ab[i] == j (both
+ * evaluated on the unfiltered arrays; two element-wise launches); d_best / d_second are not filtered.
+ * Sizes: any pair size is correct, but every workgroup (*block_rows a rows, below) streams its pair's whole b side through
+ * LDS: the call is meant for pairs of up to about 4096 rows per side.  One large pair belongs to lf_mkd_match_q8_device.
+ * One launch (three with LF_MKD_MATCH_MUTUAL), no scratch (the handle's q8 scratch is not touched), no allocation, no host
+ * synchronisation, asynchronous on `stream` (NULL: the handle's own): capturable in a hipGraph.  n_pairs == 0 is LF_MKD_OK
+ * and writes nothing.  lf_mkd_match_overflowed is not affected.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "match_q8_pairs_device" and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; null d_a, d_b, offsets or d_match_ab;
+ * LF_MKD_MATCH_MUTUAL without d_match_ba; unknown flag bits; d_a or d_b not 16-byte aligned; a total above 2^31 - 1; a grid
+ * (the plan below, with both_directions = d_match_ba given) above 2^31 - 1 workgroups. */
+int lf_mkd_match_q8_pairs_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *d_offsets_a, uint64_t na_total,
+                                 const uint8_t *d_b, const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs,
+                                 float ratio, uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba,
+                                 int32_t *d_best, int32_t *d_second, void *stream);
+/* The grid lf_mkd_match_q8_pairs_device launches -- host-only, no device, no handle, no environment variable; the launch path
+ * calls this very function.  *block_rows = R, the a rows one workgroup owns (a power of two; a build-time constant);
+ * *workgroups = floor(na_total / R) + n_pairs, plus floor(nb_total / R) + n_pairs when both_directions != 0.  Output pointers
+ * may be NULL.  LF_MKD_ERR_BAD_ARG (message "match_q8_pairs_plan: ...", through lf_mkd_last_error(NULL)): a total above
+ * 2^31 - 1, or more than 2^31 - 1 workgroups. */
+int lf_mkd_match_q8_pairs_plan(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, uint32_t both_directions,
+                               uint32_t *block_rows, uint64_t *workgroups);
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

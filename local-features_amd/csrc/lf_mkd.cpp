@@ -1990,6 +1990,45 @@ int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, 
     return LF_MKD_OK;
 }
 
+// Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device's layout and refusals, the int8 matcher's decisions.
+static const char *match_q8_pairs_sizes(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, bool both) {
+    if (na_total > 0x7FFFFFFFull || nb_total > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";
+    if (match_q8_pairs_slots(na_total, n_pairs) + (both ? match_q8_pairs_slots(nb_total, n_pairs) : 0) > 0x7FFFFFFFull)
+        return "too many rows and pairs for one call (the grid needs floor(rows / block_rows) + n_pairs workgroups per "
+               "direction, at most 2^31 - 1 in all)";
+    return nullptr;
+}
+
+int lf_mkd_match_q8_pairs_plan(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, uint32_t both_directions,
+                               uint32_t *block_rows, uint64_t *workgroups) {
+    if (const char *msg = match_q8_pairs_sizes(na_total, nb_total, n_pairs, both_directions != 0))
+        return q8_refuse(nullptr, "match_q8_pairs_plan", msg);
+    if (block_rows) *block_rows = match_q8_pairs_block_rows();
+    if (workgroups)
+        *workgroups = match_q8_pairs_slots(na_total, n_pairs) + (both_directions ? match_q8_pairs_slots(nb_total, n_pairs) : 0);
+    return LF_MKD_OK;
+}
+
+int lf_mkd_match_q8_pairs_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *d_offsets_a, uint64_t na_total,
+                                 const uint8_t *d_b, const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs,
+                                 float ratio, uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba, int32_t *d_best,
+                                 int32_t *d_second, void *stream) {
+    const bool mutual = flags & LF_MKD_MATCH_MUTUAL;
+    const char *msg = nullptr;
+    if (!d_a || !d_b || !d_offsets_a || !d_offsets_b || !d_match_ab) msg = "null pointer";
+    else if (flags & ~LF_MKD_MATCH_MUTUAL) msg = "unknown flag bits";
+    else if (mutual && !d_match_ba) msg = "LF_MKD_MATCH_MUTUAL needs d_match_ba";
+    else if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 15) msg = "d_a and d_b must be 16-byte aligned";
+    else if (!(msg = match_q8_pairs_sizes(na_total, nb_total, n_pairs, d_match_ba != nullptr)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "match_q8_pairs_device", msg);
+    if (n_pairs == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_match_q8_pairs(d_a, d_offsets_a, na_total, d_b, d_offsets_b, nb_total, n_pairs, ratio, mutual, d_match_ab, d_match_ba,
+                          d_best, d_second, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 // The arguments of both verification entry points, checked before the handle so that every bad argument is reported without
 // a device: the message goes to the handle, or to lf_mkd_last_error(NULL) when there is none.
 static int verify_args(lf_mkd *h, bool null_pointer, uint32_t n_hypotheses, float threshold_px, const char *what) {

@@ -210,6 +210,14 @@ Q8Plan match_q8_plan(long na, long nb, int num_cus);
 void launch_match_q8(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *excl_lo,
                      const unsigned *excl_hi, float ratio, const Q8Plan &plan, void *scratch, int *match, int *best,
                      int *second, hipStream_t stream);
+// many pairs of 8-bit rows in one launch (lf_mkd_match_q8_pairs_device): launch_match_small_pairs' layout and slot map at
+// match_q8_pairs_block_rows() rows per workgroup; each pair decided as launch_match_q8 decides it alone.  No scratch.
+// match_ba (nullable): the other direction from the same launch; mutual: launch_match_mutual's two launches on top.
+unsigned match_q8_pairs_block_rows();
+uint64_t match_q8_pairs_slots(uint64_t n_total, unsigned n_pairs);
+void launch_match_q8_pairs(const unsigned char *a, const uint64_t *off_a, uint64_t na_total, const unsigned char *b,
+                           const uint64_t *off_b, uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab,
+                           int *match_ba, int *best, int *second, hipStream_t stream);
 
 // RANSAC homography verification (mkd_verify.hip; algorithm: include/lf_mkd.h).  Keypoints are read as rows of 5 floats
 // (lf_mkd_keypoint).  Scratch the caller owns: pairs [n_pairs], counts [n_pairs][slices][n_hyp]; `verified` also holds each

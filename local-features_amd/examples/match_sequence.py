@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_sequence [--fundamental] [--guided] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
+"""match_sequence [--fundamental] [--guided] [--q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
 device, every stage launched once for all of them and nothing copied to the host in between:
 
   detect_top_n(2000, min_size 0) on all frames      lf_mkd_detect_frames_device
@@ -10,6 +10,9 @@ device, every stage launched once for all of them and nothing copied to the host
   --fundamental epipolar geometry (1.5 px)
   with --guided: every pair matched again under its   LocalFeatures.match_guided_batch (lf_mkd_match_guided_pairs_device):
   model, then verified once more with the same seed   candidates restricted to the model's transfer disc / epipolar band
+
+  with --q8: the descriptors quantised once to 8 bits  LocalFeatures.quantize, then LocalFeatures.match_q8_batch(mutual=True)
+  and the first pass matched on exact integer sums    (lf_mkd_match_q8_pairs_device); a --guided second pass stays on f32
 
 and prints one line per pair: ratio-test matches t -> t + 1, those the other direction confirms, those the geometry keeps
 (and with --guided: the guided mutual matches -- never fewer than the geometry kept -- and those the second verification keeps).
@@ -31,11 +34,12 @@ def load_gray(path):
     return np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
 
 
-def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None, guided=False):
+def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None, guided=False, q8=False):
     """frames [n, h, w] float32 in [0, 1].  Returns device tensors (keypoints [m,5], descriptors [m,128], frame offsets
     [n + 1], mutual matches t -> t + 1 [m] local to frame t + 1, verified matches [m], model [n - 1,3,3], per pair
     [n - 1, 3]: ratio-test matches, mutual matches, verified inliers).  guided: the matches, the verified matches and the
-    model are those of the guided second pass, and per pair has two more columns: guided mutual matches, verified again."""
+    model are those of the guided second pass, and per pair has two more columns: guided mutual matches, verified again.
+    q8: the first-pass matches come from the 8-bit rows (quantised once, on the device); the guided pass, if any, from `desc`."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -55,7 +59,13 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
         # frame t against frame t + 1: the a side is `desc` with the offsets of frames 0 .. n-2, the b side the same array
         # with the offsets of frames 1 .. n-1 -- no row is copied and no offset is read back to the host
         oa, ob = o[:n], o[1:]
-        m_ab, m_ba, best, second = feats.match_batch(desc, oa, desc, ob, ratio=ratio, mutual=True)
+        if q8:
+            q = feats.quantize(desc)
+            m_ab, m_ba, best, second = feats.match_q8_batch(q, oa, q, ob, ratio=ratio, mutual=True)
+            # the int32 scores as floats (exact: |sums| < 2^24), "no candidate" (INT32_MIN) as the f32 path's -inf
+            best, second = (torch.where(x == -2 ** 31, float("-inf"), x.float()) for x in (best, second))
+        else:
+            m_ab, m_ba, best, second = feats.match_batch(desc, oa, desc, ob, ratio=ratio, mutual=True)
         verify = feats.verify_fundamental_batch if fundamental else feats.verify_homography_batch
         model, ver, stats = verify(kps, oa, kps, ob, m_ab, seed=seed)
         # per pair: a row of frame t belongs to pair t; the ratio-test matches are told by best / second, which the
@@ -75,16 +85,16 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
 
 def main():
     args = sys.argv[1:]
-    fundamental, guided = "--fundamental" in args, "--guided" in args
-    args = [a for a in args if a not in ("--fundamental", "--guided")]
+    fundamental, guided, q8 = "--fundamental" in args, "--guided" in args, "--q8" in args
+    args = [a for a in args if a not in ("--fundamental", "--guided", "--q8")]
     if len(args) < 2:
-        print("Required arguments: [--fundamental] [--guided] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
+        print("Required arguments: [--fundamental] [--guided] [--q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
         return 1
     imgs = [load_gray(a) for a in args]
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental, guided=guided)
+    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental, guided=guided, q8=q8)
     o, per_pair = o.cpu().tolist(), per_pair.cpu().tolist()
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"

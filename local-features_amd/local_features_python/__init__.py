@@ -15,12 +15,12 @@ import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
                    POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, load_library, match_q8_plan, model_path, plan_upload)
+                   MkdHandle, Q8_SCALE, comm_unique_id, load_library, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
-           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan"]
+           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan"]
 
 
 class Keypoint:
@@ -301,6 +301,39 @@ class LocalFeatures:
             m, best, second = m.cpu().numpy(), best.cpu().numpy(), second.cpu().numpy()
         pairs = [(int(i), int(j)) for i, j in enumerate(m) if j >= 0]
         return (pairs, best, second) if scores else pairs
+
+    def match_q8_batch(self, qa, offsets_a, qb, offsets_b, ratio=0.8, mutual=False, both=False, stream=None):
+        """match_batch over 8-bit descriptors (lf_mkd_match_q8_pairs_device: one launch, three with `mutual`): the same
+        layouts, the same offsets (any integer dtype, host or device), each pair decided exactly as `match_q8` decides it
+        alone.  qa [Na,128] / qb [Nb,128] must be uint8 (what `quantize` returns); they are moved to the handle's device if
+        they are elsewhere.  Returns device tensors (match_ab [Na] int32, match_ba [Nb] int32 or None, best [Na] int32,
+        second [Na] int32): the scores are the exact integer similarities of the a -> b direction; rows outside every pair
+        hold -1 / INT32_MIN.  Enqueued on `stream` (default: torch's current stream on the handle's device), asynchronously."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError("match_q8_batch: offsets_a and offsets_b need n_pairs + 1 entries each")
+        for q in (qa, qb):
+            if q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] != 128:
+                raise RuntimeError("match_q8_batch: qa and qb must be uint8 [n, 128] (LocalFeatures.quantize)")
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):      # the copies and the fills below are ordered with the call
+            a, b = qa.to(dev).contiguous(), qb.to(dev).contiguous()
+            oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+            na, nb = a.shape[0], b.shape[0]
+            int32_min = -2 ** 31
+            m_ab = torch.full((na,), -1, dtype=torch.int32, device=dev)
+            m_ba = torch.full((nb,), -1, dtype=torch.int32, device=dev) if (both or mutual) else None
+            best = torch.full((na,), int32_min, dtype=torch.int32, device=dev)
+            second = torch.full((na,), int32_min, dtype=torch.int32, device=dev)
+            if n_pairs and na and nb:       # (an empty side: every pair has too few candidates, the fills above are the answer)
+                with self._lock:
+                    self._inner.match_q8_pairs_device(a.data_ptr(), oa.data_ptr(), na, b.data_ptr(), ob.data_ptr(), nb, n_pairs,
+                                                      m_ab.data_ptr(), m_ba.data_ptr() if m_ba is not None else None, ratio,
+                                                      MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
+                                                      s.cuda_stream)
+        return m_ab, m_ba, best, second
 
     def match_ip_distance(self, desc_a, desc_b, factor=0.75):
         """The webcam example's acceptance rule (examples/webcam/src/main.rs:97-104,261-265): nearest and second-nearest
