@@ -46,10 +46,10 @@ def bits(x):
 
 
 class Dev:
-    """cases.batch(kind) on the device, and outputs pre-filled with sentinels (-7 / NaN)."""
+    """cases.batch(kind), or another batch of its layout, on the device, and outputs pre-filled with sentinels (-7 / NaN)."""
 
-    def __init__(self, torch, kind):
-        self.B = B = cases.batch(kind)
+    def __init__(self, torch, kind, B=None):
+        self.B = B = cases.batch(kind) if B is None else B
         self.kind, self.torch = kind, torch
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
         self.a, self.b, self.ka, self.kb = up(B.a), up(B.b), up(B.ka), up(B.kb)
