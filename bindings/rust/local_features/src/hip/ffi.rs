@@ -191,6 +191,14 @@ extern "C" {
                                         d_b: *const u8, d_offsets_b: *const u64, nb_total: u64, n_pairs: u32, ratio: f32,
                                         flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut i32,
                                         d_second: *mut i32, stream: *mut c_void) -> c_int;
+    // that batch under each pair's verified model: lf_mkd_match_guided_pairs_device's keypoints, model, kind and threshold over
+    // 8-bit rows, decided on the exact integer sums of the admissible rows; the grid is lf_mkd_match_q8_pairs_plan's
+    pub fn lf_mkd_match_q8_guided_pairs_device(h: *mut lf_mkd, d_a: *const u8, d_kps_a: *const lf_mkd_keypoint,
+                                               d_offsets_a: *const u64, na_total: u64, d_b: *const u8,
+                                               d_kps_b: *const lf_mkd_keypoint, d_offsets_b: *const u64, nb_total: u64,
+                                               d_model: *const f32, n_pairs: u32, kind: u32, threshold_px: f32, ratio: f32,
+                                               flags: u32, d_match_ab: *mut i32, d_match_ba: *mut i32, d_best: *mut i32,
+                                               d_second: *mut i32, stream: *mut c_void) -> c_int;
     // the a rows one workgroup of that launch owns and its grid, floor(rows / block_rows) + n_pairs per direction; host only
     pub fn lf_mkd_match_q8_pairs_plan(na_total: u64, nb_total: u64, n_pairs: u32, both_directions: u32,
                                       block_rows: *mut u32, workgroups: *mut u64) -> c_int;

@@ -342,6 +342,53 @@ impl LocalFeaturesHip {
         }).collect())
     }
 
+    /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates
+    /// are the rows of the other side that pass the verifier's inlier test with it under `models[p]` (row-major H or F, as the
+    /// verifiers return it; `kind`: `GUIDE_HOMOGRAPHY` / `GUIDE_FUNDAMENTAL`) within `threshold_px`.  `kps_a` / `kps_b` are
+    /// indexed like the descriptor rows.  Lowe's ratio 0.8, both directions, kept only where they agree.  Returns, per pair,
+    /// the (row of the pair's a rows, row of its b rows) matches; with the verifier's model, kind and threshold every
+    /// verified match is among them.
+    pub fn match_q8_guided_batch(&mut self, a: &ArrayView2<u8>, kps_a: &[Keypoint], offsets_a: &[u64], b: &ArrayView2<u8>,
+                                 kps_b: &[Keypoint], offsets_b: &[u64], models: &[[f32; 9]], kind: u32, threshold_px: f32)
+        -> Result<Vec<Vec<(usize, usize)>>, Error> {
+        assert_eq!(a.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(b.ncols(), DESCRIPTOR_LEN);
+        if offsets_a.is_empty() || offsets_a.len() != offsets_b.len() || models.len() + 1 != offsets_a.len() {
+            return Err(Error::BadArgument("match_q8_guided_batch: n_pairs + 1 offsets on either side, one model per pair".into()));
+        }
+        if kps_a.len() != a.nrows() || kps_b.len() != b.nrows() {
+            return Err(Error::BadArgument("match_q8_guided_batch: one keypoint per descriptor row on either side".into()));
+        }
+        let n_pairs = models.len();
+        let (a, b) = (a.as_standard_layout(), b.as_standard_layout());
+        let (na, nb) = (a.nrows(), b.nrows());
+        let mut m = vec![-1i32; na];
+        if n_pairs > 0 && na > 0 && nb > 0 {
+            let (ka, kb): (Vec<ffi::lf_mkd_keypoint>, Vec<ffi::lf_mkd_keypoint>) =
+                (kps_a.iter().map(from_keypoint).collect(), kps_b.iter().map(from_keypoint).collect());
+            let flat: Vec<f32> = models.iter().flatten().copied().collect();
+            // SAFETY: a, b are contiguous [n][128]; device buffers sized as declared; `m` has na entries
+            unsafe {
+                let (d_a, d_b) = (DeviceBuffer::from_slice(a.as_slice().unwrap())?, DeviceBuffer::from_slice(b.as_slice().unwrap())?);
+                let (d_ka, d_kb) = (DeviceBuffer::from_slice(&ka)?, DeviceBuffer::from_slice(&kb)?);
+                let (d_oa, d_ob) = (DeviceBuffer::from_slice(offsets_a)?, DeviceBuffer::from_slice(offsets_b)?);
+                let d_model = DeviceBuffer::from_slice(&flat)?;
+                let d_ab = DeviceBuffer::from_slice(&m)?;                    // rows outside every pair stay -1
+                let d_ba = DeviceBuffer::<i32>::new(nb)?;
+                check(self.h, ffi::lf_mkd_match_q8_guided_pairs_device(
+                    self.h, d_a.as_ptr(), d_ka.as_ptr(), d_oa.as_ptr(), na as u64, d_b.as_ptr(), d_kb.as_ptr(), d_ob.as_ptr(),
+                    nb as u64, d_model.as_ptr(), n_pairs as u32, kind, threshold_px, 0.8, MATCH_MUTUAL, d_ab.as_mut_ptr(),
+                    d_ba.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()))?;
+                check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+                d_ab.download(&mut m)?;
+            }
+        }
+        Ok((0..n_pairs).map(|p| {
+            let (lo, hi) = ((offsets_a[p] as usize).min(na), (offsets_a[p + 1] as usize).min(na));
+            (lo..hi.max(lo)).filter(|&i| m[i] >= 0).map(|i| (i - lo, m[i] as usize)).collect()
+        }).collect())
+    }
+
     /// RANSAC fundamental-matrix verification of matches (`lf_mkd_verify_fundamental`, `include/lf_mkd.h` states the
     /// algorithm): 7-point samples scored by Sampson distance on the GPU, then a rank-2 least-squares refit.  `matches` are
     /// (row of `kps_a`, row of `kps_b`) pairs as `match_features` returns them.  Returns F (row-major, b^T F a = 0 in pixels,

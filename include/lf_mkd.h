@@ -535,6 +535,54 @@ int lf_mkd_match_q8_pairs_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *
                                  const uint8_t *d_b, const uint64_t *d_offsets_b, uint64_t nb_total, uint32_t n_pairs,
                                  float ratio, uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba,
                                  int32_t *d_best, int32_t *d_second, void *stream);
+/* Guided matching over 8-bit rows: lf_mkd_match_q8_pairs_device once more, under each pair's verified model -- the conjunction
+ * of that call's contract and lf_mkd_match_guided_pairs_device's.  A caller who quantised once and dropped the f32 rows can
+ * run the pass behind verification on the bytes.
+ *   Layout, offsets, outputs and LF_MKD_MATCH_MUTUAL are those of lf_mkd_match_q8_pairs_device: pair p is a rows
+ *   [offsets_a[p], offsets_a[p+1]) against b rows [offsets_b[p], offsets_b[p+1]); both offset arrays hold n_pairs + 1 uint64
+ *   entries, live on the device, are non-decreasing and are never read by the host.  An offset beyond a total is read as the
+ *   total; an inverted pair is empty; match values are local to the pair; no row at or beyond a total is read or written; rows
+ *   outside [offsets[0], offsets[n_pairs]) are neither read nor written.  Rows are 128 offset-binary bytes; d_a and d_b must be
+ *   16-byte aligned.  d_best / d_second [na_total] are the int32 sums of the a -> b direction and may be NULL.
+ *   Keypoints and model are those of lf_mkd_match_guided_pairs_device: d_kps_a [na_total] / d_kps_b [nb_total] are indexed like
+ *   the descriptor rows, only x and y are read; d_model is [n_pairs][9] floats, exactly what the verifiers write as d_H / d_F.
+ * Candidates: that call's relation, bit for bit.  Row j of pair p's b side is admissible for row i of its a side iff the
+ * verifier's own step-4 test holds for the point pair (a_i, b_j) with thr2 = threshold_px * threshold_px formed on the host
+ * as the verifiers form it (LF_MKD_GUIDE_HOMOGRAPHY: w > 0 and fmaf(ex, ex, ey * ey) < thr2 * (w * w); LF_MKD_GUIDE_FUNDAMENTAL:
+ * the Sampson test -- the same correctly rounded operations in the same order, stated above).  Both directions evaluate
+ * pred(a_i, b_j); no inverse model is formed.  An all-zero model, a NaN anywhere in the model and a NaN coordinate need no
+ * special case: the comparison is false, the row has no candidate.
+ * Decision, per row: lf_mkd_match_q8_device's over the admissible rows ONLY -- the similarity is the exact int32 sum; ties go
+ * to the highest index; second == best when the maximum occurs twice among the admissible rows; match = the best's index if
+ * ratio <= 0 || (float)best * ratio > (float)second, else -1.  A row with one candidate has second = INT32_MIN and is
+ * accepted; a row with none gets -1 and INT32_MIN in both scores.  A small side is not refused here: nb_p == 1 is a legitimate
+ * candidate set, as in the f32 guided call (the unguided q8 pairs call refuses nb_p < 2; this one does not).  The result of a
+ * pair depends on its inputs alone: not on n_pairs, not on the other pairs, not on the run, not on the device's CU count.
+ * Superset property: take `verified` from lf_mkd_verify_*_device run on the LF_MKD_MATCH_MUTUAL output of
+ * lf_mkd_match_q8_pairs_device; run this call with that model, the same kind, the same ratio, LF_MKD_MATCH_MUTUAL and a
+ * threshold not below the verifier's.  Then every verified[i] = j >= 0 has match_ab[i] == j and match_ba[j] == i: j was i's
+ * best over a superset of the admissible rows, with ties to the highest index, so it is the best of the subset (the sums are
+ * the same integers in both calls); the subset's second is not above the superset's, and int32 -> f32 is monotone, so
+ * (float)best * ratio > (float)second still holds -- or ratio <= 0 held already; the reverse direction likewise; and
+ * thr2 * den is monotone in thr2, so an inlier of the verifier is admissible here.  (A verified match implies nb_p >= 2 and
+ * na_p >= 2: the unguided call accepted it.)  Guided matching never loses a verified match.
+ * Cost: every workgroup streams its pair's whole b side through LDS as the unguided call does; a 32 x 32 tile of candidates
+ * is tested on its rows' keypoints first, and a tile without an admissible pair costs no matrix instruction.
+ * One launch (three with LF_MKD_MATCH_MUTUAL: the two extra are lf_mkd_match_pairs_device's filter), no scratch, no
+ * allocation, no host synchronisation, asynchronous on `stream` (NULL: the handle's own): capturable in a hipGraph.
+ * n_pairs == 0 is LF_MKD_OK and writes nothing.  The grid is exactly what lf_mkd_match_q8_pairs_plan reports (the same R, the
+ * same slot map, both_directions = d_match_ba given).  lf_mkd_match_overflowed is not affected.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "match_q8_guided_pairs_device" and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; null d_a, d_b, d_kps_a, d_kps_b, offsets, d_model
+ * or d_match_ab; LF_MKD_MATCH_MUTUAL without d_match_ba; unknown flag bits; kind > 1; threshold_px not positive or its f32
+ * square not a finite normal number (the verifiers' rule); d_a or d_b not 16-byte aligned; a total above 2^31 - 1; a grid (the
+ * plan below) above 2^31 - 1 workgroups. */
+int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a,
+                                        const uint64_t *d_offsets_a, uint64_t na_total, const uint8_t *d_b,
+                                        const lf_mkd_keypoint *d_kps_b, const uint64_t *d_offsets_b, uint64_t nb_total,
+                                        const float *d_model, uint32_t n_pairs, uint32_t kind, float threshold_px, float ratio,
+                                        uint32_t flags, int32_t *d_match_ab, int32_t *d_match_ba, int32_t *d_best,
+                                        int32_t *d_second, void *stream);
 /* The grid lf_mkd_match_q8_pairs_device launches -- host-only, no device, no handle, no environment variable; the launch path
  * calls this very function.  *block_rows = R, the a rows one workgroup owns (a power of two; a build-time constant);
  * *workgroups = floor(na_total / R) + n_pairs, plus floor(nb_total / R) + n_pairs when both_directions != 0.  Output pointers

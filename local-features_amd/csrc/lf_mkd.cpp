@@ -2029,6 +2029,34 @@ int lf_mkd_match_q8_pairs_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *
     return LF_MKD_OK;
 }
 
+// Guided matching over 8-bit rows: the two calls' refusals together, the q8 pairs call's grid.
+int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
+                                        uint64_t na_total, const uint8_t *d_b, const lf_mkd_keypoint *d_kps_b,
+                                        const uint64_t *d_offsets_b, uint64_t nb_total, const float *d_model, uint32_t n_pairs,
+                                        uint32_t kind, float threshold_px, float ratio, uint32_t flags, int32_t *d_match_ab,
+                                        int32_t *d_match_ba, int32_t *d_best, int32_t *d_second, void *stream) {
+    const bool mutual = flags & LF_MKD_MATCH_MUTUAL;
+    const char *msg = nullptr;
+    if (!d_a || !d_b || !d_kps_a || !d_kps_b || !d_offsets_a || !d_offsets_b || !d_model || !d_match_ab) msg = "null pointer";
+    else if (flags & ~LF_MKD_MATCH_MUTUAL) msg = "unknown flag bits";
+    else if (mutual && !d_match_ba) msg = "LF_MKD_MATCH_MUTUAL needs d_match_ba";
+    else if (kind > LF_MKD_GUIDE_FUNDAMENTAL) msg = "kind must be LF_MKD_GUIDE_HOMOGRAPHY or LF_MKD_GUIDE_FUNDAMENTAL";
+    // (the verifiers' rule, verify_args below: the kernel compares against thr^2 in f32)
+    else if (!(threshold_px > 0.f) || !std::isnormal(threshold_px * threshold_px))
+        msg = "threshold_px must be positive, with a finite normal f32 square (about 1.09e-19 .. 1.84e19)";
+    else if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 15) msg = "d_a and d_b must be 16-byte aligned";
+    else if (!(msg = match_q8_pairs_sizes(na_total, nb_total, n_pairs, d_match_ba != nullptr)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "match_q8_guided_pairs_device", msg);
+    if (n_pairs == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_match_q8_guided_pairs(d_a, reinterpret_cast<const float *>(d_kps_a), d_offsets_a, na_total, d_b,
+                                 reinterpret_cast<const float *>(d_kps_b), d_offsets_b, nb_total, d_model, n_pairs, kind,
+                                 threshold_px, ratio, mutual, d_match_ab, d_match_ba, d_best, d_second,
+                                 stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 // The arguments of both verification entry points, checked before the handle so that every bad argument is reported without
 // a device: the message goes to the handle, or to lf_mkd_last_error(NULL) when there is none.
 static int verify_args(lf_mkd *h, bool null_pointer, uint32_t n_hypotheses, float threshold_px, const char *what) {

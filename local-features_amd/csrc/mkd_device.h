@@ -218,6 +218,12 @@ uint64_t match_q8_pairs_slots(uint64_t n_total, unsigned n_pairs);
 void launch_match_q8_pairs(const unsigned char *a, const uint64_t *off_a, uint64_t na_total, const unsigned char *b,
                            const uint64_t *off_b, uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab,
                            int *match_ba, int *best, int *second, hipStream_t stream);
+// guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
+// batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
+void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,
+                                  const unsigned char *b, const float *kps_b, const uint64_t *off_b, uint64_t nb_total,
+                                  const float *model, unsigned n_pairs, unsigned kind, float threshold, float ratio, bool mutual,
+                                  int *match_ab, int *match_ba, int *best, int *second, hipStream_t stream);
 
 // RANSAC homography verification (mkd_verify.hip; algorithm: include/lf_mkd.h).  Keypoints are read as rows of 5 floats
 // (lf_mkd_keypoint).  Scratch the caller owns: pairs [n_pairs], counts [n_pairs][slices][n_hyp]; `verified` also holds each

@@ -23,33 +23,16 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
-#include "mkd_match_small.h"   // pair_rows, last_pair_at_or_before: the batched forms' pair arithmetic
+#include "mkd_match_small.h"       // pair_rows, last_pair_at_or_before: the batched forms' pair arithmetic
+#include "mkd_match_q8_common.h"   // the tile constants, q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
 
 namespace lfmkd {
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kQTileRows = 32;                     // rows of a / b per MFMA tile
-constexpr int kQTileBytes = kQTileRows * 128;      // [chunk 8][row 32][16 B] = 4 KiB
 constexpr int kQWaves = 8, kQTiles = 4;            // per wave: 4 a tiles = 64 VGPRs of fragments
 constexpr int kQStage = 4;                         // b tiles per LDS stage: 16 KiB = 512 threads x 2 x 16 B
 constexpr int kQBlockRows = kQWaves * kQTiles * kQTileRows;
 constexpr int kQMaxSplits = 1024;
-constexpr int kSignBits = (int)0x80808080u;
-
-__device__ __forceinline__ void q8_lds_dma16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds(g, reinterpret_cast<__attribute__((address_space(3))) void *>(
-                                            reinterpret_cast<uintptr_t>(l)), 16, 0, 0);
-}
-
-__device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }   // (v_max3_i32)
-
-// the acceptance rule (lf_mkd.h): both conversions are exact (|sums| < 2^24, INT32_MIN = -2^31), one f32 multiplication
-__device__ __forceinline__ int q8_decide(int best, int index, int second, float ratio) {
-    return (index >= 0 && (ratio <= 0.f || (float)best * ratio > (float)second)) ? index : -1;
-}
 
 }  // namespace
 
@@ -240,21 +223,7 @@ __global__ __launch_bounds__(256) void match_q8_merge(const int *__restrict__ p_
 // (likewise y, ny), so a DMA lane beyond the pair's last y row reads the pair's last y row (masked to INT32_MIN in the
 // epilogue) and an idle x row redoes the pair's last x row.  No byte of another pair, of the rows in front of the first or
 // behind the last pair, or at or beyond a total is ever requested.
-#ifndef LF_Q8_PAIRS_WAVES
-#define LF_Q8_PAIRS_WAVES 4
-#endif
-#ifndef LF_Q8_PAIRS_TILES
-#define LF_Q8_PAIRS_TILES 1
-#endif
-namespace {
-constexpr int kPWaves = LF_Q8_PAIRS_WAVES, kPTiles = LF_Q8_PAIRS_TILES;   // 4 x 1 tile = 128 rows (measured beside 256 and 512)
-constexpr int kPStage = 4;                                                // y tiles per LDS stage: 16 KiB
-constexpr int kPThreads = 64 * kPWaves;
-constexpr int kPRows = kPWaves * kPTiles * kQTileRows;
-constexpr int kPPieces = kPStage * 256 / kPThreads;                       // 16-byte DMA pieces per thread and stage
-static_assert(kPPieces * kPThreads == kPStage * 256 && (kPRows & (kPRows - 1)) == 0, "whole pieces, R a power of two");
-}  // namespace
-
+// (the workgroup's shape -- kPWaves, kPTiles, kPStage, R = kPRows -- is in mkd_match_q8_common.h: the guided form shares it)
 __global__ __launch_bounds__(kPThreads) void match_q8_pairs(const unsigned char *__restrict__ a,
                                                             const uint64_t *__restrict__ off_a, uint64_t na_total,
                                                             const unsigned char *__restrict__ b,

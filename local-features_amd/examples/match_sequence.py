@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_sequence [--fundamental] [--guided] [--q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
+"""match_sequence [--fundamental] [--guided] [--q8] [--guided-q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size through the whole pipeline on the
 device, every stage launched once for all of them and nothing copied to the host in between:
 
   detect_top_n(2000, min_size 0) on all frames      lf_mkd_detect_frames_device
@@ -13,9 +13,12 @@ device, every stage launched once for all of them and nothing copied to the host
 
   with --q8: the descriptors quantised once to 8 bits  LocalFeatures.quantize, then LocalFeatures.match_q8_batch(mutual=True)
   and the first pass matched on exact integer sums    (lf_mkd_match_q8_pairs_device); a --guided second pass stays on f32
+  with --guided-q8: both passes on the 8-bit rows --   LocalFeatures.match_q8_batch, then LocalFeatures.match_q8_guided_batch
+  quantised once, matched, verified, matched again     (lf_mkd_match_q8_guided_pairs_device) and verified once more with the
+  under each pair's model on the same bytes            same seed; the f32 rows are not read after the quantiser
 
 and prints one line per pair: ratio-test matches t -> t + 1, those the other direction confirms, those the geometry keeps
-(and with --guided: the guided mutual matches -- never fewer than the geometry kept -- and those the second verification keeps).
+(and with --guided or --guided-q8: the guided mutual matches -- never fewer than the geometry kept -- and those the second verification keeps).
 The frames are ONE descriptor array; the matcher is given it twice -- with the offsets of frames 0 .. N-2 as the a side and
 with the offsets of frames 1 .. N-1 as the b side -- so no row is duplicated.
 
@@ -34,12 +37,14 @@ def load_gray(path):
     return np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
 
 
-def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None, guided=False, q8=False):
+def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.8, seed=0, feats=None, guided=False, q8=False,
+                   guided_q8=False):
     """frames [n, h, w] float32 in [0, 1].  Returns device tensors (keypoints [m,5], descriptors [m,128], frame offsets
     [n + 1], mutual matches t -> t + 1 [m] local to frame t + 1, verified matches [m], model [n - 1,3,3], per pair
     [n - 1, 3]: ratio-test matches, mutual matches, verified inliers).  guided: the matches, the verified matches and the
     model are those of the guided second pass, and per pair has two more columns: guided mutual matches, verified again.
-    q8: the first-pass matches come from the 8-bit rows (quantised once, on the device); the guided pass, if any, from `desc`."""
+    q8: the first-pass matches come from the 8-bit rows (quantised once, on the device); the guided pass, if any, from `desc`.
+    guided_q8: both passes on the 8-bit rows (it implies q8's first pass); the returns and the columns are those of `guided`."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -59,7 +64,7 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
         # frame t against frame t + 1: the a side is `desc` with the offsets of frames 0 .. n-2, the b side the same array
         # with the offsets of frames 1 .. n-1 -- no row is copied and no offset is read back to the host
         oa, ob = o[:n], o[1:]
-        if q8:
+        if q8 or guided_q8:
             q = feats.quantize(desc)
             m_ab, m_ba, best, second = feats.match_q8_batch(q, oa, q, ob, ratio=ratio, mutual=True)
             # the int32 scores as floats (exact: |sums| < 2^24), "no candidate" (INT32_MIN) as the f32 path's -inf
@@ -73,10 +78,13 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
         in_pair = frame_of < n - 1
         count = lambda mask: torch.bincount(frame_of[mask & in_pair], minlength=n)[:n - 1]
         columns = [count(best * ratio > second), count(m_ab >= 0), count(ver >= 0)]
-        if guided:
+        if guided or guided_q8:
             # the verifier's model, threshold (the defaults of both calls) and ratio: every verified match is found again
-            m_ab, _, _, _ = feats.match_guided_batch(desc, kps, oa, desc, kps, ob, model,
-                                                     kind="fundamental" if fundamental else "homography", ratio=ratio, mutual=True)
+            kind = "fundamental" if fundamental else "homography"
+            if guided_q8:
+                m_ab, _, _, _ = feats.match_q8_guided_batch(q, kps, oa, q, kps, ob, model, kind=kind, ratio=ratio, mutual=True)
+            else:
+                m_ab, _, _, _ = feats.match_guided_batch(desc, kps, oa, desc, kps, ob, model, kind=kind, ratio=ratio, mutual=True)
             model, ver, stats = verify(kps, oa, kps, ob, m_ab, seed=seed)
             columns += [count(m_ab >= 0), count(ver >= 0)]
         per_pair = torch.stack(columns, dim=1)
@@ -85,21 +93,22 @@ def match_sequence(frames, top_n=2000, min_size=0.0, fundamental=False, ratio=0.
 
 def main():
     args = sys.argv[1:]
-    fundamental, guided, q8 = "--fundamental" in args, "--guided" in args, "--q8" in args
-    args = [a for a in args if a not in ("--fundamental", "--guided", "--q8")]
+    flags = ("--fundamental", "--guided", "--q8", "--guided-q8")
+    fundamental, guided, q8, guided_q8 = (f in args for f in flags)
+    args = [a for a in args if a not in flags]
     if len(args) < 2:
-        print("Required arguments: [--fundamental] [--guided] [--q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
+        print("Required arguments: [--fundamental] [--guided] [--q8] [--guided-q8] IMAGE_1 IMAGE_2 [IMAGE_3 ...]", file=sys.stderr)
         return 1
     imgs = [load_gray(a) for a in args]
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental, guided=guided, q8=q8)
+    _, _, o, _, _, _, per_pair = match_sequence(np.stack(imgs), fundamental=fundamental, guided=guided, q8=q8, guided_q8=guided_q8)
     o, per_pair = o.cpu().tolist(), per_pair.cpu().tolist()
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
     for t, (raw, mutual, inl, *again) in enumerate(per_pair):
-        more = f", {again[0]} guided, {again[1]} agree after re-verification" if guided else ""
+        more = f", {again[0]} guided, {again[1]} agree after re-verification" if guided or guided_q8 else ""
         print(f"Pair {t + 1} -> {t + 2}: {raw} matches, {mutual} mutual, {inl} agree with {what}{more}")
     return 0
 

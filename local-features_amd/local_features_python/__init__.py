@@ -335,6 +335,68 @@ class LocalFeatures:
                                                       s.cuda_stream)
         return m_ab, m_ba, best, second
 
+    def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
+                              ratio=0.8, mutual=True, both=False, stream=None):
+        """match_guided_batch over 8-bit descriptors (lf_mkd_match_q8_guided_pairs_device: one launch, three with `mutual`):
+        match_q8_batch once more, with the candidates of every row restricted to the rows of the other side that pass the
+        verifier's inlier test with it under the pair's model -- the relation match_guided_batch uses, bit for bit.  qa
+        [Na,128] / qb [Nb,128] must be uint8 (what `quantize` returns); kps_a [Na,5] / kps_b [Nb,5], the offsets and model
+        [n_pairs,3,3] (or [n_pairs,9]) as match_guided_batch takes them.  kind: "homography" or "fundamental" (or GUIDE_*);
+        threshold in pixels, default the verifier's own (3.0 for H, 1.5 for F).  Returns device tensors (match_ab [Na] int32,
+        match_ba [Nb] int32 or None -- given with `mutual` or `both` --, best [Na] int32, second [Na] int32): the scores are
+        the exact integer similarities of the a -> b direction over the admissible rows; rows outside every pair hold
+        -1 / INT32_MIN.  With the model verification gave on match_q8_batch(mutual=True)'s output, the verifier's threshold and
+        the same ratio, every verified match is found again (include/lf_mkd.h).  Enqueued on `stream` (default: torch's
+        current stream on the handle's device), asynchronously."""
+        import torch
+        kinds = {"homography": GUIDE_HOMOGRAPHY, "fundamental": GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY: GUIDE_HOMOGRAPHY,
+                 GUIDE_FUNDAMENTAL: GUIDE_FUNDAMENTAL}
+        if kind not in kinds:
+            raise RuntimeError('match_q8_guided_batch: kind must be "homography" or "fundamental"')
+        kind = kinds[kind]
+        if threshold is None:
+            threshold = 3.0 if kind == GUIDE_HOMOGRAPHY else 1.5
+        dev = torch.device("cuda", self.device)
+        n_pairs = int(offsets_a.numel()) - 1
+        if n_pairs < 0 or int(offsets_b.numel()) != n_pairs + 1:
+            raise RuntimeError("match_q8_guided_batch: offsets_a and offsets_b need n_pairs + 1 entries each")
+        if int(model.numel()) != 9 * n_pairs:
+            raise RuntimeError("match_q8_guided_batch: model needs 9 entries per pair")
+        for q in (qa, qb):
+            if q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] != 128:
+                raise RuntimeError("match_q8_guided_batch: qa and qb must be uint8 [n, 128] (LocalFeatures.quantize)")
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):      # the copies and the fills below are ordered with the call
+            a, b = qa.to(dev).contiguous(), qb.to(dev).contiguous()
+            ka = kps_a.to(dev, torch.float32).reshape(-1, 5).contiguous()
+            kb = kps_b.to(dev, torch.float32).reshape(-1, 5).contiguous()
+            oa, ob = offsets_a.to(dev, torch.int64).contiguous(), offsets_b.to(dev, torch.int64).contiguous()
+            md = model.to(dev, torch.float32).reshape(-1, 9).contiguous()
+            na, nb = a.shape[0], b.shape[0]
+            if ka.shape[0] != na or kb.shape[0] != nb:
+                raise RuntimeError("match_q8_guided_batch: one keypoint per descriptor row on either side")
+            int32_min = -2 ** 31
+            m_ab = torch.full((na,), -1, dtype=torch.int32, device=dev)
+            m_ba = torch.full((nb,), -1, dtype=torch.int32, device=dev) if (both or mutual) else None
+            best = torch.full((na,), int32_min, dtype=torch.int32, device=dev)
+            second = torch.full((na,), int32_min, dtype=torch.int32, device=dev)
+            if n_pairs and na and nb:       # (an empty side: no row has a candidate, the fills above are the answer)
+                with self._lock:
+                    self._inner.match_q8_guided_pairs_device(a.data_ptr(), ka.data_ptr(), oa.data_ptr(), na, b.data_ptr(),
+                                                             kb.data_ptr(), ob.data_ptr(), nb, md.data_ptr(), n_pairs,
+                                                             m_ab.data_ptr(), m_ba.data_ptr() if m_ba is not None else None,
+                                                             kind, threshold, ratio, MATCH_MUTUAL if mutual else 0,
+                                                             best.data_ptr(), second.data_ptr(), s.cuda_stream)
+        return m_ab, m_ba, best, second
+
+    def match_q8_guided(self, qa, kps_a, qb, kps_b, model, kind="homography", threshold=None, ratio=0.8, mutual=True, both=False,
+                        stream=None):
+        """match_q8_guided_batch for one pair (n_pairs = 1: all of qa against all of qb under `model` [3,3])."""
+        import torch
+        na, nb = int(qa.numel()) // 128, int(qb.numel()) // 128
+        return self.match_q8_guided_batch(qa, kps_a, torch.tensor([0, na]), qb, kps_b, torch.tensor([0, nb]), model, kind,
+                                          threshold, ratio, mutual, both, stream)
+
     def match_ip_distance(self, desc_a, desc_b, factor=0.75):
         """The webcam example's acceptance rule (examples/webcam/src/main.rs:97-104,261-265): nearest and second-nearest
         neighbour of desc_a[i] in desc_b under the inner-product distance d = 1 - <a, b> (usearch MetricKind::IP), accepted

@@ -39,7 +39,7 @@ SYMBOLS = (
     "lf_mkd_verify_homography", "lf_mkd_verify_homography_device",
     "lf_mkd_verify_fundamental", "lf_mkd_verify_fundamental_device",
     "lf_mkd_quantize_descriptors", "lf_mkd_quantize_descriptors_device", "lf_mkd_match_q8", "lf_mkd_match_q8_device",
-    "lf_mkd_match_q8_plan", "lf_mkd_match_q8_pairs_device", "lf_mkd_match_q8_pairs_plan",
+    "lf_mkd_match_q8_plan", "lf_mkd_match_q8_pairs_device", "lf_mkd_match_q8_guided_pairs_device", "lf_mkd_match_q8_pairs_plan",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 COMM_ID_BYTES = 128
@@ -132,6 +132,7 @@ def load_library():
     L.lf_mkd_match_q8.argtypes = [vp, vp, u64, vp, u64, ctypes.c_float, vp]
     L.lf_mkd_match_q8_plan.argtypes = [u64, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
     L.lf_mkd_match_q8_pairs_device.argtypes = L.lf_mkd_match_pairs_device.argtypes
+    L.lf_mkd_match_q8_guided_pairs_device.argtypes = L.lf_mkd_match_guided_pairs_device.argtypes
     L.lf_mkd_match_q8_pairs_plan.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u64)]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
@@ -588,6 +589,16 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_match_guided_pairs_device(
             self._h, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs, kind, threshold,
             ratio, flags, d_match_ab, d_match_ba, d_best, d_second, s), "lf_mkd_match_guided_pairs_device")
+
+    def match_q8_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
+                                     d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
+                                     d_best=None, d_second=None, stream=None):
+        """lf_mkd_match_q8_guided_pairs_device: match_guided_pairs_device over 8-bit rows -- the same keypoints, model, kind and
+        threshold, each row decided as match_q8_device decides it over its admissible rows alone; d_best / d_second are int32
+        (device pointers; see include/lf_mkd.h).  flags: MATCH_MUTUAL."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_guided_pairs_device(
+            self._h, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs, kind, threshold,
+            ratio, flags, d_match_ab, d_match_ba, d_best, d_second, s), "lf_mkd_match_q8_guided_pairs_device")
 
     def verify_homography_device(self, d_kps_a, d_offsets_a, d_kps_b, d_offsets_b, d_match, n_pairs, d_H, d_verified, d_stats,
                                  n_hypotheses=2048, threshold=3.0, seed=0, flags=0, stream=None):
