@@ -11,7 +11,8 @@
 //   LF_ABLATE_FORCE_W4     the 4-wave form at every request size
 //   LF_KP_ABLATE_PRODUCER  keypoint mode: the describe waves alone   LF_KP_ABLATE_TAPS   ... everything but a sample's loads
 //   LF_KP_PRODUCER_PRIO=n / LF_KP_CONSUMER_PRIO=n                    wave priorities of the two kinds of wave
-//   LF_ABLATE_ROWS=n       the row loop walks n of a patch's 32 rows (producers too): the bound of a row-split form
+//   LF_ABLATE_ROWS=n       the row loop walks n of a patch's 32 rows (producers too): the bound of a row-split form.  Keypoint
+//                          mode, and patch mode in F32 / F16_FP6; f16x3's patch mode walks row pairs and refuses to compile
 //   LF_PHASE_TIMING        per-wave clocks of the phases of a patch row, left by workgroup 0 in out[wave * 128 + phase]
 #pragma once
 #include <hip/hip_runtime.h>

@@ -119,7 +119,9 @@ __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ 
     const unsigned lane16 = (unsigned)lane * 16u;
 #pragma unroll
     for (int j = 0; j < (kPieces + W - 1) / W; ++j) {
-        if (wave + W * j < kPieces) {   // uniform
+        // uniform; `wave` is in [0, W), so where W divides the pieces every wave takes every turn and nothing is asked (asked,
+        // the two answers of f16x3's 8-wave form sit in registers through the row loop, which has none to spare)
+        if (kPieces % W == 0 || wave + W * j < kPieces) {
             const int i = wave + W * j, piece = ODDV ? i + 2 * (i >> 2) : i;
             const unsigned char *g = lut_rows + ((size_t)row * row_bytes(FOLD) + (size_t)piece * 1024);   // uniform
             lds_dma16_sv(g, lane16, lds_row + piece * 1024);
@@ -155,12 +157,13 @@ __device__ __forceinline__ void issue_w_step(const unsigned char *__restrict__ w
 // ScratchSize is not 0 (tools/check_scratch.py), and the raw_out verification tap, which stores, waits with vmcnt(0).
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// one raw patch row (16 patches x 128 B) of this wave into ring slot `slot`; rows outside [0,31] replicate.
+// one raw patch row, `row` in [0, 31] (16 patches x 128 B), of this wave into ring slot `slot`.  The one-row patch forms keep
+// copies of rows 0 and 31 in slots of their own for the rows beyond the patch (clamp_row); the pair forms request no row twice.
 // src = the wave's (uniform) first patch, lane_off = byte offset of the lane's patch and 16-byte chunk from it.
 struct RawSrc { const unsigned char *base; unsigned lane_off; };
+__device__ __forceinline__ constexpr int clamp_row(int row) { return row < 0 ? 0 : (row > 31 ? 31 : row); }
 __device__ __forceinline__ void issue_raw_row(const RawSrc &src, int row, unsigned char *ring, int slot) {
-    const int y = row < 0 ? 0 : (row > 31 ? 31 : row);
-    const unsigned char *g = src.base + y * 128;   // uniform
+    const unsigned char *g = src.base + row * 128;   // uniform
     lds_dma16_sv(g, src.lane_off, ring + slot * 2048);
     lds_dma16_sv(g + 64, src.lane_off, ring + slot * 2048 + 1024);
 }
@@ -414,38 +417,85 @@ __device__ __forceinline__ void mma_part(const AFrag<POOL> &a, const BFrag &b, f
     }
 }
 
-// Blurred row of this lane's segment from the raw-row ring (patch_gradients.glsl:72-92): vertical 5 taps over
-// ring slots s0..s0+4, then horizontal 5 taps with the neighbours fetched from lanes -/+16.
-// Returns the row plus its x-1 / x+8 neighbours.
-// slot_of_tap(i): ring slot of the i-th of the five raw rows.
+// Blurred row of this lane's segment from the raw-row ring (patch_gradients.glsl:72-92): vertical 5 taps over five ring
+// slots, then horizontal 5 taps with the neighbours fetched from lanes -/+16.  The two halves are separate functions: patch
+// mode runs the vertical half for two rows at once (vblur_pair).
+// Vertical half.  The lane's two 16-byte blocks of a raw row sit at ring_a and ring_b + slot * 2048; slot_of_tap(i) = ring slot of
+// the i-th of the five raw rows.  v = the eight pixels, first block then second, both in ascending x.
 template <class SlotOfTap>
-__device__ __forceinline__ void blur_row_impl(const unsigned char *ring_lane, SlotOfTap slot_of_tap, int addr_l, int addr_r,
-                                              bool has_l, bool has_r, float (&out)[8], float &out_l, float &out_r) {
+__device__ __forceinline__ void vblur_row(const unsigned char *ring_a, const unsigned char *ring_b, SlotOfTap slot_of_tap,
+                                          float (&v)[8]) {
     if constexpr (ablate::kNoFrontEnd) {   // no blur: the first tap's raw row as it is
         const int sl = slot_of_tap(0);
-        const f32x4 a_ = *reinterpret_cast<const f32x4 *>(ring_lane + sl * 2048);
-        const f32x4 b_ = *reinterpret_cast<const f32x4 *>(ring_lane + sl * 2048 + 256);
+        const f32x4 a_ = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
+        const f32x4 b_ = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
 #pragma unroll
-        for (int x = 0; x < 4; ++x) { out[x] = a_[x]; out[4 + x] = b_[x]; }
+        for (int x = 0; x < 4; ++x) { v[x] = a_[x]; v[4 + x] = b_[x]; }
+        return;
+    }
+    const float kk[5] = {kB0, kB1, kB2, kB1, kB0};
+    f32x2 v2[4];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int sl = slot_of_tap(i);
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
+        const f32x4 hi = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
+        const f32x2 r[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v2[e] = i == 0 ? pk_set(kk[0]) * r[e] : pk_fma(pk_set(kk[i]), r[e], v2[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[2 * e] = v2[e].x; v[2 * e + 1] = v2[e].y; }
+}
+
+// Vertical half of TWO blurred rows at once (patch mode's row pairs): the NR raw rows the two need between them are read
+// from the ring once each -- row j from slot_of_row(j) -- and feed two accumulations, tap i of the first row being raw row
+// tap_a(i) and of the second tap_b(i).  Each accumulation is vblur_row's: the same five operations in the same order, a
+// replicated row (the patch's first and last rows) as a tap of its own with its own coefficient.
+template <int NR, class SlotOfRow, class TapA, class TapB>
+__device__ __forceinline__ void vblur_pair(const unsigned char *ring_a, const unsigned char *ring_b, SlotOfRow slot_of_row,
+                                           TapA tap_a, TapB tap_b, float (&va)[8], float (&vb)[8]) {
+    f32x2 r[NR][4];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int sl = slot_of_row(j);
+        const f32x4 lo = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
+        const f32x4 hi = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
+        r[j][0] = f32x2{lo[0], lo[1]}; r[j][1] = f32x2{lo[2], lo[3]};
+        r[j][2] = f32x2{hi[0], hi[1]}; r[j][3] = f32x2{hi[2], hi[3]};
+    }
+    f32x2 a2[4], b2[4];
+    if constexpr (ablate::kNoFrontEnd) {   // no blur: the first taps' raw rows as they are
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { a2[e] = r[tap_a(0)][e]; b2[e] = r[tap_b(0)][e]; }
+    } else {
+        const float kk[5] = {kB0, kB1, kB2, kB1, kB0};
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int ja = tap_a(i), jb = tap_b(i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a2[e] = i == 0 ? pk_set(kk[0]) * r[ja][e] : pk_fma(pk_set(kk[i]), r[ja][e], a2[e]);
+                b2[e] = i == 0 ? pk_set(kk[0]) * r[jb][e] : pk_fma(pk_set(kk[i]), r[jb][e], b2[e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        va[2 * e] = a2[e].x; va[2 * e + 1] = a2[e].y;
+        vb[2 * e] = b2[e].x; vb[2 * e + 1] = b2[e].y;
+    }
+}
+
+// Horizontal half: vb = the lane's eight pixels of the vertically blurred row.  Returns the row plus its x-1 / x+8 neighbours.
+__device__ __forceinline__ void hblur_row(const float (&vb)[8], int addr_l, int addr_r, bool has_l, bool has_r, float (&out)[8],
+                                          float &out_l, float &out_r) {
+    if constexpr (ablate::kNoFrontEnd) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) out[x] = vb[x];
         out_l = out[0];
         out_r = out[7];
         return;
-    }
-    float vb[8];
-    {
-        const float kk[5] = {kB0, kB1, kB2, kB1, kB0};
-        f32x2 v2[4];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int sl = slot_of_tap(i);
-            const f32x4 lo = *reinterpret_cast<const f32x4 *>(ring_lane + sl * 2048);
-            const f32x4 hi = *reinterpret_cast<const f32x4 *>(ring_lane + sl * 2048 + 256);
-            const f32x2 r[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v2[e] = i == 0 ? pk_set(kk[0]) * r[e] : pk_fma(pk_set(kk[i]), r[e], v2[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { vb[2 * e] = v2[e].x; vb[2 * e + 1] = v2[e].y; }
     }
     float ext[12];
     const float l0 = lane_fetch(addr_l, vb[6]), l1 = lane_fetch(addr_l, vb[7]);
@@ -473,41 +523,30 @@ __device__ __forceinline__ void blur_row_impl(const unsigned char *ring_lane, Sl
     out_r = has_r ? hr : out[7];
 }
 
+template <class SlotOfTap>
+__device__ __forceinline__ void blur_row_impl(const unsigned char *ring_lane, SlotOfTap slot_of_tap, int addr_l, int addr_r,
+                                              bool has_l, bool has_r, float (&out)[8], float &out_l, float &out_r) {
+    float vb[8];
+    vblur_row(ring_lane, ring_lane + 256, slot_of_tap, vb);
+    hblur_row(vb, addr_l, addr_r, has_l, has_r, out, out_l, out_r);
+}
+
 // The same for the folded forms' lane map.  The lane's two blocks of the raw row come from ring_a (x in [4q, 4q+4)) and
 // ring_b (x in [28-4q, 32-4q)).  out[0..3] = the first block in ascending x, out[4..7] = the second in DESCENDING x: out[4 + i]
 // is the mirror pixel of out[i].  Each block needs two neighbours a side of the vertically blurred row and one of the
 // blurred row: the first block's from the first blocks of lanes -/+16, the second block's from the second blocks of
 // lanes +/-16; where the two blocks touch (q == 3) they are the lane's own values, at the patch's edges (q == 0) they replicate.
 // nb = the blurred row at x = 4q-1, 4q+4, 27-4q, 32-4q.  Per pixel the arithmetic and its order are blur_row_impl's.
-template <class SlotOfTap>
-__device__ __forceinline__ void blur_row_fold_impl(const unsigned char *ring_a, const unsigned char *ring_b, SlotOfTap slot_of_tap,
-                                                   int addr_l, int addr_r, bool has_l, bool has_r, float (&out)[8],
-                                                   float (&nb)[4]) {
-    if constexpr (ablate::kNoFrontEnd) {   // no blur: the first tap's raw row as it is
-        const int sl = slot_of_tap(0);
-        const f32x4 a_ = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
-        const f32x4 b_ = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
+__device__ __forceinline__ void hblur_row_fold(const float (&v)[8], int addr_l, int addr_r, bool has_l, bool has_r,
+                                               float (&out)[8], float (&nb)[4]) {
+    if constexpr (ablate::kNoFrontEnd) {
 #pragma unroll
-        for (int x = 0; x < 4; ++x) { out[x] = a_[x]; out[4 + x] = b_[3 - x]; }
+        for (int x = 0; x < 4; ++x) { out[x] = v[x]; out[4 + x] = v[7 - x]; }
         nb[0] = out[0]; nb[1] = out[3]; nb[2] = out[7]; nb[3] = out[4];
         return;
     }
-    float va[4], vb[4];   // vertically blurred, both blocks in ascending x
-    {
-        const float kk[5] = {kB0, kB1, kB2, kB1, kB0};
-        f32x2 v2[4];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int sl = slot_of_tap(i);
-            const f32x4 lo = *reinterpret_cast<const f32x4 *>(ring_a + sl * 2048);
-            const f32x4 hi = *reinterpret_cast<const f32x4 *>(ring_b + sl * 2048);
-            const f32x2 r[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v2[e] = i == 0 ? pk_set(kk[0]) * r[e] : pk_fma(pk_set(kk[i]), r[e], v2[e]);
-        }
-        va[0] = v2[0].x; va[1] = v2[0].y; va[2] = v2[1].x; va[3] = v2[1].y;
-        vb[0] = v2[2].x; vb[1] = v2[2].y; vb[2] = v2[3].x; vb[3] = v2[3].y;
-    }
+    // vertically blurred (vblur_row), both blocks in ascending x
+    const float va[4] = {v[0], v[1], v[2], v[3]}, vb[4] = {v[4], v[5], v[6], v[7]};
     float ea[8], eb[8];
     {
         const float la0 = lane_fetch(addr_l, va[2]), la1 = lane_fetch(addr_l, va[3]);   // x = 4q-2, 4q-1
@@ -551,6 +590,15 @@ __device__ __forceinline__ void blur_row_fold_impl(const unsigned char *ring_a, 
     nb[3] = has_l ? hbr : ob[3];
 }
 
+template <class SlotOfTap>
+__device__ __forceinline__ void blur_row_fold_impl(const unsigned char *ring_a, const unsigned char *ring_b, SlotOfTap slot_of_tap,
+                                                   int addr_l, int addr_r, bool has_l, bool has_r, float (&out)[8],
+                                                   float (&nb)[4]) {
+    float v[8];
+    vblur_row(ring_a, ring_b, slot_of_tap, v);
+    hblur_row_fold(v, addr_l, addr_r, has_l, has_r, out, nb);
+}
+
 // Folds a stream about the row's middle: s[0], s[1] = the lane's first block, s[2], s[3] = the mirror pixels of the same.
 __device__ __forceinline__ void fold_sum(const f32x2 (&s)[4], f32x2 &e0, f32x2 &e1) { e0 = s[0] + s[2]; e1 = s[1] + s[3]; }
 __device__ __forceinline__ void fold_diff(const f32x2 (&s)[4], f32x2 &o0, f32x2 &o1) { o0 = s[0] - s[2]; o1 = s[1] - s[3]; }
@@ -571,6 +619,9 @@ __device__ __forceinline__ void odd_cart_row(const f32x2 (&fx)[2], const f32x4 &
 // packed tiles' own layout (column 4 (lane >> 4) + register of patch lane & 15), with no lane exchange.
 __device__ __forceinline__ void rebuild_odd_cart(const float (&oc)[kOddCartSums][3], int lane, f32x4 (&acc)[kAccTiles]) {
     constexpr float kVm[4] = {0.37872374f, 0.51796234f, 0.46882015f, 0.39798096f};   // c_k: kVmN3K8 of mkd_consts.cpp
+    // (the twelve selects below are made here, once per batch: as loop invariants of the lane they are hoisted to the top of
+    //  the kernel and held in registers through the row loop, which has none to spare)
+    asm volatile("" : "+v"(lane));
 #pragma unroll
     for (int s = 0; s < kOddCartSums; ++s) {
         const int k = (s + 1) / 2, t = s == 0 ? 2 : 3 + 6 * (k - 1) + 4 + ((s - 1) & 1);
@@ -1311,6 +1362,9 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     static_assert(!kKp || POOL == LF_POOL_F16X3, "keypoint mode pools in f16x3");
     constexpr int kMPool = POOL == LF_POOL_F16_FP6 ? LF_POOL_F16X3 : POOL;   // the m stream keeps the three-term form
     constexpr bool kFold = fold_form(POOL), kOddV = valu_odd_cart(POOL);
+    // Patch mode, f16x3: the middle rows go in pairs over fixed ring slots (see patch_row).  LF_POOL_F32 and LF_POOL_F16_FP6
+    // keep the one-row body and its rotating slots: with the pair body their 8-wave forms need 290-420 bytes of scratch a lane.
+    constexpr bool kPairs = SRC == kSrcPatches && POOL == LF_POOL_F16X3;
     static_assert(!kKp || (kFold && kOddV), "the producers write the folded forms' LDS map and request f16x3's LUT pieces");
     constexpr int kNAcc = acc_tiles(kFold), kRowB = row_bytes(kFold), kRingO = ring_off(kFold);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRingO + W * kSlots * 2048 +
@@ -1392,8 +1446,13 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     {
         if constexpr (!kKp) {
             const RawSrc src = raw_src(patches, batch);
+            if constexpr (kPairs) {
 #pragma unroll
-            for (int r = -2; r <= 3; ++r) issue_raw_row(src, r, ring, r + 2);
+                for (int r = 0; r < kRingSlots; ++r) issue_raw_row(src, r, ring, r);
+            } else {
+#pragma unroll
+                for (int r = -2; r <= 3; ++r) issue_raw_row(src, clamp_row(r), ring, r + 2);
+            }
         }
         issue_lut_row<W, kFold, kOddV>(lut_rows, kSplit ? span.lo : 0, s_mem, wave, lane);
     }
@@ -1433,17 +1492,35 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         // blurred rows g and g-1 (row -1 replicates row 0) in the lane's pixel order, and row g just outside the lane's
         // pixels: folded (blur_row_fold_impl) x = 4q-1, 4q+4, 27-4q, 32-4q; unfolded x = 8q-1, 8q+8
         float cur[8], prv[8], cur_nb[4] = {0.f, 0.f, 0.f, 0.f};
-        int s0 = 1;                                      // ring slot of raw row g-1 (rows g-1..g+3 feed hb(g+1))
+        // patch mode: the vertical sums of hb(g+2), carried from the first body of a row pair (g, g+1) to its second
+        [[maybe_unused]] float vnext[8];
+        [[maybe_unused]] bool last_six = false;          // pair forms: the middle-row loop is on rows 25..30
+        [[maybe_unused]] int s0 = 1;                     // one-row patch forms: ring slot of raw row g-1 (rows g-1..g+3 feed hb(g+1))
 
-        // The first and the last row of a batch differ from the 30 between them (two blurs and a later ring request /
-        // no blur and the next batch's first rows): they are separate copies of the row body, so that the loop over the
-        // middle rows carries none of their branches -- hipcc speculated the last row's "row 32 = row 31" copy into
-        // every row (ten v_mov).
-        auto patch_row = [&](auto kind, const int g) __attribute__((always_inline)) {
+        // The first and the last row of a batch differ from the 30 between them (two blurs / no blur): they are separate
+        // copies of the row body, so that the loop over the middle rows carries none of their branches -- hipcc speculated
+        // the last row's "row 32 = row 31" copy into every row (ten v_mov).
+        //
+        // The pair forms (kPairs: patch mode, f16x3) walk the middle rows in PAIRS (g, g+1), g odd.  Raw row r of the batch
+        // lives in ring slot r mod 6 -- a compile-time slot in every body, because the middle-row loop is unrolled over three
+        // pairs (six rows) -- and the six slots hold exactly raw rows g-1 .. g+4, which hb(g+1) (rows g-1 .. g+3) and hb(g+2)
+        // (rows g .. g+4) need between them.  The pair's first body reads each slot ONCE (6 ring reads per row instead of
+        // 10), runs both vertical passes and the horizontal pass of hb(g+1); its second body runs the horizontal pass of
+        // hb(g+2) and touches the ring not at all.  Once read, the slots of rows g-1 and g take rows g+5 and g+6.  Rows beyond
+        // the patch are never fetched: the taps of hb(0), hb(1), hb(30) and hb(31) that fall outside read the slot of row 0 or
+        // row 31 (compile-time maps of row 0's body and of the last pair's).
+        // The next batch's rows 0..5 go into their own slots as those fall free: 2 and 3 in pair (27, 28), the rest in pair
+        // (29, 30).  pos = -1: a body of its own (rows 0 and 31; every row of the one-row forms); 2 P + s: body s of pair P of
+        // the three.
+        auto patch_row = [&](auto kind, const int g, auto pos) __attribute__((always_inline)) {
             constexpr bool kFirst = decltype(kind)::value == 0, kLast = decltype(kind)::value == 2;
             constexpr bool kFirstInner = decltype(kind)::value == 3;   // row-split form: a first row that is not row 0
+            constexpr int kPos = decltype(pos)::value;
+            constexpr bool kPairFirst = kPos >= 0 && (kPos & 1) == 0, kPairSecond = kPos >= 0 && (kPos & 1) == 1;
+            constexpr int kSlot0 = kPos >= 0 ? (kPos & ~1) : 0;   // ring slot of raw row g-1 in a pair's first body
+            static_assert(kPairs ? (kFirst || kLast) == (kPos < 0) : kPos < 0, "the pair forms' rows 1..30 go in pairs");
 
-            // LUT row g and ring row g+3 have landed (own DMA: vmcnt; everyone's: barrier); row g-1 is done
+            // LUT row g and the ring rows the body reads have landed (own DMA: vmcnt; everyone's: barrier); row g-1 is done
             phase.mark(7);
             if constexpr (!ablate::kNoRowSync) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1468,58 +1545,107 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             [[maybe_unused]] f32x4 oc_gy = {0.f, 0.f, 0.f, 0.f};
             if constexpr (kOddV) oc_gy = *reinterpret_cast<const f32x4 *>(oc_tab + 16 + 4 * g);
 
-            // Raw row g+4 goes into the slot of row g-2, whose last reader was the blur of the previous iteration: for
-            // g >= 1 it is requested here, a whole row before the vmcnt(0) that waits for it (counters: the waves spend
-            // 29 % of their time in s_waitcnt and only 2 % of that on LDS), for g == 0 after the first blur below.
-            if constexpr (!kKp)
-                if (!kFirst && !kLast && g <= 29) issue_raw_row(src, g + 4, ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
-            // keypoint mode: the five raw rows of hb(y) are rows y-2 .. y+2 clamped to the patch (replicate border), each in
-            // its slot of the producer's ring
-            auto kp_slot = [&](int y, int i) {
-                int r_ = y - 2 + i;
-                r_ = r_ < 0 ? 0 : (r_ > 31 ? 31 : r_);
-                return (slot0 + r_) % kRingSlotsKp;
-            };
-            // one blurred row, by either lane map; tap(i) = ring slot of the i-th of its five raw rows
-            auto blur = [&](auto tap, float (&o)[8], float (&o_nb)[4]) __attribute__((always_inline)) {
-                if constexpr (kFold) blur_row_fold_impl(ring_lane, ring_mirror, tap, addr_l, addr_r, has_l, has_r, o, o_nb);
-                else blur_row_impl(ring_lane, tap, addr_l, addr_r, has_l, has_r, o, o_nb[0], o_nb[1]);
-            };
-            auto ring_tap = [](int first) {   // patch mode: consecutive slots of the 6-slot ring from `first`
-                return [first](int i) { const int sl = first + i; return sl >= kRingSlots ? sl - kRingSlots : sl; };
-            };
-            if (kFirst) {  // first blurred row of the batch: rows -2..2 sit in slots 0..4
-                if constexpr (kKp) blur([&](int i) { return kp_slot(0, i); }, cur, cur_nb);
-                else blur(ring_tap(0), cur, cur_nb);
-#pragma unroll
-                for (int x = 0; x < 8; ++x) prv[x] = cur[x];
-            }
-            if constexpr (kFirstInner) {   // blurred rows g - 1 and g themselves: nothing replicates
-                float edge[4];
-                blur([&](int i) { return kp_slot(g - 1, i); }, prv, edge);
-                blur([&](int i) { return kp_slot(g, i); }, cur, cur_nb);
-            }
+            // One-row patch forms: raw row g+4 goes into the slot of row g-2, whose last reader was the blur of the previous
+            // iteration: for g >= 1 it is requested here, a whole row before the vmcnt(0) that waits for it (counters: the
+            // waves spend 29 % of their time in s_waitcnt and only 2 % of that on LDS), for g == 0 after the first blur below.
+            if constexpr (!kKp && !kPairs)
+                if (!kFirst && !kLast && g <= 29) issue_raw_row(src, clamp_row(g + 4), ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
             float nxt[8], nxt_nb[4] = {0.f, 0.f, 0.f, 0.f};
-            if (!kLast) {  // hb(g+1) from raw rows g-1..g+3 = slots s0..s0+4
-                if constexpr (kKp) blur([&](int i) { return kp_slot(g + 1, i); }, nxt, nxt_nb);
-                else blur(ring_tap(s0), nxt, nxt_nb);
-            } else {  // row 32 replicates row 31
+            if constexpr (!kPairs) {
+                // keypoint mode: the five raw rows of hb(y) are rows y-2 .. y+2 clamped to the patch (replicate border), each
+                // in its slot of the producer's ring
+                auto kp_slot = [&](int y, int i) {
+                    int r_ = y - 2 + i;
+                    r_ = r_ < 0 ? 0 : (r_ > 31 ? 31 : r_);
+                    return (slot0 + r_) % kRingSlotsKp;
+                };
+                // one blurred row, by either lane map; tap(i) = ring slot of the i-th of its five raw rows
+                auto blur = [&](auto tap, float (&o)[8], float (&o_nb)[4]) __attribute__((always_inline)) {
+                    if constexpr (kFold) blur_row_fold_impl(ring_lane, ring_mirror, tap, addr_l, addr_r, has_l, has_r, o, o_nb);
+                    else blur_row_impl(ring_lane, tap, addr_l, addr_r, has_l, has_r, o, o_nb[0], o_nb[1]);
+                };
+                auto ring_tap = [](int first) {   // one-row patch forms: consecutive slots of the 6-slot ring from `first`
+                    return [first](int i) { const int sl = first + i; return sl >= kRingSlots ? sl - kRingSlots : sl; };
+                };
+                if (kFirst) {  // first blurred row of the batch (one-row patch forms: rows -2..2 sit in slots 0..4)
+                    if constexpr (kKp) blur([&](int i) { return kp_slot(0, i); }, cur, cur_nb);
+                    else blur(ring_tap(0), cur, cur_nb);
+#pragma unroll
+                    for (int x = 0; x < 8; ++x) prv[x] = cur[x];
+                }
+                if constexpr (kFirstInner) {   // blurred rows g - 1 and g themselves: nothing replicates
+                    float edge[4];
+                    blur([&](int i) { return kp_slot(g - 1, i); }, prv, edge);
+                    blur([&](int i) { return kp_slot(g, i); }, cur, cur_nb);
+                }
+                if (!kLast) {  // hb(g+1) from raw rows g-1..g+3 (one-row patch forms: slots s0..s0+4)
+                    if constexpr (kKp) blur([&](int i) { return kp_slot(g + 1, i); }, nxt, nxt_nb);
+                    else blur(ring_tap(s0), nxt, nxt_nb);
+                }
+            } else {
+                const unsigned char *ring_b = kFold ? ring_mirror : ring_lane + 256;   // the lane's second block of a raw row
+                auto hblur = [&](const float (&v)[8], float (&o)[8], float (&o_nb)[4]) __attribute__((always_inline)) {
+                    if constexpr (kFold) hblur_row_fold(v, addr_l, addr_r, has_l, has_r, o, o_nb);
+                    else hblur_row(v, addr_l, addr_r, has_l, has_r, o, o_nb[0], o_nb[1]);
+                };
+                auto slot = [](int j) { return (kSlot0 + j) % kRingSlots; };   // of the j-th raw row a body reads
+                if constexpr (kFirst) {  // hb(0) from raw rows {0, 0, 0, 1, 2}, hb(1) from {0, 0, 1, 2, 3}: slots 0..3
+                    float v0[8];
+                    vblur_pair<4>(ring_lane, ring_b, slot, [](int i) { return i < 2 ? 0 : i - 2; },
+                                  [](int i) { return i < 1 ? 0 : i - 1; }, v0, vnext);
+                    hblur(v0, cur, cur_nb);
+#pragma unroll
+                    for (int x = 0; x < 8; ++x) prv[x] = cur[x];
+                    hblur(vnext, nxt, nxt_nb);
+                } else if constexpr (kPairFirst) {
+                    float v1[8];
+                    if (kPos == 4 && last_six)   // pair (29, 30): raw rows 28..31, row 31 standing in for rows 32 and 33
+                        vblur_pair<4>(ring_lane, ring_b, slot, [](int i) { return i < 3 ? i : 3; },
+                                      [](int i) { return i < 2 ? i + 1 : 3; }, v1, vnext);
+                    else                         // raw rows g-1 .. g+4
+                        vblur_pair<6>(ring_lane, ring_b, slot, [](int i) { return i; }, [](int i) { return i + 1; }, v1, vnext);
+                    // The slots of raw rows g-1 and g are free once read: they take rows g+5 and g+6, requested here, nearly a
+                    // whole row before the vmcnt(0) at the top of the pair's second body.  (The second body reads no ring
+                    // row and could let them fly on behind a counted wait for its LUT row alone -- but hipcc puts a vmcnt(0)
+                    // of its own before that body's LDS reads, which it cannot tell from the LDS these requests write.)
+                    // The last two pairs request the next batch's first rows instead, into their own slots.
+                    // The wait makes "once read" an ordering: the ring reads above have returned before a request can write.
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (!last_six || kPos == 0) {            // (rows 30 and 31 are the last of the batch)
+                        issue_raw_row(src, g + 5, ring, kSlot0);
+                        issue_raw_row(src, g + 6, ring, kSlot0 + 1);
+                    } else if (more) {
+                        if constexpr (kPos == 2) {
+                            issue_raw_row(src_next, 2, ring, 2);
+                            issue_raw_row(src_next, 3, ring, 3);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < kRingSlots; ++r)
+                                if (r != 2 && r != 3) issue_raw_row(src_next, r, ring, r);
+                        }
+                    }
+                    hblur(v1, nxt, nxt_nb);
+                } else if constexpr (kPairSecond) {
+                    hblur(vnext, nxt, nxt_nb);
+                }
+            }
+            if (kLast) {  // row 32 replicates row 31
 #pragma unroll
                 for (int x = 0; x < 8; ++x) nxt[x] = cur[x];
 #pragma unroll
                 for (int x = 0; x < 4; ++x) nxt_nb[x] = cur_nb[x];
             }
-            // the slot of raw row g-2 is free now (its last reader was the blur above when g == 0)
+            // one-row patch forms: the slot of raw row g-2 is free now (its last reader was the blur above when g == 0)
             asm volatile("" ::: "memory");
-            if constexpr (!kKp) {
+            if constexpr (!kKp && !kPairs) {
                 if (kFirst) {
                     issue_raw_row(src, g + 4, ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
                 } else if (kLast && more) {
 #pragma unroll
-                    for (int r = -2; r <= 3; ++r) issue_raw_row(src_next, r, ring, r + 2);  // next batch's first rows
+                    for (int r = -2; r <= 3; ++r) issue_raw_row(src_next, clamp_row(r), ring, r + 2);  // next batch's first rows
                 }
+                s0 = s0 == kRingSlots - 1 ? 0 : s0 + 1;
             }
-            s0 = s0 == kRingSlots - 1 ? 0 : s0 + 1;
             phase.mark(1);
 
             f32x2 m[4], c1[4], s1[4];
@@ -1589,15 +1715,21 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             if constexpr (POOL == LF_POOL_F16_FP6) pool_harmonics_fp6(m, c1, s1, brow, gfrag, acc);
             else pool_harmonics<POOL>(m, c1, s1, brow, gfrag, acc, oc_fx, oc_gy, oc);
             phase.mark(4);
+            // (patch mode: the row's share of the 21 sums is added HERE -- left alone, hipcc sinks the six rows' additions to
+            //  the end of the unrolled loop body and spills their operands on the way)
+            if constexpr (kPairs)
+#pragma unroll
+                for (int s = 0; s < kOddCartSums; ++s) asm volatile("" : "+v"(oc[s][0]), "+v"(oc[s][1]), "+v"(oc[s][2]));
             phase.mark(5);
         };
+        constexpr std::integral_constant<int, -1> kOwnBody{};
         if constexpr (kSplit) {
-            if (span.lo == 0) patch_row(std::integral_constant<int, 0>(), 0);
-            else patch_row(std::integral_constant<int, 3>(), span.lo);
+            if (span.lo == 0) patch_row(std::integral_constant<int, 0>(), 0, kOwnBody);
+            else patch_row(std::integral_constant<int, 3>(), span.lo, kOwnBody);
 #pragma unroll 1
-            for (int g = span.lo + 1; g < span.hi - 1; ++g) patch_row(std::integral_constant<int, 1>(), g);
-            if (span.consumer) patch_row(std::integral_constant<int, 2>(), span.hi - 1);
-            else patch_row(std::integral_constant<int, 1>(), span.hi - 1);
+            for (int g = span.lo + 1; g < span.hi - 1; ++g) patch_row(std::integral_constant<int, 1>(), g, kOwnBody);
+            if (span.consumer) patch_row(std::integral_constant<int, 2>(), span.hi - 1, kOwnBody);
+            else patch_row(std::integral_constant<int, 1>(), span.hi - 1, kOwnBody);
             // (before the partial sums are published: sums over row subsets add, and the exchange keeps its 21 tiles)
             if constexpr (kOddV) rebuild_odd_cart(oc, lane, acc);
             // the partial sums meet: [batch][role][wave][tile][lane] f32x4, one counter per (batch, wave)
@@ -1651,10 +1783,25 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             // (the epilogue counts its own LDS-DMA requests on vmcnt: nothing of the above may still be in flight)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else {
-            patch_row(std::integral_constant<int, 0>(), 0);
+            patch_row(std::integral_constant<int, 0>(), 0, kOwnBody);
+            if constexpr (!kPairs) {
 #pragma unroll 1
-            for (int g = 1; g < ablate::kRows - 1; ++g) patch_row(std::integral_constant<int, 1>(), g);
-            patch_row(std::integral_constant<int, 2>(), ablate::kRows - 1);
+                for (int g = 1; g < ablate::kRows - 1; ++g) patch_row(std::integral_constant<int, 1>(), g, kOwnBody);
+                patch_row(std::integral_constant<int, 2>(), ablate::kRows - 1, kOwnBody);
+            } else {   // five times three row pairs
+                static_assert(ablate::kRows == 32, "LF_ABLATE_ROWS: the pair forms walk whole patches only");
+#pragma unroll 1
+                for (int g = 1; g < 31; g += 6) {
+                    last_six = g == 25;
+                    patch_row(std::integral_constant<int, 1>(), g, std::integral_constant<int, 0>());
+                    patch_row(std::integral_constant<int, 1>(), g + 1, std::integral_constant<int, 1>());
+                    patch_row(std::integral_constant<int, 1>(), g + 2, std::integral_constant<int, 2>());
+                    patch_row(std::integral_constant<int, 1>(), g + 3, std::integral_constant<int, 3>());
+                    patch_row(std::integral_constant<int, 1>(), g + 4, std::integral_constant<int, 4>());
+                    patch_row(std::integral_constant<int, 1>(), g + 5, std::integral_constant<int, 5>());
+                }
+                patch_row(std::integral_constant<int, 2>(), 31, kOwnBody);
+            }
             if constexpr (kOddV) rebuild_odd_cart(oc, lane, acc);
         }
         if constexpr (ablate::kNoEpilogue) {
@@ -1666,7 +1813,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 if (more) issue_lut_row<W, kFold, kOddV>(lr, 0, s_mem, wave, lane);
             }
         } else {
-            finish_descriptors<POOL, W>(acc, lane, wave, base + p < n, base + p, cm, wf, bs, o, ro, s_mem, lr, more);
+            // (pair forms: whatever the epilogue derives from the lane's number alone is derived here, once per batch -- hoisted
+            //  out of the batch loop it is seven registers held through a row loop that has none to spare)
+            int lane_e = lane;
+            if constexpr (kPairs) asm volatile("" : "+v"(lane_e));
+            const long patch_e = base + (lane_e & 15);
+            finish_descriptors<POOL, W>(acc, lane_e, wave, patch_e < n, patch_e, cm, wf, bs, o, ro, s_mem, lr, more);
         }
         phase.mark(6);
         if constexpr (kKp) slot0 = (slot0 + 8) % kRingSlotsKp;

@@ -1,0 +1,27 @@
+#!/usr/bin/env python3
+"""LF_MKD_POOL_F16X3 descriptors, shader and exact angle, of the 256 seeded patches of tools/dump_pool_mode_rows.py and of
+tests/row_pairs_cases.py's structured patches, as tests/golden/pool_f16x3_<angle>_rows.npy (128 KiB each) and
+pool_f16x3_<angle>_structured_rows.npy; tests/test_gpu_row_pairs.py holds a build to these bits.  Run on the build whose
+bits are to be kept (LF_MKD_LIB=...):
+    tools/dump_f16x3_rows.py OUT_DIR"""
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "local-features_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+import local_features_python as lfp
+from row_pairs_cases import seeded_patches, structured_patches
+
+out_dir = sys.argv[1]
+os.makedirs(out_dir, exist_ok=True)
+for patches, suffix in ((seeded_patches(), "rows"), (structured_patches(), "structured_rows")):
+    n = len(patches)
+    p = torch.from_numpy(patches).cuda()
+    for angle, aname in ((lfp.ANGLE_SHADER, "shader"), (lfp.ANGLE_EXACT, "exact")):
+        h = lfp.MkdHandle(max_features=n, angle_mode=angle, pool_mode=lfp.POOL_F16X3)
+        out = torch.empty((n, 128), device="cuda")
+        h.describe_patches_device(p.data_ptr(), n, out.data_ptr())
+        h.synchronize()
+        np.save(os.path.join(out_dir, f"pool_f16x3_{aname}_{suffix}.npy"), out.cpu().numpy())
+        print(f"pool_f16x3_{aname}_{suffix}.npy written")
