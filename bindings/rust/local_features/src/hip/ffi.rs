@@ -185,6 +185,16 @@ extern "C" {
     // the grid (a blocks x b splits) and the scratch lf_mkd_match_q8_device takes for a size; host only, no handle
     pub fn lf_mkd_match_q8_plan(na: u64, nb: u64, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
                                 scratch_bytes: *mut u64) -> c_int;
+    // each a row's k best b rows over 8-bit rows (1 <= k <= LF_MKD_KNN_MAX): d_index / d_score [na][k] i32, larger sum first,
+    // among equal sums the higher index first; -1 / i32::MIN beyond the number of candidates; d_score / score may be null
+    pub fn lf_mkd_knn_q8_device(h: *mut lf_mkd, d_a: *const u8, na: u64, d_b: *const u8, nb: u64,
+                                d_exclude_lo: *const u32, d_exclude_hi: *const u32, k: u32, d_index: *mut i32,
+                                d_score: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_knn_q8(h: *mut lf_mkd, a: *const u8, na: u64, b: *const u8, nb: u64, k: u32, index: *mut i32,
+                         score: *mut i32) -> c_int;
+    // the grid (a blocks x b splits) and the scratch lf_mkd_knn_q8_device takes for a size and k; host only, no handle
+    pub fn lf_mkd_knn_q8_plan(na: u64, nb: u64, k: u32, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
+                              scratch_bytes: *mut u64) -> c_int;
     // n_pairs match problems over 8-bit rows in one launch: lf_mkd_match_pairs_device's layout (offsets on the device), each
     // pair decided as lf_mkd_match_q8_device decides it alone; d_best / d_second are i32; flags: LF_MKD_MATCH_MUTUAL
     pub fn lf_mkd_match_q8_pairs_device(h: *mut lf_mkd, d_a: *const u8, d_offsets_a: *const u64, na_total: u64,

@@ -303,6 +303,23 @@ impl LocalFeaturesHip {
         Ok(m.iter().enumerate().filter(|(_, j)| **j >= 0).map(|(i, j)| (i, *j as usize)).collect())
     }
 
+    /// k-nearest-neighbour search over 8-bit descriptors (`lf_mkd_knn_q8`): for each row of `a` its `k` best rows of `b` as
+    /// `(index [na, k], score [na, k])`, larger similarity first and among equal similarities the higher index first; slots
+    /// beyond the number of candidates hold `-1` / `i32::MIN`.  `1 <= k <= 16`.
+    pub fn knn_q8(&mut self, a: &ArrayView2<u8>, b: &ArrayView2<u8>, k: usize) -> Result<(Array2<i32>, Array2<i32>), Error> {
+        assert_eq!(a.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(b.ncols(), DESCRIPTOR_LEN);
+        let (a, b) = (a.as_standard_layout(), b.as_standard_layout());
+        let mut index = Array2::<i32>::from_elem((a.nrows(), k), -1);
+        let mut score = Array2::<i32>::from_elem((a.nrows(), k), i32::MIN);
+        // SAFETY: a, b are contiguous [n][128]; `index` and `score` have a.nrows() * k entries each
+        unsafe {
+            check(self.h, ffi::lf_mkd_knn_q8(self.h, a.as_ptr(), a.nrows() as u64, b.as_ptr(), b.nrows() as u64, k as u32,
+                                             index.as_mut_ptr(), score.as_mut_ptr()))?;
+        }
+        Ok((index, score))
+    }
+
     /// Many pairs of 8-bit descriptors in one call (`lf_mkd_match_q8_pairs_device`): pair p is rows
     /// `offsets_a[p]..offsets_a[p + 1]` of `a` against rows `offsets_b[p]..offsets_b[p + 1]` of `b` (`n_pairs + 1`
     /// non-decreasing offsets each), every pair decided exactly as `match_q8` decides it alone, Lowe's ratio 0.8.  With

@@ -506,6 +506,51 @@ int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, 
  * lf_mkd_last_error(NULL)): nb < 2, na or nb above 2^31 - 1. */
 int lf_mkd_match_q8_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
                          uint64_t *scratch_bytes);
+/* k-nearest-neighbour search over quantised rows: each a row's k best b rows, exact.
+ *   Rows, similarity and exclusion are lf_mkd_match_q8_device's, word for word: rows are 128 offset-binary bytes; s(i, j) is
+ *   the exact int32 sum; b rows [lo[i], hi[i]) are not candidates of a row i (both pointers NULL: none; one NULL: refused); an
+ *   inverted or empty range excludes nothing; a bound beyond nb is read as nb.
+ *   order       a row's candidates are totally ordered: larger s first, and among equal s the HIGHER index first;
+ *   output      d_index[i * k + c] / d_score[i * k + c], c = 0 .. k - 1, are the first k candidates of row i in that order;
+ *               slots beyond the number of candidates hold -1 / INT32_MIN.  Exactly na * k entries of each array are
+ *               written.  d_score may be NULL.
+ *   matcher     column 0 is what lf_mkd_match_q8_device returns with ratio <= 0 (its index and its best) and column 1's
+ *               score is its second -- by construction: that call's best is the first candidate of this order and its
+ *               second the score of the next one, so second == best when the maximum occurs twice falls out of the order.
+ * 1 <= k <= LF_MKD_KNN_MAX.  nb >= 1: one candidate is a legitimate answer here, unlike the ratio-test call.  na == 0 is
+ * LF_MKD_OK and writes nothing.  na and nb are at most 2^31 - 1.  d_a and d_b must be 16-byte aligned, d_index and d_score
+ * 4-byte aligned.  The result depends on the inputs alone: not on the run, not on the split count, not on the device's CU
+ * count -- a candidate is one 64-bit key (s + 2^21) << 32 | index, keys are unique per row, and every step is a max-merge of
+ * keys.
+ * One launch (the scan over a grid of a blocks x b splits) or two (a merge of the splits' lists when the plan below has more
+ * than one split).  Asynchronous on `stream` (NULL: the handle's own), no host synchronisation, no allocation once the
+ * handle's q8 scratch has grown to the largest plan seen; a warmed-up call can be captured in a hipGraph.  The scratch is the
+ * one lf_mkd_match_q8_device uses, so the calls of one handle must be stream-ordered, as that call already requires.
+ * lf_mkd_match_overflowed is not affected.  lf_mkd_knn_q8 is the same for host pointers (any alignment), synchronous, without
+ * exclusion ranges, through the handle's staging; `score` may be NULL.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "knn_q8_device: " / "knn_q8: " and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; with na > 0 a null d_a, d_b or d_index; one
+ * exclusion pointer without the other; d_a or d_b not 16-byte aligned; k == 0 or k > LF_MKD_KNN_MAX (the message names k);
+ * nb == 0; na or nb above 2^31 - 1. */
+#define LF_MKD_KNN_MAX (16)
+int lf_mkd_knn_q8_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                         const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi, uint32_t k, int32_t *d_index,
+                         int32_t *d_score, void *stream);
+int lf_mkd_knn_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb, uint32_t k, int32_t *index,
+                  int32_t *score);
+/* What lf_mkd_knn_q8_device launches for a problem size, and the scratch it needs -- host-only, no device, no handle, no
+ * environment variable; the launch path calls this very function.  num_cus: the device's compute units, 0 means 256.
+ * *a_blocks x *b_splits is the scan's grid: an a block is 256 rows (8 waves x 1 tile of 32), a split a contiguous range of
+ * 32-row b tiles, none empty.  b_splits is 1 when all of b is one LDS stage (nb <= 128); otherwise about two workgroups per
+ * CU, at least 2 and at most one per b tile (and at most 1024) -- a condition on nb alone.  *scratch_bytes is 0 exactly when
+ * b_splits == 1 (the scan then writes the result itself) and otherwise 8 k bytes per (split, a row), stated as an upper
+ * bound that is non-decreasing in na for a given nb, k and num_cus (a handle warmed up on its largest problem never
+ * allocates again):
+ *   8 k * 256 * min(A + max(W, A), A * ceil(nb / 32)),  A = a_blocks, W = 2 * num_cus.
+ * na == 0: (0, 1, 0).  Output pointers may be NULL.  LF_MKD_ERR_BAD_ARG (message "knn_q8_plan: ...", through
+ * lf_mkd_last_error(NULL)): k == 0 or k > LF_MKD_KNN_MAX, nb == 0, na or nb above 2^31 - 1. */
+int lf_mkd_knn_q8_plan(uint64_t na, uint64_t nb, uint32_t k, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                       uint64_t *scratch_bytes);
 /* Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device over the q8 format above, for the multi-frame pipeline.
  *   Layout and offsets are those of lf_mkd_match_pairs_device, word for word: pair p is a rows [offsets_a[p], offsets_a[p+1])
  *   against b rows [offsets_b[p], offsets_b[p+1]); both offset arrays hold n_pairs + 1 uint64 entries, live on the device, are

@@ -1990,6 +1990,69 @@ int lf_mkd_match_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, 
     return LF_MKD_OK;
 }
 
+// The exact top-k over 8-bit rows (csrc/mkd_match_q8_knn.hip): the matcher's refusals, except that one candidate is an answer.
+static const char *knn_q8_sizes(uint64_t na, uint64_t nb, uint32_t k) {
+    if (k == 0 || k > LF_MKD_KNN_MAX) return "k must be 1 .. LF_MKD_KNN_MAX (16)";
+    if (nb == 0) return "needs at least one candidate in b";
+    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";
+    return nullptr;
+}
+
+int lf_mkd_knn_q8_plan(uint64_t na, uint64_t nb, uint32_t k, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                       uint64_t *scratch_bytes) {
+    if (const char *msg = knn_q8_sizes(na, nb, k)) return q8_refuse(nullptr, "knn_q8_plan", msg);
+    const KnnQ8Plan p = knn_q8_plan(long(na), long(nb), int(k), int(std::min<uint32_t>(num_cus, 1u << 20)));
+    if (a_blocks) *a_blocks = p.a_blocks;
+    if (b_splits) *b_splits = p.splits;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+static const char *knn_q8_args(const lf_mkd *h, const void *a, uint64_t na, const void *b, uint64_t nb, const void *lo,
+                               const void *hi, uint32_t k, const void *index, bool device) {
+    if (na && (!a || !b || !index)) return "null pointer";
+    if ((lo == nullptr) != (hi == nullptr)) return "exclude_lo and exclude_hi go together";
+    if (device && na && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15))
+        return "d_a and d_b must be 16-byte aligned";
+    if (const char *msg = knn_q8_sizes(na, nb, k)) return msg;
+    return h ? nullptr : "null handle";
+}
+
+int lf_mkd_knn_q8_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                         const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi, uint32_t k, int32_t *d_index,
+                         int32_t *d_score, void *stream) {
+    if (const char *msg = knn_q8_args(h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, k, d_index, true))
+        return q8_refuse(h, "knn_q8_device", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const KnnQ8Plan plan = knn_q8_plan(long(na), long(nb), int(k), h->num_cus);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_q8_part, plan.scratch_bytes)) return rc;
+    launch_knn_q8(d_a, long(na), d_b, long(nb), d_exclude_lo, d_exclude_hi, int(k), plan,
+                  plan.scratch_bytes ? h->d_q8_part.get() : nullptr, d_index, d_score,
+                  stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_knn_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb, uint32_t k, int32_t *index,
+                  int32_t *score) {
+    if (const char *msg = knn_q8_args(h, a, na, b, nb, nullptr, nullptr, k, index, false)) return q8_refuse(h, "knn_q8", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_q8_io, (na + nb) * kOut)) return rc;
+    if (int rc = grow(h, h->d_match_out, 2 * na * k)) return rc;
+    LF_HIP(h, hipMemcpyAsync(h->d_q8_io, a, na * kOut, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(h->d_q8_io + na * kOut, b, nb * kOut, hipMemcpyHostToDevice, h->stream));
+    if (int rc = lf_mkd_knn_q8_device(h, h->d_q8_io, na, h->d_q8_io + na * kOut, nb, nullptr, nullptr, k, h->d_match_out,
+                                      score ? h->d_match_out + na * k : nullptr, h->stream))
+        return rc;
+    LF_HIP(h, hipMemcpyAsync(index, h->d_match_out, na * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (score) LF_HIP(h, hipMemcpyAsync(score, h->d_match_out + na * k, na * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
 // Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device's layout and refusals, the int8 matcher's decisions.
 static const char *match_q8_pairs_sizes(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, bool both) {
     if (na_total > 0x7FFFFFFFull || nb_total > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";

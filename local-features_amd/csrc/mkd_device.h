@@ -210,6 +210,20 @@ Q8Plan match_q8_plan(long na, long nb, int num_cus);
 void launch_match_q8(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *excl_lo,
                      const unsigned *excl_hi, float ratio, const Q8Plan &plan, void *scratch, int *match, int *best,
                      int *second, hipStream_t stream);
+// the exact top-k over 8-bit rows (csrc/mkd_match_q8_knn.hip, lf_mkd_knn_q8_device): what lf_mkd_knn_q8_plan reports and
+// launch_knn_q8 launches
+struct KnnQ8Plan {
+    unsigned a_blocks, splits;         // the scan's grid; splits == 1: it writes the result itself, no merge launch
+    long tiles_per_split;              // 32-row b tiles one split scans
+    unsigned long long scratch_bytes;  // k 64-bit keys per (split, a row); 0 exactly when splits == 1
+};
+KnnQ8Plan knn_q8_plan(long na, long nb, int k, int num_cus);
+unsigned knn_q8_block_rows();
+// a [na][128] against b [nb][128] bytes -> index / score (nullable) [na][k], 1 <= k <= LF_MKD_KNN_MAX: each row's k best
+// candidates, larger sum first, among equal sums the higher index first; scratch: plan.scratch_bytes
+void launch_knn_q8(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *excl_lo,
+                   const unsigned *excl_hi, int k, const KnnQ8Plan &plan, void *scratch, int *index, int *score,
+                   hipStream_t stream);
 // many pairs of 8-bit rows in one launch (lf_mkd_match_q8_pairs_device): launch_match_small_pairs' layout and slot map at
 // match_q8_pairs_block_rows() rows per workgroup; each pair decided as launch_match_q8 decides it alone.  No scratch.
 // match_ba (nullable): the other direction from the same launch; mutual: launch_match_mutual's two launches on top.

@@ -13,14 +13,15 @@ import threading
 
 import numpy as np
 
-from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, LIB_PATH, MODEL_DIR, PCA_NAMES,
+from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
                    POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, load_library, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
-           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan"]
+           "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
+           "KNN_MAX", "knn_q8_plan"]
 
 
 class Keypoint:
@@ -301,6 +302,46 @@ class LocalFeatures:
             m, best, second = m.cpu().numpy(), best.cpu().numpy(), second.cpu().numpy()
         pairs = [(int(i), int(j)) for i, j in enumerate(m) if j >= 0]
         return (pairs, best, second) if scores else pairs
+
+    def knn_q8(self, qa, qb, k, exclude=None, stream=None):
+        """k-nearest-neighbour search over 8-bit descriptors (lf_mkd_knn_q8_device): for each row of qa its k best rows of qb,
+        larger similarity first and among equal similarities the higher index first -- exact integers, one right answer.
+        qa [na,128] / qb [nb,128] uint8, numpy arrays or torch tensors; 1 <= k <= KNN_MAX; exclude: None or (lo, hi),
+        uint32 [na] each -- b rows lo[i] .. hi[i] - 1 are no candidates for row i.  Returns (index [na,k] int32,
+        score [na,k] int32); slots beyond the number of candidates hold -1 / INT32_MIN.  Column 0 is `match_q8`'s answer at
+        ratio 0 and its best, column 1's score its second.  With device tensors in, the result is device tensors and the call
+        is asynchronous on `stream` (None: torch's current stream) and keeps nothing on the host; otherwise numpy arrays."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        on_device = all(hasattr(x, "data_ptr") and x.is_cuda for x in (qa, qb))
+
+        def rows(x):
+            t = torch.from_numpy(np.ascontiguousarray(x, np.uint8)) if not hasattr(x, "data_ptr") else x
+            return t.to(dev, torch.uint8).reshape(-1, 128).contiguous()
+
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            a, b = rows(qa), rows(qb)
+            na, nb = a.shape[0], b.shape[0]
+            index = torch.empty((na, int(k)), dtype=torch.int32, device=dev)
+            score = torch.empty((na, int(k)), dtype=torch.int32, device=dev)
+            lo = hi = None
+            if exclude is not None:
+                # (the uint32 bounds travel as their int32 bit patterns: torch's uint32 support is partial)
+                lo, hi = (e.to(dev).reshape(-1).contiguous().view(torch.int32) if hasattr(e, "data_ptr") and e.is_cuda and e.element_size() == 4
+                          else torch.from_numpy(np.ascontiguousarray(np.asarray(e.cpu() if hasattr(e, "cpu") else e))
+                                                .astype(np.uint32).view(np.int32)).to(dev) for e in exclude)
+                if lo.numel() != na or hi.numel() != na:
+                    raise RuntimeError("knn_q8: exclude needs one (lo, hi) per row of qa")
+            with self._lock:
+                # (with na == 0 the call checks its arguments and writes nothing)
+                self._inner.knn_q8_device(a.data_ptr(), na, b.data_ptr(), nb, int(k), index.data_ptr(), score.data_ptr(),
+                                          lo.data_ptr() if lo is not None else None, hi.data_ptr() if hi is not None else None,
+                                          s.cuda_stream)
+            if on_device:
+                return index, score
+            s.synchronize()
+            return index.cpu().numpy(), score.cpu().numpy()
 
     def match_q8_batch(self, qa, offsets_a, qb, offsets_b, ratio=0.8, mutual=False, both=False, stream=None):
         """match_batch over 8-bit descriptors (lf_mkd_match_q8_pairs_device: one launch, three with `mutual`): the same

@@ -40,8 +40,10 @@ SYMBOLS = (
     "lf_mkd_verify_fundamental", "lf_mkd_verify_fundamental_device",
     "lf_mkd_quantize_descriptors", "lf_mkd_quantize_descriptors_device", "lf_mkd_match_q8", "lf_mkd_match_q8_device",
     "lf_mkd_match_q8_plan", "lf_mkd_match_q8_pairs_device", "lf_mkd_match_q8_guided_pairs_device", "lf_mkd_match_q8_pairs_plan",
+    "lf_mkd_knn_q8", "lf_mkd_knn_q8_device", "lf_mkd_knn_q8_plan",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
+KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -134,6 +136,9 @@ def load_library():
     L.lf_mkd_match_q8_pairs_device.argtypes = L.lf_mkd_match_pairs_device.argtypes
     L.lf_mkd_match_q8_guided_pairs_device.argtypes = L.lf_mkd_match_guided_pairs_device.argtypes
     L.lf_mkd_match_q8_pairs_plan.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u64)]
+    L.lf_mkd_knn_q8_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, vp, vp, vp]
+    L.lf_mkd_knn_q8.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp]
+    L.lf_mkd_knn_q8_plan.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -190,6 +195,17 @@ def match_q8_plan(na, nb, num_cus=0):
     rc = L.lf_mkd_match_q8_plan(na, nb, num_cus, ctypes.byref(a), ctypes.byref(s), ctypes.byref(b))
     if rc != 0:
         raise RuntimeError(f"lf_mkd_match_q8_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return a.value, s.value, b.value
+
+
+def knn_q8_plan(na, nb, k, num_cus=0):
+    """(a_blocks, b_splits, scratch_bytes): the grid lf_mkd_knn_q8_device launches for this size and k and the scratch it
+    needs (lf_mkd_knn_q8_plan; needs no device).  num_cus 0: 256."""
+    a, s, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_knn_q8_plan(na, nb, k, num_cus, ctypes.byref(a), ctypes.byref(s), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_knn_q8_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return a.value, s.value, b.value
 
 
@@ -406,6 +422,17 @@ class MkdHandle:
                     "lf_mkd_match_q8")
         return out
 
+    def knn_q8(self, qa, qb, k):
+        """lf_mkd_knn_q8: each row's k best rows of qb over 8-bit descriptors [n,128] uint8 -> (index [na,k] int32,
+        score [na,k] int32), larger similarity first, among equal ones the higher index first; -1 / INT32_MIN beyond the
+        number of candidates."""
+        a = np.ascontiguousarray(qa, np.uint8).reshape(-1, 128)
+        b = np.ascontiguousarray(qb, np.uint8).reshape(-1, 128)
+        index, score = np.empty((len(a), int(k)), np.int32), np.empty((len(a), int(k)), np.int32)
+        self._check(self.L.lf_mkd_knn_q8(self._h, a.ctypes.data, len(a), b.ctypes.data, len(b), k, index.ctypes.data,
+                                         score.ctypes.data), "lf_mkd_knn_q8")
+        return index, score
+
     def verify_homography(self, kps_a, kps_b, match, n_hypotheses=2048, threshold=3.0, seed=0, flags=0):
         """lf_mkd_verify_homography: kps_a [na,5], kps_b [nb,5] f32 rows, match int32 [na] (index into b or -1) ->
         (H [3,3] f32, verified int32 [na], stats uint32 [4])."""
@@ -558,6 +585,11 @@ class MkdHandle:
         """lf_mkd_match_q8_device: match_device over 8-bit rows; d_best / d_second are int32 (exact integer similarities)"""
         self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_device(
             self._h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, ratio, d_match, d_best, d_second, s), "lf_mkd_match_q8_device")
+
+    def knn_q8_device(self, d_a, na, d_b, nb, k, d_index, d_score=None, d_exclude_lo=None, d_exclude_hi=None, stream=None):
+        """lf_mkd_knn_q8_device: d_index / d_score [na][k] int32, each a row's k best b rows (exact integer similarities)"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_knn_q8_device(
+            self._h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, k, d_index, d_score, s), "lf_mkd_knn_q8_device")
 
     def match_both_device(self, d_a, na, d_b, nb, d_match_ab, d_match_ba, ratio=0.8, stream=None):
         """both directions in one call: match_ab [na] = match(a, b), match_ba [nb] = match(b, a)"""
