@@ -195,6 +195,23 @@ extern "C" {
     // the grid (a blocks x b splits) and the scratch lf_mkd_knn_q8_device takes for a size and k; host only, no handle
     pub fn lf_mkd_knn_q8_plan(na: u64, nb: u64, k: u32, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
                               scratch_bytes: *mut u64) -> c_int;
+    // the ratio test against the best neighbour from another group over 8-bit rows: d_group_of_b [nb] u32 (only equality is
+    // used); d_best is the best score, d_rival the best score among the rows of another group than the best's (i32::MIN:
+    // none); d_match is the best's index if ratio <= 0 or best * ratio > rival, else -1; d_best / d_rival may be null
+    pub fn lf_mkd_match_q8_grouped_device(h: *mut lf_mkd, d_a: *const u8, na: u64, d_b: *const u8, nb: u64,
+                                          d_group_of_b: *const u32, d_exclude_lo: *const u32, d_exclude_hi: *const u32,
+                                          ratio: f32, d_match: *mut i32, d_best: *mut i32, d_rival: *mut i32,
+                                          stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_match_q8_grouped(h: *mut lf_mkd, a: *const u8, na: u64, b: *const u8, nb: u64, group_of_b: *const u32,
+                                   ratio: f32, matches: *mut i32, best: *mut i32, rival: *mut i32) -> c_int;
+    // the grid (a blocks x b splits) and the scratch lf_mkd_match_q8_grouped_device takes for a size; host only, no handle
+    pub fn lf_mkd_match_q8_grouped_plan(na: u64, nb: u64, num_cus: u32, a_blocks: *mut u32, b_splits: *mut u32,
+                                        scratch_bytes: *mut u64) -> c_int;
+    // d_votes [n_groups_a][n_groups_b] u32, zeroed and then counted: one vote per row with 0 <= d_match[i] < nb and both
+    // group ids below their counts; d_group_of_a may be null (group 0)
+    pub fn lf_mkd_vote_groups_device(h: *mut lf_mkd, d_match: *const i32, na: u64, d_group_of_a: *const u32, n_groups_a: u32,
+                                     d_group_of_b: *const u32, nb: u64, n_groups_b: u32, d_votes: *mut u32,
+                                     stream: *mut c_void) -> c_int;
     // n_pairs match problems over 8-bit rows in one launch: lf_mkd_match_pairs_device's layout (offsets on the device), each
     // pair decided as lf_mkd_match_q8_device decides it alone; d_best / d_second are i32; flags: LF_MKD_MATCH_MUTUAL
     pub fn lf_mkd_match_q8_pairs_device(h: *mut lf_mkd, d_a: *const u8, d_offsets_a: *const u64, na_total: u64,

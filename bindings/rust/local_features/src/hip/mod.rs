@@ -320,6 +320,26 @@ impl LocalFeaturesHip {
         Ok((index, score))
     }
 
+    /// The ratio test against the best neighbour from another group over 8-bit descriptors (`lf_mkd_match_q8_grouped`):
+    /// `groups_b[j]` is the group (image, object) of row j of `b`.  Returns `(matches, best, rival)`: `matches[i]` is the
+    /// best row of `b` for row i of `a`, or -1 when `best * ratio > rival` fails; `rival[i]` is the best score among the rows
+    /// whose group differs from the best's, `i32::MIN` if there is none.
+    pub fn match_q8_grouped(&mut self, a: &ArrayView2<u8>, b: &ArrayView2<u8>, groups_b: &[u32], ratio: f32)
+                            -> Result<(Vec<i32>, Vec<i32>, Vec<i32>), Error> {
+        assert_eq!(a.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(b.ncols(), DESCRIPTOR_LEN);
+        assert_eq!(groups_b.len(), b.nrows());
+        let (a, b) = (a.as_standard_layout(), b.as_standard_layout());
+        let (mut m, mut best, mut rival) = (vec![-1i32; a.nrows()], vec![i32::MIN; a.nrows()], vec![i32::MIN; a.nrows()]);
+        // SAFETY: a, b are contiguous [n][128]; groups_b has b.nrows() entries; the outputs have a.nrows() entries each
+        unsafe {
+            check(self.h, ffi::lf_mkd_match_q8_grouped(self.h, a.as_ptr(), a.nrows() as u64, b.as_ptr(), b.nrows() as u64,
+                                                       groups_b.as_ptr(), ratio, m.as_mut_ptr(), best.as_mut_ptr(),
+                                                       rival.as_mut_ptr()))?;
+        }
+        Ok((m, best, rival))
+    }
+
     /// Many pairs of 8-bit descriptors in one call (`lf_mkd_match_q8_pairs_device`): pair p is rows
     /// `offsets_a[p]..offsets_a[p + 1]` of `a` against rows `offsets_b[p]..offsets_b[p + 1]` of `b` (`n_pairs + 1`
     /// non-decreasing offsets each), every pair decided exactly as `match_q8` decides it alone, Lowe's ratio 0.8.  With

@@ -551,6 +551,74 @@ int lf_mkd_knn_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, ui
  * lf_mkd_last_error(NULL)): k == 0 or k > LF_MKD_KNN_MAX, nb == 0, na or nb above 2^31 - 1. */
 int lf_mkd_knn_q8_plan(uint64_t na, uint64_t nb, uint32_t k, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
                        uint64_t *scratch_bytes);
+/* Grouped matching over quantised rows: the ratio test against the best neighbour from ANOTHER group (image, object,
+ * landmark) -- Lowe's object-recognition rule for a pooled database, exact.
+ *   Rows, similarity and exclusion are lf_mkd_match_q8_device's, word for word: rows are 128 offset-binary bytes; s(i, j) is
+ *   the exact int32 sum; b rows [lo[i], hi[i]) are not candidates of a row i (both pointers NULL: none; one NULL: refused); an
+ *   inverted or empty range excludes nothing; a bound beyond nb is read as nb.
+ *   groups      d_group_of_b[j] is any uint32, the group of b row j.  The ids need not be sorted, dense or contiguous: only
+ *               the equality of two ids is ever used.
+ *   order       a row's candidates are totally ordered as in lf_mkd_knn_q8_device: larger s first, and among equal s the
+ *               HIGHER index first.
+ *   output      d_best[i] is the score of the first candidate of that order and its index is the row's match; d_rival[i] is
+ *               the score of the first candidate of that order whose group differs from the best's group, INT32_MIN if there
+ *               is none.  d_match[i] is the best's index if  ratio <= 0 || (float)best * ratio > (float)rival,  else -1: both
+ *               conversions are exact and there is one f32 multiplication.  A row without a candidate gets -1 and INT32_MIN in
+ *               both scores.  Exactly na entries of each array are written.  d_best and d_rival may be NULL.
+ * By construction:
+ *   (a) with d_group_of_b[j] = j every output equals lf_mkd_match_q8_device's, with rival == second;
+ *   (b) with all groups equal, rival == INT32_MIN and every row with a candidate is accepted at any ratio;
+ *   (c) best and, at ratio 0, match are column 0 of lf_mkd_knn_q8_device; rival is the score of the first of that call's
+ *       columns whose row has another group than column 0's, whenever there is one among the k.
+ * nb >= 1: a pool of one row, or of one group, is a legitimate question here, as in the top-k call.  na == 0 is LF_MKD_OK and
+ * writes nothing.  na and nb are at most 2^31 - 1.  d_a and d_b must be 16-byte aligned, the other arrays 4-byte aligned.
+ * The result depends on the inputs alone: not on the run, not on the split count, not on the device's CU count -- a row's
+ * state is (best, index, group of best, rival), and two states over disjoint row sets merge exactly: the one with the larger
+ * (best, index) wins and its rival becomes the maximum of its own and, if the best groups differ, the loser's best, else the
+ * loser's rival.
+ * One launch (the scan over a grid of a blocks x b splits) or two (a merge of the splits' states when the plan below has more
+ * than one split).  Asynchronous on `stream` (NULL: the handle's own), no host synchronisation, no allocation once the
+ * handle's q8 scratch has grown to the largest plan seen; a warmed-up call can be captured in a hipGraph.  The scratch is the
+ * one lf_mkd_match_q8_device and lf_mkd_knn_q8_device use, so the calls of one handle must be stream-ordered, as those calls
+ * already require.  lf_mkd_match_overflowed is not affected.  lf_mkd_match_q8_grouped is the same for host pointers (any
+ * alignment), synchronous, without exclusion ranges, through the handle's staging; `best` and `rival` may be NULL.
+ * Cost: group ids are read only for the candidates that pass the top-2 code's gate (a tile's maximum above the rival or at
+ * least the best).  With a SINGLE group nothing ever raises the rival, so that gate never closes and every tile pays the
+ * update: such a pool belongs to lf_mkd_match_q8_device at ratio 0.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "match_q8_grouped_device: " /
+ * "match_q8_grouped: " and is reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; with na > 0 a null
+ * d_a, d_b, d_group_of_b or d_match; one exclusion pointer without the other; d_a or d_b not 16-byte aligned or another array
+ * not 4-byte aligned; nb == 0; na or nb above 2^31 - 1. */
+int lf_mkd_match_q8_grouped_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                                   const uint32_t *d_group_of_b, const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi,
+                                   float ratio, int32_t *d_match, int32_t *d_best, int32_t *d_rival, void *stream);
+int lf_mkd_match_q8_grouped(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb,
+                            const uint32_t *group_of_b, float ratio, int32_t *match, int32_t *best, int32_t *rival);
+/* What lf_mkd_match_q8_grouped_device launches for a problem size, and the scratch it needs -- host-only, no device, no
+ * handle, no environment variable; the launch path calls this very function.  num_cus: the device's compute units, 0 means
+ * 256.  *a_blocks x *b_splits is the scan's grid: an a block is 256 rows (8 waves x 1 tile of 32), a split a contiguous range
+ * of 32-row b tiles, none empty.  b_splits is 1 when all of b is one LDS stage (nb <= 128); otherwise about two workgroups per
+ * CU, at least 2 and at most one per b tile (and at most 1024) -- a condition on nb alone.  *scratch_bytes is 0 exactly when
+ * b_splits == 1 (the scan then writes the result itself) and otherwise 16 bytes per (split, a row), stated as an upper bound
+ * that is non-decreasing in na for a given nb and num_cus (a handle warmed up on its largest problem never allocates again):
+ *   16 * 256 * min(A + max(W, A), A * ceil(nb / 32)),  A = a_blocks, W = 2 * num_cus.
+ * na == 0: (0, 1, 0).  Output pointers may be NULL.  LF_MKD_ERR_BAD_ARG (message "match_q8_grouped_plan: ...", through
+ * lf_mkd_last_error(NULL)): nb == 0, na or nb above 2^31 - 1. */
+int lf_mkd_match_q8_grouped_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                                 uint64_t *scratch_bytes);
+/* The group-by-group vote table of a match array: the second half of retrieval, on the device.
+ *   d_votes is [n_groups_a][n_groups_b] uint32; exactly that many entries are written (the call zeroes them first).
+ *   votes[ga][gb] is the number of rows i with  0 <= d_match[i] < nb,  ga = d_group_of_a[i] < n_groups_a  (d_group_of_a NULL:
+ *   ga = 0 for every row) and  gb = d_group_of_b[d_match[i]] < n_groups_b.  Rows failing any of the three are not counted;
+ *   nothing is read out of range.
+ * Integer atomic adds, so the table does not depend on the order.  Two launches (the zeroing is a kernel, not a memset: a
+ * captured memset node of this size was seen to replay a stale fill pattern on ROCm 7.2), asynchronous on `stream` (NULL:
+ * the handle's own), no scratch, capturable.  LF_MKD_ERR_BAD_ARG before any device is touched (message
+ * "vote_groups_device: ...", through lf_mkd_last_error(NULL) when h is NULL): a null handle; with na > 0 a null d_match or
+ * d_group_of_b; a null d_votes; a group count of zero; n_groups_a * n_groups_b above 2^31 - 1; na or nb above 2^31 - 1; an
+ * array that is not 4-byte aligned. */
+int lf_mkd_vote_groups_device(lf_mkd *h, const int32_t *d_match, uint64_t na, const uint32_t *d_group_of_a, uint32_t n_groups_a,
+                              const uint32_t *d_group_of_b, uint64_t nb, uint32_t n_groups_b, uint32_t *d_votes, void *stream);
 /* Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device over the q8 format above, for the multi-frame pipeline.
  *   Layout and offsets are those of lf_mkd_match_pairs_device, word for word: pair p is a rows [offsets_a[p], offsets_a[p+1])
  *   against b rows [offsets_b[p], offsets_b[p+1]); both offset arrays hold n_pairs + 1 uint64 entries, live on the device, are

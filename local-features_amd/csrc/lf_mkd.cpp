@@ -2053,6 +2053,103 @@ int lf_mkd_knn_q8(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, ui
     return LF_MKD_OK;
 }
 
+// Grouped matching over 8-bit rows (csrc/mkd_match_q8_grouped.hip): the matcher's refusals, except that one candidate is an
+// answer; the rival is the best score of another group than the best's.
+static const char *match_q8_grouped_sizes(uint64_t na, uint64_t nb) {
+    if (nb == 0) return "needs at least one candidate in b";
+    if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";
+    return nullptr;
+}
+
+int lf_mkd_match_q8_grouped_plan(uint64_t na, uint64_t nb, uint32_t num_cus, uint32_t *a_blocks, uint32_t *b_splits,
+                                 uint64_t *scratch_bytes) {
+    if (const char *msg = match_q8_grouped_sizes(na, nb)) return q8_refuse(nullptr, "match_q8_grouped_plan", msg);
+    const Q8GroupedPlan p = match_q8_grouped_plan(long(na), long(nb), int(std::min<uint32_t>(num_cus, 1u << 20)));
+    if (a_blocks) *a_blocks = p.a_blocks;
+    if (b_splits) *b_splits = p.splits;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+static const char *match_q8_grouped_args(const lf_mkd *h, const void *a, uint64_t na, const void *b, uint64_t nb,
+                                         const void *group, const void *lo, const void *hi, const void *match,
+                                         const void *best, const void *rival, bool device) {
+    if (na && (!a || !b || !group || !match)) return "null pointer";
+    if ((lo == nullptr) != (hi == nullptr)) return "exclude_lo and exclude_hi go together";
+    if (device && na && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15))
+        return "d_a and d_b must be 16-byte aligned";
+    if (device && na && ((reinterpret_cast<uintptr_t>(group) | reinterpret_cast<uintptr_t>(lo) | reinterpret_cast<uintptr_t>(hi) |
+                          reinterpret_cast<uintptr_t>(match) | reinterpret_cast<uintptr_t>(best) |
+                          reinterpret_cast<uintptr_t>(rival)) & 3))
+        return "d_group_of_b, the exclusion bounds and the outputs must be 4-byte aligned";
+    if (const char *msg = match_q8_grouped_sizes(na, nb)) return msg;
+    return h ? nullptr : "null handle";
+}
+
+int lf_mkd_match_q8_grouped_device(lf_mkd *h, const uint8_t *d_a, uint64_t na, const uint8_t *d_b, uint64_t nb,
+                                   const uint32_t *d_group_of_b, const uint32_t *d_exclude_lo, const uint32_t *d_exclude_hi,
+                                   float ratio, int32_t *d_match, int32_t *d_best, int32_t *d_rival, void *stream) {
+    if (const char *msg = match_q8_grouped_args(h, d_a, na, d_b, nb, d_group_of_b, d_exclude_lo, d_exclude_hi, d_match, d_best,
+                                                d_rival, true))
+        return q8_refuse(h, "match_q8_grouped_device", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const Q8GroupedPlan plan = match_q8_grouped_plan(long(na), long(nb), h->num_cus);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_q8_part, plan.scratch_bytes)) return rc;
+    launch_match_q8_grouped(d_a, long(na), d_b, long(nb), d_group_of_b, d_exclude_lo, d_exclude_hi, ratio, plan,
+                            plan.scratch_bytes ? h->d_q8_part.get() : nullptr, d_match, d_best, d_rival,
+                            stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_match_q8_grouped(lf_mkd *h, const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb,
+                            const uint32_t *group_of_b, float ratio, int32_t *match, int32_t *best, int32_t *rival) {
+    if (const char *msg = match_q8_grouped_args(h, a, na, b, nb, group_of_b, nullptr, nullptr, match, best, rival, false))
+        return q8_refuse(h, "match_q8_grouped", msg);
+    if (na == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    // the staging holds a's rows, b's rows and then b's group ids ((na + nb) * 128 keeps them 4-byte aligned)
+    if (int rc = grow(h, h->d_q8_io, (na + nb) * kOut + nb * sizeof(uint32_t))) return rc;
+    if (int rc = grow(h, h->d_match_out, 3 * na)) return rc;
+    unsigned char *d_b = h->d_q8_io + na * kOut;
+    uint32_t *d_group = reinterpret_cast<uint32_t *>(h->d_q8_io + (na + nb) * kOut);
+    LF_HIP(h, hipMemcpyAsync(h->d_q8_io, a, na * kOut, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(d_b, b, nb * kOut, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(d_group, group_of_b, nb * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (int rc = lf_mkd_match_q8_grouped_device(h, h->d_q8_io, na, d_b, nb, d_group, nullptr, nullptr, ratio, h->d_match_out,
+                                                best ? h->d_match_out + na : nullptr,
+                                                rival ? h->d_match_out + 2 * na : nullptr, h->stream))
+        return rc;
+    LF_HIP(h, hipMemcpyAsync(match, h->d_match_out, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (best) LF_HIP(h, hipMemcpyAsync(best, h->d_match_out + na, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (rival) LF_HIP(h, hipMemcpyAsync(rival, h->d_match_out + 2 * na, na * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// The group-by-group vote table of a match array: a zeroing launch and one launch of integer atomic adds.
+int lf_mkd_vote_groups_device(lf_mkd *h, const int32_t *d_match, uint64_t na, const uint32_t *d_group_of_a, uint32_t n_groups_a,
+                              const uint32_t *d_group_of_b, uint64_t nb, uint32_t n_groups_b, uint32_t *d_votes, void *stream) {
+    const char *msg = nullptr;
+    if (na && (!d_match || !d_group_of_b)) msg = "null pointer";
+    else if (n_groups_a == 0 || n_groups_b == 0) msg = "a group count of zero";
+    else if (uint64_t(n_groups_a) * n_groups_b > 0x7FFFFFFFull) msg = "more than 2^31 - 1 entries in the vote table";
+    else if (!d_votes) msg = "null d_votes";
+    else if (na > 0x7FFFFFFFull || nb > 0x7FFFFFFFull) msg = "more than 2^31 - 1 rows on a side";
+    else if ((reinterpret_cast<uintptr_t>(d_match) | reinterpret_cast<uintptr_t>(d_group_of_a) |
+              reinterpret_cast<uintptr_t>(d_group_of_b) | reinterpret_cast<uintptr_t>(d_votes)) & 3)
+        msg = "the arrays must be 4-byte aligned";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "vote_groups_device", msg);
+    LF_ENTER(h);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    launch_vote_groups(d_match, long(na), d_group_of_a, n_groups_a, d_group_of_b, long(nb), n_groups_b, d_votes, s);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 // Many pairs of 8-bit rows in one call: lf_mkd_match_pairs_device's layout and refusals, the int8 matcher's decisions.
 static const char *match_q8_pairs_sizes(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, bool both) {
     if (na_total > 0x7FFFFFFFull || nb_total > 0x7FFFFFFFull) return "more than 2^31 - 1 rows on a side";

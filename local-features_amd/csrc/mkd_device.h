@@ -224,6 +224,24 @@ unsigned knn_q8_block_rows();
 void launch_knn_q8(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *excl_lo,
                    const unsigned *excl_hi, int k, const KnnQ8Plan &plan, void *scratch, int *index, int *score,
                    hipStream_t stream);
+// grouped matching over 8-bit rows (csrc/mkd_match_q8_grouped.hip, lf_mkd_match_q8_grouped_device): what
+// lf_mkd_match_q8_grouped_plan reports and launch_match_q8_grouped launches
+struct Q8GroupedPlan {
+    unsigned a_blocks, splits;         // the scan's grid; splits == 1: it writes the result itself, no merge launch
+    long tiles_per_split;              // 32-row b tiles one split scans
+    unsigned long long scratch_bytes;  // one 16-byte state per (split, a row); 0 exactly when splits == 1
+};
+Q8GroupedPlan match_q8_grouped_plan(long na, long nb, int num_cus);
+unsigned match_q8_grouped_block_rows();
+// a [na][128] against b [nb][128] bytes with group_of_b [nb] -> match [na], best / rival (nullable) [na]: the best candidate
+// and the best score among the candidates of another group than the best's; scratch: plan.scratch_bytes
+void launch_match_q8_grouped(const unsigned char *a, long na, const unsigned char *b, long nb, const unsigned *group_of_b,
+                             const unsigned *excl_lo, const unsigned *excl_hi, float ratio, const Q8GroupedPlan &plan,
+                             void *scratch, int *match, int *best, int *rival, hipStream_t stream);
+// votes [n_groups_a][n_groups_b] = 0, then += 1 per row with 0 <= match < nb and both group ids in range (two launches);
+// group_of_a nullable: group 0
+void launch_vote_groups(const int *match, long na, const unsigned *group_of_a, unsigned n_groups_a,
+                        const unsigned *group_of_b, long nb, unsigned n_groups_b, unsigned *votes, hipStream_t stream);
 // many pairs of 8-bit rows in one launch (lf_mkd_match_q8_pairs_device): launch_match_small_pairs' layout and slot map at
 // match_q8_pairs_block_rows() rows per workgroup; each pair decided as launch_match_q8 decides it alone.  No scratch.
 // match_ba (nullable): the other direction from the same launch; mutual: launch_match_mutual's two launches on top.

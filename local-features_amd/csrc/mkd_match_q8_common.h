@@ -1,5 +1,6 @@
 // The int8 matchers' small helpers and the batched form's workgroup shape, shared by mkd_match_q8.hip (match_q8_scan,
-// match_q8_merge, match_q8_pairs) and mkd_match_q8_guided.hip (match_q8_guided_pairs): each of the two units compiles its own
+// match_q8_merge, match_q8_pairs), mkd_match_q8_guided.hip (match_q8_guided_pairs), mkd_match_q8_knn.hip and
+// mkd_match_q8_grouped.hip: each unit compiles its own
 // copy, no device code crosses a translation unit.  The notes on the forms are in mkd_match_q8.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,12 @@ constexpr int kSignBits = (int)0x80808080u;
 __device__ __forceinline__ void q8_lds_dma16(const void *g, void *l) {
     __builtin_amdgcn_global_load_lds(g, reinterpret_cast<__attribute__((address_space(3))) void *>(
                                             reinterpret_cast<uintptr_t>(l)), 16, 0, 0);
+}
+
+// the same for one dword per lane
+__device__ __forceinline__ void q8_lds_dma4(const void *g, void *l) {
+    __builtin_amdgcn_global_load_lds(g, reinterpret_cast<__attribute__((address_space(3))) void *>(
+                                            reinterpret_cast<uintptr_t>(l)), 4, 0, 0);
 }
 
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }   // (v_max3_i32)

@@ -9,6 +9,11 @@ query row votes for the image of its nearest neighbour; the vote counts iff (flo
 first of its k neighbours that lies in a different image (none among the k, or fewer than two candidates: the vote counts).
 The database images are printed ranked by votes.
 
+--exact asks the device for that rule itself instead of approximating it from k neighbours: the pool carries one image id per
+row, ONE LocalFeatures.match_q8_grouped call (ratio 0.8) accepts a query row's nearest neighbour iff it beats the best pool
+row of any other image -- however many near-duplicates the matched image holds -- and ONE LocalFeatures.vote_groups call counts
+the accepted rows per image.  Nothing but the vote table comes back to the host.  The ranking lines are the same.
+
 Image decoding is match_images.py's (8-bit luma, then f32 / 255).  Needs Pillow."""
 import os
 import sys
@@ -50,6 +55,46 @@ def rank_images(index, score, image_offsets, ratio=RATIO):
     return votes
 
 
+def rank_images_exact(match, groups, n_images):
+    """match [n] int32 as match_q8_grouped returns it (a pool row or -1) and groups [n_pool], the image of every pool row
+    -> votes [n_images] int64: the numpy statement of vote_groups with one group of query rows.  Row i votes for
+    groups[match[i]] iff 0 <= match[i] < n_pool and that image id is below n_images."""
+    match, groups = np.asarray(match, np.int64).reshape(-1), np.asarray(groups, np.int64).reshape(-1)
+    votes = np.zeros(n_images, np.int64)
+    ok = (match >= 0) & (match < len(groups))
+    image = groups[match[ok]]
+    np.add.at(votes, image[image < n_images], 1)
+    return votes
+
+
+def describe_all(query, database, top_n=2000, min_size=0.0, feats=None):
+    """(feats, query rows, pool rows, image_offsets): the quantised descriptors of the query and of the pooled database"""
+    images = [query] + list(database)
+    if feats is None:
+        feats = lfp.LocalFeatures(max(i.shape[1] for i in images), max(i.shape[0] for i in images), 3000, max_blobs=8000,
+                                  n_scales=5, pca="liberty", pool_mode=lfp.POOL_F16X3)
+    rows = [feats.quantize(feats.detect_top_n(img, top_n, min_size)[1]) for img in images]
+    q, pool = rows[0], np.concatenate(rows[1:]) if len(rows) > 1 else np.zeros((0, 128), np.uint8)
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in rows[1:]])]).astype(np.int64)
+    return feats, q, pool, offsets
+
+
+def find_image_exact(query, database, top_n=2000, min_size=0.0, feats=None, ratio=RATIO):
+    """query and database: f32 images.  Returns (votes [n_images], image_offsets, query rows, pool rows, groups, match): the
+    exact rule, one match_q8_grouped call and one vote_groups call on the device."""
+    import torch
+    feats, q, pool, offsets = describe_all(query, database, top_n, min_size, feats)
+    n_images = len(database)
+    groups = np.repeat(np.arange(n_images, dtype=np.uint32), np.diff(offsets))
+    if len(pool) == 0 or len(q) == 0:
+        return np.zeros(n_images, np.int64), offsets, q, pool, groups, np.full(len(q), -1, np.int32)
+    dev = torch.device("cuda", feats.device)
+    d_groups = torch.from_numpy(groups.view(np.int32)).to(dev)
+    match = feats.match_q8_grouped(torch.from_numpy(q).to(dev), torch.from_numpy(pool).to(dev), d_groups, ratio)
+    votes = feats.vote_groups(match, d_groups, n_images)
+    return votes.cpu().numpy().reshape(-1).astype(np.int64), offsets, q, pool, groups, match.cpu().numpy()
+
+
 def find_image(query, database, top_n=2000, min_size=0.0, feats=None, k=K, ratio=RATIO):
     """query and database: f32 images.  Returns (votes [n_images], image_offsets, query rows, pool rows, index, score)."""
     images = [query] + list(database)
@@ -67,11 +112,12 @@ def find_image(query, database, top_n=2000, min_size=0.0, feats=None, k=K, ratio
 
 
 def main():
-    args = sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--exact"]
+    exact = len(args) != len(sys.argv) - 1
     if len(args) < 2:
-        print("Required arguments: QUERY DB_1 [DB_2 ...]", file=sys.stderr)
+        print("Required arguments: [--exact] QUERY DB_1 [DB_2 ...]", file=sys.stderr)
         return 1
-    votes, offsets, q, _, _, _ = find_image(load_gray(args[0]), [load_gray(p) for p in args[1:]])
+    votes, offsets, q, _, _, _ = (find_image_exact if exact else find_image)(load_gray(args[0]), [load_gray(p) for p in args[1:]])
     print(f"Query: {len(q)} keypoints against {int(offsets[-1])} in {len(args) - 1} images")
     for rank, m in enumerate(sorted(range(len(votes)), key=lambda m: (-votes[m], m)), 1):
         print(f"{rank}. {args[1 + m]}: {int(votes[m])} votes ({int(offsets[m + 1] - offsets[m])} keypoints)")

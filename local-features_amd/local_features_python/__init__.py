@@ -15,13 +15,13 @@ import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
                    POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
-           "KNN_MAX", "knn_q8_plan"]
+           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan"]
 
 
 class Keypoint:
@@ -342,6 +342,90 @@ class LocalFeatures:
                 return index, score
             s.synchronize()
             return index.cpu().numpy(), score.cpu().numpy()
+
+    def match_q8_grouped(self, qa, qb, groups_b, ratio=0.8, exclude=None, scores=False, stream=None):
+        """The ratio test against the best neighbour from ANOTHER group over 8-bit descriptors
+        (lf_mkd_match_q8_grouped_device): Lowe's object-recognition rule for a pooled database, exact.  qa [na,128] /
+        qb [nb,128] uint8 and groups_b [nb] (any uint32 ids: only their equality is used), numpy arrays or torch tensors;
+        exclude: None or (lo, hi), uint32 [na] each -- b rows lo[i] .. hi[i] - 1 are no candidates for row i.
+        Returns match [na] int32: the row's best row of qb (larger similarity first, among equal ones the higher index) if
+        ratio <= 0 or best * ratio > rival, else -1, where rival is the best score among the rows whose group differs from
+        the best's (INT32_MIN: none, the row is accepted).  With scores=True: (match, best, rival).  numpy in: numpy out
+        (through the host form when there are no exclusion ranges); device tensors in: device tensors out, asynchronously
+        on `stream` (None: torch's current stream) with nothing kept on the host."""
+        if exclude is None and not any(hasattr(x, "data_ptr") for x in (qa, qb, groups_b)):
+            with self._lock:
+                m, best, rival = self._inner.match_q8_grouped(qa, qb, groups_b, ratio)
+            return (m, best, rival) if scores else m
+        import torch
+        dev = torch.device("cuda", self.device)
+        on_device = all(hasattr(x, "data_ptr") and x.is_cuda for x in (qa, qb))
+
+        def rows(x):
+            t = torch.from_numpy(np.ascontiguousarray(x, np.uint8)) if not hasattr(x, "data_ptr") else x
+            return t.to(dev, torch.uint8).reshape(-1, 128).contiguous()
+
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            a, b = rows(qa), rows(qb)
+            na, nb = a.shape[0], b.shape[0]
+            g = self._words(groups_b, dev)
+            if g.numel() != nb:
+                raise RuntimeError("match_q8_grouped: groups_b needs one id per row of qb")
+            lo = hi = None
+            if exclude is not None:
+                lo, hi = (self._words(e, dev) for e in exclude)
+                if lo.numel() != na or hi.numel() != na:
+                    raise RuntimeError("match_q8_grouped: exclude needs one (lo, hi) per row of qa")
+            m = torch.empty((na,), dtype=torch.int32, device=dev)
+            best = torch.empty((na,), dtype=torch.int32, device=dev)
+            rival = torch.empty((na,), dtype=torch.int32, device=dev)
+            with self._lock:
+                # (with na == 0 the call checks its arguments and writes nothing)
+                self._inner.match_q8_grouped_device(a.data_ptr(), na, b.data_ptr(), nb, g.data_ptr(), m.data_ptr(), ratio,
+                                                    lo.data_ptr() if lo is not None else None,
+                                                    hi.data_ptr() if hi is not None else None, best.data_ptr(), rival.data_ptr(),
+                                                    s.cuda_stream)
+            if not on_device:
+                s.synchronize()
+                m, best, rival = m.cpu().numpy(), best.cpu().numpy(), rival.cpu().numpy()
+        return (m, best, rival) if scores else m
+
+    @staticmethod
+    def _words(x, dev):
+        """uint32 values as a contiguous int32 device tensor of their bit patterns (torch's uint32 support is partial)"""
+        import torch
+        if hasattr(x, "data_ptr") and x.is_cuda and x.element_size() == 4 and not x.is_floating_point():
+            return x.to(dev).reshape(-1).contiguous().view(torch.int32)
+        host = np.ascontiguousarray(np.asarray(x.cpu() if hasattr(x, "cpu") else x)).astype(np.uint32).view(np.int32)
+        return torch.from_numpy(host.reshape(-1)).to(dev)
+
+    def vote_groups(self, match, groups_b, n_groups_b, groups_a=None, n_groups_a=1, stream=None):
+        """The group-by-group vote table of a match array (lf_mkd_vote_groups_device): votes [n_groups_a, n_groups_b], where
+        votes[ga, gb] counts the rows i with 0 <= match[i] < nb, ga = groups_a[i] < n_groups_a (groups_a None: 0) and
+        gb = groups_b[match[i]] < n_groups_b; other rows are not counted.  match [na] int32 and the uint32 ids are numpy
+        arrays or torch tensors.  With a device tensor `match` the table is an int32 device tensor (a count is at most
+        2^31 - 1) and the call is asynchronous on `stream` (None: torch's current stream); otherwise a numpy uint32 array."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        on_device = hasattr(match, "data_ptr") and match.is_cuda
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            m = match if hasattr(match, "data_ptr") else torch.from_numpy(np.ascontiguousarray(match, np.int32))
+            m = m.to(dev, torch.int32).reshape(-1).contiguous()
+            gb = self._words(groups_b, dev)
+            ga = self._words(groups_a, dev) if groups_a is not None else None
+            if ga is not None and ga.numel() != m.numel():
+                raise RuntimeError("vote_groups: groups_a needs one id per entry of match")
+            votes = torch.empty((int(n_groups_a), int(n_groups_b)), dtype=torch.int32, device=dev)
+            with self._lock:
+                self._inner.vote_groups_device(m.data_ptr(), m.numel(), gb.data_ptr(), gb.numel(), int(n_groups_b),
+                                               votes.data_ptr(), ga.data_ptr() if ga is not None else None, int(n_groups_a),
+                                               s.cuda_stream)
+            if on_device:
+                return votes
+            s.synchronize()
+            return votes.cpu().numpy().view(np.uint32)
 
     def match_q8_batch(self, qa, offsets_a, qb, offsets_b, ratio=0.8, mutual=False, both=False, stream=None):
         """match_batch over 8-bit descriptors (lf_mkd_match_q8_pairs_device: one launch, three with `mutual`): the same

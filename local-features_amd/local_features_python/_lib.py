@@ -41,6 +41,7 @@ SYMBOLS = (
     "lf_mkd_quantize_descriptors", "lf_mkd_quantize_descriptors_device", "lf_mkd_match_q8", "lf_mkd_match_q8_device",
     "lf_mkd_match_q8_plan", "lf_mkd_match_q8_pairs_device", "lf_mkd_match_q8_guided_pairs_device", "lf_mkd_match_q8_pairs_plan",
     "lf_mkd_knn_q8", "lf_mkd_knn_q8_device", "lf_mkd_knn_q8_plan",
+    "lf_mkd_match_q8_grouped", "lf_mkd_match_q8_grouped_device", "lf_mkd_match_q8_grouped_plan", "lf_mkd_vote_groups_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -139,6 +140,10 @@ def load_library():
     L.lf_mkd_knn_q8_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, vp, vp, vp]
     L.lf_mkd_knn_q8.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp]
     L.lf_mkd_knn_q8_plan.argtypes = [u64, u64, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
+    L.lf_mkd_match_q8_grouped_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp]
+    L.lf_mkd_match_q8_grouped.argtypes = [vp, vp, u64, vp, u64, vp, ctypes.c_float, vp, vp, vp]
+    L.lf_mkd_match_q8_grouped_plan.argtypes = [u64, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
+    L.lf_mkd_vote_groups_device.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -206,6 +211,17 @@ def knn_q8_plan(na, nb, k, num_cus=0):
     rc = L.lf_mkd_knn_q8_plan(na, nb, k, num_cus, ctypes.byref(a), ctypes.byref(s), ctypes.byref(b))
     if rc != 0:
         raise RuntimeError(f"lf_mkd_knn_q8_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return a.value, s.value, b.value
+
+
+def match_q8_grouped_plan(na, nb, num_cus=0):
+    """(a_blocks, b_splits, scratch_bytes): the grid lf_mkd_match_q8_grouped_device launches for this size and the scratch it
+    needs (lf_mkd_match_q8_grouped_plan; needs no device).  num_cus 0: 256."""
+    a, s, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_match_q8_grouped_plan(na, nb, num_cus, ctypes.byref(a), ctypes.byref(s), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_match_q8_grouped_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return a.value, s.value, b.value
 
 
@@ -433,6 +449,21 @@ class MkdHandle:
                                          score.ctypes.data), "lf_mkd_knn_q8")
         return index, score
 
+    def match_q8_grouped(self, qa, qb, groups_b, ratio=0.8):
+        """lf_mkd_match_q8_grouped: the ratio test against the best neighbour from another group over 8-bit descriptors
+        [n,128] uint8, groups_b [nb] uint32 -> (match [na] int32: the best row of qb or -1, best [na] int32, rival [na] int32:
+        the best score among the rows of another group than the best's, INT32_MIN if there is none)."""
+        a = np.ascontiguousarray(qa, np.uint8).reshape(-1, 128)
+        b = np.ascontiguousarray(qb, np.uint8).reshape(-1, 128)
+        g = np.ascontiguousarray(groups_b, np.uint32).reshape(-1)
+        if len(g) != len(b):
+            raise RuntimeError("match_q8_grouped: groups_b needs one id per row of qb")
+        match, best, rival = (np.empty(len(a), np.int32) for _ in range(3))
+        self._check(self.L.lf_mkd_match_q8_grouped(self._h, a.ctypes.data, len(a), b.ctypes.data, len(b), g.ctypes.data, ratio,
+                                                   match.ctypes.data, best.ctypes.data, rival.ctypes.data),
+                    "lf_mkd_match_q8_grouped")
+        return match, best, rival
+
     def verify_homography(self, kps_a, kps_b, match, n_hypotheses=2048, threshold=3.0, seed=0, flags=0):
         """lf_mkd_verify_homography: kps_a [na,5], kps_b [nb,5] f32 rows, match int32 [na] (index into b or -1) ->
         (H [3,3] f32, verified int32 [na], stats uint32 [4])."""
@@ -590,6 +621,19 @@ class MkdHandle:
         """lf_mkd_knn_q8_device: d_index / d_score [na][k] int32, each a row's k best b rows (exact integer similarities)"""
         self._device_call(stream, lambda s: self.L.lf_mkd_knn_q8_device(
             self._h, d_a, na, d_b, nb, d_exclude_lo, d_exclude_hi, k, d_index, d_score, s), "lf_mkd_knn_q8_device")
+
+    def match_q8_grouped_device(self, d_a, na, d_b, nb, d_group_of_b, d_match, ratio=0.8, d_exclude_lo=None, d_exclude_hi=None,
+                                d_best=None, d_rival=None, stream=None):
+        """lf_mkd_match_q8_grouped_device: d_match / d_best / d_rival [na] int32; the rival is the best score among the b rows
+        whose group (d_group_of_b [nb] uint32) differs from the best's"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_grouped_device(
+            self._h, d_a, na, d_b, nb, d_group_of_b, d_exclude_lo, d_exclude_hi, ratio, d_match, d_best, d_rival, s),
+            "lf_mkd_match_q8_grouped_device")
+
+    def vote_groups_device(self, d_match, na, d_group_of_b, nb, n_groups_b, d_votes, d_group_of_a=None, n_groups_a=1, stream=None):
+        """lf_mkd_vote_groups_device: d_votes [n_groups_a][n_groups_b] uint32, zeroed and then counted"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_vote_groups_device(
+            self._h, d_match, na, d_group_of_a, n_groups_a, d_group_of_b, nb, n_groups_b, d_votes, s), "lf_mkd_vote_groups_device")
 
     def match_both_device(self, d_a, na, d_b, nb, d_match_ab, d_match_ba, ratio=0.8, stream=None):
         """both directions in one call: match_ab [na] = match(a, b), match_ba [nb] = match(b, a)"""
