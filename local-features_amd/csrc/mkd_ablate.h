@@ -9,6 +9,8 @@
 //   LF_ABLATE_MMA          no matrix instructions (operands kept)    LF_ABLATE_FRONT     no blur, no gradient direction
 //   LF_ABLATE_SYNC         no row barrier, no wait for the LDS-DMA   LF_ABLATE_EPILOGUE  no normalisation / whitening
 //   LF_ABLATE_FORCE_W4     the 4-wave form at every request size
+//   LF_ABLATE_ROW_DMA      patch mode: the row loop forms its LDS-DMA requests (raw rows, LUT rows) and issues none: every row
+//                          computes on what the first requests of the launch left in LDS
 //   LF_KP_ABLATE_PRODUCER  keypoint mode: the describe waves alone   LF_KP_ABLATE_TAPS   ... everything but a sample's loads
 //   LF_KP_PRODUCER_PRIO=n / LF_KP_CONSUMER_PRIO=n                    wave priorities of the two kinds of wave
 //   LF_ABLATE_ROWS=n       the row loop walks n of a patch's 32 rows (producers too): the bound of a row-split form.  Keypoint
@@ -59,6 +61,11 @@ constexpr bool kNoEpilogue = false;
 constexpr bool kForceFourWaves = true;
 #else
 constexpr bool kForceFourWaves = false;
+#endif
+#ifdef LF_ABLATE_ROW_DMA   // the rows compute on what the first requests left in LDS: what the requests cost their issuer
+constexpr bool kNoRowDma = true;
+#else
+constexpr bool kNoRowDma = false;
 #endif
 #ifdef LF_KP_ABLATE_PRODUCER
 constexpr bool kNoProducer = true;

@@ -11,8 +11,8 @@
 // LUT column is even or odd in x: mkd_consts.hpp) -- the folded values' K slots are exactly the operand lane map of the
 // 16x16 MFMAs (column = l & 15, k-group = l >> 4).  So blur, gradients and the von-Mises
 // embedding are computed in the registers that feed the matrix cores; nothing but the final
-// sums leaves the wave.  Horizontal neighbours come from lanes l -/+ 16 via ds_bpermute; vertical
-// neighbours from a ring of raw patch rows that LDS-DMA keeps filled.
+// sums leaves the wave.  Horizontal neighbours come from lanes l -/+ 16 via ds_bpermute (patch mode in LF_POOL_F16X3: via
+// records in a per-wave LDS area, halo_records); vertical neighbours from a ring of raw patch rows that LDS-DMA keeps filled.
 // (LF_POOL_F16_FP6, an experiment frozen as a mode, keeps the earlier unfolded form: x in [8q, 8q+8) per lane.)
 // LF_POOL_F16X3 leaves three of the 211 LUT columns to the vector ALU: the x-odd cartesian kernels are a product fx(x) gy_b(y),
 // so their 21 packed columns cost ~40 f32 instructions per row instead of 21 matrix instructions (valu_odd_cart below).
@@ -97,12 +97,15 @@ __device__ __forceinline__ void lds_dma16(const void *gsrc, void *ldst) {
 }
 // (uniform base) + (32-bit lane offset).  The base goes through an opaque SGPR constraint so that hipcc cannot
 // re-associate it with the lane offset into a per-lane 64-bit base plus a uniform offset (which it then hoists).
+// LIVE = false (LF_ABLATE_ROW_DMA, a timing-only build): the addresses are formed and the request is left out.
+template <bool LIVE = true>
 __device__ __forceinline__ void lds_dma16_sv(const unsigned char *uniform_base, unsigned lane_off, void *ldst) {
     asm("" : "+s"(uniform_base));
     // volatile: keeps the 32-bit offset's zero-extension in the basic block of its use, where instruction selection can
     // fold it into the addressing mode (hoisted out of the row loop it becomes a 64-bit VGPR pair and an add per request)
     asm volatile("" : "+v"(lane_off));
-    lds_dma16(uniform_base + lane_off, ldst);
+    if constexpr (LIVE) lds_dma16(uniform_base + lane_off, ldst);
+    else asm volatile("" ::"s"(uniform_base), "v"(lane_off), "s"((unsigned)(size_t)(__attribute__((address_space(3))) void *)ldst) : "memory");
 }
 
 // Global addresses of the DMA requests are formed as (wave-uniform 64-bit base) + (32-bit lane offset), in that order:
@@ -111,7 +114,7 @@ __device__ __forceinline__ void lds_dma16_sv(const unsigned char *uniform_base, 
 // and the hoisted address pairs were spilled).
 // one LUT row (24 pieces; 30 unfolded) into an LDS row buffer, piece p by wave p mod W (the first waves take one piece more).
 // ODDV (valu_odd_cart): the two pieces of tile 2 of each group stay behind -- 16 pieces, the i-th of them piece i + 2 (i / 4).
-template <int W, bool FOLD, bool ODDV>
+template <int W, bool FOLD, bool ODDV, bool LIVE = true>
 __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ lut_rows, int row,
                                               unsigned char *lds_row, int wave, int lane) {
     static_assert(!ODDV || FOLD, "the folded forms' tiles");
@@ -124,7 +127,7 @@ __device__ __forceinline__ void issue_lut_row(const unsigned char *__restrict__ 
         if (kPieces % W == 0 || wave + W * j < kPieces) {
             const int i = wave + W * j, piece = ODDV ? i + 2 * (i >> 2) : i;
             const unsigned char *g = lut_rows + ((size_t)row * row_bytes(FOLD) + (size_t)piece * 1024);   // uniform
-            lds_dma16_sv(g, lane16, lds_row + piece * 1024);
+            lds_dma16_sv<LIVE>(g, lane16, lds_row + piece * 1024);
         }
     }
 }
@@ -162,10 +165,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // src = the wave's (uniform) first patch, lane_off = byte offset of the lane's patch and 16-byte chunk from it.
 struct RawSrc { const unsigned char *base; unsigned lane_off; };
 __device__ __forceinline__ constexpr int clamp_row(int row) { return row < 0 ? 0 : (row > 31 ? 31 : row); }
+template <bool LIVE = true>
 __device__ __forceinline__ void issue_raw_row(const RawSrc &src, int row, unsigned char *ring, int slot) {
     const unsigned char *g = src.base + row * 128;   // uniform
-    lds_dma16_sv(g, src.lane_off, ring + slot * 2048);
-    lds_dma16_sv(g + 64, src.lane_off, ring + slot * 2048 + 1024);
+    lds_dma16_sv<LIVE>(g, src.lane_off, ring + slot * 2048);
+    lds_dma16_sv<LIVE>(g + 64, src.lane_off, ring + slot * 2048 + 1024);
 }
 
 // No implicit contraction in the describe kernel (down to the end of mkd_pool): every fused multiply-add in it is written
@@ -588,6 +592,93 @@ __device__ __forceinline__ void hblur_row_fold(const float (&v)[8], int addr_l, 
     nb[1] = has_r ? har : ob[0];
     nb[2] = has_r ? hbl : out[3];
     nb[3] = has_l ? hbr : ob[3];
+}
+
+// The pair forms' horizontal half (patch mode, f16x3): hblur_row_fold with the twelve lane fetches replaced by RECORDS in an
+// LDS area private to the wave (2 KiB: two lane-linear planes of 16 bytes a lane, plane 0 = v[0..3], plane 1 = v[4..7],
+// 1 KiB apart).  A lane writes its eight vertical sums (2 ds_write_b128) and reads, from the record of lane - 16, v[2..5]
+// and, from that of lane + 16, v[0], v[1], v[6], v[7]: one ds_read2_b64 each.  The blurred row's four edge pixels go the
+// same way through plane 0, as {out[3], ob[0], out[0], ob[3]}: one write and two 8-byte reads, which hipcc issues as one
+// ds_read2_b64.  6 LDS instructions instead of 12.  halo_records is the first exchange, hblur_row_fold_rec the filter and the second.
+// rec = the lane's record LESS kRecBack bytes, so that the record of lane - 16 lies at rec + 0, the lane's own at
+// rec + 256 and that of lane + 16 at rec + 512: one address register, every distance an instruction offset.  A lane without a
+// neighbour (q == 0 on the left, q == 3 on the right) reads the 256 bytes of the wave's LDS next to the area on that side
+// and drops them in the has_l / has_r selects, as the fetches' wrapped lanes were dropped.
+// Order: the exchange is inside ONE wave, whose LDS instructions execute in the order of issue for all 64 lanes -- no
+// barrier; the empty asm statements keep hipcc from moving a read above the write it depends on (to the compiler a lane
+// reads what it never wrote), and the area may be written again as soon as the earlier reads have been issued.
+// The values, the selects and the arithmetic are hblur_row_fold's: the descriptors keep their bits.
+constexpr int kRecBack = 256, kRecPlane = 1024;
+typedef __attribute__((address_space(3))) unsigned char lds_u8;
+typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
+typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
+// the four pairs a lane takes from its neighbours' records of the vertical sums
+struct Halo { f32x2 la, rb, ra, lb; };
+__device__ __forceinline__ Halo halo_records(const float (&v)[8], lds_u8 *rec) {
+    Halo h{pk_set(0.f), pk_set(0.f), pk_set(0.f), pk_set(0.f)};
+    if constexpr (ablate::kNoFrontEnd) return h;
+    lds_u8 *own = rec + kRecBack;
+    const lds_u8 *left = rec, *right = rec + 2 * kRecBack;
+    *reinterpret_cast<lds_f32x4 *>(own) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<lds_f32x4 *>(own + kRecPlane) = f32x4{v[4], v[5], v[6], v[7]};
+    asm volatile("" ::: "memory");
+    h.la = *reinterpret_cast<const lds_f32x2 *>(left + 8);                // va[2], va[3] of lane - 16: x = 4q-2, 4q-1
+    h.rb = *reinterpret_cast<const lds_f32x2 *>(left + kRecPlane);        // vb[0], vb[1] of lane - 16: x = 32-4q, 33-4q
+    h.ra = *reinterpret_cast<const lds_f32x2 *>(right);                   // va[0], va[1] of lane + 16: x = 4q+4, 4q+5
+    h.lb = *reinterpret_cast<const lds_f32x2 *>(right + kRecPlane + 8);   // vb[2], vb[3] of lane + 16: x = 26-4q, 27-4q
+    asm volatile("" ::: "memory");
+    return h;
+}
+__device__ __forceinline__ void hblur_row_fold_rec(const float (&v)[8], const Halo &h, lds_u8 *rec, bool has_l, bool has_r,
+                                                   float (&out)[8], float (&nb)[4]) {
+    if constexpr (ablate::kNoFrontEnd) {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) { out[x] = v[x]; out[4 + x] = v[7 - x]; }
+        nb[0] = out[0]; nb[1] = out[3]; nb[2] = out[7]; nb[3] = out[4];
+        return;
+    }
+    const float va[4] = {v[0], v[1], v[2], v[3]}, vb[4] = {v[4], v[5], v[6], v[7]};
+    lds_u8 *own = rec + kRecBack;
+    const lds_u8 *left = rec, *right = rec + 2 * kRecBack;
+    const f32x2 la = h.la, rb = h.rb, ra = h.ra, lb = h.lb;
+    float ea[8], eb[8];
+    ea[0] = has_l ? la.x : va[0];
+    ea[1] = has_l ? la.y : va[0];
+    ea[6] = has_r ? ra.x : vb[0];
+    ea[7] = has_r ? ra.y : vb[1];
+    eb[0] = has_r ? lb.x : va[2];
+    eb[1] = has_r ? lb.y : va[3];
+    eb[6] = has_l ? rb.x : vb[3];
+    eb[7] = has_l ? rb.y : vb[3];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) { ea[2 + x] = va[x]; eb[2 + x] = vb[x]; }
+    float ob[4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {   // (the first tap as an fma onto +0.0: see blur_row_impl)
+        float s = ablate::kMulFirstTap ? kB0 * ea[x] : fmaf(kB0, ea[x], 0.0f);
+        s = fmaf(kB1, ea[x + 1], s);
+        s = fmaf(kB2, ea[x + 2], s);
+        s = fmaf(kB1, ea[x + 3], s);
+        s = fmaf(kB0, ea[x + 4], s);
+        out[x] = s;
+        float t = ablate::kMulFirstTap ? kB0 * eb[x] : fmaf(kB0, eb[x], 0.0f);
+        t = fmaf(kB1, eb[x + 1], t);
+        t = fmaf(kB2, eb[x + 2], t);
+        t = fmaf(kB1, eb[x + 3], t);
+        t = fmaf(kB0, eb[x + 4], t);
+        ob[x] = t;
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) out[4 + x] = ob[3 - x];
+    *reinterpret_cast<lds_f32x4 *>(own) = f32x4{out[3], ob[0], out[0], ob[3]};   // (behind the reads of plane 0 above: issue order)
+    asm volatile("" ::: "memory");
+    const f32x2 el = *reinterpret_cast<const lds_f32x2 *>(left);        // out[3], ob[0] of lane - 16
+    const f32x2 er = *reinterpret_cast<const lds_f32x2 *>(right + 8);   // out[0], ob[3] of lane + 16
+    asm volatile("" ::: "memory");
+    nb[0] = has_l ? el.x : out[0];
+    nb[1] = has_r ? er.x : ob[0];
+    nb[2] = has_r ? er.y : out[3];
+    nb[3] = has_l ? el.y : ob[3];
 }
 
 template <class SlotOfTap>
@@ -1376,6 +1467,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     const int p = lane & 15, q = lane >> 4;
     const int addr_l = ((lane - 16) & 63) * 4, addr_r = ((lane + 16) & 63) * 4;
     const bool has_l = q > 0, has_r = q < 3;
+    // The pair forms' halo records (hblur_row_fold_rec): wave w's 2 KiB area is the w-th of the eight holes that the x-odd
+    // cartesian tiles leave in the two LUT row buffers -- pieces 6 j + 4, 6 j + 5 of a buffer, which issue_lut_row<ODDV>
+    // never requests and the row loop never reads (the LDS map, says why nothing else touches them in rows 0..30)
+    // (one opaque LDS address: left to itself hipcc keeps a register per distance through the row loop, which has none to spare)
+    [[maybe_unused]] lds_u8 *rec = (lds_u8 *)s_mem + ((wave >> 2) * kRowB + (6 * (wave & 3) + 4) * 1024 + lane * 16 - kRecBack);
+    if constexpr (kPairs) asm volatile("" : "+v"(rec));
     const long nbatch = (n + 16 * W - 1) / (16 * W);
     unsigned char *ring = s_mem + kRingO + wave * (kSlots * 2048);
     BatchWalk walk{(long)blockIdx.x, nbatch, (long)gridDim.x};
@@ -1494,6 +1591,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         float cur[8], prv[8], cur_nb[4] = {0.f, 0.f, 0.f, 0.f};
         // patch mode: the vertical sums of hb(g+2), carried from the first body of a row pair (g, g+1) to its second
         [[maybe_unused]] float vnext[8];
+        [[maybe_unused]] Halo hnext;
         [[maybe_unused]] bool last_six = false;          // pair forms: the middle-row loop is on rows 25..30
         [[maybe_unused]] int s0 = 1;                     // one-row patch forms: ring slot of raw row g-1 (rows g-1..g+3 feed hb(g+1))
 
@@ -1519,6 +1617,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             constexpr bool kPairFirst = kPos >= 0 && (kPos & 1) == 0, kPairSecond = kPos >= 0 && (kPos & 1) == 1;
             constexpr int kSlot0 = kPos >= 0 ? (kPos & ~1) : 0;   // ring slot of raw row g-1 in a pair's first body
             static_assert(kPairs ? (kFirst || kLast) == (kPos < 0) : kPos < 0, "the pair forms' rows 1..30 go in pairs");
+            constexpr bool kRowDma = !ablate::kNoRowDma;   // (LF_ABLATE_ROW_DMA: the row loop's requests are formed, not issued)
 
             // LUT row g and the ring rows the body reads have landed (own DMA: vmcnt; everyone's: barrier); row g-1 is done
             phase.mark(7);
@@ -1532,7 +1631,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             // (keypoint mode: the producer waves request LUT rows 1..31 -- an LDS-DMA request stalls its issuer for 60-180
             // cycles, which a producer can afford -- so a describe wave issues no memory instruction in the row loop)
             if (f16_family(POOL) ? !kLast : (!kLast || more)) {
-                if constexpr (!kKp) issue_lut_row<W, kFold, kOddV>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowB, wave, lane);
+                if constexpr (!kKp) issue_lut_row<W, kFold, kOddV, kRowDma>(lr, (g + 1) & 31, s_mem + (par ^ 1) * kRowB, wave, lane);
             } else if (f16_family(POOL)) {
                 issue_w_step<W>(wf, 0, s_mem, wave, lane);
             }
@@ -1549,7 +1648,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             // iteration: for g >= 1 it is requested here, a whole row before the vmcnt(0) that waits for it (counters: the
             // waves spend 29 % of their time in s_waitcnt and only 2 % of that on LDS), for g == 0 after the first blur below.
             if constexpr (!kKp && !kPairs)
-                if (!kFirst && !kLast && g <= 29) issue_raw_row(src, clamp_row(g + 4), ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
+                if (!kFirst && !kLast && g <= 29) issue_raw_row<kRowDma>(src, clamp_row(g + 4), ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
             float nxt[8], nxt_nb[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (!kPairs) {
                 // keypoint mode: the five raw rows of hb(y) are rows y-2 .. y+2 clamped to the patch (replicate border), each
@@ -1585,7 +1684,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             } else {
                 const unsigned char *ring_b = kFold ? ring_mirror : ring_lane + 256;   // the lane's second block of a raw row
                 auto hblur = [&](const float (&v)[8], float (&o)[8], float (&o_nb)[4]) __attribute__((always_inline)) {
-                    if constexpr (kFold) hblur_row_fold(v, addr_l, addr_r, has_l, has_r, o, o_nb);
+                    if constexpr (kFold) hblur_row_fold_rec(v, halo_records(v, rec), rec, has_l, has_r, o, o_nb);
                     else hblur_row(v, addr_l, addr_r, has_l, has_r, o, o_nb[0], o_nb[1]);
                 };
                 auto slot = [](int j) { return (kSlot0 + j) % kRingSlots; };   // of the j-th raw row a body reads
@@ -1612,21 +1711,25 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                     // The wait makes "once read" an ordering: the ring reads above have returned before a request can write.
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     if (!last_six || kPos == 0) {            // (rows 30 and 31 are the last of the batch)
-                        issue_raw_row(src, g + 5, ring, kSlot0);
-                        issue_raw_row(src, g + 6, ring, kSlot0 + 1);
+                        issue_raw_row<kRowDma>(src, g + 5, ring, kSlot0);
+                        issue_raw_row<kRowDma>(src, g + 6, ring, kSlot0 + 1);
                     } else if (more) {
                         if constexpr (kPos == 2) {
-                            issue_raw_row(src_next, 2, ring, 2);
-                            issue_raw_row(src_next, 3, ring, 3);
+                            issue_raw_row<kRowDma>(src_next, 2, ring, 2);
+                            issue_raw_row<kRowDma>(src_next, 3, ring, 3);
                         } else {
 #pragma unroll
                             for (int r = 0; r < kRingSlots; ++r)
-                                if (r != 2 && r != 3) issue_raw_row(src_next, r, ring, r);
+                                if (r != 2 && r != 3) issue_raw_row<kRowDma>(src_next, r, ring, r);
                         }
                     }
-                    hblur(v1, nxt, nxt_nb);
+                    // both rows' halos now, behind the requests (the second body then starts on its filter at once and
+                    // the area is free for its edge pixels): hb(g+2)'s four pairs wait with its vertical sums
+                    const Halo h1 = halo_records(v1, rec);
+                    hnext = halo_records(vnext, rec);
+                    hblur_row_fold_rec(v1, h1, rec, has_l, has_r, nxt, nxt_nb);
                 } else if constexpr (kPairSecond) {
-                    hblur(vnext, nxt, nxt_nb);
+                    hblur_row_fold_rec(vnext, hnext, rec, has_l, has_r, nxt, nxt_nb);
                 }
             }
             if (kLast) {  // row 32 replicates row 31
@@ -1639,10 +1742,10 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             asm volatile("" ::: "memory");
             if constexpr (!kKp && !kPairs) {
                 if (kFirst) {
-                    issue_raw_row(src, g + 4, ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
+                    issue_raw_row<kRowDma>(src, g + 4, ring, s0 == 0 ? kRingSlots - 1 : s0 - 1);
                 } else if (kLast && more) {
 #pragma unroll
-                    for (int r = -2; r <= 3; ++r) issue_raw_row(src_next, clamp_row(r), ring, r + 2);  // next batch's first rows
+                    for (int r = -2; r <= 3; ++r) issue_raw_row<kRowDma>(src_next, clamp_row(r), ring, r + 2);  // next batch's first rows
                 }
                 s0 = s0 == kRingSlots - 1 ? 0 : s0 + 1;
             }
@@ -1667,7 +1770,11 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                     // left - right, plus +0.0: the value unchanged, but -0.0 (a blurred -0.0 on the left of a +0.0 -- the blur of
                     // negative denormals underflows to it, fma or not) becomes +0.0, so that the sign bit gradient_direction
                     // takes from gx is never the sign of a zero: the shader's (cos, sin) = (1, 0) at gx == -0.0, atan2.glsl:29-45
-                    gx[e] = (left - right) + pk_set(0.0f);
+                    // (pair forms: left and right straddle the register pairs cur lives in, and a packed subtraction wants each of
+                    //  them in an aligned pair of its own -- ten moves a row; two single subtractions need none and write the pair
+                    //  the packed + 0.0 then takes.  Per lane the same two IEEE operations.)
+                    if constexpr (kPairs) gx[e] = f32x2{left.x - right.x, left.y - right.y} + pk_set(0.0f);
+                    else gx[e] = (left - right) + pk_set(0.0f);
                     gy[e] = f32x2{nxt[x], nxt[x + 1]} - f32x2{prv[x], prv[x + 1]};      // down - up
                     r2n[e] = pk_fma(gy[e], gy[e], gx[e] * gx[e]);
                     const f32x2 r2 = r2n[e] + pk_set(1e-8f);
