@@ -230,6 +230,27 @@ extern "C" {
     pub fn lf_mkd_match_q8_pairs_plan(na_total: u64, nb_total: u64, n_pairs: u32, both_directions: u32,
                                       block_rows: *mut u32, workgroups: *mut u64) -> c_int;
 
+    // edge lists over a pool (rows + image offsets): any pairs of images in one call, no row copied.  The edge layout of a side
+    // is the pair layout whose pair e has the rows of that side's image of edge e; one call per side writes it
+    pub fn lf_mkd_edge_layout_device(h: *mut lf_mkd, d_image_offsets: *const u64, n_images: u32, n_rows_total: u64,
+                                     d_edge_image: *const u32, n_edges: u32, d_edge_offsets: *mut u64,
+                                     stream: *mut c_void) -> c_int;
+    // rows of row_bytes bytes (a multiple of 4 up to 512: keypoints 20, q8 rows 128, f32 rows 512) from the pool into the
+    // edge layout
+    pub fn lf_mkd_gather_edge_rows_device(h: *mut lf_mkd, d_src: *const c_void, row_bytes: u32, d_image_offsets: *const u64,
+                                          n_images: u32, n_rows_total: u64, d_edge_image: *const u32,
+                                          d_edge_offsets: *const u64, capacity_rows: u64, n_edges: u32, d_dst: *mut c_void,
+                                          stream: *mut c_void) -> c_int;
+    // edge e = image d_edge_a[e] of pool a against image d_edge_b[e] of pool b, decided as lf_mkd_match_q8_device decides the
+    // two images alone; outputs in the edge layouts; the grid is lf_mkd_match_q8_pairs_plan's over the capacities
+    pub fn lf_mkd_match_q8_edges_device(h: *mut lf_mkd, d_a: *const u8, d_image_offsets_a: *const u64, n_images_a: u32,
+                                        na_total: u64, d_b: *const u8, d_image_offsets_b: *const u64, n_images_b: u32,
+                                        nb_total: u64, d_edge_a: *const u32, d_edge_b: *const u32,
+                                        d_edge_offsets_a: *const u64, ea_capacity: u64, d_edge_offsets_b: *const u64,
+                                        eb_capacity: u64, n_edges: u32, ratio: f32, flags: u32, d_match_ab: *mut i32,
+                                        d_match_ba: *mut i32, d_best: *mut i32, d_second: *mut i32,
+                                        stream: *mut c_void) -> c_int;
+
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,
                                     nb: u64, matches: *const i32, n_hypotheses: u32, threshold_px: f32, seed: u32, flags: u32,

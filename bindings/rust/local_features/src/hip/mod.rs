@@ -379,6 +379,62 @@ impl LocalFeaturesHip {
         }).collect())
     }
 
+    /// Any pairs of images from one pool in one call (`lf_mkd_match_q8_edges_device`): image m is rows
+    /// `image_offsets[m]..image_offsets[m + 1]` of `q`, and edge (i, j) matches image i against image j, decided exactly as
+    /// `match_q8` decides the two images alone, Lowe's ratio 0.8.  An image may sit on any number of edges -- a window, all
+    /// i < j, a query against its ranked candidates -- and no descriptor row is copied: the pool crosses the bus once.  With
+    /// `mutual` a match is kept only if the other direction agrees.  Returns, per edge, the (row of image i, row of image j)
+    /// matches.  The edge layouts (`lf_mkd_edge_layout_device`) are made on the device; the host sizes the outputs from its
+    /// own copy of the offsets.
+    pub fn match_q8_edges(&mut self, q: &ArrayView2<u8>, image_offsets: &[u64], edges: &[(u32, u32)], mutual: bool)
+        -> Result<Vec<Vec<(usize, usize)>>, Error> {
+        assert_eq!(q.ncols(), DESCRIPTOR_LEN);
+        if image_offsets.is_empty() {
+            return Err(Error::BadArgument("match_q8_edges: image_offsets needs n_images + 1 entries".into()));
+        }
+        let q = q.as_standard_layout();
+        let (n, n_images, n_edges) = (q.nrows(), image_offsets.len() - 1, edges.len());
+        let rows = |m: u32| -> usize {
+            let m = m as usize;
+            if m >= n_images { return 0; }
+            let (lo, hi) = ((image_offsets[m] as usize).min(n), (image_offsets[m + 1] as usize).min(n));
+            hi.max(lo) - lo
+        };
+        let (ea, eb): (Vec<u32>, Vec<u32>) = edges.iter().copied().unzip();
+        let (cap_a, cap_b): (usize, usize) = (ea.iter().map(|&m| rows(m)).sum(), eb.iter().map(|&m| rows(m)).sum());
+        let mut m = vec![-1i32; cap_a];
+        let mut layout = vec![0u64; n_edges + 1];
+        if n_edges > 0 && n > 0 {
+            // SAFETY: q is contiguous [n][128]; device buffers sized as declared; the capacities bound what is written
+            unsafe {
+                let d_q = DeviceBuffer::from_slice(q.as_slice().unwrap())?;
+                let d_io = DeviceBuffer::from_slice(image_offsets)?;
+                let (d_ea, d_eb) = (DeviceBuffer::from_slice(&ea)?, DeviceBuffer::from_slice(&eb)?);
+                let (d_la, d_lb) = (DeviceBuffer::<u64>::new(n_edges + 1)?, DeviceBuffer::<u64>::new(n_edges + 1)?);
+                let d_ab = DeviceBuffer::from_slice(&m)?;                    // entries of no edge stay -1
+                let d_ba = DeviceBuffer::<i32>::new(if mutual { cap_b } else { 0 })?;
+                for (d_e, d_l) in [(&d_ea, &d_la), (&d_eb, &d_lb)] {
+                    check(self.h, ffi::lf_mkd_edge_layout_device(self.h, d_io.as_ptr(), n_images as u32, n as u64, d_e.as_ptr(),
+                                                                 n_edges as u32, d_l.as_mut_ptr(), std::ptr::null_mut()))?;
+                }
+                check(self.h, ffi::lf_mkd_match_q8_edges_device(
+                    self.h, d_q.as_ptr(), d_io.as_ptr(), n_images as u32, n as u64, d_q.as_ptr(), d_io.as_ptr(), n_images as u32,
+                    n as u64, d_ea.as_ptr(), d_eb.as_ptr(), d_la.as_ptr(), cap_a as u64,
+                    if mutual { d_lb.as_ptr() } else { std::ptr::null() }, if mutual { cap_b as u64 } else { 0 }, n_edges as u32,
+                    0.8, if mutual { MATCH_MUTUAL } else { 0 }, d_ab.as_mut_ptr(),
+                    if mutual { d_ba.as_mut_ptr() } else { std::ptr::null_mut() }, std::ptr::null_mut(), std::ptr::null_mut(),
+                    std::ptr::null_mut()))?;
+                check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+                d_ab.download(&mut m)?;
+                d_la.download(&mut layout)?;
+            }
+        }
+        Ok((0..n_edges).map(|e| {
+            let (lo, hi) = ((layout[e] as usize).min(cap_a), (layout[e + 1] as usize).min(cap_a));
+            (lo..hi.max(lo)).filter(|&i| m[i] >= 0).map(|i| (i - lo, m[i] as usize)).collect()
+        }).collect())
+    }
+
     /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates
     /// are the rows of the other side that pass the verifier's inlier test with it under `models[p]` (row-major H or F, as the
     /// verifiers return it; `kind`: `GUIDE_HOMOGRAPHY` / `GUIDE_FUNDAMENTAL`) within `threshold_px`.  `kps_a` / `kps_b` are

@@ -703,6 +703,81 @@ int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_
  * 2^31 - 1, or more than 2^31 - 1 workgroups. */
 int lf_mkd_match_q8_pairs_plan(uint64_t na_total, uint64_t nb_total, uint32_t n_pairs, uint32_t both_directions,
                                uint32_t *block_rows, uint64_t *workgroups);
+/* ---- edge lists: any pairs of images from one pool, over 8-bit rows, no row copied -------------------------------
+ * The pair layout above gives every image to one pair.  A window wider than one, exhaustive matching of N images, a query
+ * against its ranked candidates and loop-closure candidates all put one image on MANY pairs; these three calls take such a
+ * batch as a list of edges over a pool.
+ *   pool        one row array plus d_image_offsets (uint64 [n_images + 1], on the device, never read by the host): image m owns
+ *               rows [image_offsets[m], image_offsets[m+1]).  An offset beyond the pool's total is read as the total and an
+ *               inverted range is empty, as for a pair; rows that belong to no image are never read.
+ *   edge        edge e is (d_edge_a[e], d_edge_b[e]), two uint32 image ids on the device: image edge_a[e] of the a pool against
+ *               image edge_b[e] of the b pool.  The two pools are separate arguments and may be the same arrays.  A self edge, a
+ *               repeated edge and (j, i) beside (i, j) are ordinary edges.  An id at or beyond n_images names an empty image.
+ *   edge layout of one side: an ordinary pair layout, d_edge_offsets (uint64 [n_edges + 1]) with edge_offsets[e+1] -
+ *               edge_offsets[e] = the rows of that side's image of edge e.  Everything that is indexed "like a" -- match, best,
+ *               second, verified, the keypoints of the rows -- lives in it, so LF_MKD_MATCH_MUTUAL, both verifiers and the
+ *               guided calls take (edge_offsets_a, edge_offsets_b) as their offsets, unchanged.
+ *
+ * lf_mkd_edge_layout_device writes the layout of one side (call it once per side): d_edge_offsets[0] = 0 and
+ * d_edge_offsets[e+1] = d_edge_offsets[e] + rows(d_edge_image[e]), where rows(m) is image m's row count against n_rows_total
+ * for m < n_images and 0 for any other id.  Exactly n_edges + 1 entries are written; n_edges == 0 is LF_MKD_OK and writes
+ * nothing.  Integer sums: the result is exact.  Two launches (one up to 1024 edges), no scratch, no allocation, no host
+ * synchronisation, asynchronous on `stream` (NULL: the handle's own): capturable.  LF_MKD_ERR_BAD_ARG before any device is
+ * touched (message "edge_layout_device: ...", through lf_mkd_last_error(NULL) when h is NULL): a null handle; with
+ * n_edges > 0 a null pointer; an offset array not 8-byte or d_edge_image not 4-byte aligned; n_rows_total above 2^31 - 1.
+ *
+ * lf_mkd_gather_edge_rows_device brings rows of any kind from a pool into the edge layout -- keypoints (row_bytes 20) for
+ * the verifiers, q8 rows (128) or f32 rows (512) for a call that has no edges form.  For edge e let (lo, len) be the range
+ * [edge_offsets[e], edge_offsets[e+1]) read against capacity_rows as a pair is read against a total, and (first, n) its
+ * image's rows: dst row lo + r = src row first + r for r < min(n, len).  row_bytes is a multiple of 4 in [4, 512]; d_src and
+ * d_dst are 4-byte aligned.  Rows of dst that belong to no edge are untouched; nothing at or beyond n_rows_total is read and
+ * nothing at or beyond capacity_rows is written, whatever the arrays hold.  One launch, no scratch, capturable; n_edges == 0
+ * is LF_MKD_OK.  LF_MKD_ERR_BAD_ARG before any device is touched (message "gather_edge_rows_device: ..."): a null handle; a
+ * null pointer; a bad row_bytes; d_src or d_dst not 4-byte aligned; a total or a capacity above 2^31 - 1; more than
+ * 2^31 - 1 workgroups (floor(capacity_rows / 64) + n_edges).
+ *
+ * lf_mkd_match_q8_edges_device decides every edge.  For edge e let A be image edge_a[e] of pool a (nA rows), B image
+ * edge_b[e] of pool b (nB rows), and (loA, lenA) / (loB, lenB) the edge's ranges of the two layouts against ea_capacity /
+ * eb_capacity.
+ *   a -> b      for r < min(nA, lenA) the entries loA + r of d_match_ab, d_best and d_second EQUAL what
+ *               lf_mkd_match_q8_device(A, B) writes for row r without exclusion ranges: exact int32 sums, ties to the highest
+ *               index, second == best when the maximum occurs twice, accepted iff ratio <= 0 || (float)best * ratio >
+ *               (float)second; match values are local to B.  B is always the WHOLE image, whatever the b-side layout holds.
+ *               With nB < 2 the outputs are -1 and INT32_MIN, the pairs call's rule.
+ *   b -> a      when d_match_ba is given this direction is decided in the same launch, likewise over the whole A, for
+ *               r < min(nB, lenB) at loB + r, with nA < 2 as the refusal.
+ *   mutual      LF_MKD_MATCH_MUTUAL is lf_mkd_match_pairs_device's filter, unchanged, on (d_edge_offsets_a, ea_capacity,
+ *               d_edge_offsets_b, eb_capacity).
+ * d_edge_offsets_b, eb_capacity and d_match_ba may be NULL / 0 together unless the flag is set; d_best and d_second may be
+ * NULL.  d_a and d_b must be 16-byte aligned.
+ * Capacities and the grid: ea_capacity / eb_capacity are the sizes of the caller's output arrays, upper bounds of the
+ * layouts' last entries (a caller who keeps counts on the device passes n_edges x its per-image cap).  The host sizes the
+ * grid from them and never reads a device array; the grid is exactly what lf_mkd_match_q8_pairs_plan(ea_capacity,
+ * eb_capacity, n_edges, d_match_ba != NULL) reports -- the same R, the same slot map, over the edge offsets.
+ * Bounds, whatever the arrays hold: no row at or beyond a pool's total is read, no entry at or beyond a capacity is written,
+ * entries of no edge are untouched.  The result of an edge depends on its two images, `ratio` and nothing else: not on
+ * n_edges, not on the other edges, not on the run, not on the device's CU count.
+ * Cost: as the pairs call, every workgroup streams its edge's whole other image through LDS; an image on k edges is read k
+ * times from memory (L2 permitting) and copied nowhere.
+ * One launch (three with LF_MKD_MATCH_MUTUAL), no scratch, no allocation, no host synchronisation, asynchronous on `stream`
+ * (NULL: the handle's own): capturable in a hipGraph.  n_edges == 0 is LF_MKD_OK and writes nothing.
+ * lf_mkd_match_overflowed is not affected.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "match_q8_edges_device: " and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; null d_a, d_b, image offsets or d_match_ab; a null
+ * edge or layout array (d_edge_offsets_b only when d_match_ba is given); LF_MKD_MATCH_MUTUAL without d_match_ba; unknown flag
+ * bits; d_a or d_b not 16-byte aligned; a total or a capacity above 2^31 - 1; a grid above 2^31 - 1 workgroups. */
+int lf_mkd_edge_layout_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                              const uint32_t *d_edge_image, uint32_t n_edges, uint64_t *d_edge_offsets, void *stream);
+int lf_mkd_gather_edge_rows_device(lf_mkd *h, const void *d_src, uint32_t row_bytes, const uint64_t *d_image_offsets,
+                                   uint32_t n_images, uint64_t n_rows_total, const uint32_t *d_edge_image,
+                                   const uint64_t *d_edge_offsets, uint64_t capacity_rows, uint32_t n_edges, void *d_dst,
+                                   void *stream);
+int lf_mkd_match_q8_edges_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *d_image_offsets_a, uint32_t n_images_a,
+                                 uint64_t na_total, const uint8_t *d_b, const uint64_t *d_image_offsets_b, uint32_t n_images_b,
+                                 uint64_t nb_total, const uint32_t *d_edge_a, const uint32_t *d_edge_b,
+                                 const uint64_t *d_edge_offsets_a, uint64_t ea_capacity, const uint64_t *d_edge_offsets_b,
+                                 uint64_t eb_capacity, uint32_t n_edges, float ratio, uint32_t flags, int32_t *d_match_ab,
+                                 int32_t *d_match_ba, int32_t *d_best, int32_t *d_second, void *stream);
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

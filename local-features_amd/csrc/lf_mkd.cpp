@@ -2189,6 +2189,78 @@ int lf_mkd_match_q8_pairs_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *
     return LF_MKD_OK;
 }
 
+// Edge-list matching over 8-bit rows (csrc/mkd_match_q8_edges.hip): pools, edges and edge layouts.  Every refusal comes
+// before the handle is looked at, so it is reported without a device.
+static const uint64_t kEdgeMax = 0x7FFFFFFFull;
+
+int lf_mkd_edge_layout_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                              const uint32_t *d_edge_image, uint32_t n_edges, uint64_t *d_edge_offsets, void *stream) {
+    const char *msg = nullptr;
+    if (n_edges && (!d_image_offsets || !d_edge_image || !d_edge_offsets)) msg = "null pointer";
+    else if ((reinterpret_cast<uintptr_t>(d_image_offsets) | reinterpret_cast<uintptr_t>(d_edge_offsets)) & 7)
+        msg = "the offset arrays must be 8-byte aligned";
+    else if (reinterpret_cast<uintptr_t>(d_edge_image) & 3) msg = "d_edge_image must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax) msg = "more than 2^31 - 1 rows in the pool";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "edge_layout_device", msg);
+    if (n_edges == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_edge_layout(d_image_offsets, n_images, n_rows_total, d_edge_image, n_edges, d_edge_offsets,
+                       stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_gather_edge_rows_device(lf_mkd *h, const void *d_src, uint32_t row_bytes, const uint64_t *d_image_offsets,
+                                   uint32_t n_images, uint64_t n_rows_total, const uint32_t *d_edge_image,
+                                   const uint64_t *d_edge_offsets, uint64_t capacity_rows, uint32_t n_edges, void *d_dst,
+                                   void *stream) {
+    const char *msg = nullptr;
+    if (!d_src || !d_image_offsets || !d_edge_image || !d_edge_offsets || !d_dst) msg = "null pointer";
+    else if (row_bytes < 4 || row_bytes > 512 || (row_bytes & 3)) msg = "row_bytes must be a multiple of 4 in [4, 512]";
+    else if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 3) msg = "d_src and d_dst must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || capacity_rows > kEdgeMax) msg = "a total or a capacity above 2^31 - 1 rows";
+    else if (capacity_rows / gather_edge_rows_block_rows() + n_edges > kEdgeMax)
+        msg = "too many rows and edges for one call (the grid needs floor(capacity / block_rows) + n_edges workgroups, at most 2^31 - 1)";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "gather_edge_rows_device", msg);
+    if (n_edges == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_gather_edge_rows(d_src, row_bytes, d_image_offsets, n_images, n_rows_total, d_edge_image, d_edge_offsets, capacity_rows,
+                            n_edges, d_dst, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_match_q8_edges_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *d_image_offsets_a, uint32_t n_images_a,
+                                 uint64_t na_total, const uint8_t *d_b, const uint64_t *d_image_offsets_b, uint32_t n_images_b,
+                                 uint64_t nb_total, const uint32_t *d_edge_a, const uint32_t *d_edge_b,
+                                 const uint64_t *d_edge_offsets_a, uint64_t ea_capacity, const uint64_t *d_edge_offsets_b,
+                                 uint64_t eb_capacity, uint32_t n_edges, float ratio, uint32_t flags, int32_t *d_match_ab,
+                                 int32_t *d_match_ba, int32_t *d_best, int32_t *d_second, void *stream) {
+    const bool mutual = flags & LF_MKD_MATCH_MUTUAL;
+    const char *msg = nullptr;
+    if (!d_a || !d_b || !d_image_offsets_a || !d_image_offsets_b || !d_match_ab) msg = "null pointer";
+    else if (!d_edge_a || !d_edge_b) msg = "null edge array";
+    else if (!d_edge_offsets_a) msg = "null layout array";
+    else if (flags & ~LF_MKD_MATCH_MUTUAL) msg = "unknown flag bits";
+    else if (mutual && !d_match_ba) msg = "LF_MKD_MATCH_MUTUAL needs d_match_ba";
+    else if (d_match_ba && !d_edge_offsets_b) msg = "null layout array: d_match_ba needs d_edge_offsets_b";
+    else if ((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_b)) & 15) msg = "d_a and d_b must be 16-byte aligned";
+    else if (na_total > kEdgeMax || nb_total > kEdgeMax || ea_capacity > kEdgeMax || eb_capacity > kEdgeMax)
+        msg = "a total or a capacity above 2^31 - 1 rows";
+    // the grid is the pairs call's over the capacities: the same plan, the same words
+    else if (!(msg = match_q8_pairs_sizes(ea_capacity, eb_capacity, n_edges, d_match_ba != nullptr)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "match_q8_edges_device", msg);
+    if (n_edges == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_match_q8_edges(d_a, d_image_offsets_a, n_images_a, na_total, d_b, d_image_offsets_b, n_images_b, nb_total, d_edge_a,
+                          d_edge_b, d_edge_offsets_a, ea_capacity, d_edge_offsets_b, eb_capacity, n_edges, ratio, mutual,
+                          d_match_ab, d_match_ba, d_best, d_second, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 // Guided matching over 8-bit rows: the two calls' refusals together, the q8 pairs call's grid.
 int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
                                         uint64_t na_total, const uint8_t *d_b, const lf_mkd_keypoint *d_kps_b,

@@ -250,6 +250,25 @@ uint64_t match_q8_pairs_slots(uint64_t n_total, unsigned n_pairs);
 void launch_match_q8_pairs(const unsigned char *a, const uint64_t *off_a, uint64_t na_total, const unsigned char *b,
                            const uint64_t *off_b, uint64_t nb_total, unsigned n_pairs, float ratio, bool mutual, int *match_ab,
                            int *match_ba, int *best, int *second, hipStream_t stream);
+// edge-list matching over 8-bit rows (csrc/mkd_match_q8_edges.hip; include/lf_mkd.h, "edge lists").  A pool is a row array and
+// image_off [n_images + 1]; an edge is two image ids; the edge layout of a side is a pair layout whose pair e has the rows of
+// that side's image of edge e.
+// edge_off [n_edges + 1] = the exclusive prefix sum of the edges' image row counts (two launches, one up to 1024 edges)
+void launch_edge_layout(const uint64_t *image_off, unsigned n_images, uint64_t total, const unsigned *edge_image,
+                        unsigned n_edges, uint64_t *edge_off, hipStream_t stream);
+// rows of row_bytes bytes (a multiple of 4) from the pool into the edge layout; one launch over
+// capacity / gather_edge_rows_block_rows() + n_edges workgroups
+unsigned gather_edge_rows_block_rows();
+void launch_gather_edge_rows(const void *src, unsigned row_bytes, const uint64_t *image_off, unsigned n_images, uint64_t total,
+                             const unsigned *edge_image, const uint64_t *edge_off, uint64_t capacity, unsigned n_edges, void *dst,
+                             hipStream_t stream);
+// every edge decided as launch_match_q8 decides its two images alone, outputs in the edge layouts; launch_match_q8_pairs' grid
+// over (ea_capacity, eb_capacity, n_edges).  edge_off_b / match_ba nullable together; mutual: launch_match_mutual on top.
+void launch_match_q8_edges(const unsigned char *a, const uint64_t *image_off_a, unsigned n_images_a, uint64_t na_total,
+                           const unsigned char *b, const uint64_t *image_off_b, unsigned n_images_b, uint64_t nb_total,
+                           const unsigned *edge_a, const unsigned *edge_b, const uint64_t *edge_off_a, uint64_t ea_capacity,
+                           const uint64_t *edge_off_b, uint64_t eb_capacity, unsigned n_edges, float ratio, bool mutual,
+                           int *match_ab, int *match_ba, int *best, int *second, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

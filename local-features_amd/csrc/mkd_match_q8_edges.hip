@@ -1,0 +1,331 @@
+// gfx950 edge-list matching over 8-bit descriptors (include/lf_mkd.h, "edge lists"): any pairs of images from
+// one pool in one launch, no row copied.
+//
+// A POOL is a row array plus image_offsets [n_images + 1]: image m owns rows [image_offsets[m], image_offsets[m + 1]), read
+// through pair_rows against the pool's total.  An EDGE e is (edge_a[e], edge_b[e]), two image ids; an id at or beyond
+// n_images names an empty image.  The EDGE LAYOUT of one side is an ordinary pair layout -- edge_offsets [n_edges + 1] with
+// edge_offsets[e + 1] - edge_offsets[e] = the rows of that side's image of edge e -- and everything indexed "like a" lives in
+// it, so the mutual filter, the verifiers and the guided calls take it as it is.
+//
+//   edge_layout       the exclusive prefix sum of the edges' row counts (two launches, one when a single block does it);
+//   gather_edge_rows  rows of any width from the pool into the edge layout (how keypoints reach the verifiers);
+//   match_q8_edges    match_q8_pairs' body (mkd_match_q8.hip) behind a prologue that takes the slot and the output base from
+//                     the edge layout and x / y from the pools through the edge's two ids.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "mkd_device.h"
+#include "mkd_match_small.h"       // pair_rows, last_pair_at_or_before
+#include "mkd_match_q8_common.h"   // the tile constants, q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
+
+namespace lfmkd {
+namespace {
+
+constexpr int kLayoutThreads = 256, kLayoutPer = 4;
+constexpr int kLayoutBlock = kLayoutThreads * kLayoutPer;   // edges one workgroup of edge_layout scans
+constexpr uint64_t kPartial = 1ull << 63;                   // a block's own sum, not yet the prefix (sums stay below 2^63)
+constexpr int kGatherRows = 64, kGatherThreads = 256;       // rows one workgroup of gather_edge_rows copies
+
+// the first row and the number of rows of image m of a pool; an id at or beyond n_images names an empty image
+__device__ __forceinline__ void image_rows(const uint64_t *__restrict__ image_off, unsigned n_images, uint64_t total, unsigned m,
+                                           long &lo, long &n) {
+    lo = 0;
+    n = 0;
+    if (m < n_images) pair_rows(image_off[m], image_off[m + 1], total, lo, n);
+}
+
+}  // namespace
+
+// Both launches of the layout.  Workgroup k scans edges [k B, (k + 1) B), B = kLayoutBlock.
+//   pass 0 (only when there is more than one workgroup): the block's own sum T_k, tagged with kPartial, goes to the block's
+//          last entry, out[min((k + 1) B, n_edges)]; nothing else is written.
+//   pass 1: the block's base is the sum of the T_j in front of it, then every entry of the block is written.  The base is read
+//          from those same last entries, which the blocks in front overwrite with their final values during this very launch:
+//          an entry still tagged is T_j, an entry no longer tagged is the whole prefix up to and including block j.  Either
+//          reading is usable and each entry is read once, so the base is  (the nearest untagged entry, or 0) + the tagged
+//          entries behind it  whatever the order the blocks run in -- nobody waits for anybody.
+__global__ __launch_bounds__(kLayoutThreads) void edge_layout(const uint64_t *__restrict__ image_off, unsigned n_images,
+                                                              uint64_t total, const unsigned *__restrict__ edge_image,
+                                                              unsigned n_edges, uint64_t *out, int pass) {
+    __shared__ uint64_t s_sum[kLayoutThreads];
+    __shared__ long long s_near[kLayoutThreads];
+    const unsigned k = blockIdx.x, t = threadIdx.x;
+    const uint64_t e0 = (uint64_t)k * kLayoutBlock + (uint64_t)t * kLayoutPer;
+    uint64_t rows[kLayoutPer], mine = 0;
+#pragma unroll
+    for (int i = 0; i < kLayoutPer; ++i) {
+        long lo, n = 0;
+        if (e0 + i < n_edges) image_rows(image_off, n_images, total, edge_image[e0 + i], lo, n);
+        rows[i] = (uint64_t)n;
+        mine += rows[i];
+    }
+    // inclusive scan of the threads' sums
+    s_sum[t] = mine;
+    __syncthreads();
+    for (int d = 1; d < kLayoutThreads; d <<= 1) {
+        const uint64_t v = t >= (unsigned)d ? s_sum[t - d] : 0;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    const uint64_t before = s_sum[t] - mine, block_sum = s_sum[kLayoutThreads - 1];
+    const uint64_t last = (uint64_t)(k + 1) * kLayoutBlock < n_edges ? (uint64_t)(k + 1) * kLayoutBlock : n_edges;
+    if (pass == 0) {
+        if (t == 0) __hip_atomic_store(out + last, block_sum | kPartial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    // the base: one reading of every earlier block's last entry, kLayoutThreads of them at a time from the nearest back
+    uint64_t base = 0;
+    for (long long top = (long long)k - 1; top >= 0; top -= kLayoutThreads) {   // (the same for the whole workgroup)
+        const long long j = top - t;
+        uint64_t v = kPartial;                                  // in front of block 0: a tagged zero
+        if (j >= 0) v = __hip_atomic_load(out + (uint64_t)(j + 1) * kLayoutBlock, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        s_near[t] = (v & kPartial) ? -1 : j;
+        __syncthreads();
+        for (int d = kLayoutThreads / 2; d > 0; d >>= 1) {
+            if (t < (unsigned)d) s_near[t] = s_near[t] > s_near[t + d] ? s_near[t] : s_near[t + d];
+            __syncthreads();
+        }
+        const long long nearest = s_near[0];                    // the nearest untagged entry of these, -1: none
+        // the entries behind it are all tagged: their sums, and the prefix it holds itself
+        s_sum[t] = (j < 0 || j < nearest) ? 0 : (j == nearest ? v : (v & ~kPartial));
+        __syncthreads();
+        for (int d = kLayoutThreads / 2; d > 0; d >>= 1) {
+            if (t < (unsigned)d) s_sum[t] += s_sum[t + d];
+            __syncthreads();
+        }
+        base += s_sum[0];
+        if (nearest >= 0) break;
+    }
+    if (k == 0 && t == 0) out[0] = 0;
+    uint64_t run = base + before;
+#pragma unroll
+    for (int i = 0; i < kLayoutPer; ++i) {
+        run += rows[i];
+        if (e0 + i < n_edges) {
+            if (e0 + i + 1 == last) __hip_atomic_store(out + last, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else out[e0 + i + 1] = run;
+        }
+    }
+}
+
+// dst row lo + r = src row first + r for r < min(n, len): (lo, len) the edge's range of the layout against the capacity,
+// (first, n) its image's rows.  Both runs are contiguous, so a workgroup copies kGatherRows rows as one run of dwords.  The
+// grid is the matcher's slot map at kGatherRows rows a slot: floor(capacity / kGatherRows) + n_edges workgroups.
+__global__ __launch_bounds__(kGatherThreads) void gather_edge_rows(const unsigned *__restrict__ src, unsigned row_words,
+                                                                   const uint64_t *__restrict__ image_off, unsigned n_images,
+                                                                   uint64_t total, const unsigned *__restrict__ edge_image,
+                                                                   const uint64_t *__restrict__ edge_off, uint64_t capacity,
+                                                                   unsigned n_edges, unsigned *__restrict__ dst) {
+    const uint64_t slot = blockIdx.x;
+    auto start = [&](unsigned p) { return (edge_off[p] < capacity ? edge_off[p] : capacity) / kGatherRows + p; };
+    const unsigned p = last_pair_at_or_before(n_edges, slot, start);
+    long lo, len, first, n;
+    pair_rows(edge_off[p], edge_off[p + 1], capacity, lo, len);
+    const long block = (long)slot - (lo / kGatherRows + (long)p);
+    if (block < 0) return;                                       // rows in front of the first edge
+    image_rows(image_off, n_images, total, edge_image[p], first, n);
+    n = n < len ? n : len;
+    const long r0 = block * kGatherRows;
+    if (r0 >= n) return;                                         // the edge's idle slot(s)
+    const long r1 = r0 + kGatherRows < n ? r0 + kGatherRows : n;
+    const unsigned *s = src + (first + r0) * row_words;
+    unsigned *d = dst + (lo + r0) * row_words;
+    const long words = (r1 - r0) * row_words;
+    for (long w = threadIdx.x; w < words; w += kGatherThreads) d[w] = s[w];
+}
+
+// ---- match_q8_edges (lf_mkd_match_q8_edges_device) -----------------------------------------------------------------------
+// THE TWIN OF match_q8_pairs (mkd_match_q8.hip): from "from here on the pair is the whole problem" on the two bodies are the
+// same text, and a change to one belongs in the other.  (A copy, not a shared header: the pairs kernel's code is pinned by
+// its measurements, DESIGN.md 6f, and stays byte for byte what it was.)  Only the prologue differs:
+//   * the slot map runs over the EDGE LAYOUT of the x side against its capacity -- the same R, the same map, so the grid is
+//     what lf_mkd_match_q8_pairs_plan reports for (ea_capacity, eb_capacity, n_edges);
+//   * the outputs' base is the edge's first entry of the layout, lo;
+//   * x and y are the edge's two IMAGES, taken from the pools through its two ids; y is always the whole image;
+//   * the rows served are nx = min(the x image's rows, the edge's range of the layout): entries of the range beyond the image
+//     (a layout that was not made from these ids) are left alone, rows of the image beyond the range are not decided;
+//   * the clamps are to the IMAGE, as the pairs kernel's are to the pair: a DMA lane beyond the image's last row reads the
+//     image's last row, an idle x row redoes the image's last served row.  No byte of another image, of the rows that belong
+//     to no image, or at or beyond a pool's total is ever requested; no entry at or beyond a capacity is written.
+__global__ __launch_bounds__(kPThreads) void match_q8_edges(
+    const unsigned char *__restrict__ a, const uint64_t *__restrict__ image_off_a, unsigned n_images_a, uint64_t na_total,
+    const unsigned char *__restrict__ b, const uint64_t *__restrict__ image_off_b, unsigned n_images_b, uint64_t nb_total,
+    const unsigned *__restrict__ edge_a, const unsigned *__restrict__ edge_b, const uint64_t *__restrict__ edge_off_a,
+    uint64_t ea_capacity, const uint64_t *__restrict__ edge_off_b, uint64_t eb_capacity, unsigned n_edges, unsigned slots_ab,
+    float ratio, int *__restrict__ match_ab, int *__restrict__ match_ba, int *__restrict__ best_out,
+    int *__restrict__ second_out) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_y[2][kPStage * kQTileBytes];
+    // which edge, which block of it: the same for the whole workgroup (scalar loads, no divergence)
+    const bool rev = blockIdx.x >= slots_ab;
+    const uint64_t slot = rev ? blockIdx.x - slots_ab : blockIdx.x;
+    const uint64_t *off_x = rev ? edge_off_b : edge_off_a;
+    const uint64_t x_capacity = rev ? eb_capacity : ea_capacity;
+    auto start = [&](unsigned p) { return (off_x[p] < x_capacity ? off_x[p] : x_capacity) / kPRows + p; };
+    const unsigned p = last_pair_at_or_before(n_edges, slot, start);
+    long lo, len;
+    pair_rows(off_x[p], off_x[p + 1], x_capacity, lo, len);
+    const long block = (long)slot - (lo / kPRows + (long)p);     // slot - start(p)
+    if (block < 0) return;                                       // entries in front of the first edge
+    // (requesting the two ids together with the offsets above, and the four image offsets in one round trip behind them,
+    //  was measured against this form in one run, alternating: 256 frames with window 4 at 1.010 .. 1.019 x the pairs call
+    //  against 1.013 .. 1.025 x -- not resolved, so the plain form stays)
+    const unsigned id_a = edge_a[p], id_b = edge_b[p];
+    long a_lo, a_n, b_lo, b_n;
+    image_rows(image_off_a, n_images_a, na_total, id_a, a_lo, a_n);
+    image_rows(image_off_b, n_images_b, nb_total, id_b, b_lo, b_n);
+    const long x_lo = rev ? b_lo : a_lo, y_lo = rev ? a_lo : b_lo, ny = rev ? a_n : b_n;
+    long nx = rev ? b_n : a_n;
+    nx = nx < len ? nx : len;                                    // the rows served
+    if (block * kPRows >= nx) return;                            // the edge's idle slot(s)
+    int *match = (rev ? match_ba : match_ab) + lo;
+    int *best_o = rev || !best_out ? nullptr : best_out + lo, *second_o = rev || !second_out ? nullptr : second_out + lo;
+    if (ny < 2) {                                                // a side the single-pair call refuses
+        for (long row = block * kPRows + threadIdx.x; row < nx && row < (block + 1) * kPRows; row += kPThreads) {
+            match[row] = -1;
+            if (best_o) best_o[row] = INT_MIN;
+            if (second_o) second_o[row] = INT_MIN;
+        }
+        return;
+    }
+    // from here on the pair is the whole problem: x [nx][128] against y [ny][128]
+    const unsigned char *x = (rev ? b : a) + x_lo * 128, *y = (rev ? a : b) + y_lo * 128;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = lane & 31, h = lane >> 5;
+    const long x_tile0 = (block * kPWaves + wave) * kPTiles;
+    const long x_tiles_total = (nx + kQTileRows - 1) / kQTileRows;
+    const long y_tiles_total = (ny + kQTileRows - 1) / kQTileRows;
+    // x tiles of this wave that exist: the others are skipped whole (wave-uniform; every wave still takes part in the DMA
+    // issues and the barriers)
+    const long left = x_tiles_total - x_tile0;
+    const int n_live = left < 0 ? 0 : (left < kPTiles ? (int)left : kPTiles);
+    // x fragments: B operand of the MFMA, lane (r, h) holds the bytes 32 s + 16 h .. + 15 of a column's row
+    i32x4 xf[kPTiles][4];
+#pragma unroll
+    for (int q = 0; q < kPTiles; ++q) {
+        const long xt = x_tile0 + q < x_tiles_total ? x_tile0 + q : x_tiles_total - 1;   // idle tiles load the pair's last one, unused
+        long xrow = xt * kQTileRows + r;
+        xrow = xrow < nx ? xrow : nx - 1;                                                // idle rows redo the PAIR's last one
+        const unsigned char *src = x + xrow * 128 + 16 * h;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xf[q][s] = *reinterpret_cast<const i32x4 *>(src + 32 * s) ^ kSignBits;
+    }
+    int best[kPTiles], second[kPTiles], best_i[kPTiles];
+#pragma unroll
+    for (int q = 0; q < kPTiles; ++q) { best[q] = INT_MIN; second[q] = INT_MIN; best_i[q] = -1; }
+
+    // tiles t .. t + kPStage - 1 of y -> LDS buffer `buf`.  Slot u * kPThreads + threadIdx.x of the stage's 16-byte slots is
+    // (tile, chunk c, row rr) in that order; a row beyond ny reads the PAIR's last row instead (masked in the epilogue)
+    auto issue = [&](long t, int buf) {
+#pragma unroll
+        for (int u = 0; u < kPPieces; ++u) {
+            const int sl = u * kPThreads + (int)threadIdx.x;
+            const int tile = sl >> 8, c = (sl >> 5) & 7, rr = sl & 31;
+            long row = (t + tile) * kQTileRows + rr;
+            row = row < ny ? row : ny - 1;
+            q8_lds_dma16(y + row * 128 + 16 * c, &s_y[buf][0] + u * (kPThreads * 16) + wave * 1024);
+        }
+    };
+    issue(0, 0);
+    for (long t0 = 0; t0 < y_tiles_total; t0 += kPStage) {
+        const int buf = (int)((t0 / kPStage) & 1);
+        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of the stage have landed
+        __syncthreads();                      // ... and everybody's; everybody is also done with the other buffer
+        if (t0 + kPStage < y_tiles_total) issue(t0 + kPStage, buf ^ 1);
+#pragma unroll
+        for (int u = 0; u < kPStage; ++u) {
+            const long t = t0 + u;
+            if (t >= y_tiles_total || n_live == 0) break;
+            const unsigned char *yy = &s_y[buf][0] + u * kQTileBytes + (h * 32 + r) * 16;
+            i32x4 yf[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) yf[s] = *reinterpret_cast<const i32x4 *>(yy + s * 1024) ^ kSignBits;
+            const int row0 = (int)(t * kQTileRows) + 4 * h;
+            const bool tail = (t + 1) * kQTileRows > ny;
+#pragma unroll
+            for (int q = 0; q < kPTiles; ++q) {
+                if (q >= n_live) break;
+                i32x16 acc;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(yf[s], xf[q][s], acc, 0, 0, 0);
+                if (tail) {                   // rows beyond the pair's last y row (wave-uniform)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i)
+                        if (row0 + (i & 3) + 8 * (i >> 2) >= ny) acc[i] = INT_MIN;
+                }
+                int m = max3i(acc[0], acc[1], acc[2]);
+#pragma unroll
+                for (int i = 3; i < 15; i += 2) m = max3i(m, acc[i], acc[i + 1]);
+                m = max(m, acc[15]);
+                if (__builtin_amdgcn_ballot_w64(m > second[q] || m >= best[q])) {   // rare once the scan is under way
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int v = acc[i];
+                        const int row = row0 + (i & 3) + 8 * (i >> 2);
+                        const bool nb_ = v >= best[q] && v != INT_MIN;   // later index wins among equals
+                        const bool ns = !nb_ && v > second[q];
+                        second[q] = nb_ ? best[q] : (ns ? v : second[q]);
+                        best_i[q] = nb_ ? row : best_i[q];
+                        best[q] = nb_ ? v : best[q];
+                    }
+                }
+            }
+        }
+    }
+    // fold the two lane halves' row sets (lanes l and l ^ 32 hold the same x column)
+#pragma unroll
+    for (int q = 0; q < kPTiles; ++q) {
+        const int ob = __shfl_xor(best[q], 32), os = __shfl_xor(second[q], 32), oi = __shfl_xor(best_i[q], 32);
+        const bool other = ob > best[q] || (ob == best[q] && oi > best_i[q]);
+        const int nbest = other ? ob : best[q];
+        const int nsecond = other ? max(best[q], os) : max(second[q], ob);
+        const int nidx = other ? oi : best_i[q];
+        const long xrow = (x_tile0 + q) * kQTileRows + r;
+        if (h == 0 && q < n_live && xrow < nx) {
+            match[xrow] = q8_decide(nbest, nidx, nsecond, ratio);
+            if (best_o) best_o[xrow] = nbest;
+            if (second_o) second_o[xrow] = nsecond;
+        }
+    }
+}
+
+unsigned gather_edge_rows_block_rows() { return kGatherRows; }
+
+void launch_edge_layout(const uint64_t *image_off, unsigned n_images, uint64_t total, const unsigned *edge_image,
+                        unsigned n_edges, uint64_t *edge_off, hipStream_t stream) {
+    if (n_edges == 0) return;
+    const unsigned blocks = (unsigned)(((uint64_t)n_edges + kLayoutBlock - 1) / kLayoutBlock);
+    for (int pass = blocks > 1 ? 0 : 1; pass < 2; ++pass)
+        hipLaunchKernelGGL(edge_layout, dim3(blocks), dim3(kLayoutThreads), 0, stream, image_off, n_images, total, edge_image,
+                           n_edges, edge_off, pass);
+}
+
+void launch_gather_edge_rows(const void *src, unsigned row_bytes, const uint64_t *image_off, unsigned n_images, uint64_t total,
+                             const unsigned *edge_image, const uint64_t *edge_off, uint64_t capacity, unsigned n_edges, void *dst,
+                             hipStream_t stream) {
+    if (n_edges == 0) return;
+    const uint64_t slots = capacity / kGatherRows + n_edges;
+    hipLaunchKernelGGL(gather_edge_rows, dim3((unsigned)slots), dim3(kGatherThreads), 0, stream,
+                       static_cast<const unsigned *>(src), row_bytes / 4, image_off, n_images, total, edge_image, edge_off,
+                       capacity, n_edges, static_cast<unsigned *>(dst));
+}
+
+void launch_match_q8_edges(const unsigned char *a, const uint64_t *image_off_a, unsigned n_images_a, uint64_t na_total,
+                           const unsigned char *b, const uint64_t *image_off_b, unsigned n_images_b, uint64_t nb_total,
+                           const unsigned *edge_a, const unsigned *edge_b, const uint64_t *edge_off_a, uint64_t ea_capacity,
+                           const uint64_t *edge_off_b, uint64_t eb_capacity, unsigned n_edges, float ratio, bool mutual,
+                           int *match_ab, int *match_ba, int *best, int *second, hipStream_t stream) {
+    if (n_edges == 0) return;
+    const uint64_t slots_ab = match_q8_pairs_slots(ea_capacity, n_edges);
+    const uint64_t slots = slots_ab + (match_ba ? match_q8_pairs_slots(eb_capacity, n_edges) : 0);
+    hipLaunchKernelGGL(match_q8_edges, dim3((unsigned)slots), dim3(kPThreads), 0, stream, a, image_off_a, n_images_a, na_total,
+                       b, image_off_b, n_images_b, nb_total, edge_a, edge_b, edge_off_a, ea_capacity, edge_off_b, eb_capacity,
+                       n_edges, (unsigned)slots_ab, ratio, match_ab, match_ba, best, second);
+    if (mutual) launch_match_mutual(edge_off_a, ea_capacity, edge_off_b, eb_capacity, n_edges, match_ab, match_ba, stream);
+}
+
+}  // namespace lfmkd

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""match_collection [--window W | --all | --retrieve K] [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
+descriptor row is copied for it.
+
+  detect_top_n(2000, min_size 0) on all frames       lf_mkd_detect_frames_device
+  the descriptors quantised once to 8 bits           LocalFeatures.quantize
+  the edges:  --window W  t against t + 1 .. t + W   (the default, W = 2)
+              --all       every i < j
+              --retrieve K  every image against the K images that share most exact votes with it, chosen on the device:
+                          LocalFeatures.match_q8_grouped of the pool against itself with every row's own image excluded,
+                          LocalFeatures.vote_groups into an [N][N] table, torch.topk per image
+  both sides' edge layouts                           lf_mkd_edge_layout_device (inside match_q8_edges)
+  every edge, both directions, 0.8 ratio test,       LocalFeatures.match_q8_edges(mutual=True): one matcher launch and two
+  cross-check                                        filter launches for all edges (lf_mkd_match_q8_edges_device)
+  the keypoints brought into the edge layouts        LocalFeatures.gather_edge_rows (20-byte rows: the only rows copied)
+  RANSAC homography (3 px) per edge, or with         LocalFeatures.verify_homography_batch / verify_fundamental_batch, on the
+  --fundamental epipolar geometry (1.5 px)           edge layouts as they are
+
+and prints one line per edge, ranked by the matches the geometry keeps.  Nothing is read back before those counts: the
+output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
+keypoints bounds that side's layout.
+
+Image decoding as in match_images.py (8-bit luma, then f32 / 255).  Needs Pillow and torch."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import local_features_python as lfp  # noqa: E402
+
+RATIO = 0.8
+
+
+def load_gray(path):
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
+
+
+def window_edges(n, w):
+    """(edge_a, edge_b, degree): t against t + 1 .. t + w; no image is on more than w edges of a side"""
+    pairs = [(t, t + d) for d in range(1, w + 1) for t in range(n - d)]
+    return [p[0] for p in pairs], [p[1] for p in pairs], min(w, n - 1)
+
+
+def all_edges(n):
+    """(edge_a, edge_b, degree): every i < j"""
+    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
+    return [p[0] for p in pairs], [p[1] for p in pairs], n - 1
+
+
+def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
+    """(edge_a, edge_b) as device tensors [n * k]: image i against the k images with most votes for it -- a row votes for the
+    image of its best match among the rows of all OTHER images if that beats the best row of any other image by `ratio`"""
+    import torch
+    lo, hi = o[frame_of], o[frame_of + 1]                      # every row's own image is no candidate
+    match = feats.match_q8_grouped(q, q, frame_of.int(), ratio=ratio, exclude=(lo.int(), hi.int()))
+    votes = feats.vote_groups(match, frame_of.int(), n, groups_a=frame_of.int(), n_groups_a=n)
+    votes = votes.masked_fill(torch.eye(n, dtype=torch.bool, device=votes.device), -1)
+    top = torch.topk(votes.long(), k, dim=1).indices            # [n, k]
+    return torch.arange(n, dtype=torch.int32, device=top.device).repeat_interleave(k), top.reshape(-1).int()
+
+
+def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None):
+    """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all" or "retrieve" (arg = K).  Returns a dict of device
+    tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
+    [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
+    [E,3,3] and stats [E,4] as the verifier returns them; per_edge [E,3]: ratio-test matches a -> b, mutual, verified."""
+    import torch
+    n, hgt, w = frames.shape
+    if feats is None:
+        feats = lfp.LocalFeatures(w, hgt, 3000, max_blobs=8000, n_scales=5, pca="liberty", pool_mode=lfp.POOL_F16X3, max_frames=n)
+    dev = torch.device("cuda", feats.device)
+    cap = feats.max_features * n
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev)
+        d_img = torch.from_numpy(np.ascontiguousarray(frames, np.float32)).to(dev)
+        kps = torch.empty((cap, 5), device=dev)
+        frame_of = torch.empty((cap,), dtype=torch.int32, device=dev)
+        desc = torch.empty((cap, 128), device=dev)
+        m, _, _ = feats._inner.detect_frames_device(d_img.data_ptr(), n, w, hgt, top_n, min_size, kps.data_ptr(),
+                                                    frame_of.data_ptr(), desc.data_ptr(), cap, s.cuda_stream)
+        kps, frame_of, desc = kps[:m].contiguous(), frame_of[:m].long(), desc[:m]
+        o = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(torch.bincount(frame_of, minlength=n), 0)])
+        q = feats.quantize(desc)                                # once; the f32 rows are not read again
+        if mode == "retrieve":
+            ea, eb = retrieved_edges(feats, q, o, frame_of, n, arg, ratio)
+            deg_a, deg_b = arg, n - 1                           # image i is the a side of its own k edges, the b side of at most n - 1
+        else:
+            ea, eb, deg = window_edges(n, arg) if mode == "window" else all_edges(n)
+            ea, eb = torch.tensor(ea, dtype=torch.int32, device=dev), torch.tensor(eb, dtype=torch.int32, device=dev)
+            deg_a = deg_b = deg
+        n_edges = int(ea.numel())
+        cap_a, cap_b = deg_a * m, deg_b * m                     # bounds of the two layouts that need no look at the device
+        m_ab, m_ba, best, second, la, lb = feats.match_q8_edges(q, o, q, o, ea, eb, ratio=ratio, mutual=True, capacity_a=cap_a,
+                                                               capacity_b=cap_b)
+        ka = feats.gather_edge_rows(kps, o, ea, la, capacity=cap_a)
+        kb = feats.gather_edge_rows(kps, o, eb, lb, capacity=cap_b)
+        verify = feats.verify_fundamental_batch if fundamental else feats.verify_homography_batch
+        model, ver, stats = verify(ka, la, kb, lb, m_ab, seed=seed)
+        # per edge: which edge an entry of the a side's layout belongs to (entries behind the last edge: none)
+        edge_of = torch.searchsorted(la, torch.arange(cap_a, device=dev), right=True) - 1
+        count = lambda mask: torch.bincount(edge_of[mask], minlength=n_edges + 1)[:n_edges]
+        raw = (best != -2 ** 31) & ((ratio <= 0) | (best.float() * ratio > second.float()))   # (both conversions are exact)
+        per_edge = torch.stack([count(raw), count(m_ab >= 0), count(ver >= 0)], dim=1)
+    return dict(edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
+                stats=stats, per_edge=per_edge)
+
+
+def main():
+    args = sys.argv[1:]
+    mode, arg, fundamental, paths = "window", 2, False, []
+    while args:
+        a = args.pop(0)
+        if a == "--fundamental":
+            fundamental = True
+        elif a == "--all":
+            mode = "all"
+        elif a in ("--window", "--retrieve") and args and args[0].isdigit() and int(args[0]) > 0:
+            mode, arg = a[2:], int(args.pop(0))
+        elif a.startswith("--"):
+            paths = []
+            break
+        else:
+            paths.append(a)
+    if len(paths) < 2 or (mode == "retrieve" and arg > len(paths) - 1):
+        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K below the "
+              "number of images)", file=sys.stderr)
+        return 1
+    imgs = [load_gray(p) for p in paths]
+    if any(i.shape != imgs[0].shape for i in imgs):
+        print("the images must have one size", file=sys.stderr)
+        return 1
+    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental)
+    ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
+    print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
+    what = "one epipolar geometry" if fundamental else "one homography"
+    for e in sorted(range(len(ea)), key=lambda e: (-per_edge[e][2], e)):
+        raw, mutual, inl = per_edge[e]
+        print(f"Edge {ea[e] + 1} -> {eb[e] + 1}: {raw} matches, {mutual} mutual, {inl} agree with {what}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -460,6 +460,109 @@ class LocalFeatures:
                                                       s.cuda_stream)
         return m_ab, m_ba, best, second
 
+    def edge_layout(self, image_offsets, edge_image, n_rows_total=None, stream=None):
+        """The edge layout of one side (lf_mkd_edge_layout_device): edge_offsets [n_edges + 1] int64 on the device, with
+        edge_offsets[e + 1] - edge_offsets[e] = the rows of image edge_image[e] of the pool whose image m owns rows
+        image_offsets[m] .. image_offsets[m + 1] - 1; an id at or beyond the number of images counts as an empty image.
+        image_offsets [n_images + 1] and edge_image [n_edges] are integer tensors (host or device); n_rows_total is the
+        pool's row count (None: 2^31 - 1, i.e. the offsets are taken as they are).  Asynchronous on `stream` (None: torch's
+        current stream), nothing read back.  Call it once per side; the result is what match_q8_edges, gather_edge_rows, the
+        verifiers and the guided calls take as that side's offsets."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            io = image_offsets.to(dev, torch.int64).reshape(-1).contiguous()
+            ei = self._words(edge_image, dev)
+            if io.numel() < 1:
+                raise RuntimeError("edge_layout: image_offsets needs n_images + 1 entries")
+            n_edges = ei.numel()
+            out = torch.zeros((n_edges + 1,), dtype=torch.int64, device=dev)
+            if n_edges:
+                with self._lock:
+                    self._inner.edge_layout_device(io.data_ptr(), io.numel() - 1, (1 << 31) - 1 if n_rows_total is None else
+                                                   int(n_rows_total), ei.data_ptr(), n_edges, out.data_ptr(), s.cuda_stream)
+        return out
+
+    def gather_edge_rows(self, src, image_offsets, edge_image, edge_offsets, capacity=None, out=None, stream=None):
+        """Rows of a pool brought into an edge layout (lf_mkd_gather_edge_rows_device): for edge e, out rows
+        edge_offsets[e] .. get the rows of image edge_image[e] of `src` -- keypoints [N,5] float32 for the verifiers, or
+        descriptor rows for a call that has no edges form.  src is a contiguous device tensor [N, ...] whose rows are a
+        multiple of 4 bytes, at most 512.  capacity: the rows of the result (None reads the last layout offset back, which
+        WAITS for the stream); out: a tensor to write into instead of a new zero-filled one.  Rows of no edge are untouched."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            x = src.to(dev).contiguous()
+            n = x.shape[0]
+            row_bytes = (x.numel() // n if n else int(np.prod(x.shape[1:]))) * x.element_size()
+            io = image_offsets.to(dev, torch.int64).reshape(-1).contiguous()
+            ei = self._words(edge_image, dev)
+            eo = edge_offsets.to(dev, torch.int64).reshape(-1).contiguous()
+            n_edges = ei.numel()
+            if eo.numel() != n_edges + 1:
+                raise RuntimeError("gather_edge_rows: edge_offsets needs n_edges + 1 entries")
+            if out is None:
+                cap = int(eo[-1].item()) if capacity is None else int(capacity)       # (.item() waits)
+                out = torch.zeros((cap,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
+            elif not (out.is_cuda and out.is_contiguous() and out.dtype == x.dtype and tuple(out.shape[1:]) == tuple(x.shape[1:])):
+                raise RuntimeError("gather_edge_rows: out must be a contiguous device tensor of src's dtype and row shape")
+            if n_edges and n and out.shape[0]:
+                with self._lock:
+                    self._inner.gather_edge_rows_device(x.data_ptr(), row_bytes, io.data_ptr(), io.numel() - 1, n, ei.data_ptr(),
+                                                        eo.data_ptr(), out.shape[0], n_edges, out.data_ptr(), s.cuda_stream)
+        return out
+
+    def match_q8_edges(self, qa, offsets_a, qb, offsets_b, edge_a, edge_b, ratio=0.8, mutual=False, capacity_a=None,
+                       capacity_b=None, stream=None):
+        """Any pairs of images from one pool in one call (lf_mkd_match_q8_edges_device: one launch, three with `mutual`), no
+        descriptor row copied.  qa [Na,128] / qb [Nb,128] uint8 device tensors (what `quantize` returns) are the two pools --
+        they may be the same tensor --, offsets_a [n_images_a + 1] / offsets_b [n_images_b + 1] their image offsets, and edge e
+        matches image edge_a[e] of qa against image edge_b[e] of qb, decided exactly as `match_q8` decides the two images
+        alone; an image may sit on any number of edges.  Returns device tensors (match_ab, match_ba, best, second,
+        edge_offsets_a, edge_offsets_b): the outputs live in the EDGE LAYOUT of their side (edge_layout) -- match_ab, best,
+        second [capacity_a] int32 at edge_offsets_a[e] + r for row r of edge e's a image, match_ba [capacity_b] at
+        edge_offsets_b[e] + r, values local to the other image -- which is the pair layout verify_*_batch and the guided calls
+        take with those two offset tensors.  Entries of no edge hold -1 / INT32_MIN.
+        capacity_a / capacity_b: the sizes of the output arrays, upper bounds of the layouts' totals.  None reads the last
+        layout offset back, which WAITS for the stream; a caller who knows a bound (n_edges x its per-image cap) passes it and
+        the call is asynchronous on `stream` (default: torch's current stream on the handle's device) from end to end."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        for q in (qa, qb):
+            if q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] != 128:
+                raise RuntimeError("match_q8_edges: qa and qb must be uint8 [n, 128] (LocalFeatures.quantize)")
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):      # the copies and the fills below are ordered with the call
+            a, b = qa.to(dev).contiguous(), qb.to(dev).contiguous()
+            oa = offsets_a.to(dev, torch.int64).reshape(-1).contiguous()
+            ob = offsets_b.to(dev, torch.int64).reshape(-1).contiguous()
+            ea, eb = self._words(edge_a, dev), self._words(edge_b, dev)
+            n_edges = ea.numel()
+            if eb.numel() != n_edges:
+                raise RuntimeError("match_q8_edges: edge_a and edge_b need one id per edge each")
+            if oa.numel() < 1 or ob.numel() < 1:
+                raise RuntimeError("match_q8_edges: offsets_a and offsets_b need n_images + 1 entries each")
+            na, nb = a.shape[0], b.shape[0]
+            la = self.edge_layout(oa, ea, na, stream=s)
+            lb = self.edge_layout(ob, eb, nb, stream=s)
+            cap_a = int(la[-1].item()) if capacity_a is None else int(capacity_a)     # (.item() waits)
+            cap_b = int(lb[-1].item()) if capacity_b is None else int(capacity_b)
+            int32_min = -2 ** 31
+            m_ab = torch.full((cap_a,), -1, dtype=torch.int32, device=dev)
+            m_ba = torch.full((cap_b,), -1, dtype=torch.int32, device=dev)
+            best = torch.full((cap_a,), int32_min, dtype=torch.int32, device=dev)
+            second = torch.full((cap_a,), int32_min, dtype=torch.int32, device=dev)
+            if n_edges and na and nb:       # (an empty pool: every edge has too few candidates, the fills above are the answer)
+                with self._lock:
+                    self._inner.match_q8_edges_device(a.data_ptr(), oa.data_ptr(), oa.numel() - 1, na, b.data_ptr(), ob.data_ptr(),
+                                                      ob.numel() - 1, nb, ea.data_ptr(), eb.data_ptr(), la.data_ptr(), cap_a,
+                                                      n_edges, m_ab.data_ptr(), lb.data_ptr(), cap_b, m_ba.data_ptr(), ratio,
+                                                      MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
+                                                      s.cuda_stream)
+        return m_ab, m_ba, best, second, la, lb
+
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):
         """match_guided_batch over 8-bit descriptors (lf_mkd_match_q8_guided_pairs_device: one launch, three with `mutual`):

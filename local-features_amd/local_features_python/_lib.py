@@ -42,6 +42,7 @@ SYMBOLS = (
     "lf_mkd_match_q8_plan", "lf_mkd_match_q8_pairs_device", "lf_mkd_match_q8_guided_pairs_device", "lf_mkd_match_q8_pairs_plan",
     "lf_mkd_knn_q8", "lf_mkd_knn_q8_device", "lf_mkd_knn_q8_plan",
     "lf_mkd_match_q8_grouped", "lf_mkd_match_q8_grouped_device", "lf_mkd_match_q8_grouped_plan", "lf_mkd_vote_groups_device",
+    "lf_mkd_edge_layout_device", "lf_mkd_gather_edge_rows_device", "lf_mkd_match_q8_edges_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -144,6 +145,10 @@ def load_library():
     L.lf_mkd_match_q8_grouped.argtypes = [vp, vp, u64, vp, u64, vp, ctypes.c_float, vp, vp, vp]
     L.lf_mkd_match_q8_grouped_plan.argtypes = [u64, u64, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64)]
     L.lf_mkd_vote_groups_device.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, vp]
+    L.lf_mkd_edge_layout_device.argtypes = [vp, vp, u32, u64, vp, u32, vp, vp]
+    L.lf_mkd_gather_edge_rows_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, u64, u32, vp, vp]
+    L.lf_mkd_match_q8_edges_device.argtypes = [vp, vp, vp, u32, u64, vp, vp, u32, u64, vp, vp, vp, u64, vp, u64, u32,
+                                               ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -655,6 +660,31 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_pairs_device(
             self._h, d_a, d_offsets_a, na_total, d_b, d_offsets_b, nb_total, n_pairs, ratio, flags, d_match_ab, d_match_ba,
             d_best, d_second, s), "lf_mkd_match_q8_pairs_device")
+
+    def edge_layout_device(self, d_image_offsets, n_images, n_rows_total, d_edge_image, n_edges, d_edge_offsets, stream=None):
+        """lf_mkd_edge_layout_device: d_edge_offsets [n_edges + 1] uint64 = the exclusive prefix sum of the row counts of the
+        images d_edge_image [n_edges] uint32 names in the pool (d_image_offsets [n_images + 1] uint64); one call per side"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_edge_layout_device(
+            self._h, d_image_offsets, n_images, n_rows_total, d_edge_image, n_edges, d_edge_offsets, s), "lf_mkd_edge_layout_device")
+
+    def gather_edge_rows_device(self, d_src, row_bytes, d_image_offsets, n_images, n_rows_total, d_edge_image, d_edge_offsets,
+                                capacity_rows, n_edges, d_dst, stream=None):
+        """lf_mkd_gather_edge_rows_device: the rows (row_bytes each, a multiple of 4 up to 512) of every edge's image from the
+        pool d_src into the edge layout d_dst [capacity_rows]"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_gather_edge_rows_device(
+            self._h, d_src, row_bytes, d_image_offsets, n_images, n_rows_total, d_edge_image, d_edge_offsets, capacity_rows,
+            n_edges, d_dst, s), "lf_mkd_gather_edge_rows_device")
+
+    def match_q8_edges_device(self, d_a, d_image_offsets_a, n_images_a, na_total, d_b, d_image_offsets_b, n_images_b, nb_total,
+                              d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match_ab, d_edge_offsets_b=None,
+                              eb_capacity=0, d_match_ba=None, ratio=0.8, flags=0, d_best=None, d_second=None, stream=None):
+        """lf_mkd_match_q8_edges_device: edge e = image d_edge_a[e] of pool a against image d_edge_b[e] of pool b, each decided
+        as match_q8_device decides the two images alone; the outputs live in the edge layouts (device pointers; see
+        include/lf_mkd.h).  flags: MATCH_MUTUAL."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_match_q8_edges_device(
+            self._h, d_a, d_image_offsets_a, n_images_a, na_total, d_b, d_image_offsets_b, n_images_b, nb_total, d_edge_a,
+            d_edge_b, d_edge_offsets_a, ea_capacity, d_edge_offsets_b, eb_capacity, n_edges, ratio, flags, d_match_ab, d_match_ba,
+            d_best, d_second, s), "lf_mkd_match_q8_edges_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
