@@ -250,6 +250,13 @@ extern "C" {
                                         eb_capacity: u64, n_edges: u32, ratio: f32, flags: u32, d_match_ab: *mut i32,
                                         d_match_ba: *mut i32, d_best: *mut i32, d_second: *mut i32,
                                         stream: *mut c_void) -> c_int;
+    // tracks: d_track [n_rows_total] = the smallest pool row of every row's connected component under the links d_match holds
+    // in the a side's edge layout; d_track_len / d_track_dup (nullable) per label the track's rows and its conflicting rows;
+    // flags: LF_MKD_TRACKS_ACCUMULATE
+    pub fn lf_mkd_build_tracks_device(h: *mut lf_mkd, d_image_offsets: *const u64, n_images: u32, n_rows_total: u64,
+                                      d_edge_a: *const u32, d_edge_b: *const u32, d_edge_offsets_a: *const u64,
+                                      ea_capacity: u64, n_edges: u32, d_match: *const i32, flags: u32, d_track: *mut i32,
+                                      d_track_len: *mut u32, d_track_dup: *mut u32, stream: *mut c_void) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -435,6 +435,57 @@ impl LocalFeaturesHip {
         }).collect())
     }
 
+    /// The tracks of a matched collection (`lf_mkd_build_tracks_device`): the connected components of the matches
+    /// `match_q8_edges` returned for `edges` over the pool `image_offsets` describes (`n_rows` rows).  Returns, per pool row,
+    /// (track, length, dup): the smallest pool row of the row's component, and -- at a row that is a label, 0 elsewhere -- the
+    /// rows of the track and its conflicting rows (the rows beyond the first that one image has in it; 0: a consistent
+    /// track).  A row on no match is its own track of length 1.
+    pub fn build_tracks(&mut self, n_rows: usize, image_offsets: &[u64], edges: &[(u32, u32)], matches: &[Vec<(usize, usize)>])
+        -> Result<(Vec<i32>, Vec<u32>, Vec<u32>), Error> {
+        if image_offsets.is_empty() || matches.len() != edges.len() {
+            return Err(Error::BadArgument("build_tracks: image_offsets needs n_images + 1 entries, matches one list per edge".into()));
+        }
+        let (n_images, n_edges) = (image_offsets.len() - 1, edges.len());
+        let rows = |m: u32| -> usize {
+            let m = m as usize;
+            if m >= n_images { return 0; }
+            let (lo, hi) = ((image_offsets[m] as usize).min(n_rows), (image_offsets[m + 1] as usize).min(n_rows));
+            hi.max(lo) - lo
+        };
+        let (ea, eb): (Vec<u32>, Vec<u32>) = edges.iter().copied().unzip();
+        // the a side's edge layout and the match array in it, from the host's own copy of the offsets
+        let mut layout = vec![0u64; n_edges + 1];
+        for e in 0..n_edges { layout[e + 1] = layout[e] + rows(ea[e]) as u64; }
+        let cap = layout[n_edges] as usize;
+        let mut m = vec![-1i32; cap];
+        for (e, list) in matches.iter().enumerate() {
+            for &(i, j) in list {
+                if i < rows(ea[e]) { m[layout[e] as usize + i] = j as i32; }
+            }
+        }
+        let (mut track, mut len, mut dup) = (vec![0i32; n_rows], vec![0u32; n_rows], vec![0u32; n_rows]);
+        if n_rows > 0 {
+            // SAFETY: device buffers sized as declared; n_rows and cap bound what is read and written
+            unsafe {
+                let d_io = DeviceBuffer::from_slice(image_offsets)?;
+                let (d_ea, d_eb) = (DeviceBuffer::from_slice(&ea)?, DeviceBuffer::from_slice(&eb)?);
+                let d_la = DeviceBuffer::from_slice(&layout)?;
+                let d_m = DeviceBuffer::from_slice(&m)?;
+                let d_track = DeviceBuffer::<i32>::new(n_rows)?;
+                let (d_len, d_dup) = (DeviceBuffer::<u32>::new(n_rows)?, DeviceBuffer::<u32>::new(n_rows)?);
+                check(self.h, ffi::lf_mkd_build_tracks_device(
+                    self.h, d_io.as_ptr(), n_images as u32, n_rows as u64, d_ea.as_ptr(), d_eb.as_ptr(), d_la.as_ptr(),
+                    cap as u64, n_edges as u32, d_m.as_ptr(), 0, d_track.as_mut_ptr(), d_len.as_mut_ptr(), d_dup.as_mut_ptr(),
+                    std::ptr::null_mut()))?;
+                check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+                d_track.download(&mut track)?;
+                d_len.download(&mut len)?;
+                d_dup.download(&mut dup)?;
+            }
+        }
+        Ok((track, len, dup))
+    }
+
     /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates
     /// are the rows of the other side that pass the verifier's inlier test with it under `models[p]` (row-major H or F, as the
     /// verifiers return it; `kind`: `GUIDE_HOMOGRAPHY` / `GUIDE_FUNDAMENTAL`) within `threshold_px`.  `kps_a` / `kps_b` are

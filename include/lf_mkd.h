@@ -778,6 +778,56 @@ int lf_mkd_match_q8_edges_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *
                                  const uint64_t *d_edge_offsets_a, uint64_t ea_capacity, const uint64_t *d_edge_offsets_b,
                                  uint64_t eb_capacity, uint32_t n_edges, float ratio, uint32_t flags, int32_t *d_match_ab,
                                  int32_t *d_match_ba, int32_t *d_best, int32_t *d_second, void *stream);
+/* lf_mkd_build_tracks_device turns an edge list's matches into TRACKS: the sets of keypoints across the images of ONE pool
+ * that the pairwise matches tie together -- what structure from motion, triangulation, map merging and loop closure consume.
+ * One label per pool row, and per track its length and its number of conflicting rows.  There is one pool: both ids of an edge
+ * index d_image_offsets.
+ *   links       for edge e let (lo, len) be its range of d_edge_offsets_a read against ea_capacity as a pair is read against a
+ *               total, and (firstA, nA) / (firstB, nB) the rows of images d_edge_a[e] / d_edge_b[e] against n_rows_total; an
+ *               id at or beyond n_images names an empty image.  For r < min(nA, len) let j = d_match[lo + r]: entry lo + r is a
+ *               LINK between pool rows firstA + r and firstB + j iff 0 <= j < nB; -1, any other negative value and any
+ *               j >= nB are no link.  That is the convention of lf_mkd_match_q8_edges_device's d_match_ab, of the mutual
+ *               filter's output and of both verifiers' `verified`: any of them is passed as it is.  Self edges, repeated
+ *               edges, (j, i) beside (i, j) and layouts not made from these ids are ordinary input.
+ *   d_track     int32 [n_rows_total].  Without LF_MKD_TRACKS_ACCUMULATE every entry r is written: the smallest pool row of
+ *               r's connected component under the links.  A row on no link, or of no image, is its own track.  The label is a
+ *               property of the component alone: it does not depend on the order of the edges, on n_edges beyond the link
+ *               set, on the run or on the device's CU count.
+ *   LF_MKD_TRACKS_ACCUMULATE   d_track is not initialised: it is read as the forest an earlier call left and the new links
+ *               are added to it.  An entry p at index r with p < 0 || p > r is read as r, so parent <= index holds whatever
+ *               the array holds, every walk ends, and a root is the minimum of its tree.  Links given in several calls, in any
+ *               split and order, yield == the labels of one call with all of them: this is how a second match array (the
+ *               guided matches beside the verified ones) or a later batch of edges is added.
+ *   d_track_len optional, uint32 [n_rows_total]: at a label t the number of rows r with d_track[r] == t, 0 everywhere else.
+ *   d_track_dup optional, uint32 [n_rows_total]: at a label t the sum over images m of max(c(m, t) - 1, 0), c(m, t) = the rows
+ *               of image m (its range read as above) with label t; 0 everywhere else.  dup == 0: at most one keypoint per
+ *               image, a consistent track.  Both statistics describe the whole forest after this call, accumulated links
+ *               included.  The grid of this statistic is the slot map of d_image_offsets (floor(n_rows_total /
+ *               LF_MKD_TRACKS_DUP_TILE) + n_images workgroups of LF_MKD_TRACKS_DUP_TILE rows), which serves every image when
+ *               the offsets, read against the total, do not decrease -- an inverted range between two ordered neighbours
+ *               included; its cost is quadratic in ONE image's row count (a row is compared with the labels of its image's rows
+ *               in front of it), which is nothing at the 500 .. 8000 rows an image has here.  A row whose track has length 1
+ *               skips that scan when d_track_len is given; without it every row scans (no scratch to keep the lengths in).
+ * How: a lock-free union-find whose forest lives in d_track itself; a link hangs the larger of two roots under the smaller
+ * with one compare-and-swap, so a root is the minimum of its tree (csrc/mkd_tracks.hip).  No workgroup waits for another.
+ * Integer atomics only: exact and deterministic.
+ * Launches: init (not with the flag), link (floor(ea_capacity / 256) + n_edges workgroups, only with n_edges > 0), flatten;
+ * with a statistic a zeroing launch, one for d_track_len and one for d_track_dup -- a fixed number, sized by the host from
+ * n_rows_total, ea_capacity, n_edges and n_images only; no device array is ever read by the host.  No scratch, no allocation,
+ * no host synchronisation, asynchronous on `stream` (NULL: the handle's own): capturable in a hipGraph.  n_edges == 0 still
+ * initialises, labels (every row its own track) and writes the statistics; n_rows_total == 0 is LF_MKD_OK and writes
+ * nothing.  Whatever the arrays hold, nothing at or beyond n_rows_total or ea_capacity is read or written.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "build_tracks_device: " and is
+ * reachable through lf_mkd_last_error(NULL) when h is NULL): a null handle; null d_image_offsets or d_track; with
+ * n_edges > 0 a null edge, layout or match array; an offset array not 8-byte or any other array not 4-byte aligned; unknown
+ * flag bits; n_rows_total or ea_capacity above 2^31 - 1; a grid above 2^31 - 1 workgroups (d_track_dup's only when it is
+ * given). */
+int lf_mkd_build_tracks_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                               const uint32_t *d_edge_a, const uint32_t *d_edge_b, const uint64_t *d_edge_offsets_a,
+                               uint64_t ea_capacity, uint32_t n_edges, const int32_t *d_match, uint32_t flags,
+                               int32_t *d_track, uint32_t *d_track_len, uint32_t *d_track_dup, void *stream);
+#define LF_MKD_TRACKS_ACCUMULATE 1u /* flags: d_track holds an earlier call's forest; add the links to it */
+#define LF_MKD_TRACKS_DUP_TILE (256) /* rows one workgroup of d_track_dup's launch owns (a build-time constant) */
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

@@ -2261,6 +2261,39 @@ int lf_mkd_match_q8_edges_device(lf_mkd *h, const uint8_t *d_a, const uint64_t *
     return LF_MKD_OK;
 }
 
+// Feature tracks over an edge list's matches (csrc/mkd_tracks.hip).  The grids are sized here, from the arguments alone.
+int lf_mkd_build_tracks_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                               const uint32_t *d_edge_a, const uint32_t *d_edge_b, const uint64_t *d_edge_offsets_a,
+                               uint64_t ea_capacity, uint32_t n_edges, const int32_t *d_match, uint32_t flags,
+                               int32_t *d_track, uint32_t *d_track_len, uint32_t *d_track_dup, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (!d_image_offsets || !d_track) msg = "null pointer";
+    else if (n_edges && (!d_edge_a || !d_edge_b)) msg = "null edge array";
+    else if (n_edges && !d_edge_offsets_a) msg = "null layout array";
+    else if (n_edges && !d_match) msg = "null match array";
+    else if ((at(d_image_offsets) | at(d_edge_offsets_a)) & 7) msg = "the offset arrays must be 8-byte aligned";
+    else if ((at(d_edge_a) | at(d_edge_b) | at(d_match) | at(d_track) | at(d_track_len) | at(d_track_dup)) & 3)
+        msg = "the edge, match, track and statistics arrays must be 4-byte aligned";
+    else if (flags & ~LF_MKD_TRACKS_ACCUMULATE) msg = "unknown flag bits";
+    else if (n_rows_total > kEdgeMax || ea_capacity > kEdgeMax) msg = "a total or a capacity above 2^31 - 1 rows";
+    else if (ea_capacity / build_tracks_link_entries() + n_edges > kEdgeMax)
+        msg = "too many entries and edges for one call (the link grid needs floor(ea_capacity / 256) + n_edges workgroups, at "
+              "most 2^31 - 1)";
+    else if (d_track_dup && n_rows_total / build_tracks_dup_tile() + n_images > kEdgeMax)
+        msg = "too many rows and images for one call (d_track_dup's grid needs floor(n_rows_total / LF_MKD_TRACKS_DUP_TILE) + "
+              "n_images workgroups, at most 2^31 - 1)";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "build_tracks_device", msg);
+    if (n_rows_total == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_build_tracks(d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges,
+                        d_match, (flags & LF_MKD_TRACKS_ACCUMULATE) != 0, d_track, d_track_len, d_track_dup,
+                        stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
 // Guided matching over 8-bit rows: the two calls' refusals together, the q8 pairs call's grid.
 int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
                                         uint64_t na_total, const uint8_t *d_b, const lf_mkd_keypoint *d_kps_b,

@@ -269,6 +269,17 @@ void launch_match_q8_edges(const unsigned char *a, const uint64_t *image_off_a, 
                            const unsigned *edge_a, const unsigned *edge_b, const uint64_t *edge_off_a, uint64_t ea_capacity,
                            const uint64_t *edge_off_b, uint64_t eb_capacity, unsigned n_edges, float ratio, bool mutual,
                            int *match_ab, int *match_ba, int *best, int *second, hipStream_t stream);
+// feature tracks (csrc/mkd_tracks.hip, lf_mkd_build_tracks_device): track [total] = the smallest row of every row's connected
+// component under the links match (in edge_off's layout, against capacity) holds; accumulate: track is the forest an earlier
+// call left and is not initialised.  len / dup (nullable) [total]: per label the rows of the track and its conflicting rows.
+// Launches: init (not under accumulate), link over capacity / build_tracks_link_entries() + n_edges workgroups (only with
+// n_edges > 0), flatten; with a statistic: zero, len (if given), dup over total / build_tracks_dup_tile() + n_images
+// workgroups (if given and n_images > 0).  total == 0: nothing.  No scratch.
+unsigned build_tracks_link_entries();
+unsigned build_tracks_dup_tile();
+void launch_build_tracks(const uint64_t *image_off, unsigned n_images, uint64_t total, const unsigned *edge_a,
+                         const unsigned *edge_b, const uint64_t *edge_off, uint64_t capacity, unsigned n_edges, const int *match,
+                         bool accumulate, int *track, unsigned *len, unsigned *dup, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K] [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -16,8 +16,12 @@ descriptor row is copied for it.
   the keypoints brought into the edge layouts        LocalFeatures.gather_edge_rows (20-byte rows: the only rows copied)
   RANSAC homography (3 px) per edge, or with         LocalFeatures.verify_homography_batch / verify_fundamental_batch, on the
   --fundamental epipolar geometry (1.5 px)           edge layouts as they are
+  with --tracks the tracks of the verified matches:  LocalFeatures.build_tracks (lf_mkd_build_tracks_device): per keypoint the
+  the keypoints the edges tie together               track it belongs to, per track its length and its conflicting keypoints
 
-and prints one line per edge, ranked by the matches the geometry keeps.  Nothing is read back before those counts: the
+and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
+or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
+of the keypoints that sit in a consistent track.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -62,11 +66,15 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
     return torch.arange(n, dtype=torch.int32, device=top.device).repeat_interleave(k), top.reshape(-1).int()
 
 
-def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None):
+def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all" or "retrieve" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
-    [E,3,3] and stats [E,4] as the verifier returns them; per_edge [E,3]: ratio-test matches a -> b, mutual, verified."""
+    [E,3,3] and stats [E,4] as the verifier returns them; per_edge [E,3]: ratio-test matches a -> b, mutual, verified.  With
+    `tracks` also track [m] (per keypoint the smallest keypoint of its track under the verified matches), track_len and
+    track_dup [m] (at a track's label its keypoints and its conflicting keypoints), and track_counts [6] int64: tracks of
+    length >= 2, the consistent ones among them, tracks of length >= 3, the consistent ones, the longest track, the keypoints
+    in a consistent track of length >= 2; without, those four are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -104,17 +112,25 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         count = lambda mask: torch.bincount(edge_of[mask], minlength=n_edges + 1)[:n_edges]
         raw = (best != -2 ** 31) & ((ratio <= 0) | (best.float() * ratio > second.float()))   # (both conversions are exact)
         per_edge = torch.stack([count(raw), count(m_ab >= 0), count(ver >= 0)], dim=1)
+        track = track_len = track_dup = track_counts = None
+        if tracks:
+            track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver, capacity=cap_a, n_rows=m)
+            two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
+            track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
+                                        (track_len * (two & ok)).sum()])
     return dict(edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
-                stats=stats, per_edge=per_edge)
+                stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts)
 
 
 def main():
     args = sys.argv[1:]
-    mode, arg, fundamental, paths = "window", 2, False, []
+    mode, arg, fundamental, tracks, paths = "window", 2, False, False, []
     while args:
         a = args.pop(0)
         if a == "--fundamental":
             fundamental = True
+        elif a == "--tracks":
+            tracks = True
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -125,20 +141,26 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (mode == "retrieve" and arg > len(paths) - 1):
-        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K below the "
+        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K below "
+              "the "
               "number of images)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental)
+    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
     for e in sorted(range(len(ea)), key=lambda e: (-per_edge[e][2], e)):
         raw, mutual, inl = per_edge[e]
         print(f"Edge {ea[e] + 1} -> {eb[e] + 1}: {raw} matches, {mutual} mutual, {inl} agree with {what}")
+    if tracks:
+        n2, c2, n3, c3, longest, inside = out["track_counts"].cpu().tolist()
+        print(f"Tracks: {n2} of length >= 2 ({c2} consistent), {n3} of length >= 3 ({c3} consistent)")
+        print(f"Longest track: {longest} keypoints; {100.0 * inside / max(o[-1], 1):.1f} % of the keypoints sit in a consistent track "
+              "of length >= 2")
     return 0
 
 

@@ -14,14 +14,14 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, VERIFY_NO_REFINE, Comm,
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, VERIFY_NO_REFINE, Comm,
                    MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
-           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan"]
+           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE"]
 
 
 class Keypoint:
@@ -562,6 +562,57 @@ class LocalFeatures:
                                                       MATCH_MUTUAL if mutual else 0, best.data_ptr(), second.data_ptr(),
                                                       s.cuda_stream)
         return m_ab, m_ba, best, second, la, lb
+
+    def build_tracks(self, image_offsets, edge_a, edge_b, layout_a, match, capacity=None, into=None, stats=True, n_rows=None,
+                     stream=None):
+        """Feature tracks of a matched collection (lf_mkd_build_tracks_device): the connected components of the links a match
+        array holds between the rows of one pool.  image_offsets [n_images + 1], edge_a / edge_b [n_edges] and layout_a
+        [n_edges + 1] are what match_q8_edges took and returned; match [>= capacity] int32 lives in the a side's edge layout
+        -- match_q8_edges' match_ab, the mutual filter's output or a verifier's `verified`, as it is (an entry outside
+        0 .. nB - 1 is no link).  capacity: the entries of `match` the layout may use (None: all of them).
+        Returns device tensors (track, length, dup): track [n_rows] int32, the smallest pool row of every row's component (a
+        row on no link is its own track); length / dup [n_rows] int32, at a label the track's rows and its conflicting rows --
+        the rows beyond the first that one image has in it, so dup == 0 is a consistent track -- and 0 elsewhere; both None
+        with stats=False.  into: an earlier call's `track`, to which the links are ADDED in place (LF_MKD_TRACKS_ACCUMULATE) and
+        which is returned; links given in several calls yield the labels of one call with all of them.  n_rows: the pool's
+        rows (None: into's length, else the last image offset read back, which WAITS for the stream).  Otherwise nothing is
+        read back: asynchronous on `stream` (default: torch's current stream on the handle's device), capturable."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            io = image_offsets.to(dev, torch.int64).reshape(-1).contiguous()
+            ea, eb = self._words(edge_a, dev), self._words(edge_b, dev)
+            la = layout_a.to(dev, torch.int64).reshape(-1).contiguous()
+            n_edges = ea.numel()
+            if eb.numel() != n_edges or la.numel() != n_edges + 1:
+                raise RuntimeError("build_tracks: edge_a and edge_b need one id per edge each, layout_a n_edges + 1 entries")
+            if io.numel() < 1:
+                raise RuntimeError("build_tracks: image_offsets needs n_images + 1 entries")
+            if not (hasattr(match, "is_cuda") and match.is_cuda and match.dtype == torch.int32 and match.dim() == 1
+                    and match.is_contiguous()):
+                raise RuntimeError("build_tracks: match must be a contiguous int32 device tensor in the a side's edge layout")
+            cap = match.numel() if capacity is None else int(capacity)
+            if cap > match.numel():
+                raise RuntimeError("build_tracks: capacity is larger than match")
+            if into is not None:
+                if not (into.is_cuda and into.dtype == torch.int32 and into.dim() == 1 and into.is_contiguous()):
+                    raise RuntimeError("build_tracks: into must be a contiguous int32 device tensor (an earlier call's track)")
+                if n_rows is not None and int(n_rows) != into.numel():
+                    raise RuntimeError("build_tracks: into needs n_rows entries")
+                track, n = into, into.numel()
+            else:
+                n = int(io[-1].item()) if n_rows is None else int(n_rows)             # (.item() waits)
+                track = torch.empty((n,), dtype=torch.int32, device=dev)
+            length = torch.empty((n,), dtype=torch.int32, device=dev) if stats else None
+            dup = torch.empty((n,), dtype=torch.int32, device=dev) if stats else None
+            if n:
+                with self._lock:
+                    self._inner.build_tracks_device(io.data_ptr(), io.numel() - 1, n, ea.data_ptr(), eb.data_ptr(), la.data_ptr(),
+                                                    cap, n_edges, match.data_ptr(), track.data_ptr(),
+                                                    length.data_ptr() if stats else None, dup.data_ptr() if stats else None,
+                                                    TRACKS_ACCUMULATE if into is not None else 0, s.cuda_stream)
+        return track, length, dup
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

@@ -43,9 +43,12 @@ SYMBOLS = (
     "lf_mkd_knn_q8", "lf_mkd_knn_q8_device", "lf_mkd_knn_q8_plan",
     "lf_mkd_match_q8_grouped", "lf_mkd_match_q8_grouped_device", "lf_mkd_match_q8_grouped_plan", "lf_mkd_vote_groups_device",
     "lf_mkd_edge_layout_device", "lf_mkd_gather_edge_rows_device", "lf_mkd_match_q8_edges_device",
+    "lf_mkd_build_tracks_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
+TRACKS_ACCUMULATE = 1    # LF_MKD_TRACKS_ACCUMULATE: lf_mkd_build_tracks_device adds its links to the forest d_track holds
+TRACKS_DUP_TILE = 256    # LF_MKD_TRACKS_DUP_TILE: rows one workgroup of its d_track_dup launch owns
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -149,6 +152,7 @@ def load_library():
     L.lf_mkd_gather_edge_rows_device.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp, u64, u32, vp, vp]
     L.lf_mkd_match_q8_edges_device.argtypes = [vp, vp, vp, u32, u64, vp, vp, u32, u64, vp, vp, vp, u64, vp, u64, u32,
                                                ctypes.c_float, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_build_tracks_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, u32, vp, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -685,6 +689,15 @@ class MkdHandle:
             self._h, d_a, d_image_offsets_a, n_images_a, na_total, d_b, d_image_offsets_b, n_images_b, nb_total, d_edge_a,
             d_edge_b, d_edge_offsets_a, ea_capacity, d_edge_offsets_b, eb_capacity, n_edges, ratio, flags, d_match_ab, d_match_ba,
             d_best, d_second, s), "lf_mkd_match_q8_edges_device")
+
+    def build_tracks_device(self, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity,
+                            n_edges, d_match, d_track, d_track_len=None, d_track_dup=None, flags=0, stream=None):
+        """lf_mkd_build_tracks_device: d_track [n_rows_total] int32 = the smallest pool row of every row's connected component
+        under the links d_match holds in the a side's edge layout; d_track_len / d_track_dup [n_rows_total] uint32, per label
+        the track's rows and its conflicting rows (device pointers; see include/lf_mkd.h).  flags: TRACKS_ACCUMULATE."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_build_tracks_device(
+            self._h, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match,
+            flags, d_track, d_track_len, d_track_dup, s), "lf_mkd_build_tracks_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
