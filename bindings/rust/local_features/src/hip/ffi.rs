@@ -257,6 +257,19 @@ extern "C" {
                                       d_edge_a: *const u32, d_edge_b: *const u32, d_edge_offsets_a: *const u64,
                                       ea_capacity: u64, n_edges: u32, d_match: *const i32, flags: u32, d_track: *mut i32,
                                       d_track_len: *mut u32, d_track_dup: *mut u32, stream: *mut c_void) -> c_int;
+    // track tables: the CSR table of the tracks lf_mkd_build_tracks_device labelled (d_track_offsets [track_capacity + 1],
+    // d_obs_row / d_obs_image [obs_capacity], d_row_track [n_rows_total], d_counts [4] = {T, O, selected, wanted observations});
+    // flags: LF_MKD_TRACK_TABLE_CONSISTENT; the plan is host only; the gather copies src row d_obs_row[k] to dst row k
+    pub fn lf_mkd_track_table_plan(n_rows_total: u64, min_len: u32, key_bits: *mut u32, passes: *mut u32, block_rows: *mut u32,
+                                   scratch_bytes: *mut u64) -> c_int;
+    pub fn lf_mkd_track_table_device(h: *mut lf_mkd, d_image_offsets: *const u64, n_images: u32, n_rows_total: u64,
+                                     d_track: *const i32, d_track_len: *const u32, d_track_dup: *const u32, min_len: u32,
+                                     flags: u32, track_capacity: u64, obs_capacity: u64, d_track_offsets: *mut u64,
+                                     d_obs_row: *mut i32, d_obs_image: *mut u32, d_row_track: *mut i32, d_counts: *mut u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_gather_track_rows_device(h: *mut lf_mkd, d_src: *const c_void, row_bytes: u32, n_rows_total: u64,
+                                           d_obs_row: *const i32, d_counts: *const u32, obs_capacity: u64, d_dst: *mut c_void,
+                                           stream: *mut c_void) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

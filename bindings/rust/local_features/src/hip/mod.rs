@@ -80,6 +80,10 @@ pub const MATCH_MUTUAL: u32 = 1;
 pub const GUIDE_HOMOGRAPHY: u32 = 0;
 pub const GUIDE_FUNDAMENTAL: u32 = 1;
 
+/// `flags` of `lf_mkd_track_table_device` (`include/lf_mkd.h`, `LF_MKD_TRACK_TABLE_CONSISTENT`): only tracks without
+/// conflicting rows (`dup == 0`) enter the table.
+pub const TRACK_TABLE_CONSISTENT: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,
@@ -484,6 +488,43 @@ impl LocalFeaturesHip {
             }
         }
         Ok((track, len, dup))
+    }
+
+    /// The track table of `build_tracks`' result (`lf_mkd_track_table_device`): the tracks of at least `min_len` rows -- with
+    /// `consistent` only those without conflicting rows -- in the order of their smallest row, as a CSR table.  Returns
+    /// (offsets, rows, images): track i's observations are `rows[offsets[i] .. offsets[i + 1]]`, ascending pool rows, and
+    /// `images` holds the image of each (`u32::MAX`: a row of no image).
+    pub fn track_table(&mut self, image_offsets: &[u64], track: &[i32], len: &[u32], dup: &[u32], min_len: u32, consistent: bool)
+        -> Result<(Vec<u64>, Vec<i32>, Vec<u32>), Error> {
+        let n = track.len();
+        if image_offsets.is_empty() || len.len() != n || dup.len() != n || min_len == 0 {
+            return Err(Error::BadArgument("track_table: image_offsets needs n_images + 1 entries, len and dup one entry per row, min_len >= 1".into()));
+        }
+        if n == 0 { return Ok((vec![0], Vec::new(), Vec::new())); }
+        let track_cap = n / min_len as usize;
+        let mut counts = [0u32; 4];
+        let (mut offsets, mut rows, mut images) = (vec![0u64; track_cap + 1], vec![0i32; n], vec![0u32; n]);
+        // SAFETY: device buffers sized as declared; n and the two capacities bound what is read and written
+        unsafe {
+            let d_io = DeviceBuffer::from_slice(image_offsets)?;
+            let (d_track, d_len, d_dup) = (DeviceBuffer::from_slice(track)?, DeviceBuffer::from_slice(len)?, DeviceBuffer::from_slice(dup)?);
+            let d_off = DeviceBuffer::<u64>::new(track_cap + 1)?;
+            let (d_rows, d_images) = (DeviceBuffer::<i32>::new(n)?, DeviceBuffer::<u32>::new(n)?);
+            let d_counts = DeviceBuffer::<u32>::new(4)?;
+            check(self.h, ffi::lf_mkd_track_table_device(
+                self.h, d_io.as_ptr(), (image_offsets.len() - 1) as u32, n as u64, d_track.as_ptr(), d_len.as_ptr(), d_dup.as_ptr(),
+                min_len, if consistent { TRACK_TABLE_CONSISTENT } else { 0 }, track_cap as u64, n as u64, d_off.as_mut_ptr(),
+                d_rows.as_mut_ptr(), d_images.as_mut_ptr(), std::ptr::null_mut(), d_counts.as_mut_ptr(), std::ptr::null_mut()))?;
+            check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+            d_counts.download(&mut counts)?;
+            d_off.download(&mut offsets)?;
+            d_rows.download(&mut rows)?;
+            d_images.download(&mut images)?;
+        }
+        offsets.truncate(counts[0] as usize + 1);
+        rows.truncate(counts[1] as usize);
+        images.truncate(counts[1] as usize);
+        Ok((offsets, rows, images))
     }
 
     /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates

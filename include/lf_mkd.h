@@ -828,6 +828,64 @@ int lf_mkd_build_tracks_device(lf_mkd *h, const uint64_t *d_image_offsets, uint3
                                int32_t *d_track, uint32_t *d_track_len, uint32_t *d_track_dup, void *stream);
 #define LF_MKD_TRACKS_ACCUMULATE 1u /* flags: d_track holds an earlier call's forest; add the links to it */
 #define LF_MKD_TRACKS_DUP_TILE (256) /* rows one workgroup of d_track_dup's launch owns (a build-time constant) */
+/* lf_mkd_track_table_device turns the arrays lf_mkd_build_tracks_device leaves into a TRACK TABLE: per track the list of its
+ * observations, as a CSR table, short and inconsistent tracks filtered out -- the form structure from motion, triangulation,
+ * bundle adjustment and loop closure read.  N = n_rows_total; d_track, d_track_len, d_track_dup are [N] as that call wrote
+ * them.
+ *   reading     a label t is a ROOT iff 0 <= t < N and d_track[t] == t; a root is SELECTED iff d_track_len[t] >= min_len and,
+ *               under LF_MKD_TRACK_TABLE_CONSISTENT, d_track_dup[t] == 0; row r is a MEMBER of selected t iff d_track[r] == t;
+ *               a d_track[r] outside [0, N) makes r a member of nothing.
+ *   order       the selected labels in ascending order are t_0 < t_1 < ... (the order of each track's smallest row); W_i is
+ *               the 64-bit sum of d_track_len[t_j] over j < i.  Track i is KEPT iff i < track_capacity and
+ *               W_{i+1} <= obs_capacity.  W does not decrease, so the kept tracks are a prefix 0 .. T - 1 and a track is never
+ *               cut in the middle.  track_capacity >= floor(N / min_len) and obs_capacity >= N always suffice.
+ *   d_counts    uint32 [4] = {T, O = W_T, the number of selected tracks, min(W of all selected tracks, 2^32 - 1)}; elements
+ *               2 and 3 tell a caller that a capacity cut something.
+ *   d_track_offsets   uint64, exactly track_capacity + 1 entries written: W_i for i <= T, O for T < i <= track_capacity -- a
+ *               layout of track_capacity tracks whose tail is empty.
+ *   d_obs_row   int32 [obs_capacity]: d_obs_row[W_i + k] = the k-th smallest member row of track i; entries at or beyond O
+ *               are untouched.  May be NULL iff obs_capacity == 0.
+ *   d_obs_image optional, uint32 [obs_capacity]: at the same positions the image m whose range of d_image_offsets, read
+ *               against N exactly as lf_mkd_build_tracks_device reads it, holds the row, or 0xFFFFFFFF; specified for
+ *               offsets that do not decrease.  d_image_offsets may be NULL iff d_obs_image is.
+ *   d_row_track optional, int32 [N], every entry written: the table index of the row's track, or -1.
+ * For arrays as lf_mkd_build_tracks_device leaves them a track's member count equals its d_track_len and all of the above
+ * holds with ==.  For other contents the outputs other than d_counts are unspecified; even then the call ends, d_counts[0] <=
+ * track_capacity, and nothing at or beyond N, track_capacity + 1 or obs_capacity is read or written.  N == 0 writes
+ * d_counts = 0 and the offsets 0 and is LF_MKD_OK (the [N] arrays may then be NULL).
+ * How (csrc/mkd_track_table.hip): a select-and-scan over the rows (two exact integer prefix sums), one key per row (the table
+ * index of its label; rows of no kept track get a key above every index), and a stable LSD radix sort of (key, row) over the
+ * bits of floor(N / min_len) only.  No atomic decides a position, no workgroup waits for another, integer arithmetic only:
+ * the table is exact and does not depend on the run or on the CU count, and the cost does not depend on how the rows are
+ * distributed over the tracks.
+ * Launches: 4, then 3 per radix pass and 1 (none of these when lf_mkd_track_table_plan's passes or obs_capacity is 0); 1 for
+ * N == 0 -- a fixed number, sized by the host from N, min_len and the capacities.  Asynchronous on `stream` (NULL: the
+ * handle's own), no host synchronisation; no allocation once the handle's scratch has grown to the largest plan seen
+ * (lf_mkd_track_table_plan's scratch_bytes), so a warmed-up call is capturable in a hipGraph.  The scratch belongs to the
+ * handle: calls of one handle are stream-ordered.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "track_table_device: " and is reachable
+ * through lf_mkd_last_error(NULL) when h is NULL): a null handle or a null required array; min_len == 0;
+ * LF_MKD_TRACK_TABLE_CONSISTENT without d_track_dup; d_obs_image without d_image_offsets; unknown flag bits; an offsets array
+ * not 8-byte or any other array not 4-byte aligned; N or a capacity above 2^31 - 1. */
+/* host only, no device, no handle: key_bits = the bits of floor(n_rows_total / min_len) (the bound on T the host knows), the
+ * radix passes that cover them, the rows one workgroup sorts, and the scratch the device call grows the handle to (0 for
+ * n_rows_total == 0); any output may be NULL.  LF_MKD_ERR_BAD_ARG ("track_table_plan: "): min_len == 0, n_rows_total above
+ * 2^31 - 1. */
+int lf_mkd_track_table_plan(uint64_t n_rows_total, uint32_t min_len, uint32_t *key_bits, uint32_t *passes, uint32_t *block_rows,
+                            uint64_t *scratch_bytes);
+int lf_mkd_track_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                              const int32_t *d_track, const uint32_t *d_track_len, const uint32_t *d_track_dup, uint32_t min_len,
+                              uint32_t flags, uint64_t track_capacity, uint64_t obs_capacity, uint64_t *d_track_offsets,
+                              int32_t *d_obs_row, uint32_t *d_obs_image, int32_t *d_row_track, uint32_t *d_counts, void *stream);
+#define LF_MKD_TRACK_TABLE_CONSISTENT (1u) /* flags: only tracks with d_track_dup[t] == 0 */
+/* dst row k = src row d_obs_row[k] for k < min(d_counts[1], obs_capacity), rows of row_bytes bytes (keypoints: 20, q8 rows:
+ * 128); an index outside [0, n_rows_total) writes a zero row, rows beyond the count are untouched.  One launch, its grid sized
+ * from obs_capacity; the count is read on the device.  Asynchronous, no scratch, capturable.  LF_MKD_ERR_BAD_ARG
+ * ("gather_track_rows_device: "): a null handle or array, row_bytes not a multiple of 4 within 4 .. 512, an array not 4-byte
+ * aligned, n_rows_total or obs_capacity above 2^31 - 1. */
+int lf_mkd_gather_track_rows_device(lf_mkd *h, const void *d_src, uint32_t row_bytes, uint64_t n_rows_total,
+                                    const int32_t *d_obs_row, const uint32_t *d_counts, uint64_t obs_capacity, void *d_dst,
+                                    void *stream);
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

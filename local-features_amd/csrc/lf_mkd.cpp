@@ -238,6 +238,8 @@ struct lf_mkd {
     // RANSAC verification scratch (lf_mkd_verify_homography*, lf_mkd_verify_fundamental*, which share it): per-pair
     // normalisation, per-candidate partial counts, and the host form's staging.  No recording names them; they grow only when a call asks for more, so the device form's launches
     // can be captured once warmed up.  Calls of one handle are stream-ordered (lf_mkd.h).
+    // lf_mkd_track_table_device's scratch (track_table_plan's scratch_bytes); like the verifiers' it is named by no recording
+    HipArray<unsigned char> d_track_table;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;
@@ -2290,6 +2292,71 @@ int lf_mkd_build_tracks_device(lf_mkd *h, const uint64_t *d_image_offsets, uint3
     launch_build_tracks(d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges,
                         d_match, (flags & LF_MKD_TRACKS_ACCUMULATE) != 0, d_track, d_track_len, d_track_dup,
                         stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// Track tables (csrc/mkd_track_table.hip).  Every refusal comes before the handle is looked at.
+int lf_mkd_track_table_plan(uint64_t n_rows_total, uint32_t min_len, uint32_t *key_bits, uint32_t *passes, uint32_t *block_rows,
+                            uint64_t *scratch_bytes) {
+    if (min_len == 0) return q8_refuse(nullptr, "track_table_plan", "min_len must be at least 1");
+    if (n_rows_total > kEdgeMax) return q8_refuse(nullptr, "track_table_plan", "more than 2^31 - 1 rows in the pool");
+    const TrackTablePlan p = track_table_plan(n_rows_total, min_len);
+    if (key_bits) *key_bits = p.key_bits;
+    if (passes) *passes = p.passes;
+    if (block_rows) *block_rows = p.block_rows;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_track_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                              const int32_t *d_track, const uint32_t *d_track_len, const uint32_t *d_track_dup, uint32_t min_len,
+                              uint32_t flags, uint64_t track_capacity, uint64_t obs_capacity, uint64_t *d_track_offsets,
+                              int32_t *d_obs_row, uint32_t *d_obs_image, int32_t *d_row_track, uint32_t *d_counts, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const bool consistent = flags & LF_MKD_TRACK_TABLE_CONSISTENT;
+    const char *msg = nullptr;
+    if (!d_track_offsets || !d_counts) msg = "null pointer";
+    else if (n_rows_total && (!d_track || !d_track_len)) msg = "null track or length array";
+    else if (obs_capacity && !d_obs_row) msg = "null d_obs_row";
+    else if (d_obs_image && !d_image_offsets) msg = "d_obs_image needs d_image_offsets";
+    else if (min_len == 0) msg = "min_len must be at least 1";
+    else if (flags & ~LF_MKD_TRACK_TABLE_CONSISTENT) msg = "unknown flag bits";
+    else if (consistent && n_rows_total && !d_track_dup) msg = "LF_MKD_TRACK_TABLE_CONSISTENT needs d_track_dup";
+    else if ((at(d_image_offsets) | at(d_track_offsets)) & 7) msg = "the offset arrays must be 8-byte aligned";
+    else if ((at(d_track) | at(d_track_len) | at(d_track_dup) | at(d_obs_row) | at(d_obs_image) | at(d_row_track) | at(d_counts)) & 3)
+        msg = "the track, statistics, observation and count arrays must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || track_capacity > kEdgeMax || obs_capacity > kEdgeMax)
+        msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "track_table_device", msg);
+    LF_ENTER(h);
+    const TrackTablePlan plan = track_table_plan(n_rows_total, min_len);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_track_table, plan.scratch_bytes)) return rc;
+    launch_track_table(plan, plan.scratch_bytes ? h->d_track_table.get() : nullptr, d_image_offsets, n_images, n_rows_total,
+                       d_track, d_track_len, consistent ? d_track_dup : nullptr, min_len, track_capacity, obs_capacity,
+                       d_track_offsets, d_obs_row, d_obs_image, d_row_track, d_counts,
+                       stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+int lf_mkd_gather_track_rows_device(lf_mkd *h, const void *d_src, uint32_t row_bytes, uint64_t n_rows_total,
+                                    const int32_t *d_obs_row, const uint32_t *d_counts, uint64_t obs_capacity, void *d_dst,
+                                    void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (!d_counts || (n_rows_total && !d_src) || (obs_capacity && (!d_obs_row || !d_dst))) msg = "null pointer";
+    else if (row_bytes < 4 || row_bytes > 512 || (row_bytes & 3)) msg = "row_bytes must be a multiple of 4 in [4, 512]";
+    else if ((at(d_src) | at(d_dst) | at(d_obs_row) | at(d_counts)) & 3) msg = "every array must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || obs_capacity > kEdgeMax) msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "gather_track_rows_device", msg);
+    if (obs_capacity == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_gather_track_rows(d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst,
+                             stream ? static_cast<hipStream_t>(stream) : h->stream);
     LF_HIP(h, hipGetLastError());
     return LF_MKD_OK;
 }

@@ -280,6 +280,23 @@ unsigned build_tracks_dup_tile();
 void launch_build_tracks(const uint64_t *image_off, unsigned n_images, uint64_t total, const unsigned *edge_a,
                          const unsigned *edge_b, const uint64_t *edge_off, uint64_t capacity, unsigned n_edges, const int *match,
                          bool accumulate, int *track, unsigned *len, unsigned *dup, hipStream_t stream);
+// track tables (csrc/mkd_track_table.hip, lf_mkd_track_table_device / lf_mkd_gather_track_rows_device).  The plan is the one
+// place that knows the digit width and the block size: key_bits = the bits of floor(total / min_len), passes radix passes of
+// blocks of block_rows rows, and the layout of the scratch (byte offsets; blk_len sits at 0).  key_none: the key of a row of no
+// kept track, above every table index.
+// Launches: total == 0: one (zeroes).  Otherwise select, scan_blocks, apply, keys; then, unless passes == 0 or obs_capacity
+// == 0, three per pass (hist, scan_hist, scatter) and finalise.  gather: one, over ceil(obs_capacity / 64) workgroups.
+struct TrackTablePlan {
+    unsigned key_bits, passes, block_rows, key_none;
+    uint64_t n_blocks, off_map, off_keys[2], off_rows[2], off_blk_cnt, off_hist, off_totals, scratch_bytes;
+};
+TrackTablePlan track_table_plan(uint64_t total, unsigned min_len);
+void launch_track_table(const TrackTablePlan &plan, unsigned char *scratch, const uint64_t *image_off, unsigned n_images,
+                        uint64_t total, const int *track, const unsigned *len, const unsigned *dup, unsigned min_len,
+                        uint64_t track_capacity, uint64_t obs_capacity, uint64_t *offsets, int *obs_row, unsigned *obs_image,
+                        int *row_track, unsigned *counts, hipStream_t stream);
+void launch_gather_track_rows(const void *src, unsigned row_bytes, uint64_t total, const int *obs_row, const unsigned *counts,
+                              uint64_t obs_capacity, void *dst, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

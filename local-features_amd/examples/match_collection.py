@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -18,10 +18,13 @@ descriptor row is copied for it.
   --fundamental epipolar geometry (1.5 px)           edge layouts as they are
   with --tracks the tracks of the verified matches:  LocalFeatures.build_tracks (lf_mkd_build_tracks_device): per keypoint the
   the keypoints the edges tie together               track it belongs to, per track its length and its conflicting keypoints
+  with --table (which implies --tracks) the track    LocalFeatures.track_table (lf_mkd_track_table_device): the consistent tracks
+  table, and the keypoints in its order              of two or more keypoints as a CSR table; LocalFeatures.gather_track_rows
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
-of the keypoints that sit in a consistent track.  Nothing is read back before those counts: the
+of the keypoints that sit in a consistent track; with --table also the number of tracks and observations in the table and the
+first three tracks as image:x,y lists.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -66,7 +69,8 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
     return torch.arange(n, dtype=torch.int32, device=top.device).repeat_interleave(k), top.reshape(-1).int()
 
 
-def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False):
+def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
+                     table=False):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all" or "retrieve" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -74,7 +78,10 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     `tracks` also track [m] (per keypoint the smallest keypoint of its track under the verified matches), track_len and
     track_dup [m] (at a track's label its keypoints and its conflicting keypoints), and track_counts [6] int64: tracks of
     length >= 2, the consistent ones among them, tracks of length >= 3, the consistent ones, the longest track, the keypoints
-    in a consistent track of length >= 2; without, those four are None."""
+    in a consistent track of length >= 2; without, those four are None.  With `table` (which implies `tracks`) also the table of
+    the consistent tracks of length >= 2 as LocalFeatures.track_table returns it -- table_offsets [m // 2 + 1], table_rows [m],
+    table_images [m], table_row_track [m], table_counts [4] -- and table_keypoints [m,5], the keypoints in the table's order
+    (LocalFeatures.gather_track_rows); without, those six are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -113,24 +120,33 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         raw = (best != -2 ** 31) & ((ratio <= 0) | (best.float() * ratio > second.float()))   # (both conversions are exact)
         per_edge = torch.stack([count(raw), count(m_ab >= 0), count(ver >= 0)], dim=1)
         track = track_len = track_dup = track_counts = None
-        if tracks:
+        t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
+        if tracks or table:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
             track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
                                         (track_len * (two & ok)).sum()])
+        if table:
+            t_off, t_rows, t_img, t_row_track, t_counts = feats.track_table(track, track_len, track_dup, image_offsets=o, min_len=2,
+                                                                            consistent=True)
+            t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
     return dict(edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
-                stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts)
+                stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
+                table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
+                table_keypoints=t_kps)
 
 
 def main():
     args = sys.argv[1:]
-    mode, arg, fundamental, tracks, paths = "window", 2, False, False, []
+    mode, arg, fundamental, tracks, table, paths = "window", 2, False, False, False, []
     while args:
         a = args.pop(0)
         if a == "--fundamental":
             fundamental = True
         elif a == "--tracks":
             tracks = True
+        elif a == "--table":
+            tracks = table = True
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -141,7 +157,8 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (mode == "retrieve" and arg > len(paths) - 1):
-        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K below "
+        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+              "below "
               "the "
               "number of images)", file=sys.stderr)
         return 1
@@ -149,7 +166,7 @@ def main():
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks)
+    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
@@ -161,6 +178,13 @@ def main():
         print(f"Tracks: {n2} of length >= 2 ({c2} consistent), {n3} of length >= 3 ({c3} consistent)")
         print(f"Longest track: {longest} keypoints; {100.0 * inside / max(o[-1], 1):.1f} % of the keypoints sit in a consistent track "
               "of length >= 2")
+    if table:
+        n_tracks, n_obs = out["table_counts"].cpu().tolist()[:2]
+        print(f"Track table: {n_tracks} tracks, {n_obs} observations (consistent, length >= 2)")
+        first = out["table_offsets"][:min(n_tracks, 3) + 1].cpu().tolist()
+        images, xy = out["table_images"][:first[-1]].cpu().tolist(), out["table_keypoints"][:first[-1], :2].cpu().tolist()
+        for k in range(len(first) - 1):
+            print(f"Track {k + 1}: " + " ".join(f"{images[i] + 1}:{xy[i][0]:.1f},{xy[i][1]:.1f}" for i in range(first[k], first[k + 1])))
     return 0
 
 

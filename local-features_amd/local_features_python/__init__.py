@@ -14,14 +14,14 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
-           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE"]
+           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan"]
 
 
 class Keypoint:
@@ -613,6 +613,83 @@ class LocalFeatures:
                                                     length.data_ptr() if stats else None, dup.data_ptr() if stats else None,
                                                     TRACKS_ACCUMULATE if into is not None else 0, s.cuda_stream)
         return track, length, dup
+
+    def track_table(self, track, length, dup=None, image_offsets=None, min_len=2, consistent=True, track_capacity=None,
+                    obs_capacity=None, stream=None):
+        """The track table of build_tracks' result (lf_mkd_track_table_device): per track the list of its observations, as a
+        CSR table made on the device.  track / length / dup [N] are int32 device tensors as build_tracks returned them.  A
+        track enters iff its length is at least min_len and, with `consistent`, its dup is 0 (dup is then required); the
+        tracks come in the order of their smallest row, a track's rows ascending.
+        Returns device tensors (offsets, rows, images, row_track, counts): offsets [track_capacity + 1] int64 -- track i's
+        observations are rows[offsets[i] : offsets[i + 1]], entries beyond the last track repeat the number of observations;
+        rows [obs_capacity] int32, pool rows (entries beyond the observations are left as allocated); images [obs_capacity]
+        int32, the image of each observation (-1: a row of no image), None without image_offsets; row_track [N] int32, per pool
+        row the table index of its track or -1; counts [4] int32: the tracks and the observations in the table, and the
+        tracks and (saturated at 2^32 - 1, as a bit pattern) the observations wanted -- they differ when a capacity cut the
+        table, which keeps whole tracks only.  The default capacities, N // min_len and N, always suffice.
+        Nothing is read back: asynchronous on `stream` (default: torch's current stream on the handle's device), capturable
+        once a call of this size has been made."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        min_len = int(min_len)
+        if min_len < 1:
+            raise RuntimeError("track_table: min_len must be at least 1")
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous()
+            if not (ok(track) and ok(length) and (dup is None or ok(dup))):
+                raise RuntimeError("track_table: track, length and dup must be contiguous int32 device tensors")
+            n = track.numel()
+            if length.numel() != n or (dup is not None and dup.numel() != n):
+                raise RuntimeError("track_table: length and dup need one entry per row of track")
+            if consistent and dup is None:
+                raise RuntimeError("track_table: consistent=True needs dup")
+            t_cap = n // min_len if track_capacity is None else int(track_capacity)
+            o_cap = n if obs_capacity is None else int(obs_capacity)
+            io = image_offsets.to(dev, torch.int64).reshape(-1).contiguous() if image_offsets is not None else None
+            if io is not None and io.numel() < 1:
+                raise RuntimeError("track_table: image_offsets needs n_images + 1 entries")
+            offsets = torch.empty((t_cap + 1,), dtype=torch.int64, device=dev)
+            rows = torch.empty((o_cap,), dtype=torch.int32, device=dev)
+            images = torch.empty((o_cap,), dtype=torch.int32, device=dev) if io is not None else None
+            row_track = torch.empty((n,), dtype=torch.int32, device=dev)
+            counts = torch.empty((4,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.track_table_device(ptr(io), io.numel() - 1 if io is not None else 0, n, ptr(track), ptr(length),
+                                               ptr(dup), min_len, TRACK_TABLE_CONSISTENT if consistent else 0, t_cap, o_cap,
+                                               offsets.data_ptr(), ptr(rows), ptr(images), ptr(row_track), counts.data_ptr(),
+                                               s.cuda_stream)
+        return offsets, rows, images, row_track, counts
+
+    def gather_track_rows(self, src, rows, counts, out=None, stream=None):
+        """Rows of a pool brought into a track table's order (lf_mkd_gather_track_rows_device): out[k] = src[rows[k]] for
+        k < min(counts[1], len(rows)) -- keypoints [N,5] float32, q8 rows, or any contiguous device tensor [N, ...] whose rows
+        are a multiple of 4 bytes, at most 512.  rows / counts are what track_table returned.  out: a tensor of len(rows) rows to
+        write into instead of a new zero-filled one; rows beyond the count are untouched, an index outside the pool gives a
+        zero row.  One launch, nothing read back."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            x = src.to(dev).contiguous()
+            n = x.shape[0]
+            row_bytes = int(np.prod(x.shape[1:])) * x.element_size()
+            if not (rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous()):
+                raise RuntimeError("gather_track_rows: rows must be a contiguous int32 device tensor (track_table's rows)")
+            if not (counts.is_cuda and counts.dtype == torch.int32 and counts.numel() == 4 and counts.is_contiguous()):
+                raise RuntimeError("gather_track_rows: counts must be track_table's counts")
+            cap = rows.numel()
+            if out is None:
+                out = torch.zeros((cap,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
+            elif not (out.is_cuda and out.is_contiguous() and out.dtype == x.dtype and tuple(out.shape[1:]) == tuple(x.shape[1:])
+                      and out.shape[0] >= cap):
+                raise RuntimeError("gather_track_rows: out must be a contiguous device tensor of src's dtype and row shape with "
+                                   "at least len(rows) rows")
+            with self._lock:
+                self._inner.gather_track_rows_device(x.data_ptr() if n else None, row_bytes, n, rows.data_ptr() if cap else None,
+                                                     counts.data_ptr(), cap, out.data_ptr() if cap else None, s.cuda_stream)
+        return out
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

@@ -44,11 +44,13 @@ SYMBOLS = (
     "lf_mkd_match_q8_grouped", "lf_mkd_match_q8_grouped_device", "lf_mkd_match_q8_grouped_plan", "lf_mkd_vote_groups_device",
     "lf_mkd_edge_layout_device", "lf_mkd_gather_edge_rows_device", "lf_mkd_match_q8_edges_device",
     "lf_mkd_build_tracks_device",
+    "lf_mkd_track_table_plan", "lf_mkd_track_table_device", "lf_mkd_gather_track_rows_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
 TRACKS_ACCUMULATE = 1    # LF_MKD_TRACKS_ACCUMULATE: lf_mkd_build_tracks_device adds its links to the forest d_track holds
 TRACKS_DUP_TILE = 256    # LF_MKD_TRACKS_DUP_TILE: rows one workgroup of its d_track_dup launch owns
+TRACK_TABLE_CONSISTENT = 1   # LF_MKD_TRACK_TABLE_CONSISTENT: lf_mkd_track_table_device takes only tracks with dup == 0
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -153,6 +155,9 @@ def load_library():
     L.lf_mkd_match_q8_edges_device.argtypes = [vp, vp, vp, u32, u64, vp, vp, u32, u64, vp, vp, vp, u64, vp, u64, u32,
                                                ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_build_tracks_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, u32, vp, u32, vp, vp, vp, vp]
+    L.lf_mkd_track_table_plan.argtypes = [u64, u32, vp, vp, vp, vp]
+    L.lf_mkd_track_table_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_gather_track_rows_device.argtypes = [vp, vp, u32, u64, vp, vp, u64, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -244,6 +249,18 @@ def match_q8_pairs_plan(na_total, nb_total, n_pairs, both_directions=False):
     if rc != 0:
         raise RuntimeError(f"lf_mkd_match_q8_pairs_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return r.value, w.value
+
+
+def track_table_plan(n_rows_total, min_len=2):
+    """(key_bits, passes, block_rows, scratch_bytes) of lf_mkd_track_table_device for a pool of n_rows_total rows: the bits
+    of floor(n_rows_total / min_len) -- the bound on the number of tracks the host knows --, the radix passes that sort
+    them, the rows one workgroup sorts and the handle's scratch (lf_mkd_track_table_plan; needs no device)."""
+    k, p, r, b = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_track_table_plan(n_rows_total, min_len, ctypes.byref(k), ctypes.byref(p), ctypes.byref(r), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_track_table_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return k.value, p.value, r.value, b.value
 
 
 class Comm:
@@ -698,6 +715,24 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_build_tracks_device(
             self._h, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match,
             flags, d_track, d_track_len, d_track_dup, s), "lf_mkd_build_tracks_device")
+
+    def track_table_device(self, d_image_offsets, n_images, n_rows_total, d_track, d_track_len, d_track_dup, min_len, flags,
+                           track_capacity, obs_capacity, d_track_offsets, d_obs_row, d_obs_image, d_row_track, d_counts,
+                           stream=None):
+        """lf_mkd_track_table_device: the CSR table of the tracks d_track / d_track_len / d_track_dup [n_rows_total] describe
+        -- d_track_offsets [track_capacity + 1] uint64, d_obs_row int32 and d_obs_image uint32 (nullable) [obs_capacity],
+        d_row_track int32 [n_rows_total] (nullable), d_counts uint32 [4] (device pointers; see include/lf_mkd.h).  flags:
+        TRACK_TABLE_CONSISTENT."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_track_table_device(
+            self._h, d_image_offsets, n_images, n_rows_total, d_track, d_track_len, d_track_dup, min_len, flags, track_capacity,
+            obs_capacity, d_track_offsets, d_obs_row, d_obs_image, d_row_track, d_counts, s), "lf_mkd_track_table_device")
+
+    def gather_track_rows_device(self, d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst, stream=None):
+        """lf_mkd_gather_track_rows_device: d_dst row k = d_src row d_obs_row[k] for k < min(d_counts[1], obs_capacity), rows
+        of row_bytes bytes (a multiple of 4 up to 512); an index outside the pool gives a zero row"""
+        self._device_call(stream, lambda s: self.L.lf_mkd_gather_track_rows_device(
+            self._h, d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst, s),
+            "lf_mkd_gather_track_rows_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
