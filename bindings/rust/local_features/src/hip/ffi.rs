@@ -270,6 +270,17 @@ extern "C" {
     pub fn lf_mkd_gather_track_rows_device(h: *mut lf_mkd, d_src: *const c_void, row_bytes: u32, n_rows_total: u64,
                                            d_obs_row: *const i32, d_counts: *const u32, obs_capacity: u64, d_dst: *mut c_void,
                                            stream: *mut c_void) -> c_int;
+    // link tables: the CSR table of the links d_match holds in the a side's edge layout (d_link_offsets [n_edges + 1],
+    // d_link_a / d_link_b / d_link_edge [link_capacity], d_edge_links [n_edges], d_match_kept like d_match, d_counts [4] =
+    // {kept edges, O, selected edges, wanted links}); flags: LF_MKD_LINK_TABLE_LOCAL; the plan is host only
+    pub fn lf_mkd_link_table_plan(ea_capacity: u64, n_edges: u32, slot_entries: *mut u32, slots: *mut u64,
+                                  scan_fanout: *mut u32, scan_levels: *mut u32, scratch_bytes: *mut u64) -> c_int;
+    pub fn lf_mkd_link_table_device(h: *mut lf_mkd, d_image_offsets: *const u64, n_images: u32, n_rows_total: u64,
+                                    d_edge_a: *const u32, d_edge_b: *const u32, d_edge_offsets_a: *const u64,
+                                    ea_capacity: u64, n_edges: u32, d_match: *const i32, min_links: u32, flags: u32,
+                                    link_capacity: u64, d_link_offsets: *mut u64, d_link_a: *mut i32, d_link_b: *mut i32,
+                                    d_link_edge: *mut u32, d_edge_links: *mut u32, d_match_kept: *mut i32,
+                                    d_counts: *mut u32, stream: *mut c_void) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

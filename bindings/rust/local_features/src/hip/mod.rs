@@ -84,6 +84,10 @@ pub const GUIDE_FUNDAMENTAL: u32 = 1;
 /// conflicting rows (`dup == 0`) enter the table.
 pub const TRACK_TABLE_CONSISTENT: u32 = 1;
 
+/// `flags` of `lf_mkd_link_table_device` (`include/lf_mkd.h`, `LF_MKD_LINK_TABLE_LOCAL`): the table holds rows local to
+/// their images, not pool rows.
+pub const LINK_TABLE_LOCAL: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,
@@ -525,6 +529,66 @@ impl LocalFeaturesHip {
         rows.truncate(counts[1] as usize);
         images.truncate(counts[1] as usize);
         Ok((offsets, rows, images))
+    }
+
+    /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches
+    /// `match_q8_edges` or a verifier returned for `edges` over the pool `image_offsets` describes (`n_rows` rows), edges with
+    /// fewer than `min_links` of them left out.  Returns (offsets, link_a, link_b, edge_links): edge e's correspondences are
+    /// `link_a[offsets[e] .. offsets[e + 1]]` and `link_b[..]`, pool rows -- with `local` rows within their images -- in
+    /// ascending row of a; an edge that is not kept has an empty range; `edge_links[e]` is every edge's own count.
+    pub fn link_table(&mut self, n_rows: usize, image_offsets: &[u64], edges: &[(u32, u32)], matches: &[Vec<(usize, usize)>],
+                      min_links: u32, local: bool) -> Result<(Vec<u64>, Vec<i32>, Vec<i32>, Vec<u32>), Error> {
+        if image_offsets.is_empty() || matches.len() != edges.len() {
+            return Err(Error::BadArgument("link_table: image_offsets needs n_images + 1 entries, matches one list per edge".into()));
+        }
+        let (n_images, n_edges) = (image_offsets.len() - 1, edges.len());
+        if n_edges == 0 { return Ok((vec![0], Vec::new(), Vec::new(), Vec::new())); }
+        let rows = |m: u32| -> usize {
+            let m = m as usize;
+            if m >= n_images { return 0; }
+            let (lo, hi) = ((image_offsets[m] as usize).min(n_rows), (image_offsets[m + 1] as usize).min(n_rows));
+            hi.max(lo) - lo
+        };
+        let (ea, eb): (Vec<u32>, Vec<u32>) = edges.iter().copied().unzip();
+        // the a side's edge layout and the match array in it, as build_tracks makes them
+        let mut layout = vec![0u64; n_edges + 1];
+        for e in 0..n_edges { layout[e + 1] = layout[e] + rows(ea[e]) as u64; }
+        let cap = layout[n_edges] as usize;
+        let mut m = vec![-1i32; cap];
+        for (e, list) in matches.iter().enumerate() {
+            for &(i, j) in list {
+                if i < rows(ea[e]) { m[layout[e] as usize + i] = j as i32; }
+            }
+        }
+        let mut counts = [0u32; 4];
+        let (mut offsets, mut link_a, mut link_b, mut edge_links) = (vec![0u64; n_edges + 1], vec![0i32; cap], vec![0i32; cap], vec![0u32; n_edges]);
+        // SAFETY: device buffers sized as declared; n_rows, cap and n_edges bound what is read and written
+        unsafe {
+            let d_io = DeviceBuffer::from_slice(image_offsets)?;
+            let (d_ea, d_eb) = (DeviceBuffer::from_slice(&ea)?, DeviceBuffer::from_slice(&eb)?);
+            let d_la = DeviceBuffer::from_slice(&layout)?;
+            let d_m = DeviceBuffer::from_slice(&m)?;
+            let d_off = DeviceBuffer::<u64>::new(n_edges + 1)?;
+            let (d_a, d_b) = (DeviceBuffer::<i32>::new(cap.max(1))?, DeviceBuffer::<i32>::new(cap.max(1))?);
+            let d_links = DeviceBuffer::<u32>::new(n_edges)?;
+            let d_counts = DeviceBuffer::<u32>::new(4)?;
+            check(self.h, ffi::lf_mkd_link_table_device(
+                self.h, d_io.as_ptr(), n_images as u32, n_rows as u64, d_ea.as_ptr(), d_eb.as_ptr(), d_la.as_ptr(), cap as u64,
+                n_edges as u32, d_m.as_ptr(), min_links, if local { LINK_TABLE_LOCAL } else { 0 }, cap as u64, d_off.as_mut_ptr(),
+                d_a.as_mut_ptr(), d_b.as_mut_ptr(), std::ptr::null_mut(), d_links.as_mut_ptr(), std::ptr::null_mut(),
+                d_counts.as_mut_ptr(), std::ptr::null_mut()))?;
+            check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+            d_counts.download(&mut counts)?;
+            d_off.download(&mut offsets)?;
+            d_links.download(&mut edge_links)?;
+            if cap > 0 {
+                d_a.download(&mut link_a)?;
+                d_b.download(&mut link_b)?;
+            }
+        }
+        link_a.truncate(counts[1] as usize);
+        link_b.truncate(counts[1] as usize);
+        Ok((offsets, link_a, link_b, edge_links))
     }
 
     /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates

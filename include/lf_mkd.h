@@ -886,6 +886,71 @@ int lf_mkd_track_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32
 int lf_mkd_gather_track_rows_device(lf_mkd *h, const void *d_src, uint32_t row_bytes, uint64_t n_rows_total,
                                     const int32_t *d_obs_row, const uint32_t *d_counts, uint64_t obs_capacity, void *d_dst,
                                     void *stream);
+/* lf_mkd_link_table_device turns an edge list's match array into a LINK TABLE: per edge the compact list of its
+ * correspondences, as a CSR table, with the per-edge counts and a pruned copy of the match array -- the two-view result a pose
+ * solver, a bundle adjuster and a two-view-geometry database read, and the place where an edge the geometry does not support
+ * is dropped before lf_mkd_build_tracks_device takes its links.  There is one pool: both ids of an edge index d_image_offsets.
+ * The inputs are read exactly as lf_mkd_build_tracks_device reads them; its rule, once more:
+ *   links       for edge e let (lo, len) be its range of d_edge_offsets_a read against ea_capacity as a pair is read against a
+ *               total, and (firstA, nA) / (firstB, nB) the rows of images d_edge_a[e] / d_edge_b[e] against n_rows_total; an
+ *               id at or beyond n_images names an empty image.  For r < min(nA, len) let j = d_match[lo + r]: entry lo + r is a
+ *               LINK between pool rows firstA + r and firstB + j iff 0 <= j < nB; -1, any other negative value and any
+ *               j >= nB are no link.  L_e is the number of links of edge e.
+ *   selection   edge e is SELECTED iff L_e >= min_links; min_links == 0 selects every edge.
+ *   prefix, cut W_e is the 64-bit sum of L_f over the selected f < e.  Edge e is KEPT iff it is selected and
+ *               W_{e+1} <= link_capacity.  W does not decrease, so no edge is cut in the middle and no kept edge follows a cut
+ *               one.  O is the sum of L_e over the kept edges.  link_capacity >= ea_capacity always suffices.
+ *   d_link_offsets   uint64, exactly n_edges + 1 entries written: min(W_e, O) -- an ordinary pair layout over the same edges, in
+ *               which an edge that is not kept has an empty range; model[e] / stats[e] of the verifiers stay aligned with it.
+ *   d_link_a, d_link_b   int32 [link_capacity]: at W_e + k the k-th link of kept edge e in ascending r, as the pool rows
+ *               firstA + r and firstB + j; under LF_MKD_LINK_TABLE_LOCAL as r and j, the rows local to their images.  Entries
+ *               at or beyond O are untouched.  Both may be NULL iff link_capacity == 0.
+ *   d_link_edge optional, uint32 [link_capacity]: e at the same positions.
+ *   d_edge_links optional, uint32 [n_edges]: L_e of every edge, selected or not.
+ *   d_match_kept optional, int32, indexed like d_match: for every entry lo + r, r < min(nA, len), of every edge it holds
+ *               d_match[lo + r] if the entry is a link of a KEPT edge and -1 otherwise; entries of no edge, and entries at or
+ *               beyond ea_capacity, are untouched.  It may be d_match itself (in place: every entry is read before it is
+ *               written, by the same thread).  Passed to lf_mkd_build_tracks_device it carries exactly the kept edges' links.
+ *   d_counts    uint32 [4] = {the kept edges, O, the selected edges, min(W_{n_edges}, 2^32 - 1)}; elements 2 and 3 tell a
+ *               caller what was wanted, so that a capacity that cut something shows.  Element 1 sits where
+ *               lf_mkd_gather_track_rows_device reads its count: without LF_MKD_LINK_TABLE_LOCAL that call, given d_link_a (and
+ *               once more d_link_b) as d_obs_row, this d_counts and link_capacity as obs_capacity, brings keypoints or any
+ *               4 .. 512-byte rows into the table's order.  There is no other gather.
+ * All of this is specified for layouts that do not decrease.  Whatever the arrays hold the call ends, d_counts[1] <=
+ * link_capacity, and nothing is read or written at or beyond n_rows_total, ea_capacity, n_edges + 1 or link_capacity.
+ * n_edges == 0 is LF_MKD_OK and writes d_counts = 0 and d_link_offsets[0] = 0.
+ * How (csrc/mkd_link_table.hip): lf_mkd_build_tracks_device's slot map (one workgroup per slot of slot_entries entries of one
+ * edge, so slot order is edge order, then row order); a count per slot (ballot and popcount) and per edge (an integer add: a
+ * sum does not depend on its order), an exclusive 64-bit scan of the selected slots' counts over scan_levels levels of
+ * fan-out scan_fanout, the cut per edge, and a scatter to the slot's prefix plus the rank within the slot.  No atomic decides
+ * a position, no workgroup waits for another, integer arithmetic only: the table is exact and does not depend on the run or
+ * on the CU count.
+ * Launches, with L = lf_mkd_link_table_plan's scan_levels: 2 L + 4 (zero, count, L - 1 up the scan and L down, cut, scatter,
+ * finalise); 2 L + 3 when link_capacity == 0 and d_match_kept is NULL (no scatter); 1 for n_edges == 0 -- a fixed number,
+ * sized by the host from ea_capacity, n_edges and link_capacity only; no device array is ever read by the host.  Asynchronous
+ * on `stream` (NULL: the handle's own), no host synchronisation; no allocation once the handle's scratch has grown to the
+ * largest plan seen (lf_mkd_link_table_plan's scratch_bytes), so a warmed-up call is capturable in a hipGraph.  The scratch
+ * belongs to the handle: calls of one handle are stream-ordered.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "link_table_device: " and is reachable
+ * through lf_mkd_last_error(NULL) when h is NULL): a null handle; null d_image_offsets, d_link_offsets or d_counts; with
+ * n_edges > 0 a null edge, layout or match array; with link_capacity > 0 a null d_link_a or d_link_b; unknown flag bits; an
+ * offset array not 8-byte or any other array not 4-byte aligned; n_rows_total, ea_capacity or link_capacity above 2^31 - 1; a
+ * grid above 2^31 - 1 workgroups (floor(ea_capacity / slot_entries) + n_edges). */
+/* host only, no device, no handle: what the device call will use, and the only place that knows it -- slot_entries = the
+ * entries per slot, slots = floor(ea_capacity / slot_entries) + n_edges (the grid of the count and of the scatter),
+ * scan_fanout = the slots one workgroup of the scan sums, scan_levels = the smallest L >= 1 with scan_fanout^L >= slots (0 for
+ * n_edges == 0), scratch_bytes = the scratch the device call grows the handle to (0 for n_edges == 0; otherwise 20 bytes a
+ * slot, 12 bytes a value of scan levels 1 .. L - 1, level k having ceil(slots / scan_fanout^k) values, 4 bytes an edge and
+ * 16); any output may be NULL.  LF_MKD_ERR_BAD_ARG ("link_table_plan: "): ea_capacity above 2^31 - 1, slots above 2^31 - 1. */
+int lf_mkd_link_table_plan(uint64_t ea_capacity, uint32_t n_edges, uint32_t *slot_entries, uint64_t *slots,
+                           uint32_t *scan_fanout, uint32_t *scan_levels, uint64_t *scratch_bytes);
+int lf_mkd_link_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                             const uint32_t *d_edge_a, const uint32_t *d_edge_b, const uint64_t *d_edge_offsets_a,
+                             uint64_t ea_capacity, uint32_t n_edges, const int32_t *d_match, uint32_t min_links,
+                             uint32_t flags, uint64_t link_capacity, uint64_t *d_link_offsets, int32_t *d_link_a,
+                             int32_t *d_link_b, uint32_t *d_link_edge, uint32_t *d_edge_links, int32_t *d_match_kept,
+                             uint32_t *d_counts, void *stream);
+#define LF_MKD_LINK_TABLE_LOCAL (1u)  /* d_link_a / d_link_b hold rows local to their images, not pool rows */
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

@@ -240,6 +240,8 @@ struct lf_mkd {
     // can be captured once warmed up.  Calls of one handle are stream-ordered (lf_mkd.h).
     // lf_mkd_track_table_device's scratch (track_table_plan's scratch_bytes); like the verifiers' it is named by no recording
     HipArray<unsigned char> d_track_table;
+    // lf_mkd_link_table_device's scratch (link_table_plan's scratch_bytes), in the same way
+    HipArray<unsigned char> d_link_table;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;
@@ -2357,6 +2359,60 @@ int lf_mkd_gather_track_rows_device(lf_mkd *h, const void *d_src, uint32_t row_b
     LF_ENTER(h);
     launch_gather_track_rows(d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst,
                              stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// Link tables (csrc/mkd_link_table.hip).  Every refusal comes before the handle is looked at; the grid is tracks_link's.
+static const char *link_table_sizes(uint64_t ea_capacity, uint32_t n_edges) {
+    if (ea_capacity > kEdgeMax) return "a total or a capacity above 2^31 - 1";
+    if (ea_capacity / link_table_plan(0, 0).slot_entries + n_edges > kEdgeMax)
+        return "too many entries and edges for one call (the grid needs floor(ea_capacity / slot_entries) + n_edges workgroups, at "
+               "most 2^31 - 1)";
+    return nullptr;
+}
+
+int lf_mkd_link_table_plan(uint64_t ea_capacity, uint32_t n_edges, uint32_t *slot_entries, uint64_t *slots,
+                           uint32_t *scan_fanout, uint32_t *scan_levels, uint64_t *scratch_bytes) {
+    if (const char *msg = link_table_sizes(ea_capacity, n_edges)) return q8_refuse(nullptr, "link_table_plan", msg);
+    const LinkTablePlan p = link_table_plan(ea_capacity, n_edges);
+    if (slot_entries) *slot_entries = p.slot_entries;
+    if (slots) *slots = p.slots;
+    if (scan_fanout) *scan_fanout = p.scan_fanout;
+    if (scan_levels) *scan_levels = p.scan_levels;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_link_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_t n_images, uint64_t n_rows_total,
+                             const uint32_t *d_edge_a, const uint32_t *d_edge_b, const uint64_t *d_edge_offsets_a,
+                             uint64_t ea_capacity, uint32_t n_edges, const int32_t *d_match, uint32_t min_links,
+                             uint32_t flags, uint64_t link_capacity, uint64_t *d_link_offsets, int32_t *d_link_a,
+                             int32_t *d_link_b, uint32_t *d_link_edge, uint32_t *d_edge_links, int32_t *d_match_kept,
+                             uint32_t *d_counts, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (!d_image_offsets || !d_link_offsets || !d_counts) msg = "null pointer";
+    else if (n_edges && (!d_edge_a || !d_edge_b)) msg = "null edge array";
+    else if (n_edges && !d_edge_offsets_a) msg = "null layout array";
+    else if (n_edges && !d_match) msg = "null match array";
+    else if (link_capacity && (!d_link_a || !d_link_b)) msg = "null d_link_a or d_link_b";
+    else if (flags & ~LF_MKD_LINK_TABLE_LOCAL) msg = "unknown flag bits";
+    else if ((at(d_image_offsets) | at(d_edge_offsets_a) | at(d_link_offsets)) & 7) msg = "the offset arrays must be 8-byte aligned";
+    else if ((at(d_edge_a) | at(d_edge_b) | at(d_match) | at(d_link_a) | at(d_link_b) | at(d_link_edge) | at(d_edge_links) |
+              at(d_match_kept) | at(d_counts)) & 3)
+        msg = "the edge, match, link and count arrays must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || link_capacity > kEdgeMax) msg = "a total or a capacity above 2^31 - 1";
+    else if (!(msg = link_table_sizes(ea_capacity, n_edges)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "link_table_device", msg);
+    LF_ENTER(h);
+    const LinkTablePlan plan = link_table_plan(ea_capacity, n_edges);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_link_table, plan.scratch_bytes)) return rc;
+    launch_link_table(plan, plan.scratch_bytes ? h->d_link_table.get() : nullptr, d_image_offsets, n_images, n_rows_total, d_edge_a,
+                      d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match, min_links, (flags & LF_MKD_LINK_TABLE_LOCAL) != 0,
+                      link_capacity, d_link_offsets, d_link_a, d_link_b, d_link_edge, d_edge_links, d_match_kept, d_counts,
+                      stream ? static_cast<hipStream_t>(stream) : h->stream);
     LF_HIP(h, hipGetLastError());
     return LF_MKD_OK;
 }

@@ -297,6 +297,23 @@ void launch_track_table(const TrackTablePlan &plan, unsigned char *scratch, cons
                         int *row_track, unsigned *counts, hipStream_t stream);
 void launch_gather_track_rows(const void *src, unsigned row_bytes, uint64_t total, const int *obs_row, const unsigned *counts,
                               uint64_t obs_capacity, void *dst, hipStream_t stream);
+// link tables (csrc/mkd_link_table.hip, lf_mkd_link_table_device).  The plan is the one place that knows the slot size and the
+// scan's fan-out: slots = floor(capacity / slot_entries) + n_edges (tracks_link's grid), scan_levels = the smallest L with
+// scan_fanout^L >= slots (0 for n_edges == 0), level k = 1 .. L - 1 of the scan has level_n[k] values, and the layout of the
+// scratch (byte offsets; the slots' W sits at 0).
+// Launches: n_edges == 0: one (zeroes).  Otherwise zero, count, L - 1 up, L down, cut, scatter (not when link_capacity == 0
+// and match_kept is null), finalise: 2 L + 4 or 2 L + 3.
+struct LinkTablePlan {
+    unsigned slot_entries, scan_fanout, scan_levels;
+    uint64_t slots, level_n[8], off_level_links[8], off_level_edges[8], off_totals, off_slot_cnt, off_slot_edge, off_slot_idx,
+        off_edge_links, scratch_bytes;
+};
+LinkTablePlan link_table_plan(uint64_t capacity, unsigned n_edges);
+void launch_link_table(const LinkTablePlan &plan, unsigned char *scratch, const uint64_t *image_off, unsigned n_images,
+                       uint64_t total, const unsigned *edge_a, const unsigned *edge_b, const uint64_t *edge_off, uint64_t capacity,
+                       unsigned n_edges, const int *match, unsigned min_links, bool local, uint64_t link_capacity,
+                       uint64_t *offsets, int *link_a, int *link_b, unsigned *link_edge, unsigned *edge_links, int *match_kept,
+                       unsigned *counts, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

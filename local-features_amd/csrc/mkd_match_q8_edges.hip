@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
-#include "mkd_match_small.h"       // pair_rows, last_pair_at_or_before
+#include "mkd_match_small.h"       // pair_rows, image_rows, last_pair_at_or_before
 #include "mkd_match_q8_common.h"   // the tile constants, q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
 
 namespace lfmkd {
@@ -26,14 +26,6 @@ constexpr int kLayoutThreads = 256, kLayoutPer = 4;
 constexpr int kLayoutBlock = kLayoutThreads * kLayoutPer;   // edges one workgroup of edge_layout scans
 constexpr uint64_t kPartial = 1ull << 63;                   // a block's own sum, not yet the prefix (sums stay below 2^63)
 constexpr int kGatherRows = 64, kGatherThreads = 256;       // rows one workgroup of gather_edge_rows copies
-
-// the first row and the number of rows of image m of a pool; an id at or beyond n_images names an empty image
-__device__ __forceinline__ void image_rows(const uint64_t *__restrict__ image_off, unsigned n_images, uint64_t total, unsigned m,
-                                           long &lo, long &n) {
-    lo = 0;
-    n = 0;
-    if (m < n_images) pair_rows(image_off[m], image_off[m + 1], total, lo, n);
-}
 
 }  // namespace
 

@@ -139,6 +139,14 @@ __device__ __forceinline__ void pair_rows(uint64_t first, uint64_t next, uint64_
     n = o1 > o0 ? (long)(o1 - o0) : 0;
 }
 
+// the first row and the number of rows of image m of a pool; an id at or beyond n_images names an empty image
+__device__ __forceinline__ void image_rows(const uint64_t *__restrict__ image_off, unsigned n_images, uint64_t total, unsigned m,
+                                           long &lo, long &n) {
+    lo = 0;
+    n = 0;
+    if (m < n_images) pair_rows(image_off[m], image_off[m + 1], total, lo, n);
+}
+
 // the largest p of [0, n_pairs) with key(p) <= v, for a strictly or weakly increasing key; n_pairs > 0 (the caller checks
 // key(p) <= v itself: v may lie in front of pair 0)
 template <typename Key>

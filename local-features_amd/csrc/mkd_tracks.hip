@@ -25,7 +25,7 @@
 
 #include "../../include/lf_mkd.h"   // LF_MKD_TRACKS_DUP_TILE
 #include "mkd_device.h"
-#include "mkd_match_small.h"        // pair_rows, last_pair_at_or_before
+#include "mkd_match_small.h"        // pair_rows, image_rows, last_pair_at_or_before
 
 namespace lfmkd {
 namespace {
@@ -34,15 +34,6 @@ constexpr int kRowThreads = 256;                        // rows one workgroup of
 constexpr int kLinkEntries = 256;                       // layout entries one workgroup of tracks_link serves, one a thread
 constexpr int kDupTile = LF_MKD_TRACKS_DUP_TILE;        // rows one workgroup of tracks_dup serves = labels per LDS tile
 static_assert(kDupTile % 4 == 0 && kDupTile <= 1024, "tracks_dup reads its tile four labels at a time, one thread a row");
-
-// the first row and the number of rows of image m of a pool; an id at or beyond n_images names an empty image
-// (mkd_match_q8_edges.hip's, which stays as it is)
-__device__ __forceinline__ void image_rows(const uint64_t *__restrict__ image_off, unsigned n_images, uint64_t total, unsigned m,
-                                           long &lo, long &n) {
-    lo = 0;
-    n = 0;
-    if (m < n_images) pair_rows(image_off[m], image_off[m + 1], total, lo, n);
-}
 
 // EVERY read and write of a parent while the forest changes is an agent-scope atomic (global_load / global_store ... sc1,
 // served by L2): a plain load may be served from this CU's L1, which no other CU's store ever refreshes.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -20,11 +20,17 @@ descriptor row is copied for it.
   the keypoints the edges tie together               track it belongs to, per track its length and its conflicting keypoints
   with --table (which implies --tracks) the track    LocalFeatures.track_table (lf_mkd_track_table_device): the consistent tracks
   table, and the keypoints in its order              of two or more keypoints as a CSR table; LocalFeatures.gather_track_rows
+  with --pairs the link table: per edge the list     LocalFeatures.link_table (lf_mkd_link_table_device) on the verified matches,
+  of its verified correspondences, and both          and LocalFeatures.gather_track_rows once per side
+  sides' keypoints in its order
+  with --min-inliers M (which implies the link       the same call with min_links = M: edges with fewer verified matches are
+  table) the tracks of the supported edges only      dropped on the device, and --tracks / --table build from its pruned matches
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
 of the keypoints that sit in a consistent track; with --table also the number of tracks and observations in the table and the
-first three tracks as image:x,y lists.  Nothing is read back before those counts: the
+first three tracks as image:x,y lists; with --pairs also the number of edges and correspondences in the link table and the
+first three correspondences of the best edge as x,y -> x,y.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -70,7 +76,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False):
+                     table=False, pairs=False, min_inliers=None):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all" or "retrieve" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -81,7 +87,11 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     in a consistent track of length >= 2; without, those four are None.  With `table` (which implies `tracks`) also the table of
     the consistent tracks of length >= 2 as LocalFeatures.track_table returns it -- table_offsets [m // 2 + 1], table_rows [m],
     table_images [m], table_row_track [m], table_counts [4] -- and table_keypoints [m,5], the keypoints in the table's order
-    (LocalFeatures.gather_track_rows); without, those six are None."""
+    (LocalFeatures.gather_track_rows); without, those six are None.  With `pairs`, or with min_inliers (an int: edges with
+    fewer verified matches are left out), also the link table of the verified matches as LocalFeatures.link_table returns it
+    -- link_offsets [E + 1], link_a / link_b / link_edge [layout capacity], edge_links [E], link_counts [4] --, link_keypoints_a /
+    link_keypoints_b, both sides' keypoints in the table's order, and with min_inliers match_kept, the verified matches of the
+    kept edges alone, from which the tracks are then built; without, those nine are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -119,10 +129,15 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         count = lambda mask: torch.bincount(edge_of[mask], minlength=n_edges + 1)[:n_edges]
         raw = (best != -2 ** 31) & ((ratio <= 0) | (best.float() * ratio > second.float()))   # (both conversions are exact)
         per_edge = torch.stack([count(raw), count(m_ab >= 0), count(ver >= 0)], dim=1)
+        l_off = l_a = l_b = l_edge = l_links = l_kept = l_counts = l_ka = l_kb = None
+        if pairs or min_inliers is not None:
+            l_off, l_a, l_b, l_edge, l_links, l_kept, l_counts = feats.link_table(
+                o, ea, eb, la, ver, min_links=min_inliers or 0, capacity=cap_a, n_rows=m, kept_match=min_inliers is not None)
+            l_ka, l_kb = feats.gather_track_rows(kps, l_a, l_counts), feats.gather_track_rows(kps, l_b, l_counts)
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
         if tracks or table:
-            track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver, capacity=cap_a, n_rows=m)
+            track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
             track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
                                         (track_len * (two & ok)).sum()])
@@ -133,12 +148,13 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     return dict(edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
-                table_keypoints=t_kps)
+                table_keypoints=t_kps, link_offsets=l_off, link_a=l_a, link_b=l_b, link_edge=l_edge, edge_links=l_links,
+                link_counts=l_counts, link_keypoints_a=l_ka, link_keypoints_b=l_kb, match_kept=l_kept)
 
 
 def main():
     args = sys.argv[1:]
-    mode, arg, fundamental, tracks, table, paths = "window", 2, False, False, False, []
+    mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -147,6 +163,10 @@ def main():
             tracks = True
         elif a == "--table":
             tracks = table = True
+        elif a == "--pairs":
+            pairs = True
+        elif a == "--min-inliers" and args and args[0].isdigit():
+            min_inliers = int(args.pop(0))
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -157,7 +177,7 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (mode == "retrieve" and arg > len(paths) - 1):
-        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
               "number of images)", file=sys.stderr)
@@ -166,7 +186,8 @@ def main():
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
-    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table)
+    out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
+                           min_inliers=min_inliers)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
@@ -185,6 +206,15 @@ def main():
         images, xy = out["table_images"][:first[-1]].cpu().tolist(), out["table_keypoints"][:first[-1], :2].cpu().tolist()
         for k in range(len(first) - 1):
             print(f"Track {k + 1}: " + " ".join(f"{images[i] + 1}:{xy[i][0]:.1f},{xy[i][1]:.1f}" for i in range(first[k], first[k + 1])))
+    if pairs:
+        n_kept, n_links = out["link_counts"].cpu().tolist()[:2]
+        print(f"Link table: {n_kept} edges, {n_links} correspondences")
+        best = min(range(len(ea)), key=lambda e: (-per_edge[e][2], e))
+        lo, hi = out["link_offsets"][best:best + 2].cpu().tolist()
+        hi = min(hi, lo + 3)
+        xa, xb = out["link_keypoints_a"][lo:hi, :2].cpu().tolist(), out["link_keypoints_b"][lo:hi, :2].cpu().tolist()
+        for a, b in zip(xa, xb):
+            print(f"Edge {ea[best] + 1} -> {eb[best] + 1}: {a[0]:.1f},{a[1]:.1f} -> {b[0]:.1f},{b[1]:.1f}")
     return 0
 
 

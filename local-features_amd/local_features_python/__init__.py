@@ -14,14 +14,15 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
-           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan"]
+           "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
+           "LINK_TABLE_LOCAL", "link_table_plan"]
 
 
 class Keypoint:
@@ -690,6 +691,72 @@ class LocalFeatures:
                 self._inner.gather_track_rows_device(x.data_ptr() if n else None, row_bytes, n, rows.data_ptr() if cap else None,
                                                      counts.data_ptr(), cap, out.data_ptr() if cap else None, s.cuda_stream)
         return out
+
+    def link_table(self, image_offsets, edge_a, edge_b, layout_a, match, min_links=0, local=False, capacity=None,
+                   link_capacity=None, n_rows=None, kept_match=False, stream=None):
+        """The link table of an edge list's matches (lf_mkd_link_table_device): per edge the compact list of its
+        correspondences, as a CSR table made on the device.  image_offsets, edge_a / edge_b, layout_a and match are what
+        build_tracks takes, read by the same rule: entry lo + r of edge e links rows r of its a image and match[lo + r] of its b
+        image iff that value is a row of the b image.  An edge enters iff it has at least min_links links (0: every edge);
+        link_capacity keeps whole edges only.  capacity: the entries of `match` the layout may use (None: all of them);
+        link_capacity: None is capacity, which always suffices; n_rows: the pool's rows (None: the last image offset read back,
+        which WAITS for the stream).
+        Returns device tensors (link_offsets, link_a, link_b, link_edge, edge_links, match_kept, counts): link_offsets
+        [n_edges + 1] int64 -- edge e's links are link_a / link_b [link_offsets[e] : link_offsets[e + 1]], an edge that is not
+        kept has an empty range; link_a / link_b [link_capacity] int32, pool rows -- with local=True rows within their images
+        -- in ascending row of a (entries beyond the links are left as allocated); link_edge [link_capacity] int32, the edge of
+        each link; edge_links [n_edges] int32, every edge's links, selected or not; match_kept: None, or with kept_match=True a
+        new tensor like `match` in which everything but the kept edges' links is -1 (entries of no edge are -1 too), or with
+        kept_match=match (or any int32 tensor of its size) that tensor, written in place; counts [4] int32: the kept edges,
+        the links in the table, the selected edges and (saturated at 2^32 - 1, as a bit pattern) the links wanted.
+        Without local=True, gather_track_rows(keypoints, link_a, counts) and (..., link_b, counts) bring the keypoints into the
+        table's order; build_tracks(..., match_kept) builds the tracks of the kept edges alone.  Given n_rows nothing is read
+        back: asynchronous on `stream` (default: torch's current stream on the handle's device), capturable once a call of
+        this size has been made."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        min_links = int(min_links)
+        if not 0 <= min_links < 2 ** 32:
+            raise RuntimeError("link_table: min_links must be in [0, 2^32)")
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            io = image_offsets.to(dev, torch.int64).reshape(-1).contiguous()
+            ea, eb = self._words(edge_a, dev), self._words(edge_b, dev)
+            la = layout_a.to(dev, torch.int64).reshape(-1).contiguous()
+            n_edges = ea.numel()
+            if eb.numel() != n_edges or la.numel() != n_edges + 1:
+                raise RuntimeError("link_table: edge_a and edge_b need one id per edge each, layout_a n_edges + 1 entries")
+            if io.numel() < 1:
+                raise RuntimeError("link_table: image_offsets needs n_images + 1 entries")
+            ok = lambda x: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous()
+            if not ok(match):
+                raise RuntimeError("link_table: match must be a contiguous int32 device tensor in the a side's edge layout")
+            cap = match.numel() if capacity is None else int(capacity)
+            if cap > match.numel():
+                raise RuntimeError("link_table: capacity is larger than match")
+            l_cap = cap if link_capacity is None else int(link_capacity)
+            n = int(io[-1].item()) if n_rows is None else int(n_rows)                 # (.item() waits)
+            if kept_match is True:
+                kept = torch.full_like(match, -1)
+            elif kept_match is False or kept_match is None:
+                kept = None
+            elif ok(kept_match) and kept_match.numel() == match.numel():
+                kept = kept_match
+            else:
+                raise RuntimeError("link_table: kept_match must be a bool or a contiguous int32 device tensor of match's size")
+            offsets = torch.empty((n_edges + 1,), dtype=torch.int64, device=dev)
+            link_a = torch.empty((l_cap,), dtype=torch.int32, device=dev)
+            link_b = torch.empty((l_cap,), dtype=torch.int32, device=dev)
+            link_edge = torch.empty((l_cap,), dtype=torch.int32, device=dev)
+            edge_links = torch.empty((n_edges,), dtype=torch.int32, device=dev)
+            counts = torch.empty((4,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.link_table_device(io.data_ptr(), io.numel() - 1, n, ptr(ea), ptr(eb), la.data_ptr(), cap, n_edges,
+                                              ptr(match) if n_edges else None, min_links, LINK_TABLE_LOCAL if local else 0, l_cap,
+                                              offsets.data_ptr(), ptr(link_a), ptr(link_b), ptr(link_edge), ptr(edge_links),
+                                              ptr(kept), counts.data_ptr(), s.cuda_stream)
+        return offsets, link_a, link_b, link_edge, edge_links, kept, counts
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

@@ -45,12 +45,14 @@ SYMBOLS = (
     "lf_mkd_edge_layout_device", "lf_mkd_gather_edge_rows_device", "lf_mkd_match_q8_edges_device",
     "lf_mkd_build_tracks_device",
     "lf_mkd_track_table_plan", "lf_mkd_track_table_device", "lf_mkd_gather_track_rows_device",
+    "lf_mkd_link_table_plan", "lf_mkd_link_table_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
 TRACKS_ACCUMULATE = 1    # LF_MKD_TRACKS_ACCUMULATE: lf_mkd_build_tracks_device adds its links to the forest d_track holds
 TRACKS_DUP_TILE = 256    # LF_MKD_TRACKS_DUP_TILE: rows one workgroup of its d_track_dup launch owns
 TRACK_TABLE_CONSISTENT = 1   # LF_MKD_TRACK_TABLE_CONSISTENT: lf_mkd_track_table_device takes only tracks with dup == 0
+LINK_TABLE_LOCAL = 1     # LF_MKD_LINK_TABLE_LOCAL: lf_mkd_link_table_device writes rows local to their images, not pool rows
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -158,6 +160,8 @@ def load_library():
     L.lf_mkd_track_table_plan.argtypes = [u64, u32, vp, vp, vp, vp]
     L.lf_mkd_track_table_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_gather_track_rows_device.argtypes = [vp, vp, u32, u64, vp, vp, u64, vp, vp]
+    L.lf_mkd_link_table_plan.argtypes = [u64, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_link_table_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, u32, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -261,6 +265,21 @@ def track_table_plan(n_rows_total, min_len=2):
     if rc != 0:
         raise RuntimeError(f"lf_mkd_track_table_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return k.value, p.value, r.value, b.value
+
+
+def link_table_plan(ea_capacity, n_edges):
+    """(slot_entries, slots, scan_fanout, scan_levels, scratch_bytes) of lf_mkd_link_table_device for n_edges edges whose a
+    side's layout has ea_capacity entries: the entries of one slot, the slots (floor(ea_capacity / slot_entries) + n_edges,
+    the grid), the fan-out and the levels of the scan over the slots, and the handle's scratch (lf_mkd_link_table_plan;
+    needs no device)."""
+    e, f, l = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    n, b = ctypes.c_uint64(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_link_table_plan(ea_capacity, n_edges, ctypes.byref(e), ctypes.byref(n), ctypes.byref(f), ctypes.byref(l),
+                                  ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_link_table_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return e.value, n.value, f.value, l.value, b.value
 
 
 class Comm:
@@ -733,6 +752,18 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_gather_track_rows_device(
             self._h, d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst, s),
             "lf_mkd_gather_track_rows_device")
+
+    def link_table_device(self, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity,
+                          n_edges, d_match, min_links, flags, link_capacity, d_link_offsets, d_link_a, d_link_b, d_link_edge,
+                          d_edge_links, d_match_kept, d_counts, stream=None):
+        """lf_mkd_link_table_device: the CSR table of the links d_match holds in the a side's edge layout -- d_link_offsets
+        [n_edges + 1] uint64, d_link_a / d_link_b int32 and d_link_edge uint32 (nullable) [link_capacity], d_edge_links uint32
+        [n_edges] (nullable), d_match_kept int32 like d_match (nullable; may be d_match), d_counts uint32 [4] (device pointers;
+        see include/lf_mkd.h).  flags: LINK_TABLE_LOCAL."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_link_table_device(
+            self._h, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match,
+            min_links, flags, link_capacity, d_link_offsets, d_link_a, d_link_b, d_link_edge, d_edge_links, d_match_kept,
+            d_counts, s), "lf_mkd_link_table_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
