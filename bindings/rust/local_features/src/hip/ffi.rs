@@ -281,6 +281,17 @@ extern "C" {
                                     link_capacity: u64, d_link_offsets: *mut u64, d_link_a: *mut i32, d_link_b: *mut i32,
                                     d_link_edge: *mut u32, d_edge_links: *mut u32, d_match_kept: *mut i32,
                                     d_counts: *mut u32, stream: *mut c_void) -> c_int;
+    // candidate edges: per row of d_votes [n_a][n_b] its k best columns (larger votes first, among equal ones the LOWER
+    // column: d_rank / d_rank_votes [n_a][k], nullable) and the edges those picks make (d_edge_a / d_edge_b / d_edge_votes
+    // [edge_capacity], 0xFFFFFFFF behind the edges; d_counts [4] = {kept edges, edges, picks, rows with a pick}); flags:
+    // LF_MKD_SELECT_SKIP_SELF, LF_MKD_SELECT_UNIQUE; k <= LF_MKD_SELECT_MAX_K; the plan is host only
+    pub fn lf_mkd_select_edges_plan(n_a: u32, n_b: u32, k: u32, edge_capacity: u64, flags: u32, compiled_k: *mut u32,
+                                    rows_per_workgroup: *mut u32, workgroups: *mut u64, launches: *mut u32,
+                                    scratch_bytes: *mut u64) -> c_int;
+    pub fn lf_mkd_select_edges_device(h: *mut lf_mkd, d_votes: *const u32, n_a: u32, n_b: u32, k: u32, min_votes: u32,
+                                      flags: u32, edge_capacity: u64, d_rank: *mut i32, d_rank_votes: *mut u32,
+                                      d_edge_a: *mut u32, d_edge_b: *mut u32, d_edge_votes: *mut u32, d_counts: *mut u32,
+                                      stream: *mut c_void) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -88,6 +88,13 @@ pub const TRACK_TABLE_CONSISTENT: u32 = 1;
 /// their images, not pool rows.
 pub const LINK_TABLE_LOCAL: u32 = 1;
 
+/// `flags` of `lf_mkd_select_edges_device` (`include/lf_mkd.h`, `LF_MKD_SELECT_SKIP_SELF`, `LF_MKD_SELECT_UNIQUE`): column i
+/// is no candidate of row i; one pool, every unordered pair at most once, as (smaller, larger).  `SELECT_MAX_K`: the
+/// largest k (`LF_MKD_SELECT_MAX_K`).
+pub const SELECT_SKIP_SELF: u32 = 1;
+pub const SELECT_UNIQUE: u32 = 2;
+pub const SELECT_MAX_K: u32 = 32;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,
@@ -589,6 +596,42 @@ impl LocalFeaturesHip {
         link_a.truncate(counts[1] as usize);
         link_b.truncate(counts[1] as usize);
         Ok((offsets, link_a, link_b, edge_links))
+    }
+
+    /// The candidate edges of a vote table (`lf_mkd_select_edges_device`): `votes` is `[n_a][n_b]` row-major; per row the `k`
+    /// columns with the most votes among those with at least `min_votes` (larger votes first, among equal votes the LOWER
+    /// column), `flags` of `SELECT_SKIP_SELF` / `SELECT_UNIQUE`.  Returns (edges, edge_votes, rank): the edges in the order
+    /// row, then rank -- with `SELECT_UNIQUE` every unordered pair once, as (smaller, larger) --, the votes of the pick that
+    /// made each, and the `[n_a][k]` picks of every row, -1 behind them.
+    pub fn select_edges(&mut self, votes: &[u32], n_a: usize, n_b: usize, k: u32, min_votes: u32, flags: u32)
+                        -> Result<(Vec<(u32, u32)>, Vec<u32>, Vec<i32>), Error> {
+        if votes.len() != n_a * n_b || k == 0 || k > SELECT_MAX_K {
+            return Err(Error::BadArgument("select_edges: votes needs n_a * n_b entries, k must be in 1 ..= 32".into()));
+        }
+        let slots = n_a * k as usize;
+        if slots == 0 { return Ok((Vec::new(), Vec::new(), Vec::new())); }
+        let mut counts = [0u32; 4];
+        let (mut ea, mut eb, mut ev, mut rank) = (vec![0u32; slots], vec![0u32; slots], vec![0u32; slots], vec![0i32; slots]);
+        // SAFETY: device buffers sized as declared; n_a, n_b, k and the capacity bound what is read and written
+        unsafe {
+            let d_votes = DeviceBuffer::from_slice(votes)?;
+            let (d_ea, d_eb, d_ev) = (DeviceBuffer::<u32>::new(slots)?, DeviceBuffer::<u32>::new(slots)?, DeviceBuffer::<u32>::new(slots)?);
+            let d_rank = DeviceBuffer::<i32>::new(slots)?;
+            let d_counts = DeviceBuffer::<u32>::new(4)?;
+            check(self.h, ffi::lf_mkd_select_edges_device(
+                self.h, d_votes.as_ptr(), n_a as u32, n_b as u32, k, min_votes, flags, slots as u64, d_rank.as_mut_ptr(),
+                std::ptr::null_mut(), d_ea.as_mut_ptr(), d_eb.as_mut_ptr(), d_ev.as_mut_ptr(), d_counts.as_mut_ptr(),
+                std::ptr::null_mut()))?;
+            check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+            d_counts.download(&mut counts)?;
+            d_ea.download(&mut ea)?;
+            d_eb.download(&mut eb)?;
+            d_ev.download(&mut ev)?;
+            d_rank.download(&mut rank)?;
+        }
+        let kept = counts[0] as usize;
+        ev.truncate(kept);
+        Ok((ea.into_iter().zip(eb).take(kept).collect(), ev, rank))
     }
 
     /// `match_q8_batch` once more under each pair's verified model (`lf_mkd_match_q8_guided_pairs_device`): a row's candidates

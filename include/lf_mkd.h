@@ -951,6 +951,71 @@ int lf_mkd_link_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_
                              int32_t *d_link_b, uint32_t *d_link_edge, uint32_t *d_edge_links, int32_t *d_match_kept,
                              uint32_t *d_counts, void *stream);
 #define LF_MKD_LINK_TABLE_LOCAL (1u)  /* d_link_a / d_link_b hold rows local to their images, not pool rows */
+/* lf_mkd_select_edges_device turns a vote table into CANDIDATE EDGES: per image the k images that received the most votes from
+ * it, and the edge list those picks make -- the step between lf_mkd_vote_groups_device and lf_mkd_edge_layout_device /
+ * lf_mkd_match_q8_edges_device, which take d_edge_a / d_edge_b unchanged.  d_votes is [n_a][n_b] uint32, as
+ * lf_mkd_vote_groups_device writes it.
+ *   candidates  of row i: the columns j < n_b with votes[i][j] >= min_votes and, under LF_MKD_SELECT_SKIP_SELF, j != i.
+ *               min_votes == 0 admits columns without a vote; a caller passes 1 to drop them.  Votes are compared as unsigned
+ *               32-bit values; 2^32 - 1 is an ordinary value.
+ *   order       larger votes first, among equal votes the LOWER column first: (-votes, j), the order a retrieval result is
+ *               printed in, a stable numpy argsort of -votes (as int64) over the candidates.  This is NOT the rule of
+ *               lf_mkd_knn_q8_device and of the matchers, which prefer the HIGHER index among equal scores.
+ *   picks       P(i) = the first min(k, candidates) columns of that order.
+ *   d_rank      optional, int32 [n_a][k]: P(i) in order, -1 in the slots behind it.
+ *   d_rank_votes optional, uint32 [n_a][k]: the votes of those picks, 0 behind them.  Exactly n_a * k entries of each are
+ *               written.  With n_a == 1 this is the retrieval answer for one query.
+ *   edges       the picks are walked in the order i ascending, then rank ascending.  Without LF_MKD_SELECT_UNIQUE every pick
+ *               (i, j) is the edge (i, j).  With it (one pool: n_a == n_b) a pick (i, j) is an edge iff j > i, or j < i and i is
+ *               not in P(j); a self pick is never an edge; the edge is written as (min(i, j), max(i, j)).  So a pair that
+ *               either image picked appears exactly once, at the position of the smaller image's pick if it made one, and
+ *               the matcher behind does not match a mutual pick twice.  S is the number of edges, E = min(S, edge_capacity)
+ *               the number kept: the first E.
+ *   d_edge_a, d_edge_b   uint32 [edge_capacity], exactly edge_capacity entries of each written: the kept edges, then 0xFFFFFFFF
+ *               in both, which names an empty image to every edge-list call -- a caller passes n_edges = edge_capacity
+ *               downstream and never reads the count.  Both may be NULL iff edge_capacity == 0.  edge_capacity >= n_a * k
+ *               always suffices.
+ *   d_edge_votes optional, uint32 [edge_capacity]: votes[i][j] of the pick that made the edge, 0 in the padding.
+ *   d_counts    uint32 [4] = {E, S, the number of picks, the number of rows with at least one pick}; element 1 tells a caller
+ *               what was wanted, so that a capacity that cut something shows.
+ * The result depends on the table, k, min_votes, flags and edge_capacity alone: not on the run, not on the CU count, not on
+ * the form the plan chose.  Nothing is read or written at or beyond n_a * n_b, n_a * k or edge_capacity, whatever the table
+ * holds.  n_a == 0 is LF_MKD_OK and writes d_counts = 0 and the padding.
+ * How (csrc/mkd_select_edges.hip): every candidate is one 64-bit key, votes << 32 | (0xFFFFFFFF - j), so the order is a plain
+ * unsigned maximum and keys are unique within a row.  The selection reads each row once, with 16-byte loads where its address
+ * allows; a lane keeps its compiled_k largest keys in a sorted register list behind a ballot gate (lf_mkd_knn_q8_device's
+ * pattern), and lanes, waves and -- where there are too few rows to fill the device and a row is cut into segments -- segments
+ * are merged by maxima of keys, which is exact and independent of the order of arrival.  Rows of at most 2048 columns take one
+ * wave each, four to a workgroup; longer ones a workgroup per row or segment.  Then one thread per pick slot decides whether
+ * it is an edge (under LF_MKD_SELECT_UNIQUE by k reads of the rank table, which lives in the scratch when d_rank is NULL), an
+ * exact integer exclusive scan gives every edge its position, and a scatter writes edges and padding.  No atomic at all, no
+ * workgroup waits for another, integer arithmetic only.
+ * Launches (lf_mkd_select_edges_plan's `launches`): 4 -- select, flag, scan, scatter --, 5 when rows are cut into segments
+ * (the merge), 1 for n_a == 0: a fixed number, sized by the host from the scalar arguments only; no device array is ever read
+ * by the host.  Asynchronous on `stream` (NULL: the handle's own), no host synchronisation; no allocation once the handle's
+ * scratch has grown to the largest plan seen (the plan's scratch_bytes), so a warmed-up call is capturable in a hipGraph.  The
+ * scratch belongs to the handle: calls of one handle are stream-ordered.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "select_edges_device: " and is reachable
+ * through lf_mkd_last_error(NULL) when h is NULL): a null handle; a null d_votes with n_a > 0; a null d_counts; with
+ * edge_capacity > 0 a null d_edge_a or d_edge_b; n_b == 0 with n_a > 0; k == 0 or above LF_MKD_SELECT_MAX_K; unknown flag
+ * bits; LF_MKD_SELECT_UNIQUE with n_a != n_b; an array not 4-byte aligned; n_a * n_b (lf_mkd_vote_groups_device's limit),
+ * n_a * k or edge_capacity above 2^31 - 1. */
+/* host only, no device, no handle: what the device call will use, and the only place that knows it -- compiled_k = the
+ * instantiation that serves k (4, 8, 16 or 32), rows_per_workgroup = 4 (one wave per row) or 1, workgroups = the grid of the
+ * selection (ceil(n_a / 4); n_a times the segments of a row otherwise; 0 for n_a == 0), launches and scratch_bytes = what the
+ * device call does and grows the handle to (12 bytes a pick slot, 16 bytes per 256 slots, 8 bytes a key of every segment when
+ * rows are cut; 0 for n_a == 0); any output may be NULL.  LF_MKD_ERR_BAD_ARG ("select_edges_plan: "): the device call's
+ * refusals that concern n_a, n_b, k, edge_capacity and flags. */
+int lf_mkd_select_edges_plan(uint32_t n_a, uint32_t n_b, uint32_t k, uint64_t edge_capacity, uint32_t flags,
+                             uint32_t *compiled_k, uint32_t *rows_per_workgroup, uint64_t *workgroups, uint32_t *launches,
+                             uint64_t *scratch_bytes);
+int lf_mkd_select_edges_device(lf_mkd *h, const uint32_t *d_votes, uint32_t n_a, uint32_t n_b, uint32_t k, uint32_t min_votes,
+                               uint32_t flags, uint64_t edge_capacity, int32_t *d_rank, uint32_t *d_rank_votes,
+                               uint32_t *d_edge_a, uint32_t *d_edge_b, uint32_t *d_edge_votes, uint32_t *d_counts,
+                               void *stream);
+#define LF_MKD_SELECT_SKIP_SELF (1u)  /* column i is no candidate of row i */
+#define LF_MKD_SELECT_UNIQUE (2u)     /* one pool (n_a == n_b): every unordered pair at most once, as (smaller, larger) */
+#define LF_MKD_SELECT_MAX_K (32)
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

@@ -242,6 +242,8 @@ struct lf_mkd {
     HipArray<unsigned char> d_track_table;
     // lf_mkd_link_table_device's scratch (link_table_plan's scratch_bytes), in the same way
     HipArray<unsigned char> d_link_table;
+    // lf_mkd_select_edges_device's scratch (select_edges_plan's scratch_bytes), in the same way
+    HipArray<unsigned char> d_select_edges;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;
@@ -2413,6 +2415,53 @@ int lf_mkd_link_table_device(lf_mkd *h, const uint64_t *d_image_offsets, uint32_
                       d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match, min_links, (flags & LF_MKD_LINK_TABLE_LOCAL) != 0,
                       link_capacity, d_link_offsets, d_link_a, d_link_b, d_link_edge, d_edge_links, d_match_kept, d_counts,
                       stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// Candidate edges (csrc/mkd_select_edges.hip).  Every refusal comes before the handle is looked at.
+static const char *select_edges_sizes(uint32_t n_a, uint32_t n_b, uint32_t k, uint64_t edge_capacity, uint32_t flags) {
+    if (k == 0 || k > LF_MKD_SELECT_MAX_K) return "k must be in [1, 32]";
+    if (flags & ~(LF_MKD_SELECT_SKIP_SELF | LF_MKD_SELECT_UNIQUE)) return "unknown flag bits";
+    if ((flags & LF_MKD_SELECT_UNIQUE) && n_a != n_b) return "LF_MKD_SELECT_UNIQUE needs one pool (n_a == n_b)";
+    if (n_a && n_b == 0) return "n_b == 0 with n_a > 0";
+    if ((uint64_t)n_a * n_b > kEdgeMax) return "a table of more than 2^31 - 1 entries (n_a * n_b)";
+    if ((uint64_t)n_a * k > kEdgeMax || edge_capacity > kEdgeMax) return "n_a * k or edge_capacity above 2^31 - 1";
+    return nullptr;
+}
+
+int lf_mkd_select_edges_plan(uint32_t n_a, uint32_t n_b, uint32_t k, uint64_t edge_capacity, uint32_t flags,
+                             uint32_t *compiled_k, uint32_t *rows_per_workgroup, uint64_t *workgroups, uint32_t *launches,
+                             uint64_t *scratch_bytes) {
+    if (const char *msg = select_edges_sizes(n_a, n_b, k, edge_capacity, flags)) return q8_refuse(nullptr, "select_edges_plan", msg);
+    const SelectEdgesPlan p = select_edges_plan(n_a, n_b, k, edge_capacity);
+    if (compiled_k) *compiled_k = p.compiled_k;
+    if (rows_per_workgroup) *rows_per_workgroup = p.rows_per_workgroup;
+    if (workgroups) *workgroups = p.workgroups;
+    if (launches) *launches = p.launches;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_select_edges_device(lf_mkd *h, const uint32_t *d_votes, uint32_t n_a, uint32_t n_b, uint32_t k, uint32_t min_votes,
+                               uint32_t flags, uint64_t edge_capacity, int32_t *d_rank, uint32_t *d_rank_votes,
+                               uint32_t *d_edge_a, uint32_t *d_edge_b, uint32_t *d_edge_votes, uint32_t *d_counts, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (n_a && !d_votes) msg = "null d_votes";
+    else if (!d_counts) msg = "null d_counts";
+    else if (edge_capacity && (!d_edge_a || !d_edge_b)) msg = "null d_edge_a or d_edge_b";
+    else if ((at(d_votes) | at(d_rank) | at(d_rank_votes) | at(d_edge_a) | at(d_edge_b) | at(d_edge_votes) | at(d_counts)) & 3)
+        msg = "every array must be 4-byte aligned";
+    else if (!(msg = select_edges_sizes(n_a, n_b, k, edge_capacity, flags)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "select_edges_device", msg);
+    LF_ENTER(h);
+    const SelectEdgesPlan plan = select_edges_plan(n_a, n_b, k, edge_capacity);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_select_edges, plan.scratch_bytes)) return rc;
+    launch_select_edges(plan, plan.scratch_bytes ? h->d_select_edges.get() : nullptr, d_votes, n_a, n_b, k, min_votes,
+                        (flags & LF_MKD_SELECT_SKIP_SELF) != 0, (flags & LF_MKD_SELECT_UNIQUE) != 0, edge_capacity, d_rank,
+                        d_rank_votes, d_edge_a, d_edge_b, d_edge_votes, d_counts, stream ? static_cast<hipStream_t>(stream) : h->stream);
     LF_HIP(h, hipGetLastError());
     return LF_MKD_OK;
 }

@@ -314,6 +314,21 @@ void launch_link_table(const LinkTablePlan &plan, unsigned char *scratch, const 
                        unsigned n_edges, const int *match, unsigned min_links, bool local, uint64_t link_capacity,
                        uint64_t *offsets, int *link_a, int *link_b, unsigned *link_edge, unsigned *edge_links, int *match_kept,
                        unsigned *counts, hipStream_t stream);
+// candidate edges (csrc/mkd_select_edges.hip, lf_mkd_select_edges_device).  The plan is the one place that knows the forms:
+// compiled_k = the instantiation that serves k (4, 8, 16, 32); rows_per_workgroup = 4 (one wave per row: rows of at most 2048
+// columns) or 1; splits = the segments of `segment` columns a row is cut into (1 unless there are fewer than 1024 rows of more
+// than 4096 columns); workgroups = the selection's grid; slots = n_a k, blocks = ceil(slots / 256) (the grid of the flags);
+// the layout of the scratch (byte offsets; the segments' keys sit at 0).
+// Launches: n_a == 0: one (counts and padding).  Otherwise select, merge (splits > 1 only), flag, scan, scatter: 4 or 5.
+struct SelectEdgesPlan {
+    unsigned compiled_k, rows_per_workgroup, splits, segment, launches;
+    uint64_t workgroups, slots, blocks, off_rank, off_rank_votes, off_local, off_blocks, scratch_bytes;
+};
+SelectEdgesPlan select_edges_plan(unsigned n_a, unsigned n_b, unsigned k, uint64_t edge_capacity);
+void launch_select_edges(const SelectEdgesPlan &plan, unsigned char *scratch, const unsigned *votes, unsigned n_a, unsigned n_b,
+                         unsigned k, unsigned min_votes, bool skip_self, bool unique, uint64_t edge_capacity, int *rank,
+                         unsigned *rank_votes, unsigned *edge_a, unsigned *edge_b, unsigned *edge_votes, unsigned *counts,
+                         hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

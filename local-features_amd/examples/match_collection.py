@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -10,6 +10,10 @@ descriptor row is copied for it.
               --retrieve K  every image against the K images that share most exact votes with it, chosen on the device:
                           LocalFeatures.match_q8_grouped of the pool against itself with every row's own image excluded,
                           LocalFeatures.vote_groups into an [N][N] table, torch.topk per image
+              --select K  the same vote table, the edges chosen by LocalFeatures.select_edges (lf_mkd_select_edges_device)
+                          with skip_self, unique and min_votes = 1: ties go to the lower image, a pair two images picked
+                          mutually is ONE edge (smaller, larger), an image nobody voted for is not picked; the list has
+                          N * K entries, the ones behind the edges name no image and have empty ranges everywhere
   both sides' edge layouts                           lf_mkd_edge_layout_device (inside match_q8_edges)
   every edge, both directions, 0.8 ratio test,       LocalFeatures.match_q8_edges(mutual=True): one matcher launch and two
   cross-check                                        filter launches for all edges (lf_mkd_match_q8_edges_device)
@@ -63,13 +67,19 @@ def all_edges(n):
     return [p[0] for p in pairs], [p[1] for p in pairs], n - 1
 
 
+def vote_table(feats, q, o, frame_of, n, ratio=RATIO):
+    """votes [n, n] int32 on the device: votes[i, j] = the rows of image i whose best match among the rows of all OTHER images
+    lies in image j and beats the best row of any third image by `ratio`"""
+    lo, hi = o[frame_of], o[frame_of + 1]                      # every row's own image is no candidate
+    match = feats.match_q8_grouped(q, q, frame_of.int(), ratio=ratio, exclude=(lo.int(), hi.int()))
+    return feats.vote_groups(match, frame_of.int(), n, groups_a=frame_of.int(), n_groups_a=n)
+
+
 def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
     """(edge_a, edge_b) as device tensors [n * k]: image i against the k images with most votes for it -- a row votes for the
     image of its best match among the rows of all OTHER images if that beats the best row of any other image by `ratio`"""
     import torch
-    lo, hi = o[frame_of], o[frame_of + 1]                      # every row's own image is no candidate
-    match = feats.match_q8_grouped(q, q, frame_of.int(), ratio=ratio, exclude=(lo.int(), hi.int()))
-    votes = feats.vote_groups(match, frame_of.int(), n, groups_a=frame_of.int(), n_groups_a=n)
+    votes = vote_table(feats, q, o, frame_of, n, ratio)
     votes = votes.masked_fill(torch.eye(n, dtype=torch.bool, device=votes.device), -1)
     top = torch.topk(votes.long(), k, dim=1).indices            # [n, k]
     return torch.arange(n, dtype=torch.int32, device=top.device).repeat_interleave(k), top.reshape(-1).int()
@@ -77,7 +87,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
                      table=False, pairs=False, min_inliers=None):
-    """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all" or "retrieve" (arg = K).  Returns a dict of device
+    """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
     [E,3,3] and stats [E,4] as the verifier returns them; per_edge [E,3]: ratio-test matches a -> b, mutual, verified.  With
@@ -91,7 +101,10 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     fewer verified matches are left out), also the link table of the verified matches as LocalFeatures.link_table returns it
     -- link_offsets [E + 1], link_a / link_b / link_edge [layout capacity], edge_links [E], link_counts [4] --, link_keypoints_a /
     link_keypoints_b, both sides' keypoints in the table's order, and with min_inliers match_kept, the verified matches of the
-    kept edges alone, from which the tracks are then built; without, those nine are None."""
+    kept edges alone, from which the tracks are then built; without, those nine are None.  In mode "select" edge_a / edge_b have
+    n * K entries, -1 behind the edges (an empty image to every call here), and votes [n, n], edge_votes [n * K], rank and
+    rank_votes [n, K] and select_counts [4] are what LocalFeatures.select_edges took and returned; otherwise those five are
+    None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -109,9 +122,15 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         kps, frame_of, desc = kps[:m].contiguous(), frame_of[:m].long(), desc[:m]
         o = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(torch.bincount(frame_of, minlength=n), 0)])
         q = feats.quantize(desc)                                # once; the f32 rows are not read again
+        votes = e_votes = rank = rank_votes = s_counts = None
         if mode == "retrieve":
             ea, eb = retrieved_edges(feats, q, o, frame_of, n, arg, ratio)
             deg_a, deg_b = arg, n - 1                           # image i is the a side of its own k edges, the b side of at most n - 1
+        elif mode == "select":
+            votes = vote_table(feats, q, o, frame_of, n, ratio)
+            ea, eb, e_votes, rank, rank_votes, s_counts = feats.select_edges(votes, arg, min_votes=1, skip_self=True, unique=True,
+                                                                             capacity=n * arg)
+            deg_a = deg_b = n - 1                               # (smaller, larger): an image meets every other one at most once
         else:
             ea, eb, deg = window_edges(n, arg) if mode == "window" else all_edges(n)
             ea, eb = torch.tensor(ea, dtype=torch.int32, device=dev), torch.tensor(eb, dtype=torch.int32, device=dev)
@@ -149,7 +168,8 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
                 table_keypoints=t_kps, link_offsets=l_off, link_a=l_a, link_b=l_b, link_edge=l_edge, edge_links=l_links,
-                link_counts=l_counts, link_keypoints_a=l_ka, link_keypoints_b=l_kb, match_kept=l_kept)
+                link_counts=l_counts, link_keypoints_a=l_ka, link_keypoints_b=l_kb, match_kept=l_kept, votes=votes,
+                edge_votes=e_votes, rank=rank, rank_votes=rank_votes, select_counts=s_counts)
 
 
 def main():
@@ -169,15 +189,15 @@ def main():
             min_inliers = int(args.pop(0))
         elif a == "--all":
             mode = "all"
-        elif a in ("--window", "--retrieve") and args and args[0].isdigit() and int(args[0]) > 0:
+        elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
             mode, arg = a[2:], int(args.pop(0))
         elif a.startswith("--"):
             paths = []
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (mode == "retrieve" and arg > len(paths) - 1):
-        print("Required arguments: [--window W | --all | --retrieve K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (mode in ("retrieve", "select") and arg > len(paths) - 1):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
               "number of images)", file=sys.stderr)
@@ -189,6 +209,9 @@ def main():
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
                            min_inliers=min_inliers)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
+    if mode == "select":                                        # the entries behind the edges name no image
+        kept = out["select_counts"].cpu().tolist()[0]
+        ea, eb, per_edge = ea[:kept], eb[:kept], per_edge[:kept]
     print("Extracted " + ", ".join(str(o[t + 1] - o[t]) for t in range(len(imgs))) + " keypoints")
     what = "one epipolar geometry" if fundamental else "one homography"
     for e in sorted(range(len(ea)), key=lambda e: (-per_edge[e][2], e)):

@@ -14,15 +14,15 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
-           "LINK_TABLE_LOCAL", "link_table_plan"]
+           "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan"]
 
 
 class Keypoint:
@@ -757,6 +757,48 @@ class LocalFeatures:
                                               offsets.data_ptr(), ptr(link_a), ptr(link_b), ptr(link_edge), ptr(edge_links),
                                               ptr(kept), counts.data_ptr(), s.cuda_stream)
         return offsets, link_a, link_b, link_edge, edge_links, kept, counts
+
+    def select_edges(self, votes, k, min_votes=1, skip_self=False, unique=False, capacity=None, stream=None):
+        """Candidate edges of a vote table (lf_mkd_select_edges_device): per row of votes [n_a, n_b] -- what vote_groups
+        returns, or any 32-bit integer tensor or array, read as uint32 -- the k columns with the most votes among those with
+        at least min_votes (0 admits columns without a vote) and, with skip_self, other than the row's own; larger votes
+        first, among equal votes the LOWER column first.  Every pick (i, j) is the edge (i, j); with unique=True (one pool,
+        n_a == n_b) an unordered pair that either image picked appears once, as (smaller, larger), so a mutual pick is not
+        matched twice.  capacity: the edges kept (None: n_a * k, which always suffices).
+        Returns device tensors (edge_a, edge_b, edge_votes, rank, rank_votes, counts): edge_a / edge_b [capacity] int32, the
+        edges in the order row, then rank, and behind them -1 (the bit pattern 0xFFFFFFFF), which names an empty image to
+        edge_layout / match_q8_edges / build_tracks / link_table -- pass them whole; edge_votes [capacity] int32, the votes of
+        the pick that made each edge (as a bit pattern), 0 behind them; rank [n_a, k] int32, the picks of every row in order,
+        -1 behind them; rank_votes [n_a, k] int32 (bit patterns), their votes; counts [4] int32: the edges kept, the edges
+        wanted, the picks and the rows with at least one pick.  Nothing is read back: asynchronous on `stream` (default:
+        torch's current stream on the handle's device), capturable once a call of this size has been made."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        k, min_votes = int(k), int(min_votes)
+        if not 0 <= min_votes < 2 ** 32:
+            raise RuntimeError("select_edges: min_votes must be in [0, 2^32)")
+        if not hasattr(votes, "data_ptr"):
+            votes = torch.from_numpy(np.ascontiguousarray(np.asarray(votes)).astype(np.uint32).view(np.int32))
+        if votes.dim() != 2 or votes.element_size() != 4 or votes.is_floating_point():
+            raise RuntimeError("select_edges: votes must be a 32-bit integer [n_a, n_b] table (LocalFeatures.vote_groups)")
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            v = votes.to(dev).contiguous()
+            n_a, n_b = v.shape
+            cap = n_a * max(k, 0) if capacity is None else int(capacity)
+            edge_a = torch.empty((cap,), dtype=torch.int32, device=dev)
+            edge_b = torch.empty((cap,), dtype=torch.int32, device=dev)
+            edge_votes = torch.empty((cap,), dtype=torch.int32, device=dev)
+            rank = torch.empty((n_a, max(k, 0)), dtype=torch.int32, device=dev)
+            rank_votes = torch.empty((n_a, max(k, 0)), dtype=torch.int32, device=dev)
+            counts = torch.empty((4,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x.numel() else None
+            with self._lock:
+                self._inner.select_edges_device(ptr(v), n_a, n_b, k, min_votes,
+                                                (SELECT_SKIP_SELF if skip_self else 0) | (SELECT_UNIQUE if unique else 0), cap,
+                                                ptr(rank), ptr(rank_votes), ptr(edge_a), ptr(edge_b), ptr(edge_votes),
+                                                counts.data_ptr(), s.cuda_stream)
+        return edge_a, edge_b, edge_votes, rank, rank_votes, counts
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

@@ -46,6 +46,7 @@ SYMBOLS = (
     "lf_mkd_build_tracks_device",
     "lf_mkd_track_table_plan", "lf_mkd_track_table_device", "lf_mkd_gather_track_rows_device",
     "lf_mkd_link_table_plan", "lf_mkd_link_table_device",
+    "lf_mkd_select_edges_plan", "lf_mkd_select_edges_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -53,6 +54,9 @@ TRACKS_ACCUMULATE = 1    # LF_MKD_TRACKS_ACCUMULATE: lf_mkd_build_tracks_device 
 TRACKS_DUP_TILE = 256    # LF_MKD_TRACKS_DUP_TILE: rows one workgroup of its d_track_dup launch owns
 TRACK_TABLE_CONSISTENT = 1   # LF_MKD_TRACK_TABLE_CONSISTENT: lf_mkd_track_table_device takes only tracks with dup == 0
 LINK_TABLE_LOCAL = 1     # LF_MKD_LINK_TABLE_LOCAL: lf_mkd_link_table_device writes rows local to their images, not pool rows
+SELECT_SKIP_SELF = 1     # LF_MKD_SELECT_SKIP_SELF: lf_mkd_select_edges_device does not offer column i to row i
+SELECT_UNIQUE = 2        # LF_MKD_SELECT_UNIQUE: one pool, every unordered pair at most once, as (smaller, larger)
+SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
 
@@ -162,6 +166,8 @@ def load_library():
     L.lf_mkd_gather_track_rows_device.argtypes = [vp, vp, u32, u64, vp, vp, u64, vp, vp]
     L.lf_mkd_link_table_plan.argtypes = [u64, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_link_table_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, u32, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_select_edges_plan.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_select_edges_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -280,6 +286,22 @@ def link_table_plan(ea_capacity, n_edges):
     if rc != 0:
         raise RuntimeError(f"lf_mkd_link_table_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return e.value, n.value, f.value, l.value, b.value
+
+
+def select_edges_plan(n_a, n_b, k, edge_capacity=None, flags=0):
+    """(compiled_k, rows_per_workgroup, workgroups, launches, scratch_bytes) of lf_mkd_select_edges_device for an
+    [n_a][n_b] vote table and k picks a row: the instantiation that serves k, the rows one workgroup of the selection takes
+    (4: one wave per row; 1: a workgroup per row or per segment of one), its grid, the launches of the call and the handle's
+    scratch (lf_mkd_select_edges_plan; needs no device).  edge_capacity None: n_a * k."""
+    ck, r, l = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    w, b = ctypes.c_uint64(), ctypes.c_uint64()
+    L = load_library()
+    cap = n_a * k if edge_capacity is None else edge_capacity
+    rc = L.lf_mkd_select_edges_plan(n_a, n_b, k, cap, flags, ctypes.byref(ck), ctypes.byref(r), ctypes.byref(w), ctypes.byref(l),
+                                    ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_select_edges_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return ck.value, r.value, w.value, l.value, b.value
 
 
 class Comm:
@@ -764,6 +786,16 @@ class MkdHandle:
             self._h, d_image_offsets, n_images, n_rows_total, d_edge_a, d_edge_b, d_edge_offsets_a, ea_capacity, n_edges, d_match,
             min_links, flags, link_capacity, d_link_offsets, d_link_a, d_link_b, d_link_edge, d_edge_links, d_match_kept,
             d_counts, s), "lf_mkd_link_table_device")
+
+    def select_edges_device(self, d_votes, n_a, n_b, k, min_votes, flags, edge_capacity, d_rank, d_rank_votes, d_edge_a, d_edge_b,
+                            d_edge_votes, d_counts, stream=None):
+        """lf_mkd_select_edges_device: per row of d_votes [n_a][n_b] uint32 its k best columns (larger votes first, among
+        equal ones the lower column) -- d_rank int32 / d_rank_votes uint32 [n_a][k] (nullable) -- and the edges those picks
+        make, d_edge_a / d_edge_b / d_edge_votes (nullable) uint32 [edge_capacity] padded with 0xFFFFFFFF, d_counts uint32 [4]
+        (device pointers; see include/lf_mkd.h).  flags: SELECT_SKIP_SELF, SELECT_UNIQUE."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_select_edges_device(
+            self._h, d_votes, n_a, n_b, k, min_votes, flags, edge_capacity, d_rank, d_rank_votes, d_edge_a, d_edge_b,
+            d_edge_votes, d_counts, s), "lf_mkd_select_edges_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
