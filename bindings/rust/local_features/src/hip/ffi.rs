@@ -292,6 +292,16 @@ extern "C" {
                                       flags: u32, edge_capacity: u64, d_rank: *mut i32, d_rank_votes: *mut u32,
                                       d_edge_a: *mut u32, d_edge_b: *mut u32, d_edge_votes: *mut u32, d_counts: *mut u32,
                                       stream: *mut c_void) -> c_int;
+    // covisibility tables: d_covis [n_images][n_images] = per pair of images the tracks of a track table (d_track_offsets
+    // [track_capacity + 1], d_obs_image [obs_capacity], d_table_counts: lf_mkd_track_table_device's outputs) that both see,
+    // the diagonal the tracks an image sees; the pairs d_edge_a / d_edge_b [n_edges] (nullable) name are set to 0; flags:
+    // LF_MKD_COVIS_ACCUMULATE; the plan is host only
+    pub fn lf_mkd_covisibility_plan(n_images: u32, track_capacity: u64, obs_capacity: u64, n_edges: u64, flags: u32,
+                                    form: *mut u32, workgroups: *mut u64, launches: *mut u32, scratch_bytes: *mut u64) -> c_int;
+    pub fn lf_mkd_covisibility_device(h: *mut lf_mkd, d_track_offsets: *const u64, track_capacity: u64, d_obs_image: *const u32,
+                                      obs_capacity: u64, d_table_counts: *const u32, n_images: u32, d_edge_a: *const u32,
+                                      d_edge_b: *const u32, n_edges: u64, flags: u32, d_covis: *mut u32,
+                                      stream: *mut c_void) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

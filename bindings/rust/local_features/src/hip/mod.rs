@@ -95,6 +95,10 @@ pub const SELECT_SKIP_SELF: u32 = 1;
 pub const SELECT_UNIQUE: u32 = 2;
 pub const SELECT_MAX_K: u32 = 32;
 
+/// `flags` of `lf_mkd_covisibility_device` (`include/lf_mkd.h`, `LF_MKD_COVIS_ACCUMULATE`): the table is added to what
+/// `d_covis` holds.
+pub const COVIS_ACCUMULATE: u32 = 1;
+
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
     fixed_params: BuildTimeParams,
@@ -536,6 +540,36 @@ impl LocalFeaturesHip {
         rows.truncate(counts[1] as usize);
         images.truncate(counts[1] as usize);
         Ok((offsets, rows, images))
+    }
+
+    /// The covisibility table of a track table (`lf_mkd_covisibility_device`): `offsets` and `images` are what `track_table`
+    /// returned; entry `[i * n_images + j]` of the result is the number of tracks images i and j both see, `[i * n_images + i]`
+    /// the number of tracks image i sees.  The two entries of every pair in `masked` (the pairs a round of matching used) are
+    /// set to 0, so that what is left are the pairs that share tracks without having been matched.
+    pub fn covisibility(&mut self, offsets: &[u64], images: &[u32], n_images: usize, masked: &[(u32, u32)])
+                        -> Result<Vec<u32>, Error> {
+        if offsets.is_empty() || n_images * n_images > i32::MAX as usize {
+            return Err(Error::BadArgument("covisibility: offsets needs tracks + 1 entries, n_images^2 must be below 2^31".into()));
+        }
+        let mut covis = vec![0u32; n_images * n_images];
+        if n_images == 0 { return Ok(covis); }
+        let counts = [(offsets.len() - 1) as u32, images.len() as u32, 0, 0];
+        let (ea, eb): (Vec<u32>, Vec<u32>) = masked.iter().cloned().unzip();
+        // SAFETY: device buffers sized as declared; the capacities, n_edges and n_images bound what is read and written
+        unsafe {
+            let d_off = DeviceBuffer::from_slice(offsets)?;
+            let d_images = DeviceBuffer::from_slice(if images.is_empty() { &[0u32][..] } else { images })?;
+            let d_counts = DeviceBuffer::from_slice(&counts)?;
+            let (d_ea, d_eb) = (DeviceBuffer::from_slice(if ea.is_empty() { &[0u32][..] } else { &ea[..] })?,
+                                DeviceBuffer::from_slice(if eb.is_empty() { &[0u32][..] } else { &eb[..] })?);
+            let d_covis = DeviceBuffer::<u32>::new(covis.len())?;
+            check(self.h, ffi::lf_mkd_covisibility_device(
+                self.h, d_off.as_ptr(), (offsets.len() - 1) as u64, d_images.as_ptr(), images.len() as u64, d_counts.as_ptr(),
+                n_images as u32, d_ea.as_ptr(), d_eb.as_ptr(), ea.len() as u64, 0, d_covis.as_mut_ptr(), std::ptr::null_mut()))?;
+            check(self.h, ffi::lf_mkd_synchronize(self.h))?;
+            d_covis.download(&mut covis)?;
+        }
+        Ok(covis)
     }
 
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches

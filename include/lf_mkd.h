@@ -1016,6 +1016,65 @@ int lf_mkd_select_edges_device(lf_mkd *h, const uint32_t *d_votes, uint32_t n_a,
 #define LF_MKD_SELECT_SKIP_SELF (1u)  /* column i is no candidate of row i */
 #define LF_MKD_SELECT_UNIQUE (2u)     /* one pool (n_a == n_b): every unordered pair at most once, as (smaller, larger) */
 #define LF_MKD_SELECT_MAX_K (32)
+/* lf_mkd_covisibility_device turns a track table into the COVISIBILITY TABLE: per pair of images, how many tracks they share --
+ * what structure from motion, keyframe graphs, local bundle-adjustment windows and next-best-view choice read first, and, with
+ * the pairs already matched zeroed, the [images][images] table lf_mkd_select_edges_device takes as it is for a second round
+ * of candidate edges.  Inputs are a table as lf_mkd_track_table_device leaves it: d_track_offsets (uint64, track_capacity + 1
+ * entries), d_obs_image (uint32, obs_capacity entries) and that call's d_counts as d_table_counts.
+ *   reading     T = min(d_table_counts[0], track_capacity), O = min(d_table_counts[1], obs_capacity).  Track t < T is the range
+ *               [lo, hi) of d_track_offsets[t], d_track_offsets[t + 1], each read against O as a pair is read against a total:
+ *               beyond O is O, an inverted range is empty.
+ *   counted     position k of track t is COUNTED iff (k == lo or d_obs_image[k] != d_obs_image[k - 1]) and d_obs_image[k] <
+ *               n_images.  The comparison with k - 1 is with the raw entry, before the range test; 0xFFFFFFFF and any other id
+ *               at or beyond n_images is never counted.  A table made over image offsets that do not decrease lists a
+ *               track's images in non-decreasing order, and the rule is then "one count per distinct image of the track",
+ *               inconsistent tracks included; for any other contents the rule is still exactly this rule.
+ *   table       C[i][j], i != j: the number of ordered pairs (p, q) of distinct counted positions of one track with images i
+ *               and j, summed over the tracks; C[i][i]: the number of counted positions with image i.  For such tables:
+ *               C[i][j] = the tracks seen in both i and j, C[i][i] = the tracks seen in i, C symmetric.
+ *   d_covis     uint32 [n_images][n_images]; exactly n_images^2 entries are written: C mod 2^32.  Under
+ *               LF_MKD_COVIS_ACCUMULATE the table is not zeroed and C is added to what it holds, mod 2^32: the tracks of one
+ *               table given in several calls, in any split, yield == one call with all of them.
+ *   mask        d_edge_a / d_edge_b, uint32 [n_edges], optional (both NULL iff n_edges == 0): after the counting, for every
+ *               e < n_edges with both ids < n_images, d_covis[a][b] and d_covis[b][a] are set to 0; other entries are
+ *               skipped, so lf_mkd_select_edges_device's padded lists pass whole.  Self edges, repeated edges and (j, i)
+ *               beside (i, j) are ordinary input.  Under LF_MKD_COVIS_ACCUMULATE the mask applies to the sum.
+ * For offsets that do not decrease (after the clamp to O) all of this holds with ==, whatever d_obs_image holds.  For other
+ * offsets d_covis is unspecified; the call still ends, and nothing is read or written at or beyond track_capacity + 1,
+ * obs_capacity, n_edges or n_images^2.  n_images == 0 is LF_MKD_OK and writes nothing; T == 0 still zeroes and masks.
+ * How (csrc/mkd_covisibility.hip): a group of `form` lanes (4 .. 64) holds a track's positions one per lane, a chunk at a time;
+ * the counted lanes of one chunk are visited through the set bits of a ballot, their image is broadcast by a lane permute and
+ * every counted lane of the other chunk adds one pair, so a track of L distinct images costs L ceil(L / form) steps of full
+ * lanes for its L^2 adds.  Tracks of more than 16 form positions are marked in a bitmap of the observation array (the scratch)
+ * and taken by a second launch, a wave per 64 marked positions against the whole track.  COST BOUND: only counted positions
+ * cost a step, so one track of L positions with D distinct images -- a table made without LF_MKD_TRACK_TABLE_CONSISTENT can
+ * hold one track of every row -- costs at most D ceil(L / 64) steps and D ceil(L / 64) loads of 64 positions: (distinct
+ * images) x (track length), never length squared.  Integer atomic adds only, so the table is exact and independent of the run,
+ * the CU count and the form; with at most 64 images a workgroup counts into a private table in LDS and adds it once
+ * (LF_MKD_COVIS_FORM_LDS in the plan's form).  No workgroup waits for another.
+ * Launches (lf_mkd_covisibility_plan's `launches`): zero (a kernel, not a memset node, see lf_mkd_vote_groups_device; under
+ * LF_MKD_COVIS_ACCUMULATE it zeroes the bitmap alone), the two counting launches (none when a capacity is 0), the mask
+ * (n_edges > 0): 1 to 4, none for n_images == 0 -- a fixed number, sized by the host from the scalar arguments only; no device
+ * array is ever read by the host.  Asynchronous on `stream` (NULL: the handle's own), no host synchronisation; no allocation
+ * once the handle's scratch has grown to the largest plan seen (4 bytes per 2048 observations), so a warmed-up call is
+ * capturable in a hipGraph.  The scratch belongs to the handle: calls of one handle are stream-ordered.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "covisibility_device: " and is reachable
+ * through lf_mkd_last_error(NULL) when h is NULL): a null handle; a null d_covis with n_images > 0; a null d_table_counts; a
+ * null d_track_offsets; a null d_obs_image with obs_capacity > 0; only one of the edge arrays, or n_edges > 0 without them;
+ * unknown flag bits; offsets not 8-byte aligned or another array not 4-byte aligned; n_images^2 above 2^31 - 1
+ * (lf_mkd_vote_groups_device's limit); track_capacity or obs_capacity above 2^31 - 1. */
+/* host only, no device, no handle: what the device call will do, and the only place that knows it -- form = the lanes that
+ * share a track (4, 8, 16, 32, 64: the smallest that holds twice the mean track length the capacities allow, never more than
+ * the images), plus LF_MKD_COVIS_FORM_LDS iff workgroups count in LDS first; workgroups = the grid of the first counting
+ * launch (with LF_MKD_COVIS_FORM_LDS at most 2^22 / n_images^2, or 256: every workgroup adds its table at its end); launches and scratch_bytes = what the device call does and grows the handle to; all 0 for n_images == 0; any output
+ * may be NULL.  LF_MKD_ERR_BAD_ARG ("covisibility_plan: "): the device call's refusals that concern the scalars. */
+int lf_mkd_covisibility_plan(uint32_t n_images, uint64_t track_capacity, uint64_t obs_capacity, uint64_t n_edges, uint32_t flags,
+                             uint32_t *form, uint64_t *workgroups, uint32_t *launches, uint64_t *scratch_bytes);
+int lf_mkd_covisibility_device(lf_mkd *h, const uint64_t *d_track_offsets, uint64_t track_capacity, const uint32_t *d_obs_image,
+                               uint64_t obs_capacity, const uint32_t *d_table_counts, uint32_t n_images, const uint32_t *d_edge_a,
+                               const uint32_t *d_edge_b, uint64_t n_edges, uint32_t flags, uint32_t *d_covis, void *stream);
+#define LF_MKD_COVIS_ACCUMULATE (1u)  /* flags: d_covis is not zeroed, the table is added to what it holds */
+#define LF_MKD_COVIS_FORM_LDS (256u)  /* in the plan's form: a workgroup counts into a private table in LDS first */
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

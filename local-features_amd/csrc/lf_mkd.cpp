@@ -244,6 +244,8 @@ struct lf_mkd {
     HipArray<unsigned char> d_link_table;
     // lf_mkd_select_edges_device's scratch (select_edges_plan's scratch_bytes), in the same way
     HipArray<unsigned char> d_select_edges;
+    // lf_mkd_covisibility_device's scratch (covisibility_plan's scratch_bytes), in the same way
+    HipArray<unsigned char> d_covisibility;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;
@@ -2462,6 +2464,54 @@ int lf_mkd_select_edges_device(lf_mkd *h, const uint32_t *d_votes, uint32_t n_a,
     launch_select_edges(plan, plan.scratch_bytes ? h->d_select_edges.get() : nullptr, d_votes, n_a, n_b, k, min_votes,
                         (flags & LF_MKD_SELECT_SKIP_SELF) != 0, (flags & LF_MKD_SELECT_UNIQUE) != 0, edge_capacity, d_rank,
                         d_rank_votes, d_edge_a, d_edge_b, d_edge_votes, d_counts, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// Covisibility tables (csrc/mkd_covisibility.hip).  Every refusal comes before the handle is looked at.
+static const char *covisibility_sizes(uint32_t n_images, uint64_t track_capacity, uint64_t obs_capacity, uint32_t flags) {
+    if (flags & ~LF_MKD_COVIS_ACCUMULATE) return "unknown flag bits";
+    if ((uint64_t)n_images * n_images > kEdgeMax) return "a table of more than 2^31 - 1 entries (n_images^2)";
+    if (track_capacity > kEdgeMax || obs_capacity > kEdgeMax) return "track_capacity or obs_capacity above 2^31 - 1";
+    return nullptr;
+}
+
+int lf_mkd_covisibility_plan(uint32_t n_images, uint64_t track_capacity, uint64_t obs_capacity, uint64_t n_edges, uint32_t flags,
+                             uint32_t *form, uint64_t *workgroups, uint32_t *launches, uint64_t *scratch_bytes) {
+    if (const char *msg = covisibility_sizes(n_images, track_capacity, obs_capacity, flags))
+        return q8_refuse(nullptr, "covisibility_plan", msg);
+    const CovisibilityPlan p = covisibility_plan(n_images, track_capacity, obs_capacity, n_edges);
+    if (form) *form = p.group | (p.lds ? LF_MKD_COVIS_FORM_LDS : 0u);
+    if (workgroups) *workgroups = p.short_blocks;
+    if (launches) *launches = p.launches;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_covisibility_device(lf_mkd *h, const uint64_t *d_track_offsets, uint64_t track_capacity, const uint32_t *d_obs_image,
+                               uint64_t obs_capacity, const uint32_t *d_table_counts, uint32_t n_images, const uint32_t *d_edge_a,
+                               const uint32_t *d_edge_b, uint64_t n_edges, uint32_t flags, uint32_t *d_covis, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (n_images && !d_covis) msg = "null d_covis";
+    else if (!d_table_counts) msg = "null d_table_counts";
+    else if (!d_track_offsets) msg = "null d_track_offsets";
+    else if (obs_capacity && !d_obs_image) msg = "null d_obs_image";
+    else if (!d_edge_a != !d_edge_b) msg = "only one of d_edge_a and d_edge_b";
+    else if (n_edges && !d_edge_a) msg = "n_edges > 0 without d_edge_a and d_edge_b";
+    else if (at(d_track_offsets) & 7) msg = "d_track_offsets must be 8-byte aligned";
+    else if ((at(d_obs_image) | at(d_table_counts) | at(d_edge_a) | at(d_edge_b) | at(d_covis)) & 3)
+        msg = "the observation, count, edge and table arrays must be 4-byte aligned";
+    else if (!(msg = covisibility_sizes(n_images, track_capacity, obs_capacity, flags)) && !h) msg = "null handle";
+    if (msg) return q8_refuse(h, "covisibility_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const CovisibilityPlan plan = covisibility_plan(n_images, track_capacity, obs_capacity, n_edges);
+    if (plan.scratch_bytes)
+        if (int rc = grow(h, h->d_covisibility, plan.scratch_bytes)) return rc;
+    launch_covisibility(plan, plan.scratch_bytes ? h->d_covisibility.get() : nullptr, d_track_offsets, track_capacity,
+                        d_obs_image, obs_capacity, d_table_counts, n_images, d_edge_a, d_edge_b, n_edges,
+                        (flags & LF_MKD_COVIS_ACCUMULATE) != 0, d_covis, stream ? static_cast<hipStream_t>(stream) : h->stream);
     LF_HIP(h, hipGetLastError());
     return LF_MKD_OK;
 }

@@ -329,6 +329,21 @@ void launch_select_edges(const SelectEdgesPlan &plan, unsigned char *scratch, co
                          unsigned k, unsigned min_votes, bool skip_self, bool unique, uint64_t edge_capacity, int *rank,
                          unsigned *rank_votes, unsigned *edge_a, unsigned *edge_b, unsigned *edge_votes, unsigned *counts,
                          hipStream_t stream);
+// covisibility tables (csrc/mkd_covisibility.hip, lf_mkd_covisibility_device).  The plan is the one place that knows the forms:
+// group = the lanes that share a track in cv_short (4 .. 64: the smallest power of two that holds twice the mean track length
+// the capacities allow, never more than the images there are); lds = 1 iff a workgroup counts into a private table in LDS
+// first (n_images <= LF_COVIS_LDS_IMAGES = 64; its grid is then held to 2^22 / n_images^2 workgroups, at least 256); the grids; bitmap_words = the scratch: one bit per 64 positions of the observation
+// array, set for the chunks of the tracks cv_short leaves to cv_long (more than 16 * group positions).
+// Launches: n_images == 0: none.  Otherwise zero, short and long (not with a capacity of 0), mask (n_edges > 0 only).
+struct CovisibilityPlan {
+    unsigned group, lds, zero_blocks, short_blocks, long_blocks, mask_blocks, launches;
+    uint64_t bitmap_words, scratch_bytes;
+};
+CovisibilityPlan covisibility_plan(unsigned n_images, uint64_t track_capacity, uint64_t obs_capacity, uint64_t n_edges);
+void launch_covisibility(const CovisibilityPlan &plan, unsigned char *scratch, const uint64_t *track_offsets,
+                         uint64_t track_capacity, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts,
+                         unsigned n_images, const unsigned *edge_a, const unsigned *edge_b, uint64_t n_edges, bool accumulate,
+                         unsigned *covis, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -29,12 +29,19 @@ descriptor row is copied for it.
   sides' keypoints in its order
   with --min-inliers M (which implies the link       the same call with min_links = M: edges with fewer verified matches are
   table) the tracks of the supported edges only      dropped on the device, and --tracks / --table build from its pruned matches
+  with --expand K (which implies --table) a second   LocalFeatures.covisibility (lf_mkd_covisibility_device) of the track table with
+  round: per image the K images it shares most       the first round's edges zeroed -- tracks tie together images that were never
+  tracks with without having been matched against    matched against each other --, LocalFeatures.select_edges on that table
+  them (at least --min-shared M of them, default     (min_votes = M, skip_self, unique), the same matcher and verifier on the
+  8), matched and verified like the first round,     proposed edges, their links ADDED to the forest (build_tracks(into=track)),
+  and the tracks of both rounds together             then the statistics and the table once more
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
 of the keypoints that sit in a consistent track; with --table also the number of tracks and observations in the table and the
 first three tracks as image:x,y lists; with --pairs also the number of edges and correspondences in the link table and the
-first three correspondences of the best edge as x,y -> x,y.  Nothing is read back before those counts: the
+first three correspondences of the best edge as x,y -> x,y; with --expand also one line with the proposed edges and how many of
+them kept a verified match, and the track lines once more for the expanded forest.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -86,7 +93,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -104,7 +111,13 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     kept edges alone, from which the tracks are then built; without, those nine are None.  In mode "select" edge_a / edge_b have
     n * K entries, -1 behind the edges (an empty image to every call here), and votes [n, n], edge_votes [n * K], rank and
     rank_votes [n, K] and select_counts [4] are what LocalFeatures.select_edges took and returned; otherwise those five are
-    None."""
+    None.  With `expand` (an int K; implies `table`) a second round of edges: covisibility [n, n], the tracks every two images
+    share in the first round's table with the first round's edges zeroed (LocalFeatures.covisibility); expand_edge_a /
+    expand_edge_b [n * K] and expand_counts [4], what LocalFeatures.select_edges proposes from it (min_votes = min_shared,
+    skip_self, unique); expand_layout_a, expand_verified and expand_per_edge, the proposed edges matched and verified like the
+    first round's; first_round, a dict with the first round's track_counts and table_* entries -- and track, track_len,
+    track_dup, track_counts and the table_* entries are then those of the forest with both rounds' links (the second round's
+    are added in place: build_tracks(into=track)).  Without, those seven are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -155,12 +168,41 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             l_ka, l_kb = feats.gather_track_rows(kps, l_a, l_counts), feats.gather_track_rows(kps, l_b, l_counts)
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
-        if tracks or table:
+        if tracks or table or expand:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
             track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
                                         (track_len * (two & ok)).sum()])
-        if table:
+        if table or expand:
+            t_off, t_rows, t_img, t_row_track, t_counts = feats.track_table(track, track_len, track_dup, image_offsets=o, min_len=2,
+                                                                            consistent=True)
+            t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
+        covis = x_ea = x_eb = x_counts = x_la = x_ver = x_per_edge = first = None
+        if expand:
+            first = dict(track_counts=track_counts, table_offsets=t_off, table_rows=t_rows, table_images=t_img,
+                         table_row_track=t_row_track, table_counts=t_counts, table_keypoints=t_kps)
+            # the tracks two images share, the pairs already matched zeroed: what is left was never tried
+            covis = feats.covisibility(t_off, t_img, t_counts, n, edges=(ea, eb))
+            x_ea, x_eb, _, _, _, x_counts = feats.select_edges(covis, expand, min_votes=min_shared, skip_self=True, unique=True,
+                                                               capacity=n * expand)
+            x_edges = int(x_ea.numel())
+            cap_x = (n - 1) * m                                 # (smaller, larger): an image meets every other one at most once
+            x_ab, _, _, _, x_la, x_lb = feats.match_q8_edges(q, o, q, o, x_ea, x_eb, ratio=ratio, mutual=True, capacity_a=cap_x,
+                                                             capacity_b=cap_x)
+            x_ka = feats.gather_edge_rows(kps, o, x_ea, x_la, capacity=cap_x)
+            x_kb = feats.gather_edge_rows(kps, o, x_eb, x_lb, capacity=cap_x)
+            _, x_ver, _ = verify(x_ka, x_la, x_kb, x_lb, x_ab, seed=seed)
+            x_edge_of = torch.searchsorted(x_la, torch.arange(cap_x, device=dev), right=True) - 1
+            x_count = lambda mask: torch.bincount(x_edge_of[mask], minlength=x_edges + 1)[:x_edges]
+            x_per_edge = torch.stack([x_count(x_ab >= 0), x_count(x_ver >= 0)], dim=1)
+            x_links = x_ver
+            if min_inliers is not None:
+                x_links = feats.link_table(o, x_ea, x_eb, x_la, x_ver, min_links=min_inliers, capacity=cap_x, n_rows=m,
+                                           kept_match=True)[5]
+            track, track_len, track_dup = feats.build_tracks(o, x_ea, x_eb, x_la, x_links, capacity=cap_x, into=track)
+            two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
+            track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
+                                        (track_len * (two & ok)).sum()])
             t_off, t_rows, t_img, t_row_track, t_counts = feats.track_table(track, track_len, track_dup, image_offsets=o, min_len=2,
                                                                             consistent=True)
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
@@ -169,12 +211,15 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
                 table_keypoints=t_kps, link_offsets=l_off, link_a=l_a, link_b=l_b, link_edge=l_edge, edge_links=l_links,
                 link_counts=l_counts, link_keypoints_a=l_ka, link_keypoints_b=l_kb, match_kept=l_kept, votes=votes,
-                edge_votes=e_votes, rank=rank, rank_votes=rank_votes, select_counts=s_counts)
+                edge_votes=e_votes, rank=rank, rank_votes=rank_votes, select_counts=s_counts, covisibility=covis,
+                expand_edge_a=x_ea, expand_edge_b=x_eb, expand_counts=x_counts, expand_layout_a=x_la, expand_verified=x_ver,
+                expand_per_edge=x_per_edge, first_round=first)
 
 
 def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
+    expand, min_shared = None, 8
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -187,6 +232,11 @@ def main():
             pairs = True
         elif a == "--min-inliers" and args and args[0].isdigit():
             min_inliers = int(args.pop(0))
+        elif a == "--expand" and args and args[0].isdigit() and int(args[0]) > 0:
+            tracks = table = True
+            expand = int(args.pop(0))
+        elif a == "--min-shared" and args and args[0].isdigit():
+            min_shared = int(args.pop(0))
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -196,8 +246,8 @@ def main():
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (mode in ("retrieve", "select") and arg > len(paths) - 1):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
               "number of images)", file=sys.stderr)
@@ -207,7 +257,7 @@ def main():
         print("the images must have one size", file=sys.stderr)
         return 1
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -217,18 +267,22 @@ def main():
     for e in sorted(range(len(ea)), key=lambda e: (-per_edge[e][2], e)):
         raw, mutual, inl = per_edge[e]
         print(f"Edge {ea[e] + 1} -> {eb[e] + 1}: {raw} matches, {mutual} mutual, {inl} agree with {what}")
-    if tracks:
-        n2, c2, n3, c3, longest, inside = out["track_counts"].cpu().tolist()
-        print(f"Tracks: {n2} of length >= 2 ({c2} consistent), {n3} of length >= 3 ({c3} consistent)")
-        print(f"Longest track: {longest} keypoints; {100.0 * inside / max(o[-1], 1):.1f} % of the keypoints sit in a consistent track "
-              "of length >= 2")
-    if table:
-        n_tracks, n_obs = out["table_counts"].cpu().tolist()[:2]
-        print(f"Track table: {n_tracks} tracks, {n_obs} observations (consistent, length >= 2)")
-        first = out["table_offsets"][:min(n_tracks, 3) + 1].cpu().tolist()
-        images, xy = out["table_images"][:first[-1]].cpu().tolist(), out["table_keypoints"][:first[-1], :2].cpu().tolist()
-        for k in range(len(first) - 1):
-            print(f"Track {k + 1}: " + " ".join(f"{images[i] + 1}:{xy[i][0]:.1f},{xy[i][1]:.1f}" for i in range(first[k], first[k + 1])))
+
+    def track_lines(r):
+        if tracks:
+            n2, c2, n3, c3, longest, inside = r["track_counts"].cpu().tolist()
+            print(f"Tracks: {n2} of length >= 2 ({c2} consistent), {n3} of length >= 3 ({c3} consistent)")
+            print(f"Longest track: {longest} keypoints; {100.0 * inside / max(o[-1], 1):.1f} % of the keypoints sit in a consistent track "
+                  "of length >= 2")
+        if table:
+            n_tracks, n_obs = r["table_counts"].cpu().tolist()[:2]
+            print(f"Track table: {n_tracks} tracks, {n_obs} observations (consistent, length >= 2)")
+            first = r["table_offsets"][:min(n_tracks, 3) + 1].cpu().tolist()
+            images, xy = r["table_images"][:first[-1]].cpu().tolist(), r["table_keypoints"][:first[-1], :2].cpu().tolist()
+            for k in range(len(first) - 1):
+                print(f"Track {k + 1}: " + " ".join(f"{images[i] + 1}:{xy[i][0]:.1f},{xy[i][1]:.1f}" for i in range(first[k], first[k + 1])))
+
+    track_lines(out["first_round"] if expand else out)
     if pairs:
         n_kept, n_links = out["link_counts"].cpu().tolist()[:2]
         print(f"Link table: {n_kept} edges, {n_links} correspondences")
@@ -238,6 +292,12 @@ def main():
         xa, xb = out["link_keypoints_a"][lo:hi, :2].cpu().tolist(), out["link_keypoints_b"][lo:hi, :2].cpu().tolist()
         for a, b in zip(xa, xb):
             print(f"Edge {ea[best] + 1} -> {eb[best] + 1}: {a[0]:.1f},{a[1]:.1f} -> {b[0]:.1f},{b[1]:.1f}")
+    if expand:
+        proposed = out["expand_counts"].cpu().tolist()[0]
+        kept = int((out["expand_per_edge"][:proposed, 1] > 0).sum())
+        print(f"Expanded: {proposed} edges proposed from the tracks two unmatched images share (at least {min_shared}), "
+              f"{kept} of them with verified matches")
+        track_lines(out)
     return 0
 
 

@@ -14,15 +14,16 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
            "load_library", "model_path", "plan_upload", "Comm", "comm_unique_id", "COMM_ID_BYTES", "GATHER_DIRECT", "GATHER_RING",
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
-           "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan"]
+           "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan",
+           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "covisibility_plan"]
 
 
 class Keypoint:
@@ -799,6 +800,49 @@ class LocalFeatures:
                                                 ptr(rank), ptr(rank_votes), ptr(edge_a), ptr(edge_b), ptr(edge_votes),
                                                 counts.data_ptr(), s.cuda_stream)
         return edge_a, edge_b, edge_votes, rank, rank_votes, counts
+
+    def covisibility(self, offsets, images, counts, n_images, edges=None, into=None, stream=None):
+        """The covisibility table of a track table (lf_mkd_covisibility_device): per pair of images the number of tracks both
+        see, on the diagonal the number of tracks an image sees.  offsets [track_capacity + 1] int64, images [obs_capacity]
+        int32 and counts are what track_table returned (with image_offsets given); an observation counts once per run of
+        equal images in its track, ids outside 0 .. n_images - 1 (track_table's -1) never.  edges: (edge_a, edge_b), 32-bit
+        ids of pairs whose two entries are set to 0 afterwards -- the list a round of matching used, select_edges' padded
+        arrays as they are --, so that what is left are the pairs that share tracks without having been matched: the table
+        select_edges takes for a second round.  into: an earlier call's table [n_images, n_images], to which the counts are
+        ADDED in place (LF_MKD_COVIS_ACCUMULATE; the mask then applies to the sum) and which is returned; the tracks of one
+        table given in several calls yield the table of one call with all of them.
+        Returns an int32 device tensor [n_images, n_images] (counts as bit patterns of uint32).  Nothing is read back:
+        asynchronous on `stream` (default: torch's current stream on the handle's device), capturable once a call of this
+        size has been made."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        n = int(n_images)
+        if n < 0:
+            raise RuntimeError("covisibility: n_images must not be negative")
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.dim() == 1 and x.is_contiguous()
+            if not (ok(offsets, torch.int64) and offsets.numel() >= 1 and ok(images, torch.int32) and ok(counts, torch.int32)
+                    and counts.numel() >= 2):
+                raise RuntimeError("covisibility: offsets (int64), images (int32) and counts (int32) must be contiguous device "
+                                   "tensors as track_table returned them")
+            ea = eb = None
+            if edges is not None:
+                ea, eb = self._words(edges[0], dev), self._words(edges[1], dev)
+                if ea.numel() != eb.numel():
+                    raise RuntimeError("covisibility: edges needs one id per edge in each of its two arrays")
+            if into is not None:
+                if not (into.is_cuda and into.dtype == torch.int32 and tuple(into.shape) == (n, n) and into.is_contiguous()):
+                    raise RuntimeError("covisibility: into must be a contiguous int32 [n_images, n_images] device tensor")
+                covis = into
+            else:
+                covis = torch.empty((n, n), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.covisibility_device(offsets.data_ptr(), offsets.numel() - 1, ptr(images), images.numel(),
+                                                counts.data_ptr(), n, ptr(ea), ptr(eb), ea.numel() if ea is not None else 0,
+                                                COVIS_ACCUMULATE if into is not None else 0, ptr(covis), s.cuda_stream)
+        return covis
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

@@ -47,6 +47,7 @@ SYMBOLS = (
     "lf_mkd_track_table_plan", "lf_mkd_track_table_device", "lf_mkd_gather_track_rows_device",
     "lf_mkd_link_table_plan", "lf_mkd_link_table_device",
     "lf_mkd_select_edges_plan", "lf_mkd_select_edges_device",
+    "lf_mkd_covisibility_plan", "lf_mkd_covisibility_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -56,6 +57,8 @@ TRACK_TABLE_CONSISTENT = 1   # LF_MKD_TRACK_TABLE_CONSISTENT: lf_mkd_track_table
 LINK_TABLE_LOCAL = 1     # LF_MKD_LINK_TABLE_LOCAL: lf_mkd_link_table_device writes rows local to their images, not pool rows
 SELECT_SKIP_SELF = 1     # LF_MKD_SELECT_SKIP_SELF: lf_mkd_select_edges_device does not offer column i to row i
 SELECT_UNIQUE = 2        # LF_MKD_SELECT_UNIQUE: one pool, every unordered pair at most once, as (smaller, larger)
+COVIS_ACCUMULATE = 1     # LF_MKD_COVIS_ACCUMULATE: lf_mkd_covisibility_device adds to what d_covis holds
+COVIS_FORM_LDS = 256     # LF_MKD_COVIS_FORM_LDS: in covisibility_plan's form, workgroups count in LDS first
 SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
 COMM_ID_BYTES = 128
 GATHER_DIRECT, GATHER_RING = 0, 1
@@ -168,6 +171,8 @@ def load_library():
     L.lf_mkd_link_table_device.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, u32, vp, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_select_edges_plan.argtypes = [u32, u32, u32, u64, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_select_edges_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_covisibility_plan.argtypes = [u32, u64, u64, u64, u32, vp, vp, vp, vp]
+    L.lf_mkd_covisibility_device.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, vp, u64, u32, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -302,6 +307,20 @@ def select_edges_plan(n_a, n_b, k, edge_capacity=None, flags=0):
     if rc != 0:
         raise RuntimeError(f"lf_mkd_select_edges_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return ck.value, r.value, w.value, l.value, b.value
+
+
+def covisibility_plan(n_images, track_capacity, obs_capacity, n_edges=0, flags=0):
+    """(form, workgroups, launches, scratch_bytes) of lf_mkd_covisibility_device: the lanes that share a track (4 .. 64) plus
+    COVIS_FORM_LDS iff workgroups count into a private table in LDS first, the grid of the first counting launch, the launches
+    of the call and the handle's scratch (lf_mkd_covisibility_plan; needs no device)."""
+    f, l = ctypes.c_uint32(), ctypes.c_uint32()
+    w, b = ctypes.c_uint64(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_covisibility_plan(n_images, track_capacity, obs_capacity, n_edges, flags, ctypes.byref(f), ctypes.byref(w),
+                                    ctypes.byref(l), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_covisibility_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return f.value, w.value, l.value, b.value
 
 
 class Comm:
@@ -796,6 +815,16 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_select_edges_device(
             self._h, d_votes, n_a, n_b, k, min_votes, flags, edge_capacity, d_rank, d_rank_votes, d_edge_a, d_edge_b,
             d_edge_votes, d_counts, s), "lf_mkd_select_edges_device")
+
+    def covisibility_device(self, d_track_offsets, track_capacity, d_obs_image, obs_capacity, d_table_counts, n_images, d_edge_a,
+                            d_edge_b, n_edges, flags, d_covis, stream=None):
+        """lf_mkd_covisibility_device: d_covis uint32 [n_images][n_images] = per pair of images the tracks of the table
+        d_track_offsets uint64 [track_capacity + 1] / d_obs_image uint32 [obs_capacity] / d_table_counts (lf_mkd_track_table_device's
+        outputs) that both see, the diagonal the tracks an image sees; the pairs d_edge_a / d_edge_b uint32 [n_edges] (nullable)
+        name are zeroed (device pointers; see include/lf_mkd.h).  flags: COVIS_ACCUMULATE."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_covisibility_device(
+            self._h, d_track_offsets, track_capacity, d_obs_image, obs_capacity, d_table_counts, n_images, d_edge_a, d_edge_b,
+            n_edges, flags, d_covis, s), "lf_mkd_covisibility_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
