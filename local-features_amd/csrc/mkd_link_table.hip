@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/lf_mkd.h"
+#include "mkd_block_scan.h"
 #include "mkd_device.h"
 #include "mkd_match_small.h"        // pair_rows, image_rows, last_pair_at_or_before
 
@@ -47,27 +48,6 @@ constexpr int kEdgeThreads = 256;                             // lt_zero, lt_cut
 constexpr unsigned kNoEdge = 0xFFFFFFFFu;                     // a slot in front of the first edge
 constexpr unsigned kFirst = 0x80000000u;                      // slot_edge: the edge's first slot (n_edges < 2^31: the grid)
 static_assert(kFan >= 64 && kFan <= 1024 && (kFan & (kFan - 1)) == 0, "one value a thread, a power of two");
-
-// Exclusive prefix sum over the workgroup's NT threads, in thread order, and the total.  s: 2 * NT elements of LDS.
-template <int NT>
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *s, uint64_t &total) {
-    const int t = threadIdx.x;
-    int cur = 0;
-    s[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < NT; off <<= 1) {
-        uint64_t x = s[cur * NT + t];
-        if (t >= off) x += s[cur * NT + t - off];
-        s[(cur ^ 1) * NT + t] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    const uint64_t incl = s[cur * NT + t];
-    total = s[cur * NT + NT - 1];
-    __syncthreads();                                          // s may be used again at once
-    return incl - v;
-}
 
 // what a slot is: its edge, the first entry and the number of entries of the edge, the slot's first row within the edge
 struct Slot {
@@ -181,8 +161,8 @@ __global__ __launch_bounds__(kFan) void lt_up(const unsigned *__restrict__ slot_
         }
     }
     uint64_t total_links, total_edges;
-    block_scan<kFan>(links, s_scan, total_links);
-    block_scan<kFan>(edges, s_scan, total_edges);
+    block_scan<uint64_t, kFan>(links, s_scan, total_links);
+    block_scan<uint64_t, kFan>(edges, s_scan, total_edges);
     if (threadIdx.x == 0) {
         out_links[blockIdx.x] = total_links;
         out_edges[blockIdx.x] = (unsigned)total_edges;           // (at most one a slot, slots < 2^31)
@@ -210,8 +190,8 @@ __global__ __launch_bounds__(kFan) void lt_down(const unsigned *__restrict__ slo
         }
     }
     uint64_t total_links, total_edges;
-    links = block_scan<kFan>(links, s_scan, total_links);
-    edges = block_scan<kFan>(edges, s_scan, total_edges);
+    links = block_scan<uint64_t, kFan>(links, s_scan, total_links);
+    edges = block_scan<uint64_t, kFan>(edges, s_scan, total_edges);
     if (parent_links) {
         links += parent_links[blockIdx.x];
         edges += parent_edges[blockIdx.x];

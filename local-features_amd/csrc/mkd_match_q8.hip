@@ -23,8 +23,8 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
-#include "mkd_match_small.h"       // pair_rows, last_pair_at_or_before: the batched forms' pair arithmetic
-#include "mkd_match_q8_common.h"   // the tile constants, q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
+#include "mkd_match_q8_batched.h"  // match_q8_pairs' slot map and body; through it mkd_match_q8_common.h: the tile constants,
+                                   // q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
 
 namespace lfmkd {
 namespace {
@@ -223,7 +223,8 @@ __global__ __launch_bounds__(256) void match_q8_merge(const int *__restrict__ p_
 // (likewise y, ny), so a DMA lane beyond the pair's last y row reads the pair's last y row (masked to INT32_MIN in the
 // epilogue) and an idle x row redoes the pair's last x row.  No byte of another pair, of the rows in front of the first or
 // behind the last pair, or at or beyond a total is ever requested.
-// (the workgroup's shape -- kPWaves, kPTiles, kPStage, R = kPRows -- is in mkd_match_q8_common.h: the guided form shares it)
+// (the workgroup's shape -- kPWaves, kPTiles, kPStage, R = kPRows -- is in mkd_match_q8_common.h; the slot map, q8_pairs_slot,
+// and the body, q8_pairs_block, are in mkd_match_q8_batched.h, where the edges and the guided form find them too)
 __global__ __launch_bounds__(kPThreads) void match_q8_pairs(const unsigned char *__restrict__ a,
                                                             const uint64_t *__restrict__ off_a, uint64_t na_total,
                                                             const unsigned char *__restrict__ b,
@@ -232,132 +233,18 @@ __global__ __launch_bounds__(kPThreads) void match_q8_pairs(const unsigned char 
                                                             int *__restrict__ match_ab, int *__restrict__ match_ba,
                                                             int *__restrict__ best_out, int *__restrict__ second_out) {
     __shared__ __attribute__((aligned(16))) unsigned char s_y[2][kPStage * kQTileBytes];
-    // which pair, which block of it: the same for the whole workgroup (scalar loads, no divergence)
-    const bool rev = blockIdx.x >= slots_ab;
-    const uint64_t slot = rev ? blockIdx.x - slots_ab : blockIdx.x;
-    const uint64_t *off_x = rev ? off_b : off_a, *off_y = rev ? off_a : off_b;
-    const uint64_t x_total = rev ? nb_total : na_total, y_total = rev ? na_total : nb_total;
-    auto start = [&](unsigned p) { return (off_x[p] < x_total ? off_x[p] : x_total) / kPRows + p; };
-    const unsigned p = last_pair_at_or_before(n_pairs, slot, start);
-    uint64_t x0 = off_x[p], x1 = off_x[p + 1], y0 = off_y[p], y1 = off_y[p + 1];
-    asm volatile("" : "+s"(x0), "+s"(x1), "+s"(y0), "+s"(y1));   // (requested together: see match_small_pairs)
-    long x_lo, nx, y_lo, ny;
-    pair_rows(x0, x1, x_total, x_lo, nx);
-    pair_rows(y0, y1, y_total, y_lo, ny);
-    const long block = (long)slot - (x_lo / kPRows + (long)p);   // slot - start(p)
-    if (block < 0) return;                                       // rows in front of the first pair
-    if (block * kPRows >= nx) return;                            // the pair's idle slot(s)
-    int *match = (rev ? match_ba : match_ab) + x_lo;
-    int *best_o = rev || !best_out ? nullptr : best_out + x_lo, *second_o = rev || !second_out ? nullptr : second_out + x_lo;
-    if (ny < 2) {                                                // a side the single-pair call refuses
-        for (long row = block * kPRows + threadIdx.x; row < nx && row < (block + 1) * kPRows; row += kPThreads) {
-            match[row] = -1;
-            if (best_o) best_o[row] = INT_MIN;
-            if (second_o) second_o[row] = INT_MIN;
-        }
+    Q8Slot s;
+    if (!q8_pairs_slot(off_a, na_total, off_b, nb_total, n_pairs, slots_ab, s)) return;   // an idle slot
+    int *match = (s.rev ? match_ba : match_ab) + s.out_lo;
+    int *best_o = s.rev || !best_out ? nullptr : best_out + s.out_lo;
+    int *second_o = s.rev || !second_out ? nullptr : second_out + s.out_lo;
+    if (s.ny < 2) {                                              // a side the single-pair call refuses
+        q8_fill_none(match, best_o, second_o, s.block, s.nx);
         return;
     }
     // from here on the pair is the whole problem: x [nx][128] against y [ny][128]
-    const unsigned char *x = (rev ? b : a) + x_lo * 128, *y = (rev ? a : b) + y_lo * 128;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 31, h = lane >> 5;
-    const long x_tile0 = (block * kPWaves + wave) * kPTiles;
-    const long x_tiles_total = (nx + kQTileRows - 1) / kQTileRows;
-    const long y_tiles_total = (ny + kQTileRows - 1) / kQTileRows;
-    // x tiles of this wave that exist: the others are skipped whole (wave-uniform; every wave still takes part in the DMA
-    // issues and the barriers)
-    const long left = x_tiles_total - x_tile0;
-    const int n_live = left < 0 ? 0 : (left < kPTiles ? (int)left : kPTiles);
-    // x fragments: B operand of the MFMA, lane (r, h) holds the bytes 32 s + 16 h .. + 15 of a column's row
-    i32x4 xf[kPTiles][4];
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) {
-        const long xt = x_tile0 + q < x_tiles_total ? x_tile0 + q : x_tiles_total - 1;   // idle tiles load the pair's last one, unused
-        long xrow = xt * kQTileRows + r;
-        xrow = xrow < nx ? xrow : nx - 1;                                                // idle rows redo the PAIR's last one
-        const unsigned char *src = x + xrow * 128 + 16 * h;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) xf[q][s] = *reinterpret_cast<const i32x4 *>(src + 32 * s) ^ kSignBits;
-    }
-    int best[kPTiles], second[kPTiles], best_i[kPTiles];
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) { best[q] = INT_MIN; second[q] = INT_MIN; best_i[q] = -1; }
-
-    // tiles t .. t + kPStage - 1 of y -> LDS buffer `buf`.  Slot u * kPThreads + threadIdx.x of the stage's 16-byte slots is
-    // (tile, chunk c, row rr) in that order; a row beyond ny reads the PAIR's last row instead (masked in the epilogue)
-    auto issue = [&](long t, int buf) {
-#pragma unroll
-        for (int u = 0; u < kPPieces; ++u) {
-            const int sl = u * kPThreads + (int)threadIdx.x;
-            const int tile = sl >> 8, c = (sl >> 5) & 7, rr = sl & 31;
-            long row = (t + tile) * kQTileRows + rr;
-            row = row < ny ? row : ny - 1;
-            q8_lds_dma16(y + row * 128 + 16 * c, &s_y[buf][0] + u * (kPThreads * 16) + wave * 1024);
-        }
-    };
-    issue(0, 0);
-    for (long t0 = 0; t0 < y_tiles_total; t0 += kPStage) {
-        const int buf = (int)((t0 / kPStage) & 1);
-        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of the stage have landed
-        __syncthreads();                      // ... and everybody's; everybody is also done with the other buffer
-        if (t0 + kPStage < y_tiles_total) issue(t0 + kPStage, buf ^ 1);
-#pragma unroll
-        for (int u = 0; u < kPStage; ++u) {
-            const long t = t0 + u;
-            if (t >= y_tiles_total || n_live == 0) break;
-            const unsigned char *yy = &s_y[buf][0] + u * kQTileBytes + (h * 32 + r) * 16;
-            i32x4 yf[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) yf[s] = *reinterpret_cast<const i32x4 *>(yy + s * 1024) ^ kSignBits;
-            const int row0 = (int)(t * kQTileRows) + 4 * h;
-            const bool tail = (t + 1) * kQTileRows > ny;
-#pragma unroll
-            for (int q = 0; q < kPTiles; ++q) {
-                if (q >= n_live) break;
-                i32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(yf[s], xf[q][s], acc, 0, 0, 0);
-                if (tail) {                   // rows beyond the pair's last y row (wave-uniform)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (row0 + (i & 3) + 8 * (i >> 2) >= ny) acc[i] = INT_MIN;
-                }
-                int m = max3i(acc[0], acc[1], acc[2]);
-#pragma unroll
-                for (int i = 3; i < 15; i += 2) m = max3i(m, acc[i], acc[i + 1]);
-                m = max(m, acc[15]);
-                if (__builtin_amdgcn_ballot_w64(m > second[q] || m >= best[q])) {   // rare once the scan is under way
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int v = acc[i];
-                        const int row = row0 + (i & 3) + 8 * (i >> 2);
-                        const bool nb_ = v >= best[q] && v != INT_MIN;   // later index wins among equals
-                        const bool ns = !nb_ && v > second[q];
-                        second[q] = nb_ ? best[q] : (ns ? v : second[q]);
-                        best_i[q] = nb_ ? row : best_i[q];
-                        best[q] = nb_ ? v : best[q];
-                    }
-                }
-            }
-        }
-    }
-    // fold the two lane halves' row sets (lanes l and l ^ 32 hold the same x column)
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) {
-        const int ob = __shfl_xor(best[q], 32), os = __shfl_xor(second[q], 32), oi = __shfl_xor(best_i[q], 32);
-        const bool other = ob > best[q] || (ob == best[q] && oi > best_i[q]);
-        const int nbest = other ? ob : best[q];
-        const int nsecond = other ? max(best[q], os) : max(second[q], ob);
-        const int nidx = other ? oi : best_i[q];
-        const long xrow = (x_tile0 + q) * kQTileRows + r;
-        if (h == 0 && q < n_live && xrow < nx) {
-            match[xrow] = q8_decide(nbest, nidx, nsecond, ratio);
-            if (best_o) best_o[xrow] = nbest;
-            if (second_o) second_o[xrow] = nsecond;
-        }
-    }
+    const unsigned char *x = (s.rev ? b : a) + s.x_lo * 128, *y = (s.rev ? a : b) + s.y_lo * 128;
+    q8_pairs_block(x, s.nx, y, s.ny, ratio, match, best_o, second_o, s.block, s_y);
 }
 
 // The grid and the scratch of a call (lf_mkd_match_q8_plan is this function; launch_match_q8 calls it too).

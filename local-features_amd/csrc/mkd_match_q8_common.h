@@ -1,7 +1,8 @@
 // The int8 matchers' small helpers and the batched form's workgroup shape, shared by mkd_match_q8.hip (match_q8_scan,
-// match_q8_merge, match_q8_pairs), mkd_match_q8_guided.hip (match_q8_guided_pairs), mkd_match_q8_knn.hip and
-// mkd_match_q8_grouped.hip: each unit compiles its own
-// copy, no device code crosses a translation unit.  The notes on the forms are in mkd_match_q8.hip.
+// match_q8_merge, match_q8_pairs), mkd_match_q8_edges.hip (match_q8_edges), mkd_match_q8_guided.hip (match_q8_guided_pairs),
+// mkd_match_q8_knn.hip and mkd_match_q8_grouped.hip: each unit compiles its own copy, no device code crosses a translation
+// unit.  The three batched kernels reach it through mkd_match_q8_batched.h, which holds their prologues and bodies.  The notes
+// on the forms are in mkd_match_q8.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>

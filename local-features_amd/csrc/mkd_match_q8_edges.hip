@@ -9,15 +9,15 @@
 //
 //   edge_layout       the exclusive prefix sum of the edges' row counts (two launches, one when a single block does it);
 //   gather_edge_rows  rows of any width from the pool into the edge layout (how keypoints reach the verifiers);
-//   match_q8_edges    match_q8_pairs' body (mkd_match_q8.hip) behind a prologue that takes the slot and the output base from
-//                     the edge layout and x / y from the pools through the edge's two ids.
+//   match_q8_edges    match_q8_pairs' body (mkd_match_q8_batched.h) behind a prologue that takes the slot and the output base
+//                     from the edge layout and x / y from the pools through the edge's two ids.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
 #include "mkd_device.h"
 #include "mkd_match_small.h"       // pair_rows, image_rows, last_pair_at_or_before
-#include "mkd_match_q8_common.h"   // the tile constants, q8_lds_dma16, max3i, q8_decide, the batched form's kP* shape
+#include "mkd_match_q8_batched.h"  // q8_edges_slot, q8_pairs_block, the batched form's kP* shape
 
 namespace lfmkd {
 namespace {
@@ -130,18 +130,8 @@ __global__ __launch_bounds__(kGatherThreads) void gather_edge_rows(const unsigne
 }
 
 // ---- match_q8_edges (lf_mkd_match_q8_edges_device) -----------------------------------------------------------------------
-// THE TWIN OF match_q8_pairs (mkd_match_q8.hip): from "from here on the pair is the whole problem" on the two bodies are the
-// same text, and a change to one belongs in the other.  (A copy, not a shared header: the pairs kernel's code is pinned by
-// its measurements, DESIGN.md 6f, and stays byte for byte what it was.)  Only the prologue differs:
-//   * the slot map runs over the EDGE LAYOUT of the x side against its capacity -- the same R, the same map, so the grid is
-//     what lf_mkd_match_q8_pairs_plan reports for (ea_capacity, eb_capacity, n_edges);
-//   * the outputs' base is the edge's first entry of the layout, lo;
-//   * x and y are the edge's two IMAGES, taken from the pools through its two ids; y is always the whole image;
-//   * the rows served are nx = min(the x image's rows, the edge's range of the layout): entries of the range beyond the image
-//     (a layout that was not made from these ids) are left alone, rows of the image beyond the range are not decided;
-//   * the clamps are to the IMAGE, as the pairs kernel's are to the pair: a DMA lane beyond the image's last row reads the
-//     image's last row, an idle x row redoes the image's last served row.  No byte of another image, of the rows that belong
-//     to no image, or at or beyond a pool's total is ever requested; no entry at or beyond a capacity is written.
+// match_q8_pairs' body (q8_pairs_block, mkd_match_q8_batched.h) behind the edges prologue (q8_edges_slot, the same header,
+// with the notes on what it serves and on the clamps): the two IMAGES of the edge are the body's whole problem.
 __global__ __launch_bounds__(kPThreads) void match_q8_edges(
     const unsigned char *__restrict__ a, const uint64_t *__restrict__ image_off_a, unsigned n_images_a, uint64_t na_total,
     const unsigned char *__restrict__ b, const uint64_t *__restrict__ image_off_b, unsigned n_images_b, uint64_t nb_total,
@@ -150,139 +140,19 @@ __global__ __launch_bounds__(kPThreads) void match_q8_edges(
     float ratio, int *__restrict__ match_ab, int *__restrict__ match_ba, int *__restrict__ best_out,
     int *__restrict__ second_out) {
     __shared__ __attribute__((aligned(16))) unsigned char s_y[2][kPStage * kQTileBytes];
-    // which edge, which block of it: the same for the whole workgroup (scalar loads, no divergence)
-    const bool rev = blockIdx.x >= slots_ab;
-    const uint64_t slot = rev ? blockIdx.x - slots_ab : blockIdx.x;
-    const uint64_t *off_x = rev ? edge_off_b : edge_off_a;
-    const uint64_t x_capacity = rev ? eb_capacity : ea_capacity;
-    auto start = [&](unsigned p) { return (off_x[p] < x_capacity ? off_x[p] : x_capacity) / kPRows + p; };
-    const unsigned p = last_pair_at_or_before(n_edges, slot, start);
-    long lo, len;
-    pair_rows(off_x[p], off_x[p + 1], x_capacity, lo, len);
-    const long block = (long)slot - (lo / kPRows + (long)p);     // slot - start(p)
-    if (block < 0) return;                                       // entries in front of the first edge
-    // (requesting the two ids together with the offsets above, and the four image offsets in one round trip behind them,
-    //  was measured against this form in one run, alternating: 256 frames with window 4 at 1.010 .. 1.019 x the pairs call
-    //  against 1.013 .. 1.025 x -- not resolved, so the plain form stays)
-    const unsigned id_a = edge_a[p], id_b = edge_b[p];
-    long a_lo, a_n, b_lo, b_n;
-    image_rows(image_off_a, n_images_a, na_total, id_a, a_lo, a_n);
-    image_rows(image_off_b, n_images_b, nb_total, id_b, b_lo, b_n);
-    const long x_lo = rev ? b_lo : a_lo, y_lo = rev ? a_lo : b_lo, ny = rev ? a_n : b_n;
-    long nx = rev ? b_n : a_n;
-    nx = nx < len ? nx : len;                                    // the rows served
-    if (block * kPRows >= nx) return;                            // the edge's idle slot(s)
-    int *match = (rev ? match_ba : match_ab) + lo;
-    int *best_o = rev || !best_out ? nullptr : best_out + lo, *second_o = rev || !second_out ? nullptr : second_out + lo;
-    if (ny < 2) {                                                // a side the single-pair call refuses
-        for (long row = block * kPRows + threadIdx.x; row < nx && row < (block + 1) * kPRows; row += kPThreads) {
-            match[row] = -1;
-            if (best_o) best_o[row] = INT_MIN;
-            if (second_o) second_o[row] = INT_MIN;
-        }
+    Q8Slot s;
+    if (!q8_edges_slot(image_off_a, n_images_a, na_total, image_off_b, n_images_b, nb_total, edge_a, edge_b, edge_off_a, ea_capacity,
+                       edge_off_b, eb_capacity, n_edges, slots_ab, s))
+        return;                                                  // an idle slot
+    int *match = (s.rev ? match_ba : match_ab) + s.out_lo;
+    int *best_o = s.rev || !best_out ? nullptr : best_out + s.out_lo;
+    int *second_o = s.rev || !second_out ? nullptr : second_out + s.out_lo;
+    if (s.ny < 2) {                                              // a side the single-pair call refuses
+        q8_fill_none(match, best_o, second_o, s.block, s.nx);
         return;
     }
-    // from here on the pair is the whole problem: x [nx][128] against y [ny][128]
-    const unsigned char *x = (rev ? b : a) + x_lo * 128, *y = (rev ? a : b) + y_lo * 128;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 31, h = lane >> 5;
-    const long x_tile0 = (block * kPWaves + wave) * kPTiles;
-    const long x_tiles_total = (nx + kQTileRows - 1) / kQTileRows;
-    const long y_tiles_total = (ny + kQTileRows - 1) / kQTileRows;
-    // x tiles of this wave that exist: the others are skipped whole (wave-uniform; every wave still takes part in the DMA
-    // issues and the barriers)
-    const long left = x_tiles_total - x_tile0;
-    const int n_live = left < 0 ? 0 : (left < kPTiles ? (int)left : kPTiles);
-    // x fragments: B operand of the MFMA, lane (r, h) holds the bytes 32 s + 16 h .. + 15 of a column's row
-    i32x4 xf[kPTiles][4];
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) {
-        const long xt = x_tile0 + q < x_tiles_total ? x_tile0 + q : x_tiles_total - 1;   // idle tiles load the pair's last one, unused
-        long xrow = xt * kQTileRows + r;
-        xrow = xrow < nx ? xrow : nx - 1;                                                // idle rows redo the PAIR's last one
-        const unsigned char *src = x + xrow * 128 + 16 * h;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) xf[q][s] = *reinterpret_cast<const i32x4 *>(src + 32 * s) ^ kSignBits;
-    }
-    int best[kPTiles], second[kPTiles], best_i[kPTiles];
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) { best[q] = INT_MIN; second[q] = INT_MIN; best_i[q] = -1; }
-
-    // tiles t .. t + kPStage - 1 of y -> LDS buffer `buf`.  Slot u * kPThreads + threadIdx.x of the stage's 16-byte slots is
-    // (tile, chunk c, row rr) in that order; a row beyond ny reads the PAIR's last row instead (masked in the epilogue)
-    auto issue = [&](long t, int buf) {
-#pragma unroll
-        for (int u = 0; u < kPPieces; ++u) {
-            const int sl = u * kPThreads + (int)threadIdx.x;
-            const int tile = sl >> 8, c = (sl >> 5) & 7, rr = sl & 31;
-            long row = (t + tile) * kQTileRows + rr;
-            row = row < ny ? row : ny - 1;
-            q8_lds_dma16(y + row * 128 + 16 * c, &s_y[buf][0] + u * (kPThreads * 16) + wave * 1024);
-        }
-    };
-    issue(0, 0);
-    for (long t0 = 0; t0 < y_tiles_total; t0 += kPStage) {
-        const int buf = (int)((t0 / kPStage) & 1);
-        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of the stage have landed
-        __syncthreads();                      // ... and everybody's; everybody is also done with the other buffer
-        if (t0 + kPStage < y_tiles_total) issue(t0 + kPStage, buf ^ 1);
-#pragma unroll
-        for (int u = 0; u < kPStage; ++u) {
-            const long t = t0 + u;
-            if (t >= y_tiles_total || n_live == 0) break;
-            const unsigned char *yy = &s_y[buf][0] + u * kQTileBytes + (h * 32 + r) * 16;
-            i32x4 yf[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) yf[s] = *reinterpret_cast<const i32x4 *>(yy + s * 1024) ^ kSignBits;
-            const int row0 = (int)(t * kQTileRows) + 4 * h;
-            const bool tail = (t + 1) * kQTileRows > ny;
-#pragma unroll
-            for (int q = 0; q < kPTiles; ++q) {
-                if (q >= n_live) break;
-                i32x16 acc;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(yf[s], xf[q][s], acc, 0, 0, 0);
-                if (tail) {                   // rows beyond the pair's last y row (wave-uniform)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (row0 + (i & 3) + 8 * (i >> 2) >= ny) acc[i] = INT_MIN;
-                }
-                int m = max3i(acc[0], acc[1], acc[2]);
-#pragma unroll
-                for (int i = 3; i < 15; i += 2) m = max3i(m, acc[i], acc[i + 1]);
-                m = max(m, acc[15]);
-                if (__builtin_amdgcn_ballot_w64(m > second[q] || m >= best[q])) {   // rare once the scan is under way
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int v = acc[i];
-                        const int row = row0 + (i & 3) + 8 * (i >> 2);
-                        const bool nb_ = v >= best[q] && v != INT_MIN;   // later index wins among equals
-                        const bool ns = !nb_ && v > second[q];
-                        second[q] = nb_ ? best[q] : (ns ? v : second[q]);
-                        best_i[q] = nb_ ? row : best_i[q];
-                        best[q] = nb_ ? v : best[q];
-                    }
-                }
-            }
-        }
-    }
-    // fold the two lane halves' row sets (lanes l and l ^ 32 hold the same x column)
-#pragma unroll
-    for (int q = 0; q < kPTiles; ++q) {
-        const int ob = __shfl_xor(best[q], 32), os = __shfl_xor(second[q], 32), oi = __shfl_xor(best_i[q], 32);
-        const bool other = ob > best[q] || (ob == best[q] && oi > best_i[q]);
-        const int nbest = other ? ob : best[q];
-        const int nsecond = other ? max(best[q], os) : max(second[q], ob);
-        const int nidx = other ? oi : best_i[q];
-        const long xrow = (x_tile0 + q) * kQTileRows + r;
-        if (h == 0 && q < n_live && xrow < nx) {
-            match[xrow] = q8_decide(nbest, nidx, nsecond, ratio);
-            if (best_o) best_o[xrow] = nbest;
-            if (second_o) second_o[xrow] = nsecond;
-        }
-    }
+    const unsigned char *x = (s.rev ? b : a) + s.x_lo * 128, *y = (s.rev ? a : b) + s.y_lo * 128;
+    q8_pairs_block(x, s.nx, y, s.ny, ratio, match, best_o, second_o, s.block, s_y);
 }
 
 unsigned gather_edge_rows_block_rows() { return kGatherRows; }

@@ -28,8 +28,7 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
-#include "mkd_match_small.h"       // pair_rows, last_pair_at_or_before
-#include "mkd_match_q8_common.h"
+#include "mkd_match_q8_batched.h"  // q8_pairs_slot, q8_issue_stage, q8_take_tile, q8_fold_halves, the kP* shape
 
 #include "mkd_guided_math.h"   // (last: its file-scope pragma holds from here on)
 
@@ -99,7 +98,8 @@ struct Q8GuidedShared {
     float4 kp[2][kGStageRows];                   // ... and their rows' staged keypoints: 4 KiB
 };
 
-// The body of a workgroup: match_q8_pairs' body over x [nx][128] against y [ny][128] with the vote in front of every tile.
+// The body of a workgroup: q8_pairs_block's walk (mkd_match_q8_batched.h) over x [nx][128] against y [ny][128] with the vote in
+// front of every tile.
 // kx / ky: the two sides' keypoints (rows of 5 floats), m: the pair's model.  nx >= 1 and ny >= 1.
 template <int MODE>
 __device__ __forceinline__ void q8_guided_block(const unsigned char *__restrict__ x, const float *__restrict__ kx, long nx,
@@ -129,18 +129,7 @@ __device__ __forceinline__ void q8_guided_block(const unsigned char *__restrict_
     const G mine(m, kx[xrow_c * 5], kx[xrow_c * 5 + 1], thr2);
     int best = INT_MIN, second = INT_MIN, best_i = -1;
 
-    // tiles t .. t + kPStage - 1 of y -> LDS buffer `buf`, as match_q8_pairs issues them
-    auto issue = [&](long t, int buf) {
-#pragma unroll
-        for (int u = 0; u < kPPieces; ++u) {
-            const int sl = u * kPThreads + (int)threadIdx.x;
-            const int tile = sl >> 8, c = (sl >> 5) & 7, rr = sl & 31;
-            long row = (t + tile) * kQTileRows + rr;
-            row = row < ny ? row : ny - 1;
-            q8_lds_dma16(y + row * 128 + 16 * c, &sh.y[buf][0] + u * (kPThreads * 16) + wave * 1024);
-        }
-    };
-    // ... and the keypoint of row threadIdx.x of that stage (a row beyond the pair's last: the pair's last, masked in the vote)
+    // the keypoint of row threadIdx.x of a stage (a row beyond the pair's last: the pair's last, masked in the vote)
     const bool stager = threadIdx.x < kGStageRows;                                       // (whole waves)
     float qx = 0.f, qy = 0.f;
     auto request_kp = [&](long t) {
@@ -149,7 +138,7 @@ __device__ __forceinline__ void q8_guided_block(const unsigned char *__restrict_
         qx = ky[row * 5];
         qy = ky[row * 5 + 1];
     };
-    issue(0, 0);
+    q8_issue_stage(y, ny, 0, &sh.y[0][0], wave);
     if (stager) {
         request_kp(0);
         sh.kp[0][threadIdx.x] = G::stage(m, qx, qy, thr2);
@@ -160,7 +149,7 @@ __device__ __forceinline__ void q8_guided_block(const unsigned char *__restrict_
         __syncthreads();                      // ... and everybody's, and its keypoints; everybody is done with the other buffers
         const bool more = t0 + kPStage < y_tiles_total;
         if (more) {
-            issue(t0 + kPStage, buf ^ 1);
+            q8_issue_stage(y, ny, t0 + kPStage, &sh.y[buf ^ 1][0], wave);
             if (stager) request_kp(t0 + kPStage);   // in flight beside the DMA while this stage is worked on
         }
 #pragma unroll
@@ -191,32 +180,13 @@ __device__ __forceinline__ void q8_guided_block(const unsigned char *__restrict_
 #pragma unroll
             for (int i = 0; i < 16; ++i)      // inadmissible pairs, the rows beyond the pair's last y row among them
                 if (!((adm >> i) & 1u)) acc[i] = INT_MIN;
-            int mx = max3i(acc[0], acc[1], acc[2]);
-#pragma unroll
-            for (int i = 3; i < 15; i += 2) mx = max3i(mx, acc[i], acc[i + 1]);
-            mx = max(mx, acc[15]);
-            if (__builtin_amdgcn_ballot_w64(mx > second || mx >= best)) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int v = acc[i];
-                    const int row = row0 + (i & 3) + 8 * (i >> 2);
-                    const bool nb_ = v >= best && v != INT_MIN;   // later index wins among equals
-                    const bool ns = !nb_ && v > second;
-                    second = nb_ ? best : (ns ? v : second);
-                    best_i = nb_ ? row : best_i;
-                    best = nb_ ? v : best;
-                }
-            }
+            q8_take_tile(acc, row0, best, second, best_i);
         }
         // the next stage's keypoints -> the other buffer, whose readers all passed this stage's barrier
         if (more && stager) sh.kp[buf ^ 1][threadIdx.x] = G::stage(m, qx, qy, thr2);
     }
-    // fold the two lane halves' row sets (lanes l and l ^ 32 hold the same x row)
-    const int ob = __shfl_xor(best, 32), os = __shfl_xor(second, 32), oi = __shfl_xor(best_i, 32);
-    const bool other = ob > best || (ob == best && oi > best_i);
-    const int nbest = other ? ob : best;
-    const int nsecond = other ? max(best, os) : max(second, ob);
-    const int nidx = other ? oi : best_i;
+    const Q8Top top = q8_fold_halves(best, second, best_i);
+    const int nbest = top.best, nsecond = top.second, nidx = top.index;
     if (h == 0 && x_live) {
         match[xrow] = q8_decide(nbest, nidx, nsecond, ratio);
         if (best_o) best_o[xrow] = nbest;
@@ -236,34 +206,19 @@ __global__ __launch_bounds__(kPThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     const float *__restrict__ model, unsigned n_pairs, unsigned slots_ab, unsigned kind, float thr2, float ratio,
     int *__restrict__ match_ab, int *__restrict__ match_ba, int *__restrict__ best_out, int *__restrict__ second_out) {
     __shared__ __attribute__((aligned(16))) Q8GuidedShared sh;
-    // which pair, which block of it: the same for the whole workgroup (scalar loads, no divergence)
-    const bool rev = blockIdx.x >= slots_ab;
-    const uint64_t slot = rev ? blockIdx.x - slots_ab : blockIdx.x;
-    const uint64_t *off_x = rev ? off_b : off_a, *off_y = rev ? off_a : off_b;
-    const uint64_t x_total = rev ? nb_total : na_total, y_total = rev ? na_total : nb_total;
-    auto start = [&](unsigned p) { return (off_x[p] < x_total ? off_x[p] : x_total) / kPRows + p; };
-    const unsigned p = last_pair_at_or_before(n_pairs, slot, start);
-    uint64_t x0 = off_x[p], x1 = off_x[p + 1], y0 = off_y[p], y1 = off_y[p + 1];
-    asm volatile("" : "+s"(x0), "+s"(x1), "+s"(y0), "+s"(y1));   // (requested together: see match_small_pairs)
-    long x_lo, nx, y_lo, ny;
-    pair_rows(x0, x1, x_total, x_lo, nx);
-    pair_rows(y0, y1, y_total, y_lo, ny);
-    const long block = (long)slot - (x_lo / kPRows + (long)p);   // slot - start(p)
-    if (block < 0) return;                                       // rows in front of the first pair
-    if (block * kPRows >= nx) return;                            // the pair's idle slot(s)
-    int *match = (rev ? match_ba : match_ab) + x_lo;
-    int *best_o = rev || !best_out ? nullptr : best_out + x_lo, *second_o = rev || !second_out ? nullptr : second_out + x_lo;
+    Q8Slot s;
+    if (!q8_pairs_slot(off_a, na_total, off_b, nb_total, n_pairs, slots_ab, s)) return;   // an idle slot
+    const bool rev = s.rev;
+    const long nx = s.nx, ny = s.ny, block = s.block;
+    int *match = (rev ? match_ba : match_ab) + s.out_lo;
+    int *best_o = rev || !best_out ? nullptr : best_out + s.out_lo, *second_o = rev || !second_out ? nullptr : second_out + s.out_lo;
     if (ny == 0) {                                               // no row to clamp a request to: no candidate for anybody
-        for (long row = block * kPRows + threadIdx.x; row < nx && row < (block + 1) * kPRows; row += kPThreads) {
-            match[row] = -1;
-            if (best_o) best_o[row] = INT_MIN;
-            if (second_o) second_o[row] = INT_MIN;
-        }
+        q8_fill_none(match, best_o, second_o, block, nx);
         return;
     }
-    const float *m = model + 9 * (size_t)p;
-    const unsigned char *x = (rev ? b : a) + x_lo * 128, *y = (rev ? a : b) + y_lo * 128;
-    const float *kx = (rev ? kps_b : kps_a) + x_lo * 5, *ky = (rev ? kps_a : kps_b) + y_lo * 5;
+    const float *m = model + 9 * (size_t)s.p;
+    const unsigned char *x = (rev ? b : a) + s.x_lo * 128, *y = (rev ? a : b) + s.y_lo * 128;
+    const float *kx = (rev ? kps_b : kps_a) + s.x_lo * 5, *ky = (rev ? kps_a : kps_b) + s.y_lo * 5;
     // (kind and rev are the same for the whole workgroup: a scalar branch; the four bodies share the one LDS block)
     if (kind == 0u) {
         if (!rev) q8_guided_block<0>(x, kx, nx, y, ky, ny, m, thr2, ratio, match, best_o, second_o, block, sh);

@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "../../include/lf_mkd.h"
+#include "mkd_block_scan.h"
 #include "mkd_device.h"
 
 namespace lfmkd {
@@ -323,21 +324,9 @@ __global__ __launch_bounds__(kScanThreads) void se_scan(const unsigned *__restri
             picks += block_picks[b];
             rows += block_rows[b];
         }
-        int cur = 0;
-        s_scan[t] = v;
-        __syncthreads();
-#pragma unroll
-        for (int off = 1; off < kScanThreads; off <<= 1) {
-            unsigned x = s_scan[cur * kScanThreads + t];
-            if (t >= off) x += s_scan[cur * kScanThreads + t - off];
-            s_scan[(cur ^ 1) * kScanThreads + t] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const unsigned incl = s_scan[cur * kScanThreads + t];
-        const unsigned total = s_scan[cur * kScanThreads + kScanThreads - 1];
-        __syncthreads();
-        if (b < n_blocks) block_base[b] = carry + incl - v;
+        unsigned total;
+        const unsigned before = block_scan<unsigned, kScanThreads>(v, s_scan, total);
+        if (b < n_blocks) block_base[b] = carry + before;
         carry += total;
     }
     // the two plain totals: a sum over the lanes, then over the waves

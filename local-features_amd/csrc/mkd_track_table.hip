@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/lf_mkd.h"
+#include "mkd_block_scan.h"
 #include "mkd_device.h"
 #include "mkd_match_small.h"        // pair_rows, last_pair_at_or_before
 
@@ -51,27 +52,6 @@ constexpr int kScanThreads = 1024;                            // tt_scan_blocks,
 constexpr int kGatherRows = 64;                               // rows one workgroup of gather_track_rows copies
 static_assert(kBlockRows % kThreads == 0 && kPer >= 1 && kPer <= 32, "a thread owns kPer rows");
 static_assert(kDigitBits >= 1 && kDigitBits <= 11, "kWaves * kRadix counters live in LDS");
-
-// Exclusive prefix sum over the workgroup's NT threads, in thread order, and the total.  s: 2 * NT elements of LDS.
-template <typename T, int NT>
-__device__ __forceinline__ T block_scan(T v, T *s, T &total) {
-    const int t = threadIdx.x;
-    int cur = 0;
-    s[t] = v;
-    __syncthreads();
-#pragma unroll
-    for (int off = 1; off < NT; off <<= 1) {
-        T x = s[cur * NT + t];
-        if (t >= off) x += s[cur * NT + t - off];
-        s[(cur ^ 1) * NT + t] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    const T incl = s[cur * NT + t];
-    total = s[cur * NT + NT - 1];
-    __syncthreads();                                          // s may be used again at once
-    return incl - v;
-}
 
 __device__ __forceinline__ bool selected_root(const int *__restrict__ track, const unsigned *__restrict__ len,
                                               const unsigned *__restrict__ dup, long r, unsigned min_len, unsigned &l) {
