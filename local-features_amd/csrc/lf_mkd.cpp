@@ -198,7 +198,7 @@ struct lf_mkd {
     RecordedArray<unsigned> d_topk_work;
     // multi-frame detect (lf_mkd_detect_frames_device)
     HipArray<lf_mkd_extremum> d_mf_padded, d_mf_list;
-    HipArray<unsigned> d_mf_frame_start, d_mf_offsets, d_mf_frame_of;
+    HipArray<unsigned> d_mf_frame_count, d_mf_offsets, d_mf_frame_of;
     // graph-captured per-frame pipeline (lf_mkd_stream_*)
     PyramidDesc graph_pd{};     // frame geometry the recorded pipeline was captured for
     RecordedArray<float> d_stream_patches;
@@ -1591,11 +1591,14 @@ int lf_mkd_detect_frames_device(lf_mkd *h, const float *d_images, uint32_t n_fra
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     const uint64_t cap_f = h->max_extrema;                       // extrema kept per frame (mod.rs:625-633)
     const uint64_t keep = top_n ? std::min<uint64_t>(top_n, cap_f) : cap_f;
-    const uint64_t all_cap = cap_f * n_frames * 2;               // room for frames that exceed their share
+    // the batch's extremum list: cap_f rows per frame, each frame's share its own (a frame with more than cap_f extrema
+    // loses the ones beyond them, as lf_mkd_detect does, and takes nothing from the other frames)
+    const uint64_t all_cap = cap_f * n_frames;
+    if (all_cap > 0xFFFFFFFFull) return fail(h, LF_MKD_ERR_BAD_ARG, "detect_frames: max_blobs x frames exceeds 2^32");
     if (int rc = ensure_coarse_stack(h, s)) return rc;
     if (int rc = ensure_detect_scratch(h)) return rc;
     if (int rc = grow(h, h->d_det_extrema, all_cap)) return rc;
-    if (int rc = grow(h, h->d_mf_frame_start, n_frames)) return rc;
+    if (int rc = grow(h, h->d_mf_frame_count, n_frames)) return rc;
     if (int rc = grow(h, h->d_mf_offsets, n_frames)) return rc;
     if (int rc = grow(h, h->d_mf_padded, keep * n_frames)) return rc;
     if (int rc = grow(h, h->d_mf_list, keep * n_frames)) return rc;
@@ -1603,20 +1606,19 @@ int lf_mkd_detect_frames_device(lf_mkd *h, const float *d_images, uint32_t n_fra
     // 1. every frame's extrema, ordered by frame; 2. per-frame selection; 3. one contiguous list + frame ids
     launch_detect_extrema(h->d_pyr + h->pd.offset[0], h->pyr_stride, h->pd.pitch[0], h->d_coarse, h->coarse_stride, h->layer_stride,
                           h->n_layers, int(width), int(height), int(n_frames), kBorder, kSkipLayers, kContrastThreshold,
-                          h->d_slots, h->d_cube_counts, h->d_cube_sums, h->d_det_extrema.as<float>(), nullptr, h->d_mf_frame_start,
-                          all_cap, h->d_totals + 0, s);
-    launch_topk_filter(h->d_det_extrema.as<float>(), h->d_mf_frame_start, h->d_totals + 0, 0, n_frames, unsigned(cap_f),
+                          h->d_slots, h->d_cube_counts, h->d_cube_sums, h->d_det_extrema.as<float>(), nullptr, h->d_mf_frame_count,
+                          cap_f, nullptr, s);
+    launch_topk_filter(h->d_det_extrema.as<float>(), h->d_mf_frame_count, nullptr, 0, n_frames, unsigned(cap_f),
                        unsigned(keep), top_n ? min_size : -INFINITY, h->d_mf_padded.as<float>(), nullptr, h->d_sel_count,
                        nullptr, 0, nullptr, s);
-    launch_segments_compact(h->d_mf_padded.as<float>(), h->d_sel_count, h->d_mf_frame_start, h->d_totals + 0, n_frames,
-                            unsigned(cap_f), unsigned(keep), h->d_mf_offsets, h->d_mf_list.as<float>(), h->d_mf_frame_of,
-                            h->d_totals + 2, s);
+    launch_segments_compact(h->d_mf_padded.as<float>(), h->d_sel_count, h->d_mf_frame_count, n_frames, unsigned(cap_f),
+                            unsigned(keep), h->d_mf_offsets, h->d_mf_list.as<float>(), h->d_mf_frame_of, h->d_totals + 0, s);
     LF_HIP(h, hipGetLastError());
-    unsigned long long totals[4] = {0, 0, 0, 0};
+    unsigned long long totals[2] = {0, 0};
     LF_HIP(h, hipMemcpyAsync(totals, h->d_totals, sizeof(totals), hipMemcpyDeviceToHost, s));
     LF_HIP(h, hipStreamSynchronize(s));
-    const uint64_t n_sel = totals[2];
-    if (dropped_blobs) *dropped_blobs = totals[1] + totals[3];
+    const uint64_t n_sel = totals[0];
+    if (dropped_blobs) *dropped_blobs = totals[1];
     if (n_sel == 0 || max_out == 0) return LF_MKD_OK;
     // 4. orientation over the whole list, 5. sampling + description by frame id
     if (int rc = ensure_orient_scratch(h, n_sel, false, 0)) return rc;

@@ -205,8 +205,8 @@ __global__ __launch_bounds__(256) void scan_extrema(const float *__restrict__ la
 // Ordered compaction of per-cube slots, two small launches: (1) sums of 1024 counts, (2) every workgroup adds up the sums
 // before its own (a few hundred to a few thousand words from L2: cheaper than a third launch in between, which costs
 // ~5 us of a frame's critical path), rescans its 1024 counts from that base and copies the slots; the last workgroup
-// also leaves the totals.  Item i belongs to frame i / items_per_frame; frame_start[f] (optional) receives the offset of
-// the frame's first extremum.  (cubes_scan_sums, the separate scan, still serves the orientation's batched form.)
+// also leaves the totals.  Item i belongs to frame i / items_per_frame.  (cubes_scan_sums, the separate scan, still serves
+// the orientation's batched form.)
 __global__ __launch_bounds__(1024) void cubes_block_sums(const unsigned *__restrict__ counts, long n,
                                                          unsigned *__restrict__ sums) {
     __shared__ unsigned ws[16];
@@ -256,18 +256,34 @@ __global__ __launch_bounds__(1024) void cubes_scan_sums(unsigned *__restrict__ s
     }
 }
 
+// kPerFrame: every frame has a share of max_out rows of its own, out [frames][max_out][4] -- frame f's first max_out extrema go
+// to rows f * max_out + (rank in the frame), whatever the other frames hold, and frame_count[f] receives all it holds.  A
+// rank needs the extrema between the frame's first item and the workgroup, not those of the whole batch before it: the
+// workgroup adds up the sums of the workgroups since the one that holds the first item of ITS first frame (a frame's worth
+// of them at most), less that workgroup's counts before the item; frames that begin inside the workgroup take their base
+// from its own scan.  No launch more than the batch-wide form, and fewer sums read.  (frame_of, totals: unused.)
+template <bool kPerFrame>
 __global__ __launch_bounds__(1024) void cubes_scatter(const unsigned *__restrict__ counts,
                                                       const float *__restrict__ slots,
                                                       const unsigned *__restrict__ block_sums, long n,
                                                       long items_per_frame, float *__restrict__ out /*[max_out][4]*/,
-                                                      unsigned *__restrict__ frame_of, unsigned *__restrict__ frame_start,
+                                                      unsigned *__restrict__ frame_of, unsigned *__restrict__ frame_count,
                                                       unsigned long long max_out, unsigned long long *__restrict__ totals) {
     __shared__ unsigned ws[16];
     __shared__ unsigned long long wbase[16];
+    __shared__ unsigned s_local[kPerFrame ? 1024 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // extrema in the workgroups before this one
+    const long blk0 = (long)blockIdx.x * 1024;
+    // extrema in the workgroups before this one (kPerFrame: those of them that belong to this workgroup's first frame)
     unsigned long long mine = 0;
-    for (long b = threadIdx.x; b < (long)blockIdx.x; b += 1024) mine += block_sums[b];
+    if constexpr (kPerFrame) {
+        const long fs0 = blk0 / items_per_frame * items_per_frame, b0 = fs0 / 1024;   // the frame's first item, its workgroup
+        for (long b = b0 + threadIdx.x; b < (long)blockIdx.x; b += 1024) mine += block_sums[b];
+        const long k = b0 * 1024 + threadIdx.x;
+        if (k < fs0) mine -= counts[k];                   // (modulo 2^64; the workgroup's total is not negative)
+    } else {
+        for (long b = threadIdx.x; b < (long)blockIdx.x; b += 1024) mine += block_sums[b];
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
     if (lane == 0) wbase[wave] = mine;
@@ -275,12 +291,12 @@ __global__ __launch_bounds__(1024) void cubes_scatter(const unsigned *__restrict
     unsigned long long block_base = 0;
 #pragma unroll
     for (int v = 0; v < 16; ++v) block_base += wbase[v];
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    if (!kPerFrame && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
         const unsigned long long all = block_base + block_sums[blockIdx.x];
         totals[0] = all < max_out ? all : max_out;
         totals[1] = all < max_out ? 0ull : all - max_out;
     }
-    const long i = (long)blockIdx.x * 1024 + threadIdx.x;
+    const long i = blk0 + threadIdx.x;
     const unsigned c = i < n ? counts[i] : 0u;
     unsigned incl = c;
 #pragma unroll
@@ -293,10 +309,24 @@ __global__ __launch_bounds__(1024) void cubes_scatter(const unsigned *__restrict
     unsigned before = 0;
 #pragma unroll
     for (int v = 0; v < 16; ++v) before += v < wave ? ws[v] : 0u;
-    const unsigned long long first = block_base + before + incl - c;
+    const unsigned local = before + incl - c;             // extrema of this workgroup before item i
+    if constexpr (kPerFrame) {
+        s_local[threadIdx.x] = local;
+        __syncthreads();
+    }
     if (i >= n) return;
     const unsigned f = (unsigned)(i / items_per_frame);
-    if (frame_start && i == (long)f * items_per_frame) frame_start[f] = (unsigned)(first < max_out ? first : max_out);
+    if constexpr (kPerFrame) {
+        const long fs = (long)f * items_per_frame;        // the frame's first item: in this workgroup, or before it
+        const unsigned long long rank = fs >= blk0 ? local - s_local[fs - blk0] : block_base + local;
+        for (unsigned j = 0; j < c; ++j)
+            if (rank + j < max_out)
+                *reinterpret_cast<f32x4 *>(out + ((size_t)f * max_out + rank + j) * 4) =
+                    *reinterpret_cast<const f32x4 *>(slots + ((size_t)i * 8 + j) * 4);
+        if (i == fs + items_per_frame - 1) frame_count[f] = (unsigned)(rank + c);   // the frame's last item
+        return;
+    }
+    const unsigned long long first = block_base + local;
     for (unsigned j = 0; j < c; ++j) {
         const unsigned long long o = first + j;
         if (o < max_out) {
@@ -309,11 +339,12 @@ __global__ __launch_bounds__(1024) void cubes_scatter(const unsigned *__restrict
 // TopKContrastFilter::filter (vulkan/mod.rs:1753-1786) for one frame's extrema [n][4], one workgroup per frame:
 // keep blobs with size >= min_size; if more than n_keep remain, find the (n_keep+1)-th largest contrast (radix
 // select on the float bits, contrast >= 0) and keep, in index order, the first n_keep blobs that reach it.
-// seg_start[f], seg_start[f+1] delimit frame f (seg_start == nullptr: one segment [0, *n_in)).
+// seg_count[f]: frame f's extrema start at row f * seg_cap, the first min(seg_count[f], seg_cap) of them are there
+// (cubes_scatter<true>'s layout; seg_count == nullptr: one segment [0, *n_in)).
 // out: gathered extrema from out_base(f) = f * n_keep; out_count[f].
-__global__ __launch_bounds__(1024) void topk_filter(const float *__restrict__ extrema, const unsigned *__restrict__ seg_start,
+__global__ __launch_bounds__(1024) void topk_filter(const float *__restrict__ extrema, const unsigned *__restrict__ seg_count,
                                                     const unsigned long long *__restrict__ n_in,
-                                                    unsigned long long n_host, unsigned n_frames, unsigned seg_cap,
+                                                    unsigned long long n_host, unsigned seg_cap,
                                                     unsigned n_keep, float min_size, float *__restrict__ out,
                                                     unsigned *__restrict__ out_index, unsigned *__restrict__ out_count,
                                                     unsigned long long *__restrict__ out_count64) {
@@ -321,12 +352,10 @@ __global__ __launch_bounds__(1024) void topk_filter(const float *__restrict__ ex
     __shared__ unsigned ws[16];
     __shared__ unsigned sh_prefix, sh_rank, sh_m;
     const unsigned f = blockIdx.x;
-    const unsigned total = (unsigned)(n_in ? n_in[0] : n_host);   // count on the device, or given by the host
-    unsigned lo = seg_start ? seg_start[f] : 0u;
-    unsigned hi = seg_start ? (f + 1 < n_frames ? seg_start[f + 1] : total) : total;
-    lo = lo < total ? lo : total;
-    hi = hi < total ? hi : total;
-    hi = hi - lo > seg_cap ? lo + seg_cap : hi;   // a frame's extrema beyond max_extrema are dropped (mod.rs:627)
+    // (one segment: count on the device, or given by the host)
+    const unsigned total = seg_count ? seg_count[f] : (unsigned)(n_in ? n_in[0] : n_host);
+    const unsigned lo = seg_count ? f * seg_cap : 0u;
+    const unsigned hi = lo + (total > seg_cap ? seg_cap : total);   // a frame's extrema beyond max_extrema are dropped (mod.rs:627)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // One sweep over the segment, four extrema per thread and step so that their loads are in flight together (the
     // segment is a few thousand to a few ten thousand entries: the sweeps are latency-, not bandwidth-bound).
@@ -769,7 +798,7 @@ void scan_grid(int w, int h, int n_fine, int border, int skip_layers, int &gx, i
 void launch_detect_extrema(const float *layer0, long layer0_stride, int layer0_pitch, const float *coarse, long coarse_stride,
                            long layer_stride, int n_layers, int w, int h, int frames, int border, int skip_layers,
                            float contrast_threshold, float *slots, unsigned *counts, unsigned *sums, float *extrema,
-                           unsigned *frame_of, unsigned *frame_start, unsigned long long max_out,
+                           unsigned *frame_of, unsigned *frame_count, unsigned long long max_out,
                            unsigned long long *totals, hipStream_t stream, const RowBands *bands) {
     int gx, gy, gz;
     scan_grid(w, h, n_layers - 1, border, skip_layers, gx, gy, gz);
@@ -798,28 +827,31 @@ void launch_detect_extrema(const float *layer0, long layer0_stride, int layer0_p
     } else if (bands && !bands->last) {
         return;
     }
+    // (frame_count: the per-frame form, every frame its own max_out rows)
     if (ncubes > 0)
-        hipLaunchKernelGGL(cubes_scatter, dim3((unsigned)nb), dim3(1024), 0, stream, (const unsigned *)counts,
-                           (const float *)slots, (const unsigned *)sums, n, ncubes, extrema, frame_of, frame_start,
-                           max_out, totals);
+        hipLaunchKernelGGL(frame_count ? cubes_scatter<true> : cubes_scatter<false>, dim3((unsigned)nb), dim3(1024), 0, stream,
+                           (const unsigned *)counts, (const float *)slots, (const unsigned *)sums, n, ncubes, extrema, frame_of,
+                           frame_count, max_out, totals);
+    else if (frame_count)
+        (void)hipMemsetAsync(frame_count, 0, frames * sizeof(unsigned), stream);
     else
         (void)hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), stream);
 }
 
-void launch_topk_filter(const float *extrema, const unsigned *seg_start, const unsigned long long *n_in,
+void launch_topk_filter(const float *extrema, const unsigned *seg_count, const unsigned long long *n_in,
                         unsigned long long n_host, unsigned n_frames, unsigned seg_cap, unsigned n_keep, float min_size,
                         float *out, unsigned *out_index, unsigned *out_count, unsigned long long *out_count64,
                         unsigned long long n_cap, unsigned *work, hipStream_t stream) {
     // one frame with a long list and scratch to work in: the multi-workgroup form; otherwise one workgroup per frame
     const char *form = getenv("LF_MKD_TOPK");          // "multi": the five-launch form at every size (A/B runs, tests)
     const bool multi = form && form[0] == 'm';
-    if (n_frames == 1 && !seg_start && n_cap > 8192 && n_cap <= 1024ull * kTopkOneMaxK && seg_cap >= n_cap && !multi) {
+    if (n_frames == 1 && !seg_count && n_cap > 8192 && n_cap <= 1024ull * kTopkOneMaxK && seg_cap >= n_cap && !multi) {
         // one list that fits the registers of one workgroup (K = ceil(n / 1024) <= 32 items per thread): one launch
         hipLaunchKernelGGL(topk_one<kTopkOneMaxK>, dim3(1), dim3(1024), 0, stream, extrema, n_in, n_host, min_size, n_keep, out,
                            out_index, out_count, out_count64);
         return;
     }
-    if (n_frames == 1 && !seg_start && work && n_cap > 8192 && seg_cap >= n_cap) {
+    if (n_frames == 1 && !seg_count && work && n_cap > 8192 && seg_cap >= n_cap) {
         const unsigned nb4 = (unsigned)((n_cap + 4095) / 4096), nb1 = (unsigned)((n_cap + 1023) / 1024);
         for (int pass = 0; pass < kTopkDigits; ++pass)
             hipLaunchKernelGGL(topk_hist, dim3(nb4), dim3(1024), 0, stream, extrema, n_in, n_host, min_size, pass, n_keep,
@@ -829,17 +861,17 @@ void launch_topk_filter(const float *extrema, const unsigned *seg_start, const u
                            out, out_index, out_count, out_count64);
         return;
     }
-    hipLaunchKernelGGL(topk_filter, dim3(n_frames), dim3(1024), 0, stream, extrema, seg_start, n_in, n_host, n_frames,
-                       seg_cap, n_keep, min_size, out, out_index, out_count, out_count64);
+    hipLaunchKernelGGL(topk_filter, dim3(n_frames), dim3(1024), 0, stream, extrema, seg_count, n_in, n_host, seg_cap, n_keep,
+                       min_size, out, out_index, out_count, out_count64);
 }
 
 size_t topk_work_words(unsigned long long n_cap) { return kTopkSums + (size_t)((n_cap + 1023) / 1024) + 2; }
 
 // [frames][n_keep] padded per-frame selections + counts -> one contiguous list with the frame of every entry.
-// totals[0] = entries, totals[1] = extrema the per-frame cap dropped (dropped_blobs summed over the frames).
+// seg_count[f] = extrema frame f holds; totals[0] = entries, totals[1] = extrema the per-frame cap seg_cap dropped
+// (dropped_blobs summed over the frames).
 __global__ __launch_bounds__(1024) void segments_offsets(const unsigned *__restrict__ counts, unsigned n_frames,
-                                                         const unsigned *__restrict__ seg_start,
-                                                         const unsigned long long *__restrict__ n_total, unsigned seg_cap,
+                                                         const unsigned *__restrict__ seg_count, unsigned seg_cap,
                                                          unsigned *__restrict__ offsets,
                                                          unsigned long long *__restrict__ totals) {
     __shared__ unsigned ws[16];
@@ -851,11 +883,7 @@ __global__ __launch_bounds__(1024) void segments_offsets(const unsigned *__restr
     for (unsigned chunk = 0; chunk < n_frames; chunk += 1024) {
         const unsigned f = chunk + threadIdx.x;
         const unsigned c = f < n_frames ? counts[f] : 0u;
-        if (f < n_frames) {
-            const unsigned total = (unsigned)n_total[0];
-            const unsigned lo = seg_start[f], hi = f + 1 < n_frames ? seg_start[f + 1] : total;
-            if (hi - lo > seg_cap) atomicAdd(&dropped, (unsigned long long)(hi - lo - seg_cap));
-        }
+        if (f < n_frames && seg_count[f] > seg_cap) atomicAdd(&dropped, (unsigned long long)(seg_count[f] - seg_cap));
         unsigned incl = c;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -892,12 +920,11 @@ __global__ __launch_bounds__(256) void segments_gather(const float *__restrict__
     }
 }
 
-void launch_segments_compact(const float *padded, const unsigned *counts, const unsigned *seg_start,
-                             const unsigned long long *n_total, unsigned n_frames, unsigned seg_cap, unsigned n_keep,
-                             unsigned *offsets, float *out, unsigned *frame_of, unsigned long long *totals,
-                             hipStream_t stream) {
-    hipLaunchKernelGGL(segments_offsets, dim3(1), dim3(1024), 0, stream, counts, n_frames, seg_start, n_total, seg_cap,
-                       offsets, totals);
+void launch_segments_compact(const float *padded, const unsigned *counts, const unsigned *seg_count, unsigned n_frames,
+                             unsigned seg_cap, unsigned n_keep, unsigned *offsets, float *out, unsigned *frame_of,
+                             unsigned long long *totals, hipStream_t stream) {
+    hipLaunchKernelGGL(segments_offsets, dim3(1), dim3(1024), 0, stream, counts, n_frames, seg_count, seg_cap, offsets,
+                       totals);
     hipLaunchKernelGGL(segments_gather, dim3(n_frames), dim3(256), 0, stream, padded, counts, (const unsigned *)offsets,
                        n_keep, out, frame_of);
 }

@@ -117,26 +117,28 @@ void launch_orient(const float *layer0, long layer0_stride, int layer0_pitch, co
 // cubes of the extremum scan for a w x h frame with n_fine DoG layers (tasks_detect.rs:300-310)
 void scan_grid(int w, int h, int n_fine, int border, int skip_layers, int &gx, int &gy, int &gz);
 // a-trous stack -> extrema [<= max_out][4] of all frames, ordered by frame, cube (raster), lane; scratch: slots
-// [frames*cubes][8][4], counts [frames*cubes], sums [ceil(frames*cubes/1024)]; totals[0] = written, [1] = dropped
+// [frames*cubes][8][4], counts [frames*cubes], sums [ceil(frames*cubes/1024)]; totals[0] = written, [1] = dropped.
+// frame_count (nullable) selects the per-frame form: extrema is [frames][max_out][4], frame f's first max_out extrema at
+// rows f * max_out .., frame_count[f] = all the frame holds; frame_of and totals are not written then
 void launch_detect_extrema(const float *layer0, long layer0_stride, int layer0_pitch, const float *coarse, long coarse_stride,
                            long layer_stride, int n_layers, int w, int h, int frames, int border, int skip_layers,
                            float contrast_threshold, float *slots, unsigned *counts, unsigned *sums, float *extrema,
-                           unsigned *frame_of, unsigned *frame_start, unsigned long long max_out,
+                           unsigned *frame_of, unsigned *frame_count, unsigned long long max_out,
                            unsigned long long *totals, hipStream_t stream, const RowBands *bands = nullptr);
 // per frame: blobs with size >= min_size, the n_keep best by contrast, index order; out [n_frames][n_keep][4]
-// (the number of extrema is read from n_in on the device, or taken from n_host when n_in is null)
-void launch_topk_filter(const float *extrema, const unsigned *seg_start, const unsigned long long *n_in,
+// (one list -- seg_count null: its length is read from n_in on the device, or taken from n_host when n_in is null;
+// n_frames lists -- seg_count[f] extrema of frame f, the first min(., seg_cap) of them stored from row f * seg_cap)
+void launch_topk_filter(const float *extrema, const unsigned *seg_count, const unsigned long long *n_in,
                         unsigned long long n_host, unsigned n_frames, unsigned seg_cap, unsigned n_keep, float min_size,
                         float *out, unsigned *out_index, unsigned *out_count, unsigned long long *out_count64,
                         unsigned long long n_cap, unsigned *work, hipStream_t stream);
 // u32 words of `work` for lists of up to n_cap extrema (work may be null: one workgroup per frame is used then)
 size_t topk_work_words(unsigned long long n_cap);
 // per-frame padded selections [frames][n_keep] + counts -> contiguous list + frame ids; totals[0] = entries,
-// totals[1] = extrema dropped by the per-frame cap seg_cap
-void launch_segments_compact(const float *padded, const unsigned *counts, const unsigned *seg_start,
-                             const unsigned long long *n_total, unsigned n_frames, unsigned seg_cap, unsigned n_keep,
-                             unsigned *offsets, float *out, unsigned *frame_of, unsigned long long *totals,
-                             hipStream_t stream);
+// totals[1] = extrema dropped by the per-frame cap seg_cap (seg_count[f]: extrema frame f holds)
+void launch_segments_compact(const float *padded, const unsigned *counts, const unsigned *seg_count, unsigned n_frames,
+                             unsigned seg_cap, unsigned n_keep, unsigned *offsets, float *out, unsigned *frame_of,
+                             unsigned long long *totals, hipStream_t stream);
 
 // brute-force matcher (csrc/mkd_match.hip): x [n][128] f32 -> f16 hi/lo operand tiles (match_tiles_bytes(n) bytes);
 // a tiles against b tiles -> match [na] (index into b or -1) and optionally the best / second-best similarity.
