@@ -302,6 +302,18 @@ extern "C" {
                                       obs_capacity: u64, d_table_counts: *const u32, n_images: u32, d_edge_a: *const u32,
                                       d_edge_b: *const u32, n_edges: u64, flags: u32, d_covis: *mut u32,
                                       stream: *mut c_void) -> c_int;
+    // two-view poses: per edge R [9], t [3] (x_b = R x_a + t, |t| = 1), stats [4], optional sigma [3] and per link optional
+    // points [4], from d_F [n_edges][9], d_intrinsics [n_images][4] (fx, fy, cx, cy) and a link table of pool rows; flags: 0;
+    // the host form takes one pair and a match array and returns points per row of a
+    pub fn lf_mkd_two_view_pose_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, n_rows_total: u64, d_edge_a: *const u32,
+                                       d_edge_b: *const u32, n_edges: u32, d_intrinsics: *const f32, n_images: u32,
+                                       d_f: *const f32, d_link_offsets: *const u64, d_link_a: *const i32, d_link_b: *const i32,
+                                       link_capacity: u64, min_parallax_deg: f32, flags: u32, d_r: *mut f32, d_t: *mut f32,
+                                       d_stats: *mut u32, d_sigma: *mut f32, d_points: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_two_view_pose(h: *mut lf_mkd, fundamental: *const f32, k_a: *const f32, k_b: *const f32,
+                                kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint, nb: u64,
+                                matches: *const i32, min_parallax_deg: f32, flags: u32, r: *mut f32, t: *mut f32,
+                                stats: *mut u32, sigma: *mut f32, points: *mut f32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

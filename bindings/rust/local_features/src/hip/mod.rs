@@ -572,6 +572,35 @@ impl LocalFeaturesHip {
         Ok(covis)
     }
 
+    /// The relative pose of one calibrated pair from its fundamental matrix (`lf_mkd_two_view_pose`): `f` is row-major with
+    /// b^T F a = 0 in pixels, `k_a` / `k_b` are (fx, fy, cx, cy), `matches` the verified (i, j) pairs.  Returns `None` if there
+    /// is no pose, else (R row-major, t with |t| = 1, [links in front, the best other candidate's, the candidate, links with at
+    /// least `min_parallax_deg` of parallax], E's singular values over the largest, and per keypoint of a its triangulated
+    /// point in camera a's frame with the cosine of the parallax angle, (0, 0, 0, 2) where there is none): x_b = R x_a + t.
+    #[allow(clippy::type_complexity)]
+    pub fn two_view_pose(&mut self, f: &[f32; 9], k_a: &[f32; 4], k_b: &[f32; 4], kps_a: &[ffi::lf_mkd_keypoint],
+                         kps_b: &[ffi::lf_mkd_keypoint], matches: &[(usize, usize)], min_parallax_deg: f32)
+                         -> Result<Option<([f32; 9], [f32; 3], [u32; 4], [f32; 3], Vec<[f32; 4]>)>, Error> {
+        let mut m = vec![-1i32; kps_a.len()];
+        for &(i, j) in matches {
+            if i >= kps_a.len() || j >= kps_b.len() {
+                return Err(Error::BadArgument("two_view_pose: a match outside the keypoint lists".into()));
+            }
+            m[i] = j as i32;
+        }
+        let (mut r, mut t, mut stats, mut sigma) = ([0f32; 9], [0f32; 3], [0u32; 4], [0f32; 3]);
+        let mut points = vec![[0f32; 4]; kps_a.len().max(1)];
+        // SAFETY: host arrays sized as declared; na and nb bound what is read, points has one row per keypoint of a
+        unsafe {
+            check(self.h, ffi::lf_mkd_two_view_pose(
+                self.h, f.as_ptr(), k_a.as_ptr(), k_b.as_ptr(), kps_a.as_ptr(), kps_a.len() as u64, kps_b.as_ptr(),
+                kps_b.len() as u64, m.as_ptr(), min_parallax_deg, 0, r.as_mut_ptr(), t.as_mut_ptr(), stats.as_mut_ptr(),
+                sigma.as_mut_ptr(), points.as_mut_ptr() as *mut f32))?;
+        }
+        points.truncate(kps_a.len());
+        Ok(if stats[2] == u32::MAX { None } else { Some((r, t, stats, sigma, points)) })
+    }
+
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches
     /// `match_q8_edges` or a verifier returned for `edges` over the pool `image_offsets` describes (`n_rows` rows), edges with
     /// fewer than `min_links` of them left out.  Returns (offsets, link_a, link_b, edge_links): edge e's correspondences are

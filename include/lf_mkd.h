@@ -1075,6 +1075,78 @@ int lf_mkd_covisibility_device(lf_mkd *h, const uint64_t *d_track_offsets, uint6
                                const uint32_t *d_edge_b, uint64_t n_edges, uint32_t flags, uint32_t *d_covis, void *stream);
 #define LF_MKD_COVIS_ACCUMULATE (1u)  /* flags: d_covis is not zeroed, the table is added to what it holds */
 #define LF_MKD_COVIS_FORM_LDS (256u)  /* in the plan's form: a workgroup counts into a private table in LDS first */
+/* lf_mkd_two_view_pose_device turns every verified edge of a calibrated collection into a RELATIVE POSE: the rotation R and
+ * the unit translation t of camera b relative to camera a (x_b = R x_a + t), chosen among the four candidates of the edge's
+ * essential matrix by a vote of the edge's links, with the links' triangulated points -- what structure from motion reads to
+ * pick its initial pair (many links with real parallax), to reject an edge whose F is no essential matrix under the
+ * intrinsics, and to seed points.  Inputs are what the calls above leave on the device: d_F [n_edges][9] of
+ * lf_mkd_verify_fundamental_device (b^T F a = 0, pixels), the link table d_link_offsets / d_link_a / d_link_b of
+ * lf_mkd_link_table_device WITHOUT LF_MKD_LINK_TABLE_LOCAL (pool rows), the pool's keypoints (only x and y are read), the edge
+ * list, and d_intrinsics [n_images][4] = fx, fy, cx, cy per image.
+ *   reading     edge e's links are the range of d_link_offsets[e], d_link_offsets[e + 1] read against link_capacity as a pair
+ *               is read against a total: an offset beyond it is link_capacity, an inverted range is empty.  Entry k of the
+ *               range is a LINK iff 0 <= d_link_a[k] < n_rows_total and 0 <= d_link_b[k] < n_rows_total; any other entry is
+ *               no link: it counts nowhere and its point is the "none" row.
+ * Outputs per edge e:
+ *   d_R         f32 [n_edges][9], row-major; d_t f32 [n_edges][3], |t| = 1.
+ *   d_stats     uint32 [n_edges][4] = {links in front of both cameras under the chosen pose, the largest such count among the
+ *               other three candidates, the chosen candidate c in 0 .. 3 (0xFFFFFFFF: none), in-front links whose parallax
+ *               angle is at least min_parallax_deg}.
+ *   d_sigma     optional, f32 [n_edges][3]: E's singular values over the largest, {1, s2/s1, s3/s1}.  A true essential matrix
+ *               gives {1, 1, 0}; wrong intrinsics or a wrong F show here.
+ *   d_points    optional, f32 [link_capacity][4]: per link, at its position in the table, {X, Y, Z in camera a's frame at
+ *               |t| = 1, the COSINE of the parallax angle}; {0, 0, 0, 2} (the "none" row) for an entry that is no link or not
+ *               in front under the chosen pose.  Entries outside every edge's range are untouched.
+ * The algorithm, exactly (the kernel's own arithmetic, csrc/mkd_pose_math.h, built for the host, reproduces every output bit:
+ * tests/cpp/pose_twin.cpp; a float64 numpy restatement: tests/pose_cases.py).  Only correctly rounded f64 operations are used
+ * (+ - * /, sqrt) in a fixed order without contraction, with fixed iteration counts and no transcendental on the device:
+ * cos(min_parallax_deg) is formed once on the host in double (cmin), and every point output is a cosine, not an angle.
+ *   1. E = Kb^T F Ka in f64 from the f32 inputs: M = F Ka row by row (f0 fx, f1 fy, f0 cx + f1 cy + f2), then fxb M_0,
+ *      fyb M_1, cxb M_0 + cyb M_1 + M_2, every sum left to right.
+ *   2. SVD: S = E^T E (each entry a sum of three products, left to right), eigen-decomposed by 6 sweeps of cyclic Jacobi in
+ *      f64, the F refit's rotation (pairs (0,1) (0,2) (1,2); theta = (s_qq - s_pp) / (2 s_pq), t = sign(theta) / (|theta| +
+ *      sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c; none where s_pq = 0).  Eigenvalues w are sorted descending, the lower
+ *      index first on a tie; s_i = sqrt(max(w_i, 0)).  u1 = E v1 / |E v1|; u2 = E v2 - (u1 . E v2) u1, normalised;
+ *      u3 = u1 x u2, v3 = v1 x v2 (both determinants +1).  With W = [[0,-1,0],[1,0,0],[0,0,1]]: R1 = U W V^T =
+ *      (u2 v1^T - u1 v2^T) + u3 v3^T, R2 = U W^T V^T = (u1 v2^T - u2 v1^T) + u3 v3^T.  Candidates c = 0: (R1, +u3), 1: (R1, -u3),
+ *      2: (R2, +u3), 3: (R2, -u3).  Eigenvector signs are the Jacobi's own: another SVD may number the candidates differently.
+ *   3. Vote: for a link, xa = ((x - cx) / fx, (y - cy) / fy, 1) from its a row under image a's intrinsics, xb likewise, in
+ *      f64; p = R xa, q = xb; det = (p.p)(q.q) - (p.q)^2, na = (p.q)(q.t) - (p.t)(q.q), nb = (p.p)(q.t) - (p.q)(p.t).  The link is
+ *      IN FRONT iff det > 0 and na > 0 and nb > 0 (the two depths' signs; no division decides anything).  It has PARALLAX iff it
+ *      is in front and p.q <= cmin sqrt((p.p)(q.q)).  NaN coordinates need no rule: every comparison is false.
+ *   4. Choice: the candidate with the largest in-front count, the lowest c on a tie.
+ *   5. Points: la = na / det, lb = nb / det, X = (la xa + R^T (lb xb - t)) / 2 (the midpoint of the two rays' closest points,
+ *      in camera a's frame), the cosine (p.q) / sqrt((p.p)(q.q)); rounded to f32 at the store, as R, t and sigma are.
+ *   6. No pose: R, t and sigma all zero, stats {0, 0, 0xFFFFFFFF, 0}, every entry of the edge's range the "none" row; the status
+ *      stays LF_MKD_OK.  That is the outcome iff an image id is at or beyond n_images (lf_mkd_select_edges_device's 0xFFFFFFFF
+ *      padding passes whole), an intrinsic is not finite or fx or fy is <= 0, a value of F is not finite or F is all zero, s1
+ *      is not finite and positive or s2 <= 1e-3 s1 (a rank-1 F), or the best count is 0.
+ * Counts are integer sums: every output bit depends on the edge's own inputs alone, not on the other edges of the call, the
+ * run, the CU count or the kernel's form; edge e of a batched call equals a single-edge call, a captured call replays to the
+ * same bits.  Whatever the arrays hold the call ends and nothing is read or written at or beyond n_rows_total, n_images,
+ * n_edges (+ 1 for the offsets) or link_capacity.  n_edges == 0 is LF_MKD_OK and writes nothing.
+ * How (csrc/mkd_two_view_pose.hip): ONE launch, one workgroup of 256 threads per edge; thread 0 decomposes E into LDS, the
+ * workgroup walks the links 256 at a time and counts the four candidates by ballot and popcount, chooses, and walks them once
+ * more for the points and the parallax count.  No scratch, no allocation, no atomic, nobody waits; asynchronous on `stream`
+ * (NULL: the handle's own), no host synchronisation, capturable in a hipGraph.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "two_view_pose_device: " and is reachable
+ * through lf_mkd_last_error(NULL) when h is NULL): a null handle; with n_edges > 0 a null edge array, d_F, d_link_offsets, d_R,
+ * d_t or d_stats, a null d_intrinsics with n_images > 0, a null d_link_a or d_link_b with link_capacity > 0, a null d_kps with
+ * link_capacity > 0 and n_rows_total > 0; flags other than 0 (none is defined); min_parallax_deg outside [0, 180] or NaN;
+ * d_link_offsets not 8-byte or any other array not 4-byte aligned; n_rows_total, link_capacity or n_edges above 2^31 - 1. */
+int lf_mkd_two_view_pose_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, uint64_t n_rows_total, const uint32_t *d_edge_a,
+                                const uint32_t *d_edge_b, uint32_t n_edges, const float *d_intrinsics, uint32_t n_images,
+                                const float *d_F, const uint64_t *d_link_offsets, const int32_t *d_link_a, const int32_t *d_link_b,
+                                uint64_t link_capacity, float min_parallax_deg, uint32_t flags, float *d_R, float *d_t,
+                                uint32_t *d_stats, float *d_sigma, float *d_points, void *stream);
+/* Host pointers, ONE pair, synchronous: F [9], Ka [4] and Kb [4] (fx, fy, cx, cy), the two images' keypoints and a match array
+ * [na] read by the verifiers' rule (row i of a and row match[i] of b are a link iff 0 <= match[i] < nb; pass the verifier's
+ * `verified`).  The links are built on the host and go through the device call; R [9], t [3], stats [4], optional sigma [3]
+ * and optional points [na][4], indexed like a (the "none" row where row i has no link).  LF_MKD_ERR_BAD_ARG ("two_view_pose: "):
+ * a null handle or required pointer, flags other than 0, min_parallax_deg outside [0, 180] or NaN, na + nb above 2^31 - 1. */
+int lf_mkd_two_view_pose(lf_mkd *h, const float *F, const float *Ka, const float *Kb, const lf_mkd_keypoint *kps_a, uint64_t na,
+                         const lf_mkd_keypoint *kps_b, uint64_t nb, const int32_t *match, float min_parallax_deg, uint32_t flags,
+                         float *R, float *t, uint32_t *stats, float *sigma, float *points);
 
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the

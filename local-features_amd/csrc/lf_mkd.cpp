@@ -2518,6 +2518,113 @@ int lf_mkd_covisibility_device(lf_mkd *h, const uint64_t *d_track_offsets, uint6
     return LF_MKD_OK;
 }
 
+// Two-view poses (csrc/mkd_two_view_pose.hip).  Every refusal comes before the handle is looked at.  The cosine of the
+// parallax threshold is formed here, once, in double: no transcendental runs on the device (tests/cpp/pose_twin.cpp forms it
+// with the same expression).
+static const char *two_view_pose_scalars(float min_parallax_deg, uint32_t flags) {
+    if (flags) return "unknown flag bits (no flag is defined: flags must be 0)";
+    if (!(min_parallax_deg >= 0.f && min_parallax_deg <= 180.f)) return "min_parallax_deg must be in [0, 180]";
+    return nullptr;
+}
+
+int lf_mkd_two_view_pose_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, uint64_t n_rows_total, const uint32_t *d_edge_a,
+                                const uint32_t *d_edge_b, uint32_t n_edges, const float *d_intrinsics, uint32_t n_images,
+                                const float *d_F, const uint64_t *d_link_offsets, const int32_t *d_link_a, const int32_t *d_link_b,
+                                uint64_t link_capacity, float min_parallax_deg, uint32_t flags, float *d_R, float *d_t,
+                                uint32_t *d_stats, float *d_sigma, float *d_points, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (n_edges && (!d_edge_a || !d_edge_b)) msg = "null edge array";
+    else if (n_edges && (!d_F || !d_link_offsets || !d_R || !d_t || !d_stats)) msg = "null d_F, d_link_offsets, d_R, d_t or d_stats";
+    else if (n_edges && n_images && !d_intrinsics) msg = "null d_intrinsics";
+    else if (n_edges && link_capacity && (!d_link_a || !d_link_b)) msg = "null d_link_a or d_link_b";
+    else if (n_edges && link_capacity && n_rows_total && !d_kps) msg = "null d_kps";
+    else if ((msg = two_view_pose_scalars(min_parallax_deg, flags))) {}
+    else if (at(d_link_offsets) & 7) msg = "d_link_offsets must be 8-byte aligned";
+    else if ((at(d_kps) | at(d_edge_a) | at(d_edge_b) | at(d_intrinsics) | at(d_F) | at(d_link_a) | at(d_link_b) | at(d_R) |
+              at(d_t) | at(d_stats) | at(d_sigma) | at(d_points)) & 3)
+        msg = "the keypoint, edge, intrinsics, model, link and output arrays must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || link_capacity > kEdgeMax || n_edges > kEdgeMax)
+        msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "two_view_pose_device", msg);
+    if (n_edges == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const double cmin = std::cos(double(min_parallax_deg) * (3.14159265358979323846 / 180.0));
+    launch_two_view_pose(reinterpret_cast<const float *>(d_kps), n_rows_total, d_edge_a, d_edge_b, n_edges, d_intrinsics, n_images,
+                         d_F, d_link_offsets, d_link_a, d_link_b, link_capacity, cmin, d_R, d_t, d_stats, d_sigma, d_points,
+                         stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// The host form: one pair.  The pool is a's rows then b's, the two images 0 and 1, the one edge (0, 1); the links are built
+// here by the verifiers' rule (row i of a and row match[i] of b iff 0 <= match[i] < nb), staged through the handle's d_ver_io
+// with the outputs, and the device call does the rest.  points comes back per row of a: the link's point, or the "none" row.
+int lf_mkd_two_view_pose(lf_mkd *h, const float *F, const float *Ka, const float *Kb, const lf_mkd_keypoint *kps_a, uint64_t na,
+                         const lf_mkd_keypoint *kps_b, uint64_t nb, const int32_t *match, float min_parallax_deg, uint32_t flags,
+                         float *R, float *t, uint32_t *stats, float *sigma, float *points) {
+    const char *msg = nullptr;
+    if (!F || !Ka || !Kb || !R || !t || !stats) msg = "null pointer";
+    else if ((na && (!kps_a || !match)) || (nb && !kps_b)) msg = "null keypoint or match array";
+    else if ((msg = two_view_pose_scalars(min_parallax_deg, flags))) {}
+    else if (na > kEdgeMax || nb > kEdgeMax || na + nb > kEdgeMax) msg = "more than 2^31 - 1 rows";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "two_view_pose", msg);
+    LF_ENTER(h);
+    std::vector<int32_t> links;   // a's rows, then b's
+    for (uint64_t i = 0; i < na; ++i)
+        if (match[i] >= 0 && uint64_t(match[i]) < nb) links.push_back(int32_t(i));
+    const uint64_t n_links = links.size();
+    links.resize(2 * n_links);
+    for (uint64_t k = 0; k < n_links; ++k) links[n_links + k] = int32_t(na + uint64_t(match[links[k]]));
+    auto up16 = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 15) / 16 * 16; };
+    // offsets [2] u64, edge a, edge b, K [2][4], F [9], then the outputs R [9], t [3], stats [4], sigma [3], then the arrays
+    const uint64_t o_off = 0, o_ea = 16, o_eb = 32, o_k = 48, o_f = 80, o_r = 128, o_t = 176, o_st = 192, o_sg = 208, o_kps = 224,
+                   o_la = o_kps + up16((na + nb) * sizeof(lf_mkd_keypoint)), o_lb = o_la + up16(n_links * 4),
+                   o_pt = o_lb + up16(n_links * 4), total = o_pt + up16(points ? n_links * 16 : 0);
+    if (int rc = grow(h, h->d_ver_io, total)) return rc;
+    unsigned char *io = h->d_ver_io;
+    const uint64_t offs[2] = {0, n_links};
+    const uint32_t ea = 0, eb = 1;
+    float K[8];
+    for (int i = 0; i < 4; ++i) K[i] = Ka[i], K[4 + i] = Kb[i];
+    LF_HIP(h, hipMemcpyAsync(io + o_off, offs, sizeof(offs), hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(io + o_ea, &ea, 4, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(io + o_eb, &eb, 4, hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(io + o_k, K, sizeof(K), hipMemcpyHostToDevice, h->stream));
+    LF_HIP(h, hipMemcpyAsync(io + o_f, F, 9 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (na) LF_HIP(h, hipMemcpyAsync(io + o_kps, kps_a, na * sizeof(lf_mkd_keypoint), hipMemcpyHostToDevice, h->stream));
+    if (nb)
+        LF_HIP(h, hipMemcpyAsync(io + o_kps + na * sizeof(lf_mkd_keypoint), kps_b, nb * sizeof(lf_mkd_keypoint),
+                                 hipMemcpyHostToDevice, h->stream));
+    if (n_links) {
+        LF_HIP(h, hipMemcpyAsync(io + o_la, links.data(), n_links * 4, hipMemcpyHostToDevice, h->stream));
+        LF_HIP(h, hipMemcpyAsync(io + o_lb, links.data() + n_links, n_links * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (int rc = lf_mkd_two_view_pose_device(
+            h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_kps), na + nb, reinterpret_cast<const uint32_t *>(io + o_ea),
+            reinterpret_cast<const uint32_t *>(io + o_eb), 1, reinterpret_cast<const float *>(io + o_k), 2,
+            reinterpret_cast<const float *>(io + o_f), reinterpret_cast<const uint64_t *>(io + o_off),
+            reinterpret_cast<const int32_t *>(io + o_la), reinterpret_cast<const int32_t *>(io + o_lb), n_links, min_parallax_deg,
+            flags, reinterpret_cast<float *>(io + o_r), reinterpret_cast<float *>(io + o_t), reinterpret_cast<uint32_t *>(io + o_st),
+            reinterpret_cast<float *>(io + o_sg), points ? reinterpret_cast<float *>(io + o_pt) : nullptr, h->stream))
+        return rc;
+    std::vector<float> link_points(points ? 4 * n_links : 0);
+    LF_HIP(h, hipMemcpyAsync(R, io + o_r, 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipMemcpyAsync(t, io + o_t, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipMemcpyAsync(stats, io + o_st, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (sigma) LF_HIP(h, hipMemcpyAsync(sigma, io + o_sg, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (points && n_links)
+        LF_HIP(h, hipMemcpyAsync(link_points.data(), io + o_pt, n_links * 16, hipMemcpyDeviceToHost, h->stream));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    if (points) {
+        for (uint64_t i = 0; i < na; ++i) points[4 * i] = points[4 * i + 1] = points[4 * i + 2] = 0.f, points[4 * i + 3] = 2.f;
+        for (uint64_t k = 0; k < n_links; ++k) std::memcpy(points + 4 * uint64_t(links[k]), link_points.data() + 4 * k, 16);
+    }
+    return LF_MKD_OK;
+}
+
 // Guided matching over 8-bit rows: the two calls' refusals together, the q8 pairs call's grid.
 int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
                                         uint64_t na_total, const uint8_t *d_b, const lf_mkd_keypoint *d_kps_b,

@@ -346,6 +346,12 @@ void launch_covisibility(const CovisibilityPlan &plan, unsigned char *scratch, c
                          uint64_t track_capacity, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts,
                          unsigned n_images, const unsigned *edge_a, const unsigned *edge_b, uint64_t n_edges, bool accumulate,
                          unsigned *covis, hipStream_t stream);
+// two-view poses (csrc/mkd_two_view_pose.hip, lf_mkd_two_view_pose_device): one launch, a workgroup per edge, no scratch.
+// Keypoints are read as rows of 5 floats; cmin = the cosine of the parallax threshold, formed by the host in double.
+void launch_two_view_pose(const float *kps, uint64_t n_rows, const unsigned *edge_a, const unsigned *edge_b, unsigned n_edges,
+                          const float *intrinsics, unsigned n_images, const float *F, const uint64_t *link_off, const int *link_a,
+                          const int *link_b, uint64_t link_capacity, double cmin, float *R, float *t, unsigned *stats, float *sigma,
+                          float *points, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

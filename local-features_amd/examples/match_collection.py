@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -35,13 +35,19 @@ descriptor row is copied for it.
   them (at least --min-shared M of them, default     (min_votes = M, skip_self, unique), the same matcher and verifier on the
   8), matched and verified like the first round,     proposed edges, their links ADDED to the forest (build_tracks(into=track)),
   and the tracks of both rounds together             then the statistics and the table once more
+  with --pose FOCAL[,CX,CY] (one pinhole camera for  LocalFeatures.two_view_pose (lf_mkd_two_view_pose_device) after the link
+  every image, the principal point in the middle     table: E = K^T F K per edge, its four (R, t) candidates voted by the edge's
+  of the frame unless given; implies --fundamental   links, the links triangulated; nothing leaves the device before the lines
+  and --pairs) the relative pose of every edge       are printed
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
 of the keypoints that sit in a consistent track; with --table also the number of tracks and observations in the table and the
 first three tracks as image:x,y lists; with --pairs also the number of edges and correspondences in the link table and the
 first three correspondences of the best edge as x,y -> x,y; with --expand also one line with the proposed edges and how many of
-them kept a verified match, and the track lines once more for the expanded forest.  Nothing is read back before those counts: the
+them kept a verified match, and the track lines once more for the expanded forest; with --pose per edge the rotation angle,
+the direction of t, the links in front of both cameras out of the edge's links, those with at least 1 degree of parallax and
+s2/s1 of the essential matrix (1 for a true one).  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -93,7 +99,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -117,7 +123,10 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     skip_self, unique); expand_layout_a, expand_verified and expand_per_edge, the proposed edges matched and verified like the
     first round's; first_round, a dict with the first round's track_counts and table_* entries -- and track, track_len,
     track_dup, track_counts and the table_* entries are then those of the forest with both rounds' links (the second round's
-    are added in place: build_tracks(into=track)).  Without, those seven are None."""
+    are added in place: build_tracks(into=track)).  Without, those seven are None.  With `pose` = (focal, cx, cy), one pinhole
+    camera for every image (implies `pairs`; it wants `fundamental`), also the relative pose of every edge from its F and its
+    links as LocalFeatures.two_view_pose returns it -- pose_R [E,3,3], pose_t [E,3], pose_stats [E,4], pose_sigma [E,3] and
+    pose_points [layout capacity,4], the links triangulated in the a camera's frame; without, those five are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -162,10 +171,14 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         raw = (best != -2 ** 31) & ((ratio <= 0) | (best.float() * ratio > second.float()))   # (both conversions are exact)
         per_edge = torch.stack([count(raw), count(m_ab >= 0), count(ver >= 0)], dim=1)
         l_off = l_a = l_b = l_edge = l_links = l_kept = l_counts = l_ka = l_kb = None
-        if pairs or min_inliers is not None:
+        if pairs or min_inliers is not None or pose is not None:
             l_off, l_a, l_b, l_edge, l_links, l_kept, l_counts = feats.link_table(
                 o, ea, eb, la, ver, min_links=min_inliers or 0, capacity=cap_a, n_rows=m, kept_match=min_inliers is not None)
             l_ka, l_kb = feats.gather_track_rows(kps, l_a, l_counts), feats.gather_track_rows(kps, l_b, l_counts)
+        p_R = p_t = p_stats = p_sigma = p_points = None
+        if pose is not None:
+            intr = torch.tensor([[pose[0], pose[0], pose[1], pose[2]]], dtype=torch.float32, device=dev).repeat(n, 1)
+            p_R, p_t, p_stats, p_sigma, p_points = feats.two_view_pose(model.contiguous(), intr, kps, (ea, eb), (l_off, l_a, l_b))
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
         if tracks or table or expand:
@@ -213,13 +226,25 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 link_counts=l_counts, link_keypoints_a=l_ka, link_keypoints_b=l_kb, match_kept=l_kept, votes=votes,
                 edge_votes=e_votes, rank=rank, rank_votes=rank_votes, select_counts=s_counts, covisibility=covis,
                 expand_edge_a=x_ea, expand_edge_b=x_eb, expand_counts=x_counts, expand_layout_a=x_la, expand_verified=x_ver,
-                expand_per_edge=x_per_edge, first_round=first)
+                expand_per_edge=x_per_edge, first_round=first, pose_R=p_R, pose_t=p_t, pose_stats=p_stats,
+                pose_sigma=p_sigma, pose_points=p_points)
+
+
+def parse_pose(text):
+    """FOCAL or FOCAL,CX,CY -> (focal, cx, cy), cx and cy None if not given; None if the text is neither."""
+    try:
+        v = [float(x) for x in text.split(",")]
+    except ValueError:
+        return None
+    if len(v) not in (1, 3) or not v[0] > 0:
+        return None
+    return (v[0], v[1], v[2]) if len(v) == 3 else (v[0], None, None)
 
 
 def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
-    expand, min_shared = None, 8
+    expand, min_shared, pose = None, 8, None
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -237,6 +262,9 @@ def main():
             expand = int(args.pop(0))
         elif a == "--min-shared" and args and args[0].isdigit():
             min_shared = int(args.pop(0))
+        elif a == "--pose" and args and parse_pose(args[0]) is not None:
+            pose = parse_pose(args.pop(0))
+            fundamental = pairs = True
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -247,7 +275,7 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
               "number of images)", file=sys.stderr)
@@ -256,8 +284,10 @@ def main():
     if any(i.shape != imgs[0].shape for i in imgs):
         print("the images must have one size", file=sys.stderr)
         return 1
+    if pose is not None and pose[1] is None:                    # the principal point: the middle of the frame
+        pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers, expand=expand, min_shared=min_shared)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -292,6 +322,16 @@ def main():
         xa, xb = out["link_keypoints_a"][lo:hi, :2].cpu().tolist(), out["link_keypoints_b"][lo:hi, :2].cpu().tolist()
         for a, b in zip(xa, xb):
             print(f"Edge {ea[best] + 1} -> {eb[best] + 1}: {a[0]:.1f},{a[1]:.1f} -> {b[0]:.1f},{b[1]:.1f}")
+    if pose is not None:
+        R, t, st, sg = (out[k].cpu().numpy() for k in ("pose_R", "pose_t", "pose_stats", "pose_sigma"))
+        links = out["edge_links"].cpu().tolist()
+        for e in sorted(range(len(ea)), key=lambda e: (-per_edge[e][2], e)):
+            if st[e][2] < 0:
+                print(f"Pose {ea[e] + 1} -> {eb[e] + 1}: none")
+                continue
+            angle = np.degrees(np.arccos(np.clip((np.trace(R[e].astype(np.float64)) - 1) / 2, -1, 1)))
+            print(f"Pose {ea[e] + 1} -> {eb[e] + 1}: rotation {angle:.2f} deg, t {t[e][0]:+.3f} {t[e][1]:+.3f} {t[e][2]:+.3f}, "
+                  f"{st[e][0]} / {links[e]} links in front, {st[e][3]} with parallax, s2/s1 {sg[e][1]:.3f}")
     if expand:
         proposed = out["expand_counts"].cpu().tolist()[0]
         kept = int((out["expand_per_edge"][:proposed, 1] > 0).sum())

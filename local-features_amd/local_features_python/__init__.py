@@ -844,6 +844,68 @@ class LocalFeatures:
                                                 COVIS_ACCUMULATE if into is not None else 0, ptr(covis), s.cuda_stream)
         return covis
 
+    def two_view_pose(self, F, intrinsics, kps, edges=None, links=None, min_parallax_deg=1.0, sigma=True, points=True,
+                      stream=None):
+        """The relative pose of calibrated image pairs from their fundamental matrices (lf_mkd_two_view_pose_device): x_b =
+        R x_a + t with |t| = 1, chosen among the four candidates of E = K_b^T F K_a by a vote of the pair's correspondences,
+        and those correspondences triangulated (include/lf_mkd.h states the algorithm).  Two forms:
+
+        * Device tensors, many edges: F [n_edges, 3, 3] (or [n_edges, 9]) float32 as verify_fundamental_batch returns it,
+          intrinsics [n_images, 4] float32 (fx, fy, cx, cy per image), kps [rows, 5] float32 (the pool), edges = (edge_a,
+          edge_b) 32-bit image ids, links = (link_offsets [n_edges + 1] int64, link_a, link_b int32 pool rows) as
+          link_table(local=False) returns them.  Returns device tensors (R [n_edges, 3, 3], t [n_edges, 3], stats
+          [n_edges, 4] int32 -- links in front, the best other candidate's, the candidate (-1: no pose), links with at least
+          min_parallax_deg of parallax --, sigma [n_edges, 3] or None, points [links, 4] or None: X, Y, Z in camera a's frame
+          and the cosine of the parallax angle, (0, 0, 0, 2) where a link is not in front).  Nothing is read back:
+          asynchronous on `stream` (default: torch's current stream on the handle's device), capturable.
+        * One pair as host arrays: F [3, 3], intrinsics = (K_a, K_b) each (fx, fy, cx, cy), kps = (kp_a, kp_b) keypoint lists
+          or [n, 4|5] arrays, links = the (i, j) matches (verify_fundamental's inliers); edges stays None.  Returns numpy (R
+          [3, 3], t [3], stats [4] int64, sigma [3] or None, points [len(kp_a), 4] or None), synchronously."""
+        if edges is None:
+            a, b = _keypoints_to_array(kps[0]), _keypoints_to_array(kps[1])
+            m = np.full(len(a), -1, np.int32)
+            for i, j in links:
+                if not (0 <= i < len(a) and 0 <= j < len(b)):
+                    raise RuntimeError("two_view_pose: match (%d, %d) outside the keypoint lists" % (i, j))
+                m[i] = j
+            with self._lock:
+                R, t, st, sg, pts = self._inner.two_view_pose(F, intrinsics[0], intrinsics[1], a.view(np.float32).reshape(-1, 5),
+                                                              b.view(np.float32).reshape(-1, 5), m, min_parallax_deg, 0, points)
+            st = st.astype(np.int64)
+            st[2] = -1 if st[2] == 0xFFFFFFFF else st[2]
+            return R, t, st, sg if sigma else None, pts
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            ea, eb = self._words(edges[0], dev), self._words(edges[1], dev)
+            n_edges = ea.numel()
+            off, la, lb = links
+            if not (ok(F, torch.float32) and F.numel() == 9 * n_edges and eb.numel() == n_edges):
+                raise RuntimeError("two_view_pose: F must be a contiguous float32 device tensor with 9 values per edge, edges one "
+                                   "id per edge in each of its two arrays")
+            if not (ok(intrinsics, torch.float32) and intrinsics.dim() == 2 and intrinsics.shape[1] == 4):
+                raise RuntimeError("two_view_pose: intrinsics must be a contiguous float32 [n_images, 4] device tensor")
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("two_view_pose: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(off, torch.int64) and off.numel() == n_edges + 1 and ok(la, torch.int32) and ok(lb, torch.int32)
+                    and la.numel() == lb.numel()):
+                raise RuntimeError("two_view_pose: links must be (offsets int64 [n_edges + 1], link_a int32, link_b int32) device "
+                                   "tensors as link_table returned them")
+            cap = la.numel()
+            R = torch.empty((n_edges, 3, 3), dtype=torch.float32, device=dev)
+            t = torch.empty((n_edges, 3), dtype=torch.float32, device=dev)
+            st = torch.empty((n_edges, 4), dtype=torch.int32, device=dev)
+            sg = torch.empty((n_edges, 3), dtype=torch.float32, device=dev) if sigma else None
+            pts = torch.empty((cap, 4), dtype=torch.float32, device=dev) if points else None
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.two_view_pose_device(ptr(kps), kps.shape[0], ptr(ea), ptr(eb), n_edges, ptr(intrinsics),
+                                                 intrinsics.shape[0], ptr(F), off.data_ptr(), ptr(la), ptr(lb), cap, ptr(R), ptr(t),
+                                                 ptr(st), ptr(sg), ptr(pts), min_parallax_deg, 0, s.cuda_stream)
+        return R, t, st, sg, pts
+
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):
         """match_guided_batch over 8-bit descriptors (lf_mkd_match_q8_guided_pairs_device: one launch, three with `mutual`):

@@ -48,6 +48,7 @@ SYMBOLS = (
     "lf_mkd_link_table_plan", "lf_mkd_link_table_device",
     "lf_mkd_select_edges_plan", "lf_mkd_select_edges_device",
     "lf_mkd_covisibility_plan", "lf_mkd_covisibility_device",
+    "lf_mkd_two_view_pose", "lf_mkd_two_view_pose_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -173,6 +174,9 @@ def load_library():
     L.lf_mkd_select_edges_device.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, vp, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_covisibility_plan.argtypes = [u32, u64, u64, u64, u32, vp, vp, vp, vp]
     L.lf_mkd_covisibility_device.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, vp, u64, u32, vp, vp]
+    L.lf_mkd_two_view_pose_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, ctypes.c_float, u32, vp, vp,
+                                              vp, vp, vp, vp]
+    L.lf_mkd_two_view_pose.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -581,6 +585,25 @@ class MkdHandle:
                                                       st.ctypes.data), "lf_mkd_verify_fundamental")
         return F.reshape(3, 3), ver[:len(a)].copy(), st
 
+    def two_view_pose(self, F, K_a, K_b, kps_a, kps_b, match, min_parallax_deg=1.0, flags=0, points=True):
+        """lf_mkd_two_view_pose: F [3,3] f32 (b^T F a = 0, pixels), K_a / K_b = (fx, fy, cx, cy), kps_a [na,5], kps_b [nb,5]
+        f32 rows, match int32 [na] (index into b or -1: pass the verifier's `verified`) -> (R [3,3] f32, t [3] f32, stats
+        uint32 [4], sigma [3] f32, points [na,4] f32 or None)."""
+        f = np.ascontiguousarray(F, np.float32).reshape(9)
+        ka, kb = np.ascontiguousarray(K_a, np.float32).reshape(4), np.ascontiguousarray(K_b, np.float32).reshape(4)
+        a = np.ascontiguousarray(kps_a, np.float32).reshape(-1, 5)
+        b = np.ascontiguousarray(kps_b, np.float32).reshape(-1, 5)
+        m = np.ascontiguousarray(match, np.int32).reshape(-1)
+        if len(m) != len(a):
+            raise RuntimeError("two_view_pose: match must have one entry per row of kps_a")
+        R, t, st, sg = np.empty(9, np.float32), np.empty(3, np.float32), np.empty(4, np.uint32), np.empty(3, np.float32)
+        pts = np.empty((max(len(a), 1), 4), np.float32) if points else None
+        self._check(self.L.lf_mkd_two_view_pose(self._h, f.ctypes.data, ka.ctypes.data, kb.ctypes.data, a.ctypes.data, len(a),
+                                                 b.ctypes.data, len(b), m.ctypes.data, min_parallax_deg, flags, R.ctypes.data,
+                                                 t.ctypes.data, st.ctypes.data, sg.ctypes.data,
+                                                 pts.ctypes.data if points else None), "lf_mkd_two_view_pose")
+        return R.reshape(3, 3), t, st, sg, pts[:len(a)].copy() if points else None
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -825,6 +848,18 @@ class MkdHandle:
         self._device_call(stream, lambda s: self.L.lf_mkd_covisibility_device(
             self._h, d_track_offsets, track_capacity, d_obs_image, obs_capacity, d_table_counts, n_images, d_edge_a, d_edge_b,
             n_edges, flags, d_covis, s), "lf_mkd_covisibility_device")
+
+    def two_view_pose_device(self, d_kps, n_rows_total, d_edge_a, d_edge_b, n_edges, d_intrinsics, n_images, d_F, d_link_offsets,
+                             d_link_a, d_link_b, link_capacity, d_R, d_t, d_stats, d_sigma=None, d_points=None,
+                             min_parallax_deg=1.0, flags=0, stream=None):
+        """lf_mkd_two_view_pose_device: per edge the relative pose its F gives under d_intrinsics [n_images][4] (fx, fy, cx,
+        cy), voted by the edge's links (a link table of pool rows) -- d_R f32 [n_edges][9], d_t f32 [n_edges][3], d_stats
+        uint32 [n_edges][4], d_sigma f32 [n_edges][3] (nullable), d_points f32 [link_capacity][4] (nullable) (device
+        pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_two_view_pose_device(
+            self._h, d_kps, n_rows_total, d_edge_a, d_edge_b, n_edges, d_intrinsics, n_images, d_F, d_link_offsets, d_link_a,
+            d_link_b, link_capacity, min_parallax_deg, flags, d_R, d_t, d_stats, d_sigma, d_points, s),
+            "lf_mkd_two_view_pose_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
