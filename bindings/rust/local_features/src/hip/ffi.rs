@@ -314,6 +314,20 @@ extern "C" {
                                 kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint, nb: u64,
                                 matches: *const i32, min_parallax_deg: f32, flags: u32, r: *mut f32, t: *mut f32,
                                 stats: *mut u32, sigma: *mut f32, points: *mut f32) -> c_int;
+    // track triangulation: per track of a track table points [4] (X, Y, Z, the parallax cosine), stats [4], optional err [2]
+    // and per observation an optional state, from d_intrinsics [n_images][4] and d_poses [n_images][12] (R row-major, then t;
+    // world to camera); flags: 0; the host form takes host arrays, n_tracks and n_obs
+    pub fn lf_mkd_triangulate_tracks_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, n_rows_total: u64,
+                                            d_track_offsets: *const u64, track_capacity: u64, d_obs_row: *const i32,
+                                            d_obs_image: *const u32, obs_capacity: u64, d_table_counts: *const u32,
+                                            d_intrinsics: *const f32, d_poses: *const f32, n_images: u32, max_reproj_px: f32,
+                                            rounds: u32, flags: u32, d_points: *mut f32, d_stats: *mut u32, d_err: *mut f32,
+                                            d_obs_state: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_triangulate_tracks(h: *mut lf_mkd, kps: *const lf_mkd_keypoint, n_rows_total: u64, track_offsets: *const u64,
+                                     n_tracks: u64, obs_row: *const i32, obs_image: *const u32, n_obs: u64,
+                                     intrinsics: *const f32, poses: *const f32, n_images: u32, max_reproj_px: f32, rounds: u32,
+                                     flags: u32, points: *mut f32, stats: *mut u32, err: *mut f32,
+                                     obs_state: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

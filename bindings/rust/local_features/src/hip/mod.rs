@@ -601,6 +601,38 @@ impl LocalFeaturesHip {
         Ok(if stats[2] == u32::MAX { None } else { Some((r, t, stats, sigma, points)) })
     }
 
+    /// The 3-D point of every track of a track table under known camera poses (`lf_mkd_triangulate_tracks`): `kps` is the
+    /// pool, track i's observations are `obs_row` / `obs_image[offsets[i] .. offsets[i + 1]]`, `intrinsics` holds (fx, fy, cx,
+    /// cy) and `poses` R row-major then t per image, world to camera (x_cam = R X + t); an image whose R is all zero is not
+    /// registered.  Returns per track (the point with the cosine of its parallax angle, (0, 0, 0, 2) for none; [usable
+    /// observations, inliers, reason, the winning pair]; [rms, largest] inlier reprojection error in px) and per observation
+    /// its state (0 not usable, 1 usable, 2 inlier).
+    #[allow(clippy::type_complexity)]
+    pub fn triangulate_tracks(&mut self, kps: &[ffi::lf_mkd_keypoint], offsets: &[u64], obs_row: &[i32], obs_image: &[u32],
+                              intrinsics: &[[f32; 4]], poses: &[[f32; 12]], max_reproj_px: f32, rounds: u32)
+                              -> Result<(Vec<[f32; 4]>, Vec<[u32; 4]>, Vec<[f32; 2]>, Vec<u32>), Error> {
+        if offsets.is_empty() || obs_row.len() != obs_image.len() || intrinsics.len() != poses.len() {
+            return Err(Error::BadArgument("triangulate_tracks: offsets needs n_tracks + 1 entries, obs_row and obs_image one \
+                                           entry per observation, intrinsics and poses one row per image".into()));
+        }
+        let n = offsets.len() - 1;
+        let (mut points, mut stats, mut err) = (vec![[0f32; 4]; n.max(1)], vec![[0u32; 4]; n.max(1)], vec![[0f32; 2]; n.max(1)]);
+        let mut state = vec![0u32; obs_row.len().max(1)];
+        // SAFETY: host arrays sized as declared; the counts bound what is read, the outputs have one row per track / observation
+        unsafe {
+            check(self.h, ffi::lf_mkd_triangulate_tracks(
+                self.h, kps.as_ptr(), kps.len() as u64, offsets.as_ptr(), n as u64, obs_row.as_ptr(), obs_image.as_ptr(),
+                obs_row.len() as u64, intrinsics.as_ptr() as *const f32, poses.as_ptr() as *const f32, intrinsics.len() as u32,
+                max_reproj_px, rounds, 0, points.as_mut_ptr() as *mut f32, stats.as_mut_ptr() as *mut u32,
+                err.as_mut_ptr() as *mut f32, state.as_mut_ptr()))?;
+        }
+        points.truncate(n);
+        stats.truncate(n);
+        err.truncate(n);
+        state.truncate(obs_row.len());
+        Ok((points, stats, err, state))
+    }
+
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches
     /// `match_q8_edges` or a verifier returned for `edges` over the pool `image_offsets` describes (`n_rows` rows), edges with
     /// fewer than `min_links` of them left out.  Returns (offsets, link_a, link_b, edge_links): edge e's correspondences are

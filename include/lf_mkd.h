@@ -1148,6 +1148,82 @@ int lf_mkd_two_view_pose(lf_mkd *h, const float *F, const float *Ka, const float
                          const lf_mkd_keypoint *kps_b, uint64_t nb, const int32_t *match, float min_parallax_deg, uint32_t flags,
                          float *R, float *t, uint32_t *stats, float *sigma, float *points);
 
+/* lf_mkd_triangulate_tracks_device gives every track of a track table its 3-D POINT under known camera poses: what
+ * incremental structure from motion builds after its initial pair, what a triangulator over poses from odometry or a rig
+ * builds, what seeds bundle adjustment.  ONE launch, nothing read back.
+ * Reads: the track table as lf_mkd_track_table_device leaves it, read exactly as lf_mkd_covisibility_device reads it (T =
+ * min(d_table_counts[0], track_capacity) tracks, O = min(d_table_counts[1], obs_capacity) positions, track t = positions
+ * [d_track_offsets[t], d_track_offsets[t + 1]) with both ends clamped to O, an inverted range empty); the pool keypoints (x and
+ * y alone); d_intrinsics [n_images][4] = fx, fy, cx, cy as in the pose call; d_poses [n_images][12] = R row-major, then t,
+ * WORLD TO CAMERA: x_cam = R X + t (lf_mkd_two_view_pose_device's convention with camera a's frame as the world: a = [I | 0],
+ * b = [R | t]).  R is used as given; its orthonormality is the caller's business.
+ * A position k of a track is USABLE iff 0 <= d_obs_row[k] < n_rows_total, d_obs_image[k] < n_images, that image's intrinsics
+ * are finite with fx, fy > 0, its 12 pose values are finite and R is not all zero, and the keypoint's x and y are finite.  An
+ * all-zero R is the pose call's "no pose": it says "this image is not registered yet", so a partial pose array passes as it is.
+ * The algorithm, exactly (f64, + - * / and sqrt alone, contraction off, the order csrc/mkd_triangulate_math.h fixes;
+ * thr2 = max_reproj_px^2, formed once on the host in double):
+ *   1. A usable position contributes nine values: with xn = ((x - cx) / fx, (y - cy) / fy, 1), d = R^T xn, u = d / sqrt(d.d)
+ *      and c = 0 - R^T t, the six distinct entries of P = I - u u^T and the three of P c = c - u (u.c).
+ *   2. The CANONICAL SUM over a set S of positions has 4 slots: slot j sums, from +0.0 and in ascending position, the
+ *      contributions of the positions of S with (position within the track) mod 4 == j; the slots are then combined as
+ *      (s0 + s2) + (s1 + s3).  This order is the contract: it lets 4 lanes own a track and still equal a serial twin bit
+ *      for bit, whatever the launch shape, the track's place in the call or the CU count.  (4, not 8: tracks are 3 to 4
+ *      long on average, and 8 lanes per track took 1.9 x as long on a table of pairs; profiles/triangulate.md.)
+ *   3. Solve A X = b (A symmetric 3x3 from the first six sums, b the last three) by cofactors, X = adj(A) b / det.  SINGULAR
+ *      iff not (det > 1e-12 m^3), m = (a00 + a11 + a22) / 3: a guard against exactly degenerate rays (for two rays det =
+ *      2 sin^2 of their angle, so it trips below about 1e-6 rad), not a quality gate -- the parallax output is.
+ *   4. A usable position is an INLIER of X iff, with p = R X + t (each row summed left to right), p_z > 0 and ex^2 + ey^2 <=
+ *      thr2, ex = fx (p_x / p_z) + cx - x, ey likewise.  A NaN fails every comparison.
+ *   5. PAIR HYPOTHESES: the candidates are the first min(U, 8) usable positions in ascending order (U = the usable
+ *      positions of the track), the hypotheses the pairs (ci, cj), ci < cj, of candidate indices in lexicographic order; each
+ *      is step 3 over the canonical sum of its two positions, scored by its inliers among ALL usable positions.  A singular
+ *      pair is skipped; the largest score wins, the first in order on a tie (so a winner exists iff one pair is not
+ *      singular); pairs after one that scores U are not tried (they cannot win).
+ *   6. S = the winner's inliers; fewer than 2: no point.  X = step 3 over S.  Then at most `rounds` (0 .. 4) times: S' = the
+ *      inliers of X; stop if S' == S; no point if |S'| < 2; S = S', X = step 3 over S.  The reported inliers are those of
+ *      the final X; fewer than 2: no point.
+ *   7. Parallax, two sweeps over the final inliers: a0 = the first inlier, a = the inlier with the smallest u_a0 . u_i (the
+ *      lowest position on a tie), and the reported cosine = the smallest u_a . u_i.  Exact for two inliers, otherwise a
+ *      lower bound of the largest pairwise angle in O(inliers).  (A dot product that is a NaN counts as 2.)
+ * Outputs: d_points f32 [track_capacity][4] = X, Y, Z and the parallax cosine, {0, 0, 0, 2} for no point (the pose call's
+ * "none" row); d_stats uint32 [track_capacity][4] = {U, inliers (0 for no point), reason, the winning pair as ci << 16 | cj
+ * (candidate indices) or 0xFFFFFFFF when there is none}, reason 0: point, 1: U < 2, 2: every pair singular or a later solve
+ * singular, 3: fewer than 2 inliers at some stage; optional d_err f32 [track_capacity][2] = the rms (the canonical sum of the
+ * inliers' squared errors over their number, its root) and the largest inlier reprojection error in px, {0, 0} for no point;
+ * optional d_obs_state uint32 [obs_capacity]: 0 not usable, 1 usable and no inlier, 2 inlier (a no-point track has 0 and 1
+ * only).  Rows t >= T are untouched, and so are observation entries outside every track's range.  (Ranges that overlap, which
+ * no track table has, leave d_obs_state's shared entries with either track's value.)
+ * Every output bit depends on the track's own inputs alone: a track alone equals the track in any batch, a captured call
+ * replays to the same bits, and tests/cpp/triangulate_twin.cpp (the same header under g++) gives them on the host.  Whatever
+ * the arrays hold the call ends, and nothing at or beyond a capacity (+ 1 for the offsets), n_rows_total or n_images is
+ * read or written.  track_capacity == 0 is LF_MKD_OK and writes nothing.
+ * How (csrc/mkd_triangulate.hip): ONE launch sized from track_capacity (T is read on the device); a group of 4 lanes owns a
+ * track, 16 tracks a wave; lane l is slot l, sums are combined by a ds_bpermute butterfly, counts by ballot and popcount; the
+ * first 4 positions stay in registers, later ones are read again on every walk.  COST: a walk is ceil(L / 4) steps for a
+ * track of L positions, and a track takes 1 + (pairs tried, at most 28) + (1 + rounds) + 3 walks.  ONE track of every row is
+ * slow, as one edge of every link is in the pose call: its walks run on 4 lanes of one wave, and one track of 100 000
+ * observations takes 220 ms, four times what numpy takes on the host (profiles/triangulate.md).  No
+ * scratch, no LDS, no allocation, no atomic, nobody waits; asynchronous on `stream` (NULL: the handle's own), capturable.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "triangulate_tracks_device: "): a null
+ * handle; with track_capacity > 0 a null d_track_offsets, d_table_counts, d_points or d_stats, and with obs_capacity > 0 too a
+ * null d_obs_row or d_obs_image, a null d_kps with n_rows_total > 0, a null d_intrinsics or d_poses with n_images > 0;
+ * max_reproj_px not finite or <= 0; rounds > 4; flags other than 0 (none is defined); d_track_offsets not 8-byte or any other
+ * array not 4-byte aligned; n_rows_total, track_capacity or obs_capacity above 2^31 - 1. */
+int lf_mkd_triangulate_tracks_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, uint64_t n_rows_total, const uint64_t *d_track_offsets,
+                                     uint64_t track_capacity, const int32_t *d_obs_row, const uint32_t *d_obs_image,
+                                     uint64_t obs_capacity, const uint32_t *d_table_counts, const float *d_intrinsics,
+                                     const float *d_poses, uint32_t n_images, float max_reproj_px, uint32_t rounds, uint32_t flags,
+                                     float *d_points, uint32_t *d_stats, float *d_err, uint32_t *d_obs_state, void *stream);
+/* Host pointers, synchronous: the same arrays on the host, track_offsets [n_tracks + 1], obs_row and obs_image [n_obs] (the
+ * counts are n_tracks and n_obs), points [n_tracks][4], stats [n_tracks][4], optional err [n_tracks][2] and obs_state [n_obs]
+ * (in and out: entries outside every range come back as they were).  Everything goes through the device call.
+ * LF_MKD_ERR_BAD_ARG ("triangulate_tracks: "): a null handle or required pointer, max_reproj_px not finite or <= 0, rounds > 4,
+ * flags other than 0, a total above 2^31 - 1. */
+int lf_mkd_triangulate_tracks(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows_total, const uint64_t *track_offsets,
+                              uint64_t n_tracks, const int32_t *obs_row, const uint32_t *obs_image, uint64_t n_obs,
+                              const float *intrinsics, const float *poses, uint32_t n_images, float max_reproj_px, uint32_t rounds,
+                              uint32_t flags, float *points, uint32_t *stats, float *err, uint32_t *obs_state);
+
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
  * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the

@@ -2625,6 +2625,103 @@ int lf_mkd_two_view_pose(lf_mkd *h, const float *F, const float *Ka, const float
     return LF_MKD_OK;
 }
 
+// Track triangulation (csrc/mkd_triangulate.hip).  Every refusal comes before the handle is looked at.  The squared threshold
+// is formed here, once, in double (tests/cpp/triangulate_twin.cpp forms it with the same expression).
+static const char *triangulate_scalars(float max_reproj_px, uint32_t rounds, uint32_t flags) {
+    if (flags) return "unknown flag bits (no flag is defined: flags must be 0)";
+    if (!(max_reproj_px > 0.f) || !std::isfinite(max_reproj_px)) return "max_reproj_px must be finite and positive";
+    if (rounds > 4) return "rounds must be 0 .. 4";
+    return nullptr;
+}
+
+int lf_mkd_triangulate_tracks_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, uint64_t n_rows_total, const uint64_t *d_track_offsets,
+                                     uint64_t track_capacity, const int32_t *d_obs_row, const uint32_t *d_obs_image,
+                                     uint64_t obs_capacity, const uint32_t *d_table_counts, const float *d_intrinsics,
+                                     const float *d_poses, uint32_t n_images, float max_reproj_px, uint32_t rounds, uint32_t flags,
+                                     float *d_points, uint32_t *d_stats, float *d_err, uint32_t *d_obs_state, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (track_capacity && (!d_track_offsets || !d_table_counts || !d_points || !d_stats))
+        msg = "null d_track_offsets, d_table_counts, d_points or d_stats";
+    else if (track_capacity && obs_capacity && (!d_obs_row || !d_obs_image)) msg = "null d_obs_row or d_obs_image";
+    else if (track_capacity && obs_capacity && n_rows_total && !d_kps) msg = "null d_kps";
+    else if (track_capacity && obs_capacity && n_images && (!d_intrinsics || !d_poses)) msg = "null d_intrinsics or d_poses";
+    else if ((msg = triangulate_scalars(max_reproj_px, rounds, flags))) {}
+    else if (at(d_track_offsets) & 7) msg = "d_track_offsets must be 8-byte aligned";
+    else if ((at(d_kps) | at(d_obs_row) | at(d_obs_image) | at(d_table_counts) | at(d_intrinsics) | at(d_poses) | at(d_points) |
+              at(d_stats) | at(d_err) | at(d_obs_state)) & 3)
+        msg = "the keypoint, observation, count, intrinsics, pose and output arrays must be 4-byte aligned";
+    else if (n_rows_total > kEdgeMax || track_capacity > kEdgeMax || obs_capacity > kEdgeMax)
+        msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "triangulate_tracks_device", msg);
+    if (track_capacity == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const double thr2 = double(max_reproj_px) * double(max_reproj_px);
+    launch_triangulate_tracks(reinterpret_cast<const float *>(d_kps), n_rows_total, d_track_offsets, track_capacity, d_obs_row,
+                              d_obs_image, obs_capacity, d_table_counts, d_intrinsics, d_poses, n_images, thr2, rounds, d_points,
+                              d_stats, d_err, d_obs_state, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// The host form: the arrays staged through the handle's d_ver_io with the outputs, counts = {n_tracks, n_obs}, and the device
+// call does the rest.  obs_state goes up as well as down, so its entries outside every track's range come back as they were.
+int lf_mkd_triangulate_tracks(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows_total, const uint64_t *track_offsets,
+                              uint64_t n_tracks, const int32_t *obs_row, const uint32_t *obs_image, uint64_t n_obs,
+                              const float *intrinsics, const float *poses, uint32_t n_images, float max_reproj_px, uint32_t rounds,
+                              uint32_t flags, float *points, uint32_t *stats, float *err, uint32_t *obs_state) {
+    const char *msg = nullptr;
+    if (n_tracks && (!track_offsets || !points || !stats)) msg = "null track_offsets, points or stats";
+    else if (n_tracks && n_obs && (!obs_row || !obs_image)) msg = "null obs_row or obs_image";
+    else if (n_tracks && n_obs && n_rows_total && !kps) msg = "null kps";
+    else if (n_tracks && n_obs && n_images && (!intrinsics || !poses)) msg = "null intrinsics or poses";
+    else if ((msg = triangulate_scalars(max_reproj_px, rounds, flags))) {}
+    else if (n_rows_total > kEdgeMax || n_tracks > kEdgeMax || n_obs > kEdgeMax) msg = "a total above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "triangulate_tracks", msg);
+    if (n_tracks == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    auto up16 = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 15) / 16 * 16; };
+    const uint64_t o_cnt = 0, o_off = 16, o_kps = o_off + up16((n_tracks + 1) * 8),
+                   o_row = o_kps + up16(n_rows_total * sizeof(lf_mkd_keypoint)), o_img = o_row + up16(n_obs * 4),
+                   o_k = o_img + up16(n_obs * 4), o_p = o_k + up16(uint64_t(n_images) * 16),
+                   o_pt = o_p + up16(uint64_t(n_images) * 48), o_st = o_pt + up16(n_tracks * 16), o_err = o_st + up16(n_tracks * 16),
+                   o_os = o_err + up16(err ? n_tracks * 8 : 0), total = o_os + up16(obs_state ? n_obs * 4 : 0);
+    if (int rc = grow(h, h->d_ver_io, total)) return rc;
+    unsigned char *io = h->d_ver_io;
+    // (counts saturate: the totals are below 2^31)
+    const uint32_t cnt[2] = {uint32_t(n_tracks), uint32_t(n_obs)};
+    const auto up = [&](uint64_t at_, const void *src, uint64_t bytes) {
+        return bytes ? hipMemcpyAsync(io + at_, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+    };
+    const auto down = [&](void *dst, uint64_t at_, uint64_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, io + at_, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    LF_HIP(h, up(o_cnt, cnt, sizeof(cnt)));
+    LF_HIP(h, up(o_off, track_offsets, (n_tracks + 1) * 8));
+    LF_HIP(h, up(o_kps, kps, n_obs ? n_rows_total * sizeof(lf_mkd_keypoint) : 0));
+    LF_HIP(h, up(o_row, obs_row, n_obs * 4));
+    LF_HIP(h, up(o_img, obs_image, n_obs * 4));
+    LF_HIP(h, up(o_k, intrinsics, n_obs ? uint64_t(n_images) * 16 : 0));
+    LF_HIP(h, up(o_p, poses, n_obs ? uint64_t(n_images) * 48 : 0));
+    if (obs_state) LF_HIP(h, up(o_os, obs_state, n_obs * 4));
+    if (int rc = lf_mkd_triangulate_tracks_device(
+            h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_kps), n_rows_total, reinterpret_cast<const uint64_t *>(io + o_off),
+            n_tracks, reinterpret_cast<const int32_t *>(io + o_row), reinterpret_cast<const uint32_t *>(io + o_img), n_obs,
+            reinterpret_cast<const uint32_t *>(io + o_cnt), reinterpret_cast<const float *>(io + o_k),
+            reinterpret_cast<const float *>(io + o_p), n_images, max_reproj_px, rounds, flags, reinterpret_cast<float *>(io + o_pt),
+            reinterpret_cast<uint32_t *>(io + o_st), err ? reinterpret_cast<float *>(io + o_err) : nullptr,
+            obs_state ? reinterpret_cast<uint32_t *>(io + o_os) : nullptr, h->stream))
+        return rc;
+    LF_HIP(h, down(points, o_pt, n_tracks * 16));
+    LF_HIP(h, down(stats, o_st, n_tracks * 16));
+    if (err) LF_HIP(h, down(err, o_err, n_tracks * 8));
+    if (obs_state) LF_HIP(h, down(obs_state, o_os, n_obs * 4));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
 // Guided matching over 8-bit rows: the two calls' refusals together, the q8 pairs call's grid.
 int lf_mkd_match_q8_guided_pairs_device(lf_mkd *h, const uint8_t *d_a, const lf_mkd_keypoint *d_kps_a, const uint64_t *d_offsets_a,
                                         uint64_t na_total, const uint8_t *d_b, const lf_mkd_keypoint *d_kps_b,

@@ -352,6 +352,12 @@ void launch_two_view_pose(const float *kps, uint64_t n_rows, const unsigned *edg
                           const float *intrinsics, unsigned n_images, const float *F, const uint64_t *link_off, const int *link_a,
                           const int *link_b, uint64_t link_capacity, double cmin, float *R, float *t, unsigned *stats, float *sigma,
                           float *points, hipStream_t stream);
+// track triangulation (csrc/mkd_triangulate.hip, lf_mkd_triangulate_tracks_device): one launch, 8 lanes per track, no scratch.
+// Keypoints are read as rows of 5 floats; thr2 = the squared reprojection threshold, formed by the host in double.
+void launch_triangulate_tracks(const float *kps, uint64_t n_rows, const uint64_t *track_offsets, uint64_t track_capacity,
+                               const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts,
+                               const float *intrinsics, const float *poses, unsigned n_images, double thr2, unsigned rounds,
+                               float *points, unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

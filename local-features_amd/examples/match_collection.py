@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -39,6 +39,11 @@ descriptor row is copied for it.
   every image, the principal point in the middle     table: E = K^T F K per edge, its four (R, t) candidates voted by the edge's
   of the frame unless given; implies --fundamental   links, the links triangulated; nothing leaves the device before the lines
   and --pairs) the relative pose of every edge       are printed
+  with --triangulate [POSES.npy] (needs --pose;       LocalFeatures.triangulate_tracks (lf_mkd_triangulate_tracks_device) on the track
+  implies --table) a 3-D point per track under the   table: pair hypotheses, least squares over the winner's inliers, two trimming
+  [images][12] poses of the file (R row-major, then  rounds at 4 px; without a file the edge with the most links with parallax is
+  t; world to camera)                                the initial pair, [I | 0] and its [R | t], chosen on the device, and every
+                                                     other image stays all zero: not registered
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
@@ -47,7 +52,8 @@ first three tracks as image:x,y lists; with --pairs also the number of edges and
 first three correspondences of the best edge as x,y -> x,y; with --expand also one line with the proposed edges and how many of
 them kept a verified match, and the track lines once more for the expanded forest; with --pose per edge the rotation angle,
 the direction of t, the links in front of both cameras out of the edge's links, those with at least 1 degree of parallax and
-s2/s1 of the essential matrix (1 for a true one).  Nothing is read back before those counts: the
+s2/s1 of the essential matrix (1 for a true one); with --triangulate the tracks, the registered images, the points, the inlier
+observations and the median parallax.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -99,7 +105,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -126,7 +132,12 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     are added in place: build_tracks(into=track)).  Without, those seven are None.  With `pose` = (focal, cx, cy), one pinhole
     camera for every image (implies `pairs`; it wants `fundamental`), also the relative pose of every edge from its F and its
     links as LocalFeatures.two_view_pose returns it -- pose_R [E,3,3], pose_t [E,3], pose_stats [E,4], pose_sigma [E,3] and
-    pose_points [layout capacity,4], the links triangulated in the a camera's frame; without, those five are None."""
+    pose_points [layout capacity,4], the links triangulated in the a camera's frame; without, those five are None.  With
+    `triangulate` (it wants `pose` and implies `table`) also the 3-D point of every track of the table as
+    LocalFeatures.triangulate_tracks returns it -- tri_poses [n,12] (R row-major, then t; world to camera), tri_points
+    [tracks,4], tri_stats [tracks,4], tri_err [tracks,2] and tri_obs_state [observations]; `triangulate` is an [n,12] array of
+    poses, or True: the edge with the most links with parallax is the initial pair, [I | 0] and its [R | t], and every other
+    image stays all zero, which says "not registered"; without, those five are None."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -181,12 +192,12 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             p_R, p_t, p_stats, p_sigma, p_points = feats.two_view_pose(model.contiguous(), intr, kps, (ea, eb), (l_off, l_a, l_b))
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
-        if tracks or table or expand:
+        if tracks or table or expand or triangulate is not None:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
             track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
                                         (track_len * (two & ok)).sum()])
-        if table or expand:
+        if table or expand or triangulate is not None:
             t_off, t_rows, t_img, t_row_track, t_counts = feats.track_table(track, track_len, track_dup, image_offsets=o, min_len=2,
                                                                             consistent=True)
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
@@ -219,7 +230,23 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             t_off, t_rows, t_img, t_row_track, t_counts = feats.track_table(track, track_len, track_dup, image_offsets=o, min_len=2,
                                                                             consistent=True)
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
-    return dict(edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
+        tri_poses = tri_points = tri_stats = tri_err = tri_state = None
+        if triangulate is not None and triangulate is not False:
+            if pose is None:
+                raise RuntimeError("match_collection: triangulate needs pose (the cameras' intrinsics)")
+            if triangulate is True:
+                # the initial pair, chosen on the device: nothing is read back
+                with_pose = torch.where(p_stats[:, 2] >= 0, p_stats[:, 3], torch.full_like(p_stats[:, 3], -1))
+                e = torch.argmax(with_pose).reshape(1)
+                eye = torch.tensor([[1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]], dtype=torch.float32, device=dev)
+                tri_poses = torch.zeros((n, 12), dtype=torch.float32, device=dev)
+                tri_poses.index_copy_(0, ea[e].long(), eye)
+                tri_poses.index_copy_(0, eb[e].long(), torch.cat([p_R[e].reshape(1, 9), p_t[e].reshape(1, 3)], 1))
+            else:
+                tri_poses = torch.as_tensor(np.ascontiguousarray(triangulate, np.float32).reshape(n, 12), device=dev)
+            tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr, tri_poses)
+    return dict(tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
+                edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
                 table_keypoints=t_kps, link_offsets=l_off, link_a=l_a, link_b=l_b, link_edge=l_edge, edge_links=l_links,
@@ -244,7 +271,7 @@ def parse_pose(text):
 def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
-    expand, min_shared, pose = None, 8, None
+    expand, min_shared, pose, triangulate = None, 8, None, None
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -265,6 +292,9 @@ def main():
         elif a == "--pose" and args and parse_pose(args[0]) is not None:
             pose = parse_pose(args.pop(0))
             fundamental = pairs = True
+        elif a == "--triangulate":
+            tracks = table = True
+            triangulate = np.load(args.pop(0)) if args and args[0].endswith(".npy") else True
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -274,11 +304,11 @@ def main():
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (triangulate is not None and pose is None) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images)", file=sys.stderr)
+              "number of images; --triangulate needs --pose)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -287,7 +317,7 @@ def main():
     if pose is not None and pose[1] is None:                    # the principal point: the middle of the frame
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -332,6 +362,14 @@ def main():
             angle = np.degrees(np.arccos(np.clip((np.trace(R[e].astype(np.float64)) - 1) / 2, -1, 1)))
             print(f"Pose {ea[e] + 1} -> {eb[e] + 1}: rotation {angle:.2f} deg, t {t[e][0]:+.3f} {t[e][1]:+.3f} {t[e][2]:+.3f}, "
                   f"{st[e][0]} / {links[e]} links in front, {st[e][3]} with parallax, s2/s1 {sg[e][1]:.3f}")
+    if triangulate is not None:
+        n_tracks = out["table_counts"].cpu().tolist()[0]
+        st, pts = out["tri_stats"][:n_tracks].cpu().numpy(), out["tri_points"][:n_tracks].cpu().numpy()
+        have = st[:, 2] == 0
+        registered = int((out["tri_poses"][:, :9] != 0).any(1).sum())
+        median = np.degrees(np.arccos(np.clip(np.median(pts[have, 3]), -1, 1))) if have.any() else 0.0
+        print(f"Triangulated: {n_tracks} tracks under {registered} registered images, {int(have.sum())} points, "
+              f"{int(st[have, 1].sum())} inlier observations, median parallax {median:.2f} deg")
     if expand:
         proposed = out["expand_counts"].cpu().tolist()[0]
         kept = int((out["expand_per_edge"][:proposed, 1] > 0).sum())

@@ -906,6 +906,55 @@ class LocalFeatures:
                                                  ptr(st), ptr(sg), ptr(pts), min_parallax_deg, 0, s.cuda_stream)
         return R, t, st, sg, pts
 
+    def triangulate_tracks(self, kps, table, intrinsics, poses, max_reproj_px=4.0, rounds=2, err=True, obs_state=True,
+                           stream=None):
+        """The 3-D point of every track of a track table under known camera poses (lf_mkd_triangulate_tracks_device): pair
+        hypotheses among a track's first usable observations, a midpoint least squares over the winner's inliers, `rounds`
+        (0 .. 4) trimming rounds at max_reproj_px, and the parallax of the inliers (include/lf_mkd.h states the algorithm).
+        kps [rows, 5] float32 is the pool; table = (offsets, rows, images, counts) as track_table returned them with
+        image_offsets given (its 5-tuple passes as it is); intrinsics [n_images, 4] float32 = fx, fy, cx, cy; poses
+        [n_images, 12] float32 = R row-major, then t, world to camera: x_cam = R X + t -- two_view_pose's R and t with camera
+        a at [I | 0].  An image whose R is all zero is not
+        registered: its observations are not used, so a partial pose array passes as it is.
+        Returns device tensors (points [track_capacity, 4] float32: X, Y, Z and the cosine of the parallax angle, (0, 0, 0, 2)
+        for no point; stats [track_capacity, 4] int32: usable observations, inliers, reason (0 point, 1 fewer than two usable,
+        2 singular, 3 fewer than two inliers), the winning pair ci << 16 | cj or -1; err [track_capacity, 2] float32 (rms and
+        largest inlier reprojection error, px) or None; obs_state [obs_capacity] int32 (0 not usable, 1 usable, 2 inlier) or
+        None).  Rows beyond the table's tracks and observation entries outside every track are left as allocated.  Nothing is
+        read back: asynchronous on `stream` (default: torch's current stream on the handle's device), capturable."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if len(table) == 5:
+            offsets, rows, images, _, counts = table
+        else:
+            offsets, rows, images, counts = table
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1 and ok(rows, torch.int32)
+                    and images is not None and ok(images, torch.int32) and rows.numel() == images.numel()
+                    and ok(counts, torch.int32) and counts.numel() >= 2):
+                raise RuntimeError("triangulate_tracks: table must be (offsets int64, rows int32, images int32, counts int32) "
+                                   "contiguous device tensors as track_table returned them with image_offsets")
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("triangulate_tracks: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(intrinsics, torch.float32) and intrinsics.dim() == 2 and intrinsics.shape[1] == 4):
+                raise RuntimeError("triangulate_tracks: intrinsics must be a contiguous float32 [n_images, 4] device tensor")
+            if not (ok(poses, torch.float32) and poses.numel() == 12 * intrinsics.shape[0]):
+                raise RuntimeError("triangulate_tracks: poses must be a contiguous float32 [n_images, 12] device tensor")
+            tcap, ocap = offsets.numel() - 1, rows.numel()
+            pts = torch.empty((tcap, 4), dtype=torch.float32, device=dev)
+            st = torch.empty((tcap, 4), dtype=torch.int32, device=dev)
+            er = torch.empty((tcap, 2), dtype=torch.float32, device=dev) if err else None
+            os_ = torch.empty((ocap,), dtype=torch.int32, device=dev) if obs_state else None
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.triangulate_tracks_device(ptr(kps), kps.shape[0], offsets.data_ptr(), tcap, ptr(rows), ptr(images),
+                                                      ocap, counts.data_ptr(), ptr(intrinsics), ptr(poses), intrinsics.shape[0],
+                                                      ptr(pts), ptr(st), ptr(er), ptr(os_), max_reproj_px, rounds, 0,
+                                                      s.cuda_stream)
+        return pts, st, er, os_
+
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):
         """match_guided_batch over 8-bit descriptors (lf_mkd_match_q8_guided_pairs_device: one launch, three with `mutual`):

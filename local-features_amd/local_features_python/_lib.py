@@ -49,6 +49,7 @@ SYMBOLS = (
     "lf_mkd_select_edges_plan", "lf_mkd_select_edges_device",
     "lf_mkd_covisibility_plan", "lf_mkd_covisibility_device",
     "lf_mkd_two_view_pose", "lf_mkd_two_view_pose_device",
+    "lf_mkd_triangulate_tracks", "lf_mkd_triangulate_tracks_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -177,6 +178,10 @@ def load_library():
     L.lf_mkd_two_view_pose_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, u32, vp, vp, vp, vp, u64, ctypes.c_float, u32, vp, vp,
                                               vp, vp, vp, vp]
     L.lf_mkd_two_view_pose.argtypes = [vp, vp, vp, vp, vp, u64, vp, u64, vp, ctypes.c_float, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_triangulate_tracks_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, u32, ctypes.c_float, u32, u32,
+                                                   vp, vp, vp, vp, vp]
+    L.lf_mkd_triangulate_tracks.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp,
+                                            vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -604,6 +609,37 @@ class MkdHandle:
                                                  pts.ctypes.data if points else None), "lf_mkd_two_view_pose")
         return R.reshape(3, 3), t, st, sg, pts[:len(a)].copy() if points else None
 
+    def triangulate_tracks(self, kps, track_offsets, obs_row, obs_image, intrinsics, poses, max_reproj_px=4.0, rounds=2,
+                           flags=0, err=True, obs_state=True):
+        """lf_mkd_triangulate_tracks: kps [rows,5] f32, track_offsets uint64 [n_tracks + 1], obs_row int32 / obs_image uint32
+        [n_obs], intrinsics [n_images,4] f32 (fx, fy, cx, cy), poses [n_images,12] f32 (R row-major, then t; world to camera)
+        -> (points [n_tracks,4] f32, stats uint32 [n_tracks,4], err [n_tracks,2] f32 or None, obs_state uint32 [n_obs] or None;
+        `obs_state` may be an array to start from: entries outside every track's range keep its values)."""
+        k = np.ascontiguousarray(kps, np.float32).reshape(-1, 5)
+        off = np.ascontiguousarray(track_offsets, np.uint64).reshape(-1)
+        row, img = np.ascontiguousarray(obs_row, np.int32).reshape(-1), np.ascontiguousarray(obs_image, np.uint32).reshape(-1)
+        K = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        if len(off) < 1 or len(row) != len(img) or len(K) != len(P):
+            raise RuntimeError("triangulate_tracks: track_offsets needs n_tracks + 1 entries, obs_row and obs_image one entry "
+                               "per observation, intrinsics and poses one row per image")
+        n, n_obs = len(off) - 1, len(row)
+        pts, st = np.empty((max(n, 1), 4), np.float32), np.empty((max(n, 1), 4), np.uint32)
+        er = np.empty((max(n, 1), 2), np.float32) if err else None
+        if obs_state is True:
+            os_ = np.zeros(max(n_obs, 1), np.uint32)
+        elif obs_state is None or obs_state is False:
+            os_ = None
+        else:
+            os_ = np.array(obs_state, np.uint32).reshape(-1)
+            if len(os_) != n_obs:
+                raise RuntimeError("triangulate_tracks: obs_state needs one entry per observation")
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_triangulate_tracks(self._h, at(k), len(k), off.ctypes.data, n, at(row), at(img), n_obs, at(K),
+                                                      at(P), len(K), max_reproj_px, rounds, flags, pts.ctypes.data,
+                                                      st.ctypes.data, at(er), at(os_)), "lf_mkd_triangulate_tracks")
+        return pts[:n], st[:n], er[:n] if err else None, os_[:n_obs] if os_ is not None else None
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -860,6 +896,19 @@ class MkdHandle:
             self._h, d_kps, n_rows_total, d_edge_a, d_edge_b, n_edges, d_intrinsics, n_images, d_F, d_link_offsets, d_link_a,
             d_link_b, link_capacity, min_parallax_deg, flags, d_R, d_t, d_stats, d_sigma, d_points, s),
             "lf_mkd_two_view_pose_device")
+
+    def triangulate_tracks_device(self, d_kps, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image,
+                                  obs_capacity, d_table_counts, d_intrinsics, d_poses, n_images, d_points, d_stats, d_err=None,
+                                  d_obs_state=None, max_reproj_px=4.0, rounds=2, flags=0, stream=None):
+        """lf_mkd_triangulate_tracks_device: per track of the table d_track_offsets uint64 [track_capacity + 1] / d_obs_row int32
+        / d_obs_image uint32 [obs_capacity] / d_table_counts (lf_mkd_track_table_device's outputs) its 3-D point under
+        d_intrinsics [n_images][4] and d_poses [n_images][12] (R row-major, then t; world to camera) -- d_points f32
+        [track_capacity][4], d_stats uint32 [track_capacity][4], d_err f32 [track_capacity][2] (nullable), d_obs_state uint32
+        [obs_capacity] (nullable) (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_triangulate_tracks_device(
+            self._h, d_kps, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts,
+            d_intrinsics, d_poses, n_images, max_reproj_px, rounds, flags, d_points, d_stats, d_err, d_obs_state, s),
+            "lf_mkd_triangulate_tracks_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
