@@ -328,6 +328,19 @@ extern "C" {
                                      intrinsics: *const f32, poses: *const f32, n_images: u32, max_reproj_px: f32, rounds: u32,
                                      flags: u32, points: *mut f32, stats: *mut u32, err: *mut f32,
                                      obs_state: *mut u32) -> c_int;
+    // camera resection: per image that is not registered (an all-zero R in d_poses [n_images][12]; every image with
+    // LF_MKD_RESECT_ALL = 1) its pose from the keypoints it owns in tracks with a point: poses_out [12] (may be d_poses), stats
+    // [4], optional err [2] and per row an optional state; the host form takes ONE image's host arrays
+    pub fn lf_mkd_resect_cameras_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, d_image_offsets: *const u64, n_images: u32,
+                                        n_rows_total: u64, d_row_track: *const i32, d_points: *const f32, track_capacity: u64,
+                                        d_table_counts: *const u32, d_intrinsics: *const f32, d_poses: *const f32,
+                                        max_reproj_px: f32, min_parallax_deg: f32, n_samples: u32, min_inliers: u32, rounds: u32,
+                                        seed: u32, flags: u32, d_poses_out: *mut f32, d_stats: *mut u32, d_err: *mut f32,
+                                        d_row_state: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_resect_camera(h: *mut lf_mkd, kps: *const lf_mkd_keypoint, n_rows: u64, row_track: *const i32,
+                                points: *const f32, n_tracks: u64, intrinsics: *const f32, max_reproj_px: f32,
+                                min_parallax_deg: f32, n_samples: u32, min_inliers: u32, rounds: u32, seed: u32, flags: u32,
+                                pose: *mut f32, stats: *mut u32, err: *mut f32, row_state: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -98,6 +98,8 @@ pub const SELECT_MAX_K: u32 = 32;
 /// `flags` of `lf_mkd_covisibility_device` (`include/lf_mkd.h`, `LF_MKD_COVIS_ACCUMULATE`): the table is added to what
 /// `d_covis` holds.
 pub const COVIS_ACCUMULATE: u32 = 1;
+/// `flags` of `lf_mkd_resect_cameras_device` (`include/lf_mkd.h`, `LF_MKD_RESECT_ALL`): registered images are resected too.
+pub const RESECT_ALL: u32 = 1;
 
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
@@ -631,6 +633,33 @@ impl LocalFeaturesHip {
         err.truncate(n);
         state.truncate(obs_row.len());
         Ok((points, stats, err, state))
+    }
+
+    /// The absolute pose of ONE image from the keypoints it owns in tracks that have a 3-D point (`lf_mkd_resect_camera`):
+    /// `kps` are the image's rows, `row_track[r]` the index into `points` of row r's track or -1, `points` X, Y, Z and the
+    /// parallax cosine per track ((0, 0, 0, 2): none), `intrinsics` (fx, fy, cx, cy).  P3P samples scored by reprojection
+    /// inliers at `max_reproj_px`, `rounds` (0 .. 4) Gauss-Newton steps, kept with at least max(`min_inliers`, 3) inliers.
+    /// Returns (R row-major then t, world to camera, all zero for none; [correspondences, inliers, reason, the winning
+    /// candidate]; [rms, largest] inlier reprojection error in px) and per row its state (0 no correspondence, 1
+    /// correspondence, 2 inlier).
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn resect_camera(&mut self, kps: &[ffi::lf_mkd_keypoint], row_track: &[i32], points: &[[f32; 4]], intrinsics: &[f32; 4],
+                         max_reproj_px: f32, min_parallax_deg: f32, n_samples: u32, min_inliers: u32, rounds: u32, seed: u32)
+                         -> Result<([f32; 12], [u32; 4], [f32; 2], Vec<u32>), Error> {
+        if row_track.len() != kps.len() {
+            return Err(Error::BadArgument("resect_camera: row_track needs one entry per row of kps".into()));
+        }
+        let (mut pose, mut stats, mut err) = ([0f32; 12], [0u32; 4], [0f32; 2]);
+        let mut state = vec![0u32; kps.len().max(1)];
+        // SAFETY: host arrays sized as declared; the counts bound what is read, the outputs have their stated sizes
+        unsafe {
+            check(self.h, ffi::lf_mkd_resect_camera(
+                self.h, kps.as_ptr(), kps.len() as u64, row_track.as_ptr(), points.as_ptr() as *const f32, points.len() as u64,
+                intrinsics.as_ptr(), max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed, 0,
+                pose.as_mut_ptr(), stats.as_mut_ptr(), err.as_mut_ptr(), state.as_mut_ptr()))?;
+        }
+        state.truncate(kps.len());
+        Ok((pose, stats, err, state))
     }
 
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches

@@ -1224,6 +1224,109 @@ int lf_mkd_triangulate_tracks(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_
                               const float *intrinsics, const float *poses, uint32_t n_images, float max_reproj_px, uint32_t rounds,
                               uint32_t flags, float *points, uint32_t *stats, float *err, uint32_t *obs_state);
 
+/* lf_mkd_resect_cameras_device gives images that are not registered yet their ABSOLUTE POSE [R | t] (resection, PnP) from the
+ * 2-D keypoints they own in tracks that already have a 3-D point: the step that fills the all-zero rows of d_poses that
+ * lf_mkd_triangulate_tracks_device skips, so incremental structure from motion runs triangulate, resect, triangulate, ..
+ * on the device.  Three launches, nothing read back.
+ * Reads: the pool keypoints (x and y alone) and d_image_offsets [n_images + 1] (image i's rows are [d_image_offsets[i],
+ * d_image_offsets[i + 1]), both ends clamped to n_rows_total, an inverted range empty); d_row_track [n_rows_total] as
+ * lf_mkd_track_table_device writes it (the table index of a row's track or -1); d_points [track_capacity][4] as the
+ * triangulation call writes it; T = min(d_table_counts[0], track_capacity); d_intrinsics [n_images][4] and d_poses
+ * [n_images][12] as there (R row-major, then t; world to camera).
+ * Row r of image i is a CORRESPONDENCE iff 0 <= d_row_track[r] < T, that track's d_points row has finite X, Y, Z and a fourth
+ * value w <= cmin (cmin = cos(min_parallax_deg), formed once on the host in double: 0 degrees admits every real point, the
+ * "none" row {0, 0, 0, 2} and a NaN fail), and the keypoint's x and y are finite.  M = their number; their POSITION 0 .. M - 1
+ * is their ascending row order.  Image i is a CANDIDATE iff its intrinsics are finite with fx, fy > 0, its 12 values of d_poses
+ * are finite, and R there is all zero or LF_MKD_RESECT_ALL is set.  Every other image's pose is copied to d_poses_out
+ * unchanged, with d_stats = {0, 0, 1, 0xFFFFFFFF} and d_err = {0, 0}.
+ * d_poses_out MAY be d_poses (in place): the first launch writes each image's candidacy into scratch, and the last launch,
+ * the only one that stores to d_poses_out, decides from that flag; each of its workgroups reads and writes its own image's row
+ * alone.
+ * The algorithm, exactly (f64, + - * / and sqrt alone, contraction off, the order csrc/mkd_resect_math.h fixes; thr2 =
+ * max_reproj_px^2 formed once on the host in double; the world points are d_points' f32 widened):
+ *   1. BEARING of a keypoint: xn = ((x - cx) / fx, (y - cy) / fy, 1), f = xn / sqrt(xn.xn).
+ *   2. SAMPLE k (0 <= k < n_samples) of image i draws 3 distinct positions with the verifiers' splitmix64 counter sampler:
+ *      key = (uint64(seed + i) << 32) ^ (k << 6), draw t = 0 .. 63 is r = splitmix64(key ^ t), pos = ((r >> 32) * M) >> 32,
+ *      a position already drawn is passed over; no sample if M < 3 or 64 draws give fewer than 3.  It is keyed on the image
+ *      id, so an image's result depends on neither its neighbours in the call nor on n_images.
+ *   3. P3P by Grunert's quartic (Haralick et al., Int. J. Computer Vision 13(3), 1994): with X1, X2, X3 the sample's points in
+ *      draw order, a = |X2 - X3|, b = |X1 - X3|, c = |X1 - X2|, ca = f2.f3, cb = f1.f3, cg = f1.f2, p = (a^2 - c^2) / b^2 and
+ *      q = (a^2 + c^2) / b^2,
+ *        A4 = (p - 1)^2 - 4 (c^2 / b^2) ca^2
+ *        A3 = 4 [p (1 - p) cb - (1 - q) ca cg + 2 (c^2 / b^2) ca^2 cb]
+ *        A2 = 2 [p^2 - 1 + 2 p^2 cb^2 + 2 ((b^2 - c^2) / b^2) ca^2 - 4 q ca cb cg + 2 ((b^2 - a^2) / b^2) cg^2]
+ *        A1 = 4 [-p (1 + p) cb + 2 (a^2 / b^2) cg^2 cb - (1 - q) ca cg]
+ *        A0 = (1 + p)^2 - 4 (a^2 / b^2) cg^2.
+ *      The sample is INVALID iff not (|(X2 - X1) x (X3 - X1)|^2 > 1e-12 c^2 b^2) (kRsCollinear: a guard against exactly
+ *      degenerate triangles -- it is sin^2 of the angle at X1, so it trips below about 1e-6 rad -- not a quality gate), or not
+ *      (|A4| > 2^-20 max |A0 .. A3|) (kRsLeadRel, the F verifier's: a vanishing leading coefficient sends a root to infinity),
+ *      or a coefficient is not finite.
+ *      The real roots inside the Cauchy bound B = 1 + max |A0 .. A3| / |A4| come from one fixed-iteration finder: the
+ *      breakpoints of a polynomial are -B, its derivative's real roots (recursively: the quadratic in closed form, q =
+ *      -(b + sign(b) sqrt(disc)) / 2, roots q / a and c / q; then the cubic; then the quartic) and B; an interval whose ends
+ *      differ in (value > 0) is halved kRsBisect = 64 times, then kRsNewton = 4 Newton steps from its middle, each taken iff
+ *      it stays inside the interval.  Roots are taken in ascending order; root j (0 .. 3) of sample k is candidate c = 4 k + j.
+ *      For a root v: u = ((p - 1) v^2 - 2 p cb v + 1 + p) / (2 (cg - v ca)); the candidate is skipped unless v > 0, that
+ *      denominator is not 0, u > 0 and the pose below is finite.  s1 = sqrt(b^2 / (1 + v^2 - 2 v cb)), s2 = u s1, s3 = v s1,
+ *      Yi = si fi.  The pose aligns the triangles' frames: e1 = (P2 - P1) / |.|, e3 = e1 x (P3 - P1) normalised, e2 = e3 x e1
+ *      for P = X and P = Y; R = F_Y F_X^T (F's columns e1, e2, e3), t = Y1 - R X1.
+ *   4. A correspondence is an INLIER of (R, t) by the triangulation call's rule: p = R X + t (each row summed left to right),
+ *      p_z > 0 and ex^2 + ey^2 <= thr2, ex = fx (p_x / p_z) + cx - x, ey likewise.  A candidate's SCORE is its inliers among
+ *      all M; the largest wins, the lowest c on a tie; without a candidate there is no pose.
+ *   5. REFIT, at most `rounds` (0 .. 4) Gauss-Newton steps on the reprojection error: over the inliers S of the current pose
+ *      the 21 + 6 sums of J^T J and J^T e for the step (w, dt) with R' = C(w) R, t' = t + dt and the rational Cayley map C(w) =
+ *      ((1 - w.w) I + 2 w w^T + 2 [w]x) / (1 + w.w) (J from C(w) = I + 2 [w]x + ..); the 6 x 6 system by Cholesky, a pivot
+ *      that is not positive ends the refit; the step is kept iff its MSAC cost -- the sum over all M of min(e^2, thr2), thr2
+ *      for a point not in front -- is not above the current pose's, and the refit ends with the first step not kept.
+ *   6. Every floating-point sum over correspondences is the CANONICAL SUM, the verifiers' block sum made part of the
+ *      contract: 256 slots; slot s adds, from +0.0 and in ascending position, the positions with position mod 256 == s (a
+ *      skipped position adds nothing); the 64 slots of a wave combine by the butterfly over slot xor 32, 16, .. 1; the four
+ *      wave sums add as ((w0 + w1) + w2) + w3.
+ *   7. The pose is rounded to f32; inliers, errors and states are those of the ROUNDED pose under step 4's test as the
+ *      triangulation call evaluates it, so a following lf_mkd_triangulate_tracks_device sees exactly the inliers this call
+ *      reports.  The pose is written iff their number is at least max(min_inliers, 3); otherwise the image's row of
+ *      d_poses_out is all zero.
+ * Outputs: d_poses_out f32 [n_images][12]; d_stats uint32 [n_images][4] = {M, inliers (0: no pose), reason, the winning c or
+ * 0xFFFFFFFF when there is none}, reason 0: pose, 1: not a candidate (copied through, M reported as 0), 2: M < 3 or no
+ * candidate from any sample, 3: fewer than the minimum inliers; optional d_err f32 [n_images][2] = the rms (the canonical sum
+ * of the inliers' squared errors over their number, its root) and the largest inlier error in px, {0, 0} without a pose;
+ * optional d_row_state uint32 [n_rows_total], written only in the ranges of the CANDIDATE images: 0 no correspondence, 1
+ * correspondence, 2 inlier (a no-pose image has 0 and 1 only); every other entry is untouched.  (Ranges that overlap, which no
+ * pool has, leave shared entries with either image's value.)
+ * Every output bit depends on the image's own inputs, its id and the seed alone: an image alone equals the image in any batch
+ * at the same id, a captured call replays to the same bits, and tests/cpp/resect_twin.cpp (the same header under g++) gives
+ * them on the host.  Whatever the arrays hold the call ends, and nothing at or beyond n_rows_total, track_capacity or n_images
+ * (+ 1 for the offsets) is read or written.  n_images == 0 is LF_MKD_OK and writes nothing.
+ * How (csrc/mkd_resect.hip): rs_gather, a workgroup per image, compacts the correspondences' rows in order into scratch;
+ * rs_score, image x 256 candidates x slice of positions, one candidate per lane, the correspondences staged in LDS, integer
+ * atomic adds of the counts; rs_select, a workgroup per image, the argmax, the refit as block passes, the outputs.  Scratch
+ * (4 bytes a row, 8 an image, 16 per image and sample) belongs to the handle and grows only when a call asks for more: a
+ * warmed-up call allocates nothing and is capturable (a later call that asks for MORE replaces the scratch, and a graph captured
+ * before it names the old one: capture after the largest call); asynchronous on `stream` (NULL: the handle's own).  COST: one image
+ * owning every row is walked by ONE workgroup in rs_gather and rs_select (profiles/resect.md).
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "resect_cameras_device: "): a null
+ * handle; with n_images > 0 a null d_image_offsets, d_table_counts, d_intrinsics, d_poses, d_poses_out or d_stats, with
+ * n_rows_total > 0 too a null d_kps or d_row_track, and with track_capacity > 0 too a null d_points; flags other than
+ * LF_MKD_RESECT_ALL; max_reproj_px not finite or <= 0; min_parallax_deg outside [0, 180] or a NaN; n_samples 0 or above 4096;
+ * rounds > 4; d_image_offsets not 8-byte or any other array not 4-byte aligned; n_images, n_rows_total or track_capacity above
+ * 2^31 - 1. */
+#define LF_MKD_RESECT_ALL (1u)   /* resect registered images too (re-estimate them from the points) */
+int lf_mkd_resect_cameras_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                 uint64_t n_rows_total, const int32_t *d_row_track, const float *d_points, uint64_t track_capacity,
+                                 const uint32_t *d_table_counts, const float *d_intrinsics, const float *d_poses,
+                                 float max_reproj_px, float min_parallax_deg, uint32_t n_samples, uint32_t min_inliers,
+                                 uint32_t rounds, uint32_t seed, uint32_t flags, float *d_poses_out, uint32_t *d_stats, float *d_err,
+                                 uint32_t *d_row_state, void *stream);
+/* Host pointers, synchronous, ONE image: kps [n_rows] are its rows, row_track [n_rows], points [n_tracks][4] (every row of
+ * it is read: T = n_tracks), intrinsics [4]; pose [12], stats [4], optional err [2] and row_state [n_rows].  The image is
+ * image 0 of a device call with an all-zero pose, so it is always a candidate; pass seed + i to get image i of a batch.
+ * Everything goes through the device call.  LF_MKD_ERR_BAD_ARG ("resect_camera: "): a null handle or required pointer, the
+ * scalars as above, a total above 2^31 - 1. */
+int lf_mkd_resect_camera(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows, const int32_t *row_track, const float *points,
+                         uint64_t n_tracks, const float *intrinsics, float max_reproj_px, float min_parallax_deg,
+                         uint32_t n_samples, uint32_t min_inliers, uint32_t rounds, uint32_t seed, uint32_t flags, float *pose,
+                         uint32_t *stats, float *err, uint32_t *row_state);
+
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
  * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the

@@ -246,6 +246,8 @@ struct lf_mkd {
     HipArray<unsigned char> d_select_edges;
     // lf_mkd_covisibility_device's scratch (covisibility_plan's scratch_bytes), in the same way
     HipArray<unsigned char> d_covisibility;
+    // lf_mkd_resect_cameras_device's scratch (resect_scratch_bytes), in the same way
+    HipArray<unsigned char> d_resect;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;
@@ -2718,6 +2720,106 @@ int lf_mkd_triangulate_tracks(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_
     LF_HIP(h, down(stats, o_st, n_tracks * 16));
     if (err) LF_HIP(h, down(err, o_err, n_tracks * 8));
     if (obs_state) LF_HIP(h, down(obs_state, o_os, n_obs * 4));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// Camera resection (csrc/mkd_resect.hip).  Every refusal comes before the handle is looked at.  The squared threshold and the
+// parallax cosine are formed here, once, in double (tests/cpp/resect_twin.cpp forms them with the same expressions).
+static const char *resect_scalars(float max_reproj_px, float min_parallax_deg, uint32_t n_samples, uint32_t rounds, uint32_t flags) {
+    if (flags & ~uint32_t(LF_MKD_RESECT_ALL)) return "unknown flag bits";
+    if (!(max_reproj_px > 0.f) || !std::isfinite(max_reproj_px)) return "max_reproj_px must be finite and positive";
+    if (!(min_parallax_deg >= 0.f && min_parallax_deg <= 180.f)) return "min_parallax_deg must be in [0, 180]";
+    if (n_samples < 1 || n_samples > 4096) return "n_samples must be 1 .. 4096";
+    if (rounds > 4) return "rounds must be 0 .. 4";
+    return nullptr;
+}
+
+int lf_mkd_resect_cameras_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                 uint64_t n_rows_total, const int32_t *d_row_track, const float *d_points, uint64_t track_capacity,
+                                 const uint32_t *d_table_counts, const float *d_intrinsics, const float *d_poses,
+                                 float max_reproj_px, float min_parallax_deg, uint32_t n_samples, uint32_t min_inliers,
+                                 uint32_t rounds, uint32_t seed, uint32_t flags, float *d_poses_out, uint32_t *d_stats, float *d_err,
+                                 uint32_t *d_row_state, void *stream) {
+    const auto at = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const char *msg = nullptr;
+    if (n_images && (!d_image_offsets || !d_table_counts || !d_intrinsics || !d_poses || !d_poses_out || !d_stats))
+        msg = "null d_image_offsets, d_table_counts, d_intrinsics, d_poses, d_poses_out or d_stats";
+    else if (n_images && n_rows_total && (!d_kps || !d_row_track)) msg = "null d_kps or d_row_track";
+    else if (n_images && n_rows_total && track_capacity && !d_points) msg = "null d_points";
+    else if ((msg = resect_scalars(max_reproj_px, min_parallax_deg, n_samples, rounds, flags))) {}
+    else if (at(d_image_offsets) & 7) msg = "d_image_offsets must be 8-byte aligned";
+    else if ((at(d_kps) | at(d_row_track) | at(d_points) | at(d_table_counts) | at(d_intrinsics) | at(d_poses) | at(d_poses_out) |
+              at(d_stats) | at(d_err) | at(d_row_state)) & 3)
+        msg = "the keypoint, track, point, count, intrinsics, pose and output arrays must be 4-byte aligned";
+    else if (n_images > kEdgeMax || n_rows_total > kEdgeMax || track_capacity > kEdgeMax)
+        msg = "n_images, n_rows_total or track_capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "resect_cameras_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_resect, resect_scratch_bytes(n_images, n_rows_total, n_samples))) return rc;
+    const double thr2 = double(max_reproj_px) * double(max_reproj_px);
+    const double cmin = std::cos(double(min_parallax_deg) * (3.14159265358979323846 / 180.0));
+    launch_resect_cameras(h->d_resect.get(), reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total,
+                          d_row_track, d_points, track_capacity, d_table_counts, d_intrinsics, d_poses, thr2, cmin, n_samples,
+                          min_inliers, rounds, seed, (flags & LF_MKD_RESECT_ALL) != 0, d_poses_out, d_stats, d_err, d_row_state,
+                          stream ? static_cast<hipStream_t>(stream) : h->stream);
+    LF_HIP(h, hipGetLastError());
+    return LF_MKD_OK;
+}
+
+// The host form, ONE image: the arrays staged through the handle's d_ver_io with the outputs, offsets = {0, n_rows}, counts =
+// {n_tracks}, an all-zero pose, and the device call does the rest.
+int lf_mkd_resect_camera(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows, const int32_t *row_track, const float *points,
+                         uint64_t n_tracks, const float *intrinsics, float max_reproj_px, float min_parallax_deg,
+                         uint32_t n_samples, uint32_t min_inliers, uint32_t rounds, uint32_t seed, uint32_t flags, float *pose,
+                         uint32_t *stats, float *err, uint32_t *row_state) {
+    const char *msg = nullptr;
+    if (!intrinsics || !pose || !stats) msg = "null intrinsics, pose or stats";
+    else if (n_rows && (!kps || !row_track)) msg = "null kps or row_track";
+    else if (n_rows && n_tracks && !points) msg = "null points";
+    else if ((msg = resect_scalars(max_reproj_px, min_parallax_deg, n_samples, rounds, flags))) {}
+    else if (n_rows > kEdgeMax || n_tracks > kEdgeMax) msg = "a total above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return q8_refuse(h, "resect_camera", msg);
+    LF_ENTER(h);
+    auto up16 = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 15) / 16 * 16; };
+    const uint64_t o_off = 0, o_cnt = 16, o_k = 32, o_p = 48, o_po = 96, o_st = 144, o_err = 160, o_kps = 176,
+                   o_rt = o_kps + up16(n_rows * sizeof(lf_mkd_keypoint)), o_pt = o_rt + up16(n_rows * 4),
+                   o_rs = o_pt + up16(n_tracks * 16), total = o_rs + up16(row_state ? n_rows * 4 : 0);
+    if (int rc = grow(h, h->d_ver_io, total)) return rc;
+    unsigned char *io = h->d_ver_io;
+    const uint64_t off[2] = {0, n_rows};
+    const uint32_t cnt[2] = {uint32_t(n_tracks), 0};
+    const float zero[12] = {};
+    const auto up = [&](uint64_t at_, const void *src, uint64_t bytes) {
+        return bytes ? hipMemcpyAsync(io + at_, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+    };
+    const auto down = [&](void *dst, uint64_t at_, uint64_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, io + at_, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    LF_HIP(h, up(o_off, off, sizeof(off)));
+    LF_HIP(h, up(o_cnt, cnt, sizeof(cnt)));
+    LF_HIP(h, up(o_k, intrinsics, 16));
+    LF_HIP(h, up(o_p, zero, sizeof(zero)));
+    LF_HIP(h, up(o_kps, kps, n_rows * sizeof(lf_mkd_keypoint)));
+    LF_HIP(h, up(o_rt, row_track, n_rows * 4));
+    LF_HIP(h, up(o_pt, points, n_rows ? n_tracks * 16 : 0));
+    if (row_state) LF_HIP(h, up(o_rs, row_state, n_rows * 4));
+    // (the staged copies are pageable: they have left the host arrays when the calls return)
+    if (int rc = lf_mkd_resect_cameras_device(
+            h, reinterpret_cast<const lf_mkd_keypoint *>(io + o_kps), reinterpret_cast<const uint64_t *>(io + o_off), 1, n_rows,
+            reinterpret_cast<const int32_t *>(io + o_rt), reinterpret_cast<const float *>(io + o_pt), n_tracks,
+            reinterpret_cast<const uint32_t *>(io + o_cnt), reinterpret_cast<const float *>(io + o_k),
+            reinterpret_cast<const float *>(io + o_p), max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed, flags,
+            reinterpret_cast<float *>(io + o_po), reinterpret_cast<uint32_t *>(io + o_st), reinterpret_cast<float *>(io + o_err),
+            row_state ? reinterpret_cast<uint32_t *>(io + o_rs) : nullptr, h->stream))
+        return rc;
+    LF_HIP(h, down(pose, o_po, 48));
+    LF_HIP(h, down(stats, o_st, 16));
+    if (err) LF_HIP(h, down(err, o_err, 8));
+    if (row_state) LF_HIP(h, down(row_state, o_rs, n_rows * 4));
     LF_HIP(h, hipStreamSynchronize(h->stream));
     return LF_MKD_OK;
 }

@@ -358,6 +358,15 @@ void launch_triangulate_tracks(const float *kps, uint64_t n_rows, const uint64_t
                                const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts,
                                const float *intrinsics, const float *poses, unsigned n_images, double thr2, unsigned rounds,
                                float *points, unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream);
+// camera resection (csrc/mkd_resect.hip, lf_mkd_resect_cameras_device): three launches (rs_gather, rs_score, rs_select) over
+// `scratch` of resect_scratch_bytes(..) bytes, 4-byte aligned.  thr2 = the squared reprojection threshold and cmin = the
+// cosine of the smallest parallax, both formed by the host in double.  poses_out may be poses.
+uint64_t resect_scratch_bytes(unsigned n_images, uint64_t n_rows, unsigned n_samples);
+void launch_resect_cameras(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
+                           const int *row_track, const float *points, uint64_t track_capacity, const unsigned *table_counts,
+                           const float *intrinsics, const float *poses, double thr2, double cmin, unsigned n_samples,
+                           unsigned min_inliers, unsigned rounds, unsigned seed, bool all, float *poses_out, unsigned *stats,
+                           float *err, unsigned *row_state, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -44,6 +44,10 @@ descriptor row is copied for it.
   [images][12] poses of the file (R row-major, then  rounds at 4 px; without a file the edge with the most links with parallax is
   t; world to camera)                                the initial pair, [I | 0] and its [R | t], chosen on the device, and every
                                                      other image stays all zero: not registered
+  with --register ROUNDS (needs --pose; implies       ROUNDS times LocalFeatures.resect_cameras (lf_mkd_resect_cameras_device) in
+  --triangulate) the other images registered from     place on the pose array -- P3P samples over the keypoints an image owns in
+  the points and the points triangulated again       tracks with a point, 512 samples, at least 12 inliers at 4 px -- and then
+                                                     triangulate_tracks again, nothing read back in between
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
@@ -53,7 +57,8 @@ first three correspondences of the best edge as x,y -> x,y; with --expand also o
 them kept a verified match, and the track lines once more for the expanded forest; with --pose per edge the rotation angle,
 the direction of t, the links in front of both cameras out of the edge's links, those with at least 1 degree of parallax and
 s2/s1 of the essential matrix (1 for a true one); with --triangulate the tracks, the registered images, the points, the inlier
-observations and the median parallax.  Nothing is read back before those counts: the
+observations and the median parallax; with --register per round the images registered so far, those the round added and the
+points.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -105,7 +110,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -135,7 +140,9 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     pose_points [layout capacity,4], the links triangulated in the a camera's frame; without, those five are None.  With
     `triangulate` (it wants `pose` and implies `table`) also the 3-D point of every track of the table as
     LocalFeatures.triangulate_tracks returns it -- tri_poses [n,12] (R row-major, then t; world to camera), tri_points
-    [tracks,4], tri_stats [tracks,4], tri_err [tracks,2] and tri_obs_state [observations]; `triangulate` is an [n,12] array of
+    [tracks,4], tri_stats [tracks,4], tri_err [tracks,2] and tri_obs_state [observations] (with `register` = ROUNDS > 0, which
+    implies `triangulate`, those after ROUNDS rounds of resect_cameras in place on tri_poses and triangulate_tracks, and
+    register_rounds = per round (the resection's stats [n,4], the triangulation's stats [tracks,4])); `triangulate` is an [n,12] array of
     poses, or True: the edge with the most links with parallax is the initial pair, [I | 0] and its [R | t], and every other
     image stays all zero, which says "not registered"; without, those five are None."""
     import torch
@@ -192,6 +199,8 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             p_R, p_t, p_stats, p_sigma, p_points = feats.two_view_pose(model.contiguous(), intr, kps, (ea, eb), (l_off, l_a, l_b))
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
+        if register and triangulate is None:
+            triangulate = True
         if tracks or table or expand or triangulate is not None:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
@@ -231,6 +240,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                                                                             consistent=True)
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
         tri_poses = tri_points = tri_stats = tri_err = tri_state = None
+        register_rounds = [] if register else None       # (None without `register`, like every output that was not asked for)
         if triangulate is not None and triangulate is not False:
             if pose is None:
                 raise RuntimeError("match_collection: triangulate needs pose (the cameras' intrinsics)")
@@ -245,7 +255,14 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             else:
                 tri_poses = torch.as_tensor(np.ascontiguousarray(triangulate, np.float32).reshape(n, 12), device=dev)
             tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr, tri_poses)
-    return dict(tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
+            for _ in range(register or 0):
+                # the images without a pose from the points there are, in place; then the points under every pose there is
+                _, r_stats, _, _ = feats.resect_cameras(kps, o, t_row_track, tri_points, t_counts, intr, tri_poses, seed=seed,
+                                                        out=tri_poses)
+                tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr,
+                                                                                     tri_poses)
+                register_rounds.append((r_stats, tri_stats))
+    return dict(register_rounds=register_rounds, tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
                 edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
@@ -255,6 +272,21 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 expand_edge_a=x_ea, expand_edge_b=x_eb, expand_counts=x_counts, expand_layout_a=x_la, expand_verified=x_ver,
                 expand_per_edge=x_per_edge, first_round=first, pose_R=p_R, pose_t=p_t, pose_stats=p_stats,
                 pose_sigma=p_sigma, pose_points=p_points)
+
+
+def register_lines(out):
+    """one line per round of `register`: the images registered after it, those it added, and the points"""
+    n_tracks = out["table_counts"].cpu().tolist()[0]
+    lines, registered = [], None
+    for k, (r_stats, t_stats) in enumerate(out["register_rounds"] or []):
+        reason = r_stats[:, 2].cpu().numpy()
+        if registered is None:
+            registered = int((reason == 1).sum())
+        added = int((reason == 0).sum())
+        registered += added
+        points = int((t_stats[:n_tracks, 2].cpu().numpy() == 0).sum())
+        lines.append(f"round {k + 1}: {registered} of {len(reason)} images registered ({added} added), {points} points")
+    return lines
 
 
 def parse_pose(text):
@@ -271,7 +303,7 @@ def parse_pose(text):
 def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
-    expand, min_shared, pose, triangulate = None, 8, None, None
+    expand, min_shared, pose, triangulate, register = None, 8, None, None, 0
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -295,6 +327,10 @@ def main():
         elif a == "--triangulate":
             tracks = table = True
             triangulate = np.load(args.pop(0)) if args and args[0].endswith(".npy") else True
+        elif a == "--register" and args and args[0].isdigit() and int(args[0]) > 0:
+            tracks = table = True
+            register = int(args.pop(0))
+            triangulate = True if triangulate is None else triangulate
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -305,10 +341,10 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (triangulate is not None and pose is None) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images; --triangulate needs --pose)", file=sys.stderr)
+              "number of images; --triangulate and --register need --pose)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -317,7 +353,7 @@ def main():
     if pose is not None and pose[1] is None:                    # the principal point: the middle of the frame
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -370,6 +406,8 @@ def main():
         median = np.degrees(np.arccos(np.clip(np.median(pts[have, 3]), -1, 1))) if have.any() else 0.0
         print(f"Triangulated: {n_tracks} tracks under {registered} registered images, {int(have.sum())} points, "
               f"{int(st[have, 1].sum())} inlier observations, median parallax {median:.2f} deg")
+        for line in register_lines(out):
+            print("Registered, " + line)
     if expand:
         proposed = out["expand_counts"].cpu().tolist()[0]
         kept = int((out["expand_per_edge"][:proposed, 1] > 0).sum())

@@ -14,7 +14,7 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, VERIFY_NO_REFINE, Comm,
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, VERIFY_NO_REFINE, Comm,
                    MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
@@ -23,7 +23,7 @@ __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXAC
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
            "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan",
-           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "covisibility_plan"]
+           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "covisibility_plan"]
 
 
 class Keypoint:
@@ -954,6 +954,58 @@ class LocalFeatures:
                                                       ptr(pts), ptr(st), ptr(er), ptr(os_), max_reproj_px, rounds, 0,
                                                       s.cuda_stream)
         return pts, st, er, os_
+
+    def resect_cameras(self, kps, offsets, row_track, points, table_counts, intrinsics, poses, max_reproj_px=4.0,
+                       min_parallax_deg=0.0, n_samples=512, min_inliers=12, rounds=3, seed=0, resect_all=False, out=None,
+                       stream=None):
+        """The absolute pose of every image that is not registered yet (lf_mkd_resect_cameras_device): P3P samples over the
+        keypoints an image owns in tracks that have a 3-D point, scored by reprojection inliers at max_reproj_px, a Gauss-Newton
+        refit of `rounds` (0 .. 4) steps, the pose kept with at least max(min_inliers, 3) inliers (include/lf_mkd.h states the
+        algorithm).  kps [rows, 5] float32 is the pool and offsets [n_images + 1] int64 its image offsets; row_track [rows]
+        int32 is track_table's inverse map; points [track_capacity, 4] float32 and table_counts are triangulate_tracks' points
+        and the table's counts; intrinsics [n_images, 4] float32; poses [n_images, 12] float32 = R row-major, then t, world to
+        camera, an all-zero R for an image that is not registered -- those are resected, every other image's pose is copied
+        (resect_all: every image is resected).  `out` is the pose tensor to write, `poses` itself for an in-place call
+        (default: a new tensor).  Returns device tensors (poses [n_images, 12] float32, all zero where no pose was found;
+        stats [n_images, 4] int32: correspondences, inliers, reason (0 pose, 1 not a candidate, 2 fewer than three
+        correspondences or no candidate, 3 fewer than the minimum inliers), the winning candidate or -1; err [n_images, 2]
+        float32: rms and largest inlier reprojection error, px; row_state [rows] int32: 0 no correspondence, 1 correspondence,
+        2 inlier, written in the ranges of the resected images only, -1 elsewhere).  Nothing is read back: asynchronous on
+        `stream` (default: torch's current stream on the handle's device), capturable once warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("resect_cameras: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1):
+                raise RuntimeError("resect_cameras: offsets must be a contiguous int64 [n_images + 1] device tensor")
+            n_images, n_rows = offsets.numel() - 1, kps.shape[0]
+            if not (ok(row_track, torch.int32) and row_track.numel() == n_rows):
+                raise RuntimeError("resect_cameras: row_track must be a contiguous int32 [rows] device tensor")
+            if not (ok(points, torch.float32) and points.dim() == 2 and points.shape[1] == 4 and ok(table_counts, torch.int32)
+                    and table_counts.numel() >= 1):
+                raise RuntimeError("resect_cameras: points must be float32 [track_capacity, 4] and table_counts int32 device "
+                                   "tensors as triangulate_tracks and track_table returned them")
+            if not (ok(intrinsics, torch.float32) and intrinsics.numel() == 4 * n_images and ok(poses, torch.float32)
+                    and poses.numel() == 12 * n_images):
+                raise RuntimeError("resect_cameras: intrinsics must be float32 [n_images, 4] and poses float32 [n_images, 12] "
+                                   "contiguous device tensors")
+            if out is None:
+                out = torch.empty((n_images, 12), dtype=torch.float32, device=dev)
+            elif not (ok(out, torch.float32) and out.numel() == 12 * n_images):
+                raise RuntimeError("resect_cameras: out must be a contiguous float32 [n_images, 12] device tensor")
+            st = torch.empty((n_images, 4), dtype=torch.int32, device=dev)
+            er = torch.empty((n_images, 2), dtype=torch.float32, device=dev)
+            rs = torch.full((n_rows,), -1, dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.resect_cameras_device(ptr(kps), offsets.data_ptr(), n_images, n_rows, ptr(row_track), ptr(points),
+                                                  points.shape[0], table_counts.data_ptr(), ptr(intrinsics), ptr(poses), ptr(out),
+                                                  ptr(st), ptr(er), ptr(rs), max_reproj_px, min_parallax_deg, n_samples,
+                                                  min_inliers, rounds, seed, RESECT_ALL if resect_all else 0, s.cuda_stream)
+        return out, st, er, rs
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

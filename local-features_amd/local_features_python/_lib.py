@@ -50,6 +50,7 @@ SYMBOLS = (
     "lf_mkd_covisibility_plan", "lf_mkd_covisibility_device",
     "lf_mkd_two_view_pose", "lf_mkd_two_view_pose_device",
     "lf_mkd_triangulate_tracks", "lf_mkd_triangulate_tracks_device",
+    "lf_mkd_resect_camera", "lf_mkd_resect_cameras_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -60,6 +61,7 @@ LINK_TABLE_LOCAL = 1     # LF_MKD_LINK_TABLE_LOCAL: lf_mkd_link_table_device wri
 SELECT_SKIP_SELF = 1     # LF_MKD_SELECT_SKIP_SELF: lf_mkd_select_edges_device does not offer column i to row i
 SELECT_UNIQUE = 2        # LF_MKD_SELECT_UNIQUE: one pool, every unordered pair at most once, as (smaller, larger)
 COVIS_ACCUMULATE = 1     # LF_MKD_COVIS_ACCUMULATE: lf_mkd_covisibility_device adds to what d_covis holds
+RESECT_ALL = 1           # LF_MKD_RESECT_ALL: lf_mkd_resect_cameras_device resects registered images too
 COVIS_FORM_LDS = 256     # LF_MKD_COVIS_FORM_LDS: in covisibility_plan's form, workgroups count in LDS first
 SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
 COMM_ID_BYTES = 128
@@ -182,6 +184,10 @@ def load_library():
                                                    vp, vp, vp, vp, vp]
     L.lf_mkd_triangulate_tracks.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp,
                                             vp]
+    L.lf_mkd_resect_cameras_device.argtypes = [vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp, ctypes.c_float, ctypes.c_float, u32,
+                                               u32, u32, u32, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_resect_camera.argtypes = [vp, vp, u64, vp, vp, u64, vp, ctypes.c_float, ctypes.c_float, u32, u32, u32, u32, u32, vp,
+                                       vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -640,6 +646,29 @@ class MkdHandle:
                                                       st.ctypes.data, at(er), at(os_)), "lf_mkd_triangulate_tracks")
         return pts[:n], st[:n], er[:n] if err else None, os_[:n_obs] if os_ is not None else None
 
+    def resect_camera(self, kps, row_track, points, intrinsics, max_reproj_px=4.0, min_parallax_deg=0.0, n_samples=512,
+                      min_inliers=12, rounds=3, seed=0, flags=0, err=True, row_state=True):
+        """lf_mkd_resect_camera, ONE image: kps [rows,5] f32 (its rows), row_track int32 [rows] (the table index of a row's track
+        or -1), points [n_tracks,4] f32 (X, Y, Z, the parallax cosine; (0, 0, 0, 2): none), intrinsics [4] f32 (fx, fy, cx, cy)
+        -> (pose [12] f32: R row-major, then t, all zero for none; stats uint32 [4] = M, inliers, reason, winning candidate;
+        err [2] f32 or None; row_state uint32 [rows] or None: 0 no correspondence, 1 correspondence, 2 inlier).  The image is
+        image 0 of a device call: pass seed + i to get image i of a batch."""
+        k = np.ascontiguousarray(kps, np.float32).reshape(-1, 5)
+        rt = np.ascontiguousarray(row_track, np.int32).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        K = np.ascontiguousarray(intrinsics, np.float32).reshape(-1)
+        if len(rt) != len(k) or len(K) != 4:
+            raise RuntimeError("resect_camera: row_track needs one entry per row of kps, intrinsics 4 values")
+        pose, st = np.zeros(12, np.float32), np.zeros(4, np.uint32)
+        er = np.zeros(2, np.float32) if err else None
+        rs = np.zeros(max(len(k), 1), np.uint32) if row_state else None
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_resect_camera(self._h, at(k), len(k), at(rt), at(pts), len(pts), K.ctypes.data, max_reproj_px,
+                                                min_parallax_deg, n_samples, min_inliers, rounds, seed & 0xFFFFFFFF, flags,
+                                                pose.ctypes.data, st.ctypes.data, at(er), rs.ctypes.data if row_state else None),
+                    "lf_mkd_resect_camera")
+        return pose, st, er, rs[:len(k)] if row_state else None
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -909,6 +938,20 @@ class MkdHandle:
             self._h, d_kps, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts,
             d_intrinsics, d_poses, n_images, max_reproj_px, rounds, flags, d_points, d_stats, d_err, d_obs_state, s),
             "lf_mkd_triangulate_tracks_device")
+
+    def resect_cameras_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_row_track, d_points, track_capacity,
+                              d_table_counts, d_intrinsics, d_poses, d_poses_out, d_stats, d_err=None, d_row_state=None,
+                              max_reproj_px=4.0, min_parallax_deg=0.0, n_samples=512, min_inliers=12, rounds=3, seed=0, flags=0,
+                              stream=None):
+        """lf_mkd_resect_cameras_device: per image that is not registered (an all-zero R in d_poses [n_images][12]; every image
+        with RESECT_ALL) its pose from the keypoints it owns (d_image_offsets uint64 [n_images + 1] over d_kps) in tracks with a
+        point (d_row_track int32 [n_rows_total], d_points f32 [track_capacity][4], d_table_counts) under d_intrinsics
+        [n_images][4] -- d_poses_out f32 [n_images][12] (may be d_poses), d_stats uint32 [n_images][4], d_err f32 [n_images][2]
+        (nullable), d_row_state uint32 [n_rows_total] (nullable) (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_resect_cameras_device(
+            self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_row_track, d_points, track_capacity, d_table_counts,
+            d_intrinsics, d_poses, max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed & 0xFFFFFFFF, flags,
+            d_poses_out, d_stats, d_err, d_row_state, s), "lf_mkd_resect_cameras_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
