@@ -187,6 +187,14 @@ struct lf_mkd {
     RecordedArray<float> d_det_desc;           // [max_out][128] lf_mkd_detect's descriptor staging
     HipArray<unsigned long long> d_totals;
     HipArray<unsigned long long> d_clk;        // LF_MKD_FLAG_KERNEL_TIMING: clock stamps of the latest describe launch
+    // Claim counters of the patch-mode describe launches (launch_describe): a ring, one 64-byte line per slot, a slot per
+    // launch in turn.  A launch clears its own slot on its own stream, so nothing is left over from the launch before; the
+    // ring keeps launches of one handle that overlap on different streams (up to kClaimSlots of them) on different words.
+    // A recorded pipeline keeps the slot it was recorded with: its replays are ordered on one stream.
+    static constexpr unsigned kClaimSlots = 16, kClaimStride = 16;
+    HipArray<unsigned> d_claims;
+    unsigned claim_turn = 0;
+    unsigned *next_claim() { return d_claims.get() + kClaimStride * (claim_turn++ % kClaimSlots); }
     // the row-split form of the keypoint kernel (requests of at most 16 x CUs keypoints): partial sums and their counters
     HipArray<float> d_kp_xchg;
     HipArray<unsigned> d_kp_words;
@@ -400,6 +408,7 @@ int create_impl(const lf_mkd_params *params, const PcaModel &pca, lf_mkd **out) 
     // (the staging buffers of the host-pointer and keypoint entry points -- 4.6 KiB per descriptor of the internal batch --
     // are allocated on first use: a caller of the device-pointer patch API never needs them)
     LF_CREATE_HIP(h->d_totals.allocate(8));
+    LF_CREATE_HIP(h->d_claims.allocate(lf_mkd::kClaimSlots * lf_mkd::kClaimStride));
     if (h->params.flags & LF_MKD_FLAG_KERNEL_TIMING) {
         LF_CREATE_HIP(h->d_clk.allocate(4));
         LF_CREATE_HIP(hipMemset(h->d_clk, 0, 4 * sizeof(unsigned long long)));
@@ -492,7 +501,7 @@ int ensure_side_stream(lf_mkd *h, size_t events) {
 int run_batch(lf_mkd *h, const float *d_patches, uint64_t n, float *d_out, float *d_raw, hipStream_t s, int waves = 0) {
     if (int rc = mark(h, s)) return rc;
     launch_describe(d_patches, long(n), nullptr, h->dc, h->params.angle_mode, h->params.pool_mode, d_out ? d_out : h->d_out,
-                    d_raw, h->num_cus, s, waves, h->d_clk);
+                    d_raw, h->num_cus, s, waves, h->d_clk, h->next_claim());
     LF_HIP(h, hipGetLastError());
     if (int rc = mark(h, s)) return rc;
     return LF_MKD_OK;
@@ -1311,7 +1320,7 @@ static void enqueue_pipeline(lf_mkd *h, uint32_t width, uint32_t height, uint32_
         launch_sample_patches(h->d_pyr, h->pyr_stride, h->pd, reinterpret_cast<const float *>(d_keypoints), nullptr, 1,
                               long(max_out), cnt + 3, h->params.patch_scale_factor, h->d_stream_patches, s);
         launch_describe(h->d_stream_patches, long(max_out), cnt + 3, h->dc, h->params.angle_mode, h->params.pool_mode,
-                        d_descriptors, nullptr, h->num_cus, s);
+                        d_descriptors, nullptr, h->num_cus, s, 0, nullptr, h->next_claim());
     }
     // the counts and the keypoints go to pinned host memory as the last operations (on a branch of their own beside the describe
     // launch they were measured 15 us slower: every join of two branches costs ~12 us of queue latency)

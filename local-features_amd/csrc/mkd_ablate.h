@@ -16,6 +16,8 @@
 //   LF_ABLATE_ROWS=n       the row loop walks n of a patch's 32 rows (producers too): the bound of a row-split form.  Keypoint
 //                          mode, and patch mode in F32 / F16_FP6; f16x3's patch mode walks row pairs and refuses to compile
 //   LF_PHASE_TIMING        per-wave clocks of the phases of a patch row, left by workgroup 0 in out[wave * 128 + phase]
+//   LF_WG_CLOCK            patch mode: entry and exit stamps, batch count and XCD of EVERY workgroup, left behind the descriptors
+//                          (right descriptors: it times the product's walk over the batches, tools/wg_spread.py)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -121,6 +123,48 @@ struct PhaseClock {
             __syncthreads();
             if (blockIdx.x == 0 && lane == 0)
                 for (int i = 0; i < 8; ++i) out[wave * 128 + i] = (float)clk[i];
+        }
+    }
+};
+
+// ---- per-workgroup clock (patch mode) --------------------------------------------------------------------------------
+// LF_WG_CLOCK: every workgroup stamps the constant 100 MHz clock on entry and after its last batch, counts its batches and
+// reads its XCD; thread 0 leaves the record behind the descriptors, in out[n * 128 + 8 * workgroup ..] (eight 32-bit words:
+// entry lo / hi, exit lo / hi, batches, XCD, 0, 0), so the caller's output holds 8 * grid floats more than n rows
+// (tools/wg_spread.py).  The descriptors of such a build are the product's.
+#ifdef LF_WG_CLOCK
+constexpr bool kWgClock = true;
+#else
+constexpr bool kWgClock = false;
+#endif
+struct WgClock {
+    unsigned batches = 0;
+    __device__ __forceinline__ static unsigned *record(float *out, long n) {
+        return reinterpret_cast<unsigned *>(out + n * 128) + 8 * (long)blockIdx.x;
+    }
+    __device__ __forceinline__ void enter(float *out, long n) const {
+        if constexpr (kWgClock) {
+            if (threadIdx.x == 0) {
+                const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+                unsigned xcd;
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcd));
+                unsigned *r = record(out, n);
+                r[0] = (unsigned)t; r[1] = (unsigned)(t >> 32); r[5] = xcd; r[6] = 0u; r[7] = 0u;
+            }
+        }
+    }
+    __device__ __forceinline__ void batch_done() {
+        if constexpr (kWgClock) ++batches;
+    }
+    // (every wave of the workgroup calls: the stamp is taken once all of them have left the last batch)
+    __device__ __forceinline__ void leave(float *out, long n) const {
+        if constexpr (kWgClock) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+                unsigned *r = record(out, n);
+                r[2] = (unsigned)t; r[3] = (unsigned)(t >> 32); r[4] = batches;
+            }
         }
     }
 };

@@ -153,6 +153,21 @@ __device__ __forceinline__ void issue_w_step(const unsigned char *__restrict__ w
     }
 }
 
+// One ticket of a launch's claim counter into lane 0's `t` (mkd_pool, claim forms): a relaxed agent-scope fetch-and-add
+// of 1, REQUESTED only -- `t` holds the ticket once the caller has waited for vmcnt(0) with `t` as an operand of the wait.
+// Written out: the builtin goes through hipcc's wave-level aggregation of atomics, which waits for the result on the spot.
+__device__ __forceinline__ void request_ticket(unsigned *counter, unsigned &t) {
+    unsigned long long exec_was;
+    asm volatile("s_mov_b64 %1, exec\n\t"
+                 "s_mov_b64 exec, 1\n\t"
+                 "global_atomic_add %0, %2, %3, %4 sc0\n\t"
+                 "s_mov_b64 exec, %1"
+                 : "+v"(t), "=&s"(exec_was)
+                 : "v"(0u), "v"(1u), "s"(counter)
+                 : "memory");
+}
+__device__ __forceinline__ void await_ticket(unsigned &t) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(t)::"memory"); }
+
 // Counted wait on the vector-memory counter.  INVARIANT: between the DMA requests this counts and the wait itself, the
 // wave must issue no other vector-memory instruction -- in particular no scratch spill: spill stores share vmcnt and retire
 // out of order with respect to loads, so one in flight lets the wait pass before the counted DMA has landed.  hipcc
@@ -1439,8 +1454,15 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     const float *__restrict__ patches, long n_host, const unsigned long long *__restrict__ n_dev,
     const unsigned char *__restrict__ lut_rows, const short *__restrict__ colmap, const unsigned char *__restrict__ wfrag,
     const float *__restrict__ bias, const float *__restrict__ odd_cart, float *__restrict__ out, float *__restrict__ raw_out,
-    std::conditional_t<SRC != kSrcPatches, KpSource, int> ks, unsigned long long *__restrict__ clk) {
+    std::conditional_t<SRC != kSrcPatches, KpSource, unsigned *> ks, unsigned long long *__restrict__ clk) {
     constexpr bool kKp = SRC != kSrcPatches, kSplit = SRC == kSrcKeypointsSplit;
+    // Patch mode, 8 waves: `ks` is the launch's claim counter (zero on entry), or null.  With a counter only a workgroup's
+    // FIRST batch is its id; every later one is gridDim.x + a ticket drawn from the counter at run time, so that a workgroup
+    // which runs late (a late start, a slower CU) ends up with fewer batches instead of holding the launch's end up
+    // (launch_describe says which launches claim; the batch loop below, how).  Null, and in every other form: the static
+    // walk, batch b + k gridDim.x in turn k.
+    // (LF_POOL_F32, the verification mode, stays static: its 8-wave form spills already, and the claim costs it two registers more)
+    constexpr bool kClaimForm = SRC == kSrcPatches && W == 8 && f16_family(POOL);
     static_assert(!kSplit || W == 2, "the row-split form is the narrow (2 + 2 wave) form");
     // clk (LF_MKD_FLAG_KERNEL_TIMING, else null): workgroup 0 stamps the shader clock (s_memtime) and the constant 100 MHz
     // clock (s_memrealtime) on entry and on exit -- the clock the chip sustained under THIS launch is their quotient
@@ -1449,6 +1471,8 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         clk[0] = __builtin_readcyclecounter();
         clk[1] = __builtin_amdgcn_s_memrealtime();
     }
+    [[maybe_unused]] ablate::WgClock wg_clock;   // (instrument builds only: tools/wg_spread.py)
+    if constexpr (!kKp) wg_clock.enter(out, n_host);
     constexpr int kSlots = kKp ? kRingSlotsKp : kRingSlots;
     static_assert(!kKp || POOL == LF_POOL_F16X3, "keypoint mode pools in f16x3");
     constexpr int kMPool = POOL == LF_POOL_F16_FP6 ? LF_POOL_F16X3 : POOL;   // the m stream keeps the three-term form
@@ -1459,7 +1483,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     static_assert(!kKp || (kFold && kOddV), "the producers write the folded forms' LDS map and request f16x3's LUT pieces");
     constexpr int kNAcc = acc_tiles(kFold), kRowB = row_bytes(kFold), kRingO = ring_off(kFold);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRingO + W * kSlots * 2048 +
-                                                                (kKp ? kLevelTableBytes + kMaxPyrLevels * 8 : 0)];
+                                                                (kKp ? kLevelTableBytes + kMaxPyrLevels * 8 : 0) +
+                                                                (kClaimForm ? 16 : 0)];
+    // claim forms: the word behind the rings through which wave 0 hands the workgroup's latest ticket to the other waves
+    // (an LDS pointer by type: through a generic one the accesses are flat instructions, which count on vmcnt as well)
+    typedef volatile __attribute__((address_space(3))) unsigned lds_ticket;
+    [[maybe_unused]] lds_ticket *ticket_word = (lds_ticket *)((lds_u8 *)s_mem + (kRingO + W * kSlots * 2048));
     // number of patches: given by the host, or (graph-captured pipelines) left on the device by the previous stage
     const long n = n_dev ? (long)*n_dev : n_host;
     const int lane = threadIdx.x & 63;
@@ -1524,6 +1553,32 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 
     long batch = walk.cur;
     if (batch >= walk.end) return;
+    // Claim forms: the batch after the current one is HELD, one ahead -- `more` and `src_next` are known from a batch's first
+    // instruction, as the ring prefetch of rows 27..30 and the epilogue's request for LUT row 0 need them -- and the one after
+    // that is drawn during the current batch's row 0 (patch_row).  A ticket is one relaxed agent-scope atomic add by one lane
+    // of wave 0 (request_ticket), without a fence: no data passes between workgroups, only the number.  Nobody waits for
+    // anybody: a ticket at or beyond the launch's last batch (the count may be the device's, below the host's) ends the
+    // workgroup.
+    // The first ticket is drawn here, before any LDS-DMA request is in flight, and handed over by a barrier of its own.
+    [[maybe_unused]] unsigned *claim_ctr = nullptr;
+    [[maybe_unused]] long held = 0;           // claim forms: the batch after `batch`
+    [[maybe_unused]] unsigned drawn = 0;      // ... and the ticket of the one after that, read from ticket_word in row 31
+    if constexpr (kClaimForm) {
+        claim_ctr = ks;
+        held = batch + walk.step;
+        if (claim_ctr) {
+            if (wave == 0) {
+                unsigned t = 0;
+                request_ticket(claim_ctr, t);
+                await_ticket(t);
+                if (lane == 0) *ticket_word = t;
+            }
+            __syncthreads();
+            held = (long)gridDim.x + __builtin_amdgcn_readfirstlane(*ticket_word);
+            // (the word is next written at the end of row 0, behind that row's barrier, which no wave passes before this read
+            //  has returned: __syncthreads waits for lgkmcnt(0))
+        }
+    }
     // the x-odd cartesian kernels' x-profile at the lane's folded pixels 4q .. 4q+3 (valu_odd_cart): loaded once, and landed
     // before the first LDS-DMA request -- the row loop itself issues no vector load (see wait_vmcnt)
     [[maybe_unused]] f32x2 oc_fx[2] = {pk_set(0.f), pk_set(0.f)};
@@ -1558,7 +1613,7 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
     ablate::PhaseClock phase;   // (instrument builds only: tools/phase_timing.py)
     phase.start();
 
-    for (; batch < walk.end; batch += walk.step) {
+    for (; batch < walk.end;) {
         // Launder the (uniform) table and buffer pointers once per batch.  Otherwise hipcc hoists one 64-bit per-lane VGPR
         // address per DMA / fragment load / store out of the batch loop and spills them (1.4 KB per lane for the
         // whitening fragments alone).  Spills matter beyond their cost here: scratch loads and stores count on vmcnt
@@ -1572,10 +1627,11 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         asm volatile("" : "+s"(wf), "+s"(bs), "+s"(lr), "+s"(o), "+s"(ro), "+s"(cm), "+s"(pt));
         const float *oc_tab = odd_cart;
         const long base = batch * (16 * W) + wave * 16;
-        const bool more = batch + walk.step < walk.end;
+        const long next_batch = kClaimForm ? held : batch + walk.step;
+        const bool more = next_batch < walk.end;
         // (keypoint mode: pt is null and these stay unused)
         const RawSrc src = kKp ? RawSrc{nullptr, 0u} : raw_src(pt, batch);
-        const RawSrc src_next = !kKp && more ? raw_src(pt, batch + walk.step) : src;
+        const RawSrc src_next = !kKp && more ? raw_src(pt, next_batch) : src;
 
         f32x4 acc[kNAcc];
 #pragma unroll
@@ -1626,6 +1682,17 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
                 __syncthreads();
             }
             phase.mark(0);
+            // Claim forms.  Row 31: the ticket wave 0 left at the end of row 0 is read here, right behind the barrier, where the
+            // wave has nothing in flight (an LDS read further down makes hipcc drain vmcnt first: it cannot tell the read from
+            // the LDS its DMA requests write).  Row 0: lane 0 of wave 0 draws the ticket of the batch after the held one, if
+            // the held one exists (request_ticket).  The returning atomic counts on vmcnt: it stands HERE because the next
+            // wait of every wave is then a vmcnt(0) -- row 1's, and before it wave 0's own at the end of this row, which hands
+            // the ticket over -- and 31 row barriers lie between it and the counted waits of finish_descriptors (wait_vmcnt),
+            // where nothing but the epilogue's own requests may be in flight.
+            [[maybe_unused]] unsigned ticket = 0;
+            if constexpr (kClaimForm && kLast) drawn = __builtin_amdgcn_readfirstlane(*ticket_word);
+            if constexpr (kClaimForm && kFirst)
+                if (claim_ctr && more && wave == 0) request_ticket(claim_ctr, ticket);
             const unsigned char *brow = s_mem + par * kRowB + lane * 16;
             // row buffer par ^ 1 is free: next LUT row; during row 31 the f16 epilogue's first whitening step instead
             // (keypoint mode: the producer waves request LUT rows 1..31 -- an LDS-DMA request stalls its issuer for 60-180
@@ -1827,6 +1894,13 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
             if constexpr (kPairs)
 #pragma unroll
                 for (int s = 0; s < kOddCartSums; ++s) asm volatile("" : "+v"(oc[s][0]), "+v"(oc[s][1]), "+v"(oc[s][2]));
+            // claim forms, end of row 0: the ticket has had the row to return; row 1's barrier shows the word to every wave
+            if constexpr (kClaimForm && kFirst) {
+                if (claim_ctr && wave == 0) {
+                    await_ticket(ticket);
+                    if (lane == 0) *ticket_word = ticket;
+                }
+            }
             phase.mark(5);
         };
         constexpr std::integral_constant<int, -1> kOwnBody{};
@@ -1929,8 +2003,12 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
         }
         phase.mark(6);
         if constexpr (kKp) slot0 = (slot0 + 8) % kRingSlotsKp;
+        wg_clock.batch_done();
+        batch = next_batch;
+        if constexpr (kClaimForm) held = claim_ctr ? (long)gridDim.x + drawn : batch + walk.step;
     }
     phase.dump(out, wave, lane);
+    if constexpr (!kKp) wg_clock.leave(out, n_host);
     if (clk && blockIdx.x == 0 && threadIdx.x == 0) {
         clk[2] = __builtin_readcyclecounter();
         clk[3] = __builtin_amdgcn_s_memrealtime();
@@ -1948,12 +2026,19 @@ __global__ __launch_bounds__(SRC != kSrcPatches ? 128 * W : 64 * W) void mkd_poo
 // n_dev != nullptr: the patch count is read on the device (<= n, which then only sizes the grid)
 void launch_describe(const float *patches, long n, const unsigned long long *n_dev, const DeviceConsts &dc,
                      int angle_mode, int pool_mode, float *out, float *raw_out, int num_cus, hipStream_t stream, int waves,
-                     unsigned long long *clk) {
+                     unsigned long long *clk, unsigned *claim) {
     if (n <= 0) return;
     // one 100-152 KiB-LDS workgroup per CU; requests of at most one round of 64-patch workgroups take the 4-wave form
     const bool small = ablate::kForceFourWaves || waves == 4 || (waves != 8 && n <= 64L * num_cus);
     const long nbatch = small ? (n + 63) / 64 : (n + 127) / 128;
     const unsigned grid = (unsigned)(nbatch < num_cus ? nbatch : num_cus);
+    // Batches are claimed at run time where a workgroup has at least kClaimRounds WHOLE batches to walk: whole CUs and XCDs
+    // run a few per cent apart, and dealt statically the slowest one ends the launch (NOTEBOOK.md, the claims section).  A
+    // shorter launch keeps the static walk: its tail is a round of batches whatever the dealing.  The counter is cleared on
+    // the launch stream just before the launch, so a captured launch carries its memset with it; with n_dev the host's n only
+    // bounds the tickets that can be valid.
+    if (small || !claim || !f16_family(pool_mode) || n / 128 < kClaimRounds * grid) claim = nullptr;
+    if (claim && hipMemsetAsync(claim, 0, sizeof(unsigned), stream) != hipSuccess) return;   // (the caller reads the last error)
     const bool f16 = f16_family(pool_mode);
     const unsigned char *lut = pool_mode == LF_POOL_F16_FP6 ? reinterpret_cast<const unsigned char *>(dc.pool_b_fp6)
                                : f16                        ? reinterpret_cast<const unsigned char *>(dc.pool_b_f16)
@@ -1965,7 +2050,7 @@ void launch_describe(const float *patches, long n, const unsigned long long *n_d
     const short *colmap = unfolded ? dc.colmap_unfolded : dc.colmap;
 #define LF_LAUNCH_W(A, P, WV)                                                                                          \
     hipLaunchKernelGGL((mkd_pool<A, P, WV, kSrcPatches>), dim3(grid), dim3(64 * WV), 0, stream, patches, n, n_dev, lut, \
-                       colmap, wf, dc.white_bias, dc.odd_cart, out, raw_out, 0, clk)
+                       colmap, wf, dc.white_bias, dc.odd_cart, out, raw_out, WV == 8 ? claim : (unsigned *)nullptr, clk)
 #define LF_LAUNCH(A, P)            \
     do {                           \
         if (small) LF_LAUNCH_W(A, P, 4); \

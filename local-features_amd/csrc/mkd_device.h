@@ -73,8 +73,11 @@ struct DeviceConsts {
 // waves: 0 = choose by size (4-wave workgroups when the request fits one round of them, else 8-wave), 4 / 8 = that form
 void launch_describe(const float *patches, long n, const unsigned long long *n_dev, const DeviceConsts &dc,
                      int angle_mode, int pool_mode, float *out, float *raw_out, int num_cus, hipStream_t stream,
-                     int waves = 0, unsigned long long *clk = nullptr);
+                     int waves = 0, unsigned long long *clk = nullptr, unsigned *claim = nullptr);
 // clk (nullable, device, 4 words): workgroup 0 leaves (shader clock, 100 MHz clock) on entry and on exit
+// claim (nullable, device, one word no other launch in flight uses): an 8-wave launch of at least kClaimRounds whole batches
+// per workgroup clears it on `stream` and deals its batches at run time (mkd_pool); every other launch leaves it alone
+constexpr long kClaimRounds = 4;
 // frame_of_kp == nullptr: every keypoint belongs to frame 0
 // (frame indices beyond n_frames - 1 -- caller's data -- are clamped to it: never a read outside the pyramid store)
 void launch_sample_patches(const float *pyr, long pyr_stride, const PyramidDesc &pd, const float *kps,
