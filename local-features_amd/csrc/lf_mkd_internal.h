@@ -1,4 +1,4 @@
-// What the other translation units of the C ABI may ask of a handle (its definition stays in lf_mkd.cpp).
+// What lf_mkd_comm.cpp may ask of a handle without seeing it (the handle itself is lf_mkd_handle.h, for the entry layer only).
 #pragma once
 #include <hip/hip_runtime.h>
 

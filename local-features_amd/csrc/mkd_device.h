@@ -1,5 +1,5 @@
-// Launch interface between the C ABI (lf_mkd.cpp) and the gfx950 kernels (mkd_describe.hip, mkd_pyramid.hip,
-// mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_q8.hip, mkd_match_guided.hip, mkd_verify.hip).
+// Launch interface between the C ABI (lf_mkd.cpp, lf_mkd_match.cpp, lf_mkd_tables.cpp, lf_mkd_geometry.cpp) and the gfx950 kernels
+// (mkd_describe.hip, mkd_pyramid.hip, mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_q8.hip, mkd_match_guided.hip, mkd_verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
