@@ -341,6 +341,25 @@ extern "C" {
                                 points: *const f32, n_tracks: u64, intrinsics: *const f32, max_reproj_px: f32,
                                 min_parallax_deg: f32, n_samples: u32, min_inliers: u32, rounds: u32, seed: u32, flags: u32,
                                 pose: *mut f32, stats: *mut u32, err: *mut f32, row_state: *mut u32) -> c_int;
+    // bundle adjustment: Levenberg-Marquardt over the free cameras (registered, not marked in d_camera_fixed) and the free
+    // points of a track table, the reduced camera system by preconditioned conjugate gradients: poses_out [n_images][12] (may
+    // be d_poses), points_out [track_capacity][4] (may be d_points), an optional state per observation, trace f64
+    // [iterations][8], counts [4]; the host form takes host arrays with T = n_tracks and O = n_obs
+    pub fn lf_mkd_bundle_adjust_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, d_image_offsets: *const u64, n_images: u32,
+                                       n_rows_total: u64, d_track_offsets: *const u64, track_capacity: u64,
+                                       d_obs_row: *const i32, d_obs_image: *const u32, obs_capacity: u64,
+                                       d_table_counts: *const u32, d_points: *const f32, d_intrinsics: *const f32,
+                                       d_poses: *const f32, d_obs_state: *const u32, d_camera_fixed: *const u32,
+                                       max_reproj_px: f32, lambda0: f32, iterations: u32, cg_iterations: u32, cg_tol: f32,
+                                       flags: u32, d_poses_out: *mut f32, d_points_out: *mut f32, d_obs_state_out: *mut u32,
+                                       d_trace: *mut f64, d_counts: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_bundle_adjust(h: *mut lf_mkd, kps: *const lf_mkd_keypoint, image_offsets: *const u64, n_images: u32,
+                                n_rows_total: u64, track_offsets: *const u64, n_tracks: u64, obs_row: *const i32,
+                                obs_image: *const u32, n_obs: u64, points: *const f32, intrinsics: *const f32,
+                                poses: *const f32, obs_state: *const u32, camera_fixed: *const u32, max_reproj_px: f32,
+                                lambda0: f32, iterations: u32, cg_iterations: u32, cg_tol: f32, flags: u32,
+                                poses_out: *mut f32, points_out: *mut f32, obs_state_out: *mut u32, trace: *mut f64,
+                                counts: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -662,6 +662,50 @@ impl LocalFeaturesHip {
         Ok((pose, stats, err, state))
     }
 
+    /// Bundle adjustment (`lf_mkd_bundle_adjust`): the registered cameras of `poses` (R row-major then t per image, an all-zero R
+    /// for an image that is not registered) that `camera_fixed` does not mark, and the points of the tracks, refined jointly by
+    /// `iterations` (1 .. 64) Levenberg-Marquardt steps on the reprojection error, each solving the reduced camera system by at
+    /// most `cg_iterations` (1 .. 256) preconditioned conjugate-gradient steps to `cg_tol`.  `kps` is the pool and
+    /// `image_offsets` its image ranges; the track table is `track_offsets`, `obs_row`, `obs_image`; `points` X, Y, Z and the
+    /// parallax cosine per track; `obs_state`, if given, is `triangulate_tracks`' (only its inliers are used).
+    /// Returns (poses, points, the state of every observation: 0 inactive, 1 active, 2 inlier; the trace: per iteration
+    /// [cost, the candidate's cost, lambda, accepted, CG steps, inliers, held cameras, held points]; [free cameras, free
+    /// points, active observations, accepted steps]).
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn bundle_adjust(&mut self, kps: &[ffi::lf_mkd_keypoint], image_offsets: &[u64], track_offsets: &[u64], obs_row: &[i32],
+                         obs_image: &[u32], points: &[[f32; 4]], intrinsics: &[[f32; 4]], poses: &[[f32; 12]],
+                         obs_state: Option<&[u32]>, camera_fixed: Option<&[u32]>, max_reproj_px: f32, lambda0: f32,
+                         iterations: u32, cg_iterations: u32, cg_tol: f32)
+                         -> Result<(Vec<[f32; 12]>, Vec<[f32; 4]>, Vec<u32>, Vec<[f64; 8]>, [u32; 4]), Error> {
+        let (n_images, n_tracks, n_obs) = (intrinsics.len(), points.len(), obs_row.len());
+        if image_offsets.len() != n_images + 1 || track_offsets.len() != n_tracks + 1 || obs_image.len() != n_obs
+            || poses.len() != n_images || obs_state.map_or(false, |s| s.len() != n_obs)
+            || camera_fixed.map_or(false, |f| f.len() != n_images) {
+            return Err(Error::BadArgument("bundle_adjust: image_offsets needs n_images + 1 entries, track_offsets n_tracks + 1, \
+                                           obs_row, obs_image and obs_state one entry per observation, intrinsics, poses and \
+                                           camera_fixed one row per image".into()));
+        }
+        let mut poses_out = vec![[0f32; 12]; n_images.max(1)];
+        let mut points_out = vec![[0f32; 4]; n_tracks.max(1)];
+        let mut state = vec![0u32; n_obs.max(1)];
+        let mut trace = vec![[0f64; 8]; iterations.max(1) as usize];
+        let mut counts = [0u32; 4];
+        // SAFETY: host arrays sized as declared; the counts bound what is read, the outputs have their stated sizes
+        unsafe {
+            check(self.h, ffi::lf_mkd_bundle_adjust(
+                self.h, kps.as_ptr(), image_offsets.as_ptr(), n_images as u32, kps.len() as u64, track_offsets.as_ptr(),
+                n_tracks as u64, obs_row.as_ptr(), obs_image.as_ptr(), n_obs as u64, points.as_ptr() as *const f32,
+                intrinsics.as_ptr() as *const f32, poses.as_ptr() as *const f32,
+                obs_state.map_or(std::ptr::null(), |s| s.as_ptr()), camera_fixed.map_or(std::ptr::null(), |f| f.as_ptr()),
+                max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, 0, poses_out.as_mut_ptr() as *mut f32,
+                points_out.as_mut_ptr() as *mut f32, state.as_mut_ptr(), trace.as_mut_ptr() as *mut f64, counts.as_mut_ptr()))?;
+        }
+        poses_out.truncate(n_images);
+        points_out.truncate(n_tracks);
+        state.truncate(n_obs);
+        Ok((poses_out, points_out, state, trace, counts))
+    }
+
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches
     /// `match_q8_edges` or a verifier returned for `edges` over the pool `image_offsets` describes (`n_rows` rows), edges with
     /// fewer than `min_links` of them left out.  Returns (offsets, link_a, link_b, edge_links): edge e's correspondences are

@@ -1327,6 +1327,86 @@ int lf_mkd_resect_camera(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows,
                          uint32_t n_samples, uint32_t min_inliers, uint32_t rounds, uint32_t seed, uint32_t flags, float *pose,
                          uint32_t *stats, float *err, uint32_t *row_state);
 
+/* lf_mkd_bundle_adjust_device refines the registered cameras and the tracks' points JOINTLY (bundle adjustment): Levenberg-
+ * Marquardt on the reprojection error over all free cameras (6 parameters each, intrinsics fixed) and all free points, the
+ * reduced camera system solved matrix-free by preconditioned conjugate gradients.  It is what closes the triangulate / resect
+ * loop, whose every step is conditioned on the one before it.  Nothing is read back.
+ * Inputs are what the three calls above take and leave: d_kps, n_rows_total and d_image_offsets [n_images + 1] (the pooled
+ * rows), the track table (d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts = {T, O},
+ * both clamped to the capacities), d_points [track_capacity][4] (X, Y, Z and the cosine the triangulation call writes),
+ * d_intrinsics [n_images][4], d_poses [n_images][12]; optional d_obs_state [obs_capacity] (the triangulation call's) and
+ * d_camera_fixed uint32 [n_images] (non-zero: the pose is held; hold two cameras, or one and a distance, to fix the gauge).
+ * Outputs: d_poses_out [n_images][12] (may be d_poses), d_points_out [track_capacity][4] (may be d_points), optional
+ * d_obs_state_out [obs_capacity] (may be d_obs_state), d_trace f64 [iterations][8], d_counts uint32 [4].
+ * The algorithm, exactly (f64, + - * / and sqrt alone, contraction off, the order csrc/mkd_bundle_math.h fixes; thr2 =
+ * max_reproj_px^2 and tol2 = cg_tol^2 formed in double from the f32 arguments):
+ *   1. Position p of track j < T is ACTIVE, for the whole call, iff it is usable by the triangulation call's rule (row and
+ *      image in range, a usable camera, a finite keypoint), its row lies inside its image's range of d_image_offsets (clamped
+ *      to n_rows_total as resection clamps it), the track's INPUT row of d_points has finite X, Y, Z and a fourth value <= 1,
+ *      and d_obs_state is null or d_obs_state[p] == 2.  The first launches build, in the handle's scratch, the inverse map
+ *      row -> (position, track) and each image's ascending list of active rows.  A row named by two tracks takes either;
+ *      track ranges or image ranges that overlap (no table has them) leave the result unspecified, within every bound.
+ *   2. A camera is FREE iff it is registered (usable by the triangulation call's rule) and d_camera_fixed is null or zero
+ *      there; a point is FREE iff its track has an active position.  Everything else is constant.  The state is f64, widened
+ *      from the f32 inputs; lambda = lambda0.
+ *   3. Per iteration k: an active observation is an INLIER iff p_z > 0 and e^2 <= thr2 at the state; outliers add nothing to
+ *      the normal equations.  Its camera rows Jx, Jy are resection's (step 5 there); its point rows are (a, 0, gx) R and
+ *      (0, b, gy) R.  Per point V (6 distinct entries) and g_p (3) are summed in the triangulation call's 4-slot order over
+ *      the track's positions (slot = (p - lo) mod 4, ascending, then (s0 + s2) + (s1 + s3)); per camera U (21) and g_c (6)
+ *      in resection's 256-slot order over the image's list.  cost_k = the MSAC terms (min(e^2, thr2); thr2 when not in
+ *      front) of all active observations, per track in the 4-slot order, then over the track index in the 256-slot order.
+ *   4. lambda max(d, 1e-6) is added to every diagonal entry d of U and V.  A free camera whose damped U* fails the Cholesky
+ *      pivot test is HELD for this iteration; so is a free point with fewer than 2 inliers or whose V* is singular by the
+ *      triangulation call's determinant rule.  Held items take a zero step, and the coupling W = J_c^T J_p of an observation
+ *      enters only if it is an inlier whose camera and point are both free and not held.
+ *   5. (U* - W V*^-1 W^T) x = g_c - W V*^-1 g_p by PCG from x = 0, preconditioned by U*^-1 (Cholesky).  The operator is two
+ *      passes: per track y_j = V*^-1 (the 4-slot sum of W^T p), per image U* p - (the 256-slot sum of W y).  A global dot
+ *      product is the 256-slot sum over the image id of the per-image 6-term dots (left to right).  A step: alpha = r.z /
+ *      p.Ap, x += alpha p, r -= alpha Ap, z = U*^-1 r, beta = r.z' / r.z, p = z + beta p.  CG stops for good, later steps
+ *      being no-ops, at the first step where not (p.Ap > 0) (before x moves) or, after x moved, not (r.z' > 0) or r.z' <=
+ *      tol2 r.z0.  The trace counts the steps that moved x.
+ *   6. dp_j = V*^-1 (g_p - sum W^T x); the candidate is resection's Cayley update by x per camera and X - dp per point.
+ *      cost' = step 3's cost at the candidate.  ACCEPT iff cost' <= cost_k (a NaN fails): the state becomes the candidate and
+ *      lambda = max(lambda / 4, 2^-40); else the state stays and lambda = min(8 lambda, 2^40).  Always `iterations` of them.
+ *   7. Free cameras are rounded to f32 into d_poses_out, every other image's 12 words are copied; free points are rounded
+ *      into d_points_out [.][0 .. 2], the fourth word and every other row below T are copied, rows >= T are untouched.
+ *      d_obs_state_out (positions inside a track's range): 0 inactive, 1 active, 2 inlier of the ROUNDED state under the
+ *      triangulation call's test.  d_trace [k] = {cost_k, cost', the lambda used, accepted, CG steps, inliers, held cameras,
+ *      held points}; d_counts = {free cameras, free points, active observations, accepted steps}.
+ * A call with nothing free, or with T == 0, copies its inputs through bit for bit.  n_images == 0 is LF_MKD_OK and writes
+ * nothing.  Whatever the arrays hold the call ends, and nothing at or beyond a capacity is read or written.
+ * tests/cpp/bundle_twin.cpp (the same header under g++) gives every output word on the host.
+ * How (csrc/mkd_bundle.hip): 5 + iterations x (6 + 5 cg_iterations) launches fixed by the scalars alone, a linear sequence
+ * (capturable once warmed up; capture after the largest call, as for resection).  4 lanes own a track, a workgroup owns an
+ * image, ONE workgroup does each global sum and the CG scalars; no floating-point atomic, nobody waits for another workgroup.
+ * W is formed again at every use, not stored (measured faster: profiles/bundle.md).  Scratch (4 bytes a position of
+ * obs_capacity, 156 a track, 664 an image, 12 a row) belongs to the handle and grows only when a call asks for more.  COST: one image owning every row is walked by ONE workgroup in
+ * both per-image kernels, M / 256 rounds each (profiles/bundle.md).  Asynchronous on `stream` (NULL: the handle's own).
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "bundle_adjust_device: "): a null
+ * handle; with n_images > 0 a null d_image_offsets, d_table_counts, d_intrinsics, d_poses, d_poses_out, d_trace or d_counts,
+ * with track_capacity > 0 too a null d_track_offsets, d_points or d_points_out, with obs_capacity > 0 too a null d_obs_row or
+ * d_obs_image, and with n_rows_total > 0 too a null d_kps; non-zero flags; max_reproj_px or lambda0 not finite or <= 0;
+ * iterations 0 or above 64; cg_iterations 0 or above 256; cg_tol outside [0, 1) or a NaN; d_image_offsets, d_track_offsets
+ * or d_trace not 8-byte or any other array not 4-byte aligned; a total or a capacity above 2^31 - 1. */
+int lf_mkd_bundle_adjust_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                uint64_t n_rows_total, const uint64_t *d_track_offsets, uint64_t track_capacity,
+                                const int32_t *d_obs_row, const uint32_t *d_obs_image, uint64_t obs_capacity,
+                                const uint32_t *d_table_counts, const float *d_points, const float *d_intrinsics,
+                                const float *d_poses, const uint32_t *d_obs_state, const uint32_t *d_camera_fixed,
+                                float max_reproj_px, float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol,
+                                uint32_t flags, float *d_poses_out, float *d_points_out, uint32_t *d_obs_state_out,
+                                double *d_trace, uint32_t *d_counts, void *stream);
+/* Host pointers, synchronous: the same arrays with T = n_tracks and O = n_obs; poses_out [n_images][12], points_out
+ * [n_tracks][4], optional obs_state_out [n_obs] (entries outside every track's range come back 0), trace [iterations][8],
+ * counts [4].  Everything goes through the device call.  LF_MKD_ERR_BAD_ARG ("bundle_adjust: "): a null handle or required
+ * pointer, the scalars as above, a total above 2^31 - 1. */
+int lf_mkd_bundle_adjust(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *image_offsets, uint32_t n_images,
+                         uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks, const int32_t *obs_row,
+                         const uint32_t *obs_image, uint64_t n_obs, const float *points, const float *intrinsics,
+                         const float *poses, const uint32_t *obs_state, const uint32_t *camera_fixed, float max_reproj_px,
+                         float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
+                         float *poses_out, float *points_out, uint32_t *obs_state_out, double *trace, uint32_t *counts);
+
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
  * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the

@@ -1,0 +1,810 @@
+// gfx950 bundle adjustment (include/lf_mkd.h, lf_mkd_bundle_adjust_device): Levenberg-Marquardt on the
+// reprojection error over the free cameras (6 parameters each) and the free points of a track table, the reduced camera system
+// solved matrix-free by conjugate gradients preconditioned with the damped camera blocks.  The arithmetic is
+// csrc/mkd_bundle_math.h, which the host twin compiles too.  Every launch is sized on the host from the call's arguments
+// alone; T, O, the ranges, lambda, the CG scalars and the accepted state's index are read on the device, so the sequence is
+// the same whatever the data hold (a stopped CG step and a rejected LM step are launches that do nothing).
+//
+// Two shapes of kernel, the two orders the sums run in:
+//   per TRACK   4 lanes own a track (16 tracks a wave) as in mkd_triangulate.hip: lane l reads the positions lo + l, lo + 4 + l,
+//               .. in ascending order, so the lane IS the slot of the 4-slot canonical sum; the butterfly over lane xor 2, 1.
+//   per IMAGE   a workgroup of 256 owns an image as in mkd_resect.hip: thread s reads entries s, s + 256, .. of the image's
+//               ascending list of active rows, so the thread IS the slot of the 256-slot canonical sum.
+// and ONE workgroup for every global sum (over image id, or over track index, in the 256-slot order) and the scalars.
+//
+//   ba_init, ba_setup_tracks, ba_setup_images   the f64 state, the flags, the ACTIVE set, the inverse map row -> (position,
+//               track) and every image's list, compacted in ascending order as rs_gather's
+//   per LM iteration:
+//     ba_track_lin    V, g_p and the cost of every track at the state; the damped V*, HELD points, y = V*^-1 g_p
+//     ba_image_lin    U, g_c of every free image; the damped U*, HELD cameras; which observations are coupled;
+//                     b = g_c - sum W y, and the start of CG: r = b, z = U*^-1 r, p = z, x = 0, r.z
+//     ba_scalar       (start) cost_k and r.z summed
+//     per CG step: ba_track_apply (y = V*^-1 sum W^T p), ba_image_apply (Ap = U* p - sum W y, p.Ap), ba_scalar (alpha),
+//                  ba_cg_update (x, r, z, r.z), ba_scalar (beta, and p = z + beta p)
+//     ba_cam_step     the candidate cameras rs_update(x)
+//     ba_track_step   dp = V*^-1 (g_p - sum W^T x), the candidate points, the candidate's cost per track
+//     ba_scalar       (accept) cost' summed, the verdict, lambda, the trace row; the state is two buffers and an index
+//   ba_final_images, ba_final_tracks   the rounding, the copies, the states, the counts
+//
+// W is RECOMPUTED at every use from the keypoint, the point and the pose (one division chain, 18 products) rather than stored
+// per observation (144 bytes written once and read twice a CG step): measured, recomputing is 11 % faster on a collection of
+// 128 000 observations and 5 % on a window of 256 000, equal on a single query image, the same bits, and the scratch is 4
+// bytes a position instead of 148 (profiles/bundle.md; -DLF_BA_STORE_W builds the other form).  One image owning every row
+// serialises the per-image kernels on one workgroup: its passes are M / 256 rounds of one workgroup, the cost stated in
+// the header and measured in profiles/bundle.md.
+//
+// No floating-point atomic (the integer counts of the trace are integer atomics, exact in any order), no LDS beyond the block
+// sums, scratch belongs to the handle, nobody waits for another workgroup.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mkd_bundle_math.h"
+#include "mkd_device.h"
+
+namespace lfmkd {
+namespace {
+
+constexpr int kThreads = kRsSlots;
+constexpr int kWaves = kThreads / 64;
+constexpr int G = 4;
+static_assert(kThreads == 256 && kTriSlots == G, "thread s is slot s of the 256-slot sum, lane l slot l of the 4-slot sum");
+constexpr unsigned kMaxBlocks = 16384;      // grid-stride beyond
+
+enum : int { kVecX = 0, kVecR = 1, kVecZ = 2, kVecP = 3, kVecAp = 4, kVecs = 5 };
+enum : int { kSLambda = 0, kSCost = 1, kSRz = 2, kSRz0 = 3, kSAlpha = 4, kSBeta = 5, kScalars = 8 };
+enum : int { kWCur = 0, kWStopped = 1, kWSteps = 2, kWInliers = 3, kWHeldCams = 4, kWHeldPoints = 5, kWFreeCams = 6,
+             kWFreePoints = 7, kWActive = 8, kWAccepted = 9, kWords = 16 };
+enum : unsigned { kModeStart = 0, kModeAlpha = 1, kModeBeta = 2, kModeAccept = 3 };
+
+struct BaIn {
+    const float *__restrict__ kps;
+    const uint64_t *__restrict__ off;          // image offsets
+    uint64_t n_rows;
+    unsigned n_images;
+    const uint64_t *__restrict__ toff;         // track offsets
+    uint64_t tcap;
+    const int *__restrict__ obs_row;
+    const unsigned *__restrict__ obs_image;
+    uint64_t ocap;
+    const unsigned *__restrict__ counts;
+    const float *__restrict__ intrinsics;
+};
+// scratch, in bundle_scratch_bytes' order: the f64 arrays, the 64-bit map, then the words
+struct BaScratch {
+    RsPose *cam;                 // [2][n_images]: the state and the candidate, words[kWCur] says which is which
+    double *pt;                  // [2][tcap][3]
+    double *U;                   // [n_images][27]: damped U*, then g_c
+    double *V;                   // [tcap][9]: damped V*, then g_p
+    double *W;                   // [ocap][18] in the A/B build that stores W; not allocated otherwise
+    double *vec;                 // [5][n_images][6]: x, r, z, p, Ap
+    double *y;                   // [tcap][3]
+    double *tcost;               // [tcap]
+    double *dots;                // [n_images]
+    double *scal;                // [kScalars]
+    unsigned long long *rowmap;  // [n_rows]: position | track << 32 of the active observation that names the row
+    unsigned *idx;               // [n_rows]: image i's active rows at [lo_i, lo_i + M_i)
+    unsigned *head;              // [n_images][2] = {M, flags}
+    unsigned *oflag;             // [ocap]
+    unsigned *tflag;             // [tcap]
+    unsigned *words;             // [kWords]
+};
+
+__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
+__device__ __forceinline__ void image_range(const BaIn &in, unsigned img, uint64_t &lo, uint64_t &hi) {
+    lo = clamp_to(in.off[img], in.n_rows);
+    hi = clamp_to(in.off[img + 1], in.n_rows);
+    hi = hi > lo ? hi : lo;
+}
+__device__ __forceinline__ void track_range(const BaIn &in, uint64_t t, uint64_t O, uint64_t &lo, uint64_t &hi) {
+    lo = clamp_to(in.toff[t], O);
+    hi = clamp_to(in.toff[t + 1], O);
+    hi = hi > lo ? hi : lo;
+}
+__device__ __forceinline__ double *vec_of(const BaScratch &sc, const BaIn &in, int which, unsigned img) {
+    return sc.vec + ((uint64_t)which * in.n_images + img) * 6;
+}
+__device__ __forceinline__ void load_k(const BaIn &in, unsigned img, float *K) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) K[i] = in.intrinsics[4 * (uint64_t)img + i];
+}
+// the correspondence of an ACTIVE position's row under the points `pt`
+__device__ __forceinline__ BaCorr load_corr(const BaIn &in, uint64_t row, const double *pt, uint64_t t) {
+    const float *k = in.kps + 5 * row;
+    const double *p = pt + 3 * t;
+    return BaCorr{k[0], k[1], p[0], p[1], p[2]};
+}
+
+// The coupling block of a coupled position, formed again from the state at every use (the state does not move within an
+// iteration, so these are ba_image_lin's bits), or -- the A/B build of profiles/bundle.md, -DLF_BA_STORE_W -- as ba_image_lin
+// stored it, 144 bytes a position.
+__device__ __forceinline__ void load_w(const BaIn &in, const BaScratch &sc, uint64_t pos, uint64_t t, double *W) {
+#ifndef LF_BA_STORE_W
+    const unsigned cur = sc.words[kWCur], img = in.obs_image[pos];
+    float K[4];
+    load_k(in, img, K);
+    BaLin o;
+    ba_rows(sc.cam[(uint64_t)cur * in.n_images + img], K,
+            load_corr(in, (uint64_t)in.obs_row[pos], sc.pt + (uint64_t)cur * in.tcap * 3, t), o);
+    ba_coupling(o, W);
+#else
+    const double *src = sc.W + kBaW * pos;
+#pragma unroll
+    for (int i = 0; i < kBaW; ++i) W[i] = src[i];
+#endif
+}
+
+// Workgroup sum of N values per thread in the canonical order: the butterfly within a wave, then ((w0 + w1) + w2) + w3.
+template <typename T, int N>
+__device__ __forceinline__ void block_sum(T *v, T *red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        T s = v[i];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
+        if (lane == 0) red[wave * N + i] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
+    __syncthreads();
+}
+// the butterfly of the 4-slot sum over the group's lanes
+__device__ __forceinline__ double combine(double v) {
+#pragma unroll
+    for (int m = G / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// What a per-track kernel knows of where it is: T, O, its wave's first track and stride, its lane's slot.
+struct TrackWalk {
+    uint64_t T, O, first, stride;
+    unsigned l, base;
+};
+__device__ __forceinline__ TrackWalk track_walk(const BaIn &in) {
+    TrackWalk w;
+    w.T = clamp_to(in.counts[0], in.tcap);
+    w.O = clamp_to(in.counts[1], in.ocap);
+    const unsigned lane = threadIdx.x & 63;
+    w.l = lane & (G - 1);
+    w.base = lane & ~(unsigned)(G - 1);
+    w.first = ((uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * (64 / G);
+    w.stride = (uint64_t)gridDim.x * kWaves * (64 / G);
+    return w;
+}
+__device__ __forceinline__ unsigned group_bits(bool p, unsigned base) { return (unsigned)(__ballot(p) >> base) & ((1u << G) - 1u); }
+
+}  // namespace
+
+// ---- setup ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void ba_init(BaIn in, const float *__restrict__ poses, const unsigned *__restrict__ fixed,
+                                                    double lambda0, BaScratch sc) {
+    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x, n = (uint64_t)gridDim.x * kThreads;
+    for (uint64_t r = gid; r < in.n_rows; r += n) sc.rowmap[r] = kBaNoRow;
+    for (uint64_t i = gid; i < in.n_images; i += n) {
+        float K[4], P[12];
+        load_k(in, (unsigned)i, K);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) P[k] = poses[12 * i + k];
+        const bool usable = tri_camera_usable(K, P), is_free = usable && !(fixed && fixed[i] != 0);
+        sc.head[2 * i] = 0;
+        sc.head[2 * i + 1] = (usable ? kBaCamUsable : 0u) | (is_free ? kBaCamFree : 0u);
+        RsPose S;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) S.R[k] = double(P[k]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) S.t[k] = double(P[9 + k]);
+        sc.cam[i] = S;
+        sc.cam[in.n_images + i] = S;
+    }
+    if (gid < kWords) sc.words[gid] = 0;
+    if (gid < kScalars) sc.scal[gid] = gid == kSLambda ? lambda0 : 0.0;
+}
+
+__global__ __launch_bounds__(kThreads) void ba_setup_tracks(BaIn in, const float *__restrict__ points,
+                                                            const unsigned *__restrict__ obs_state, BaScratch sc) {
+    const TrackWalk w = track_walk(in);
+    for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool alive = t < w.T;
+        uint64_t lo = 0, hi = 0;
+        bool ok = false;
+        double X[3] = {0.0, 0.0, 0.0};
+        if (alive) {
+            track_range(in, t, w.O, lo, hi);
+            const float p[4] = {points[4 * t], points[4 * t + 1], points[4 * t + 2], points[4 * t + 3]};
+            ok = rs_point_usable(p, 1.0);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) X[k] = double(p[k]);
+        }
+        const unsigned nch = (unsigned)((hi - lo + G - 1) / G);
+        unsigned n_active = 0;
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            const bool in_track = ch < nch && pos < hi;
+            bool act = false;
+            if (in_track) {
+                const int row = in.obs_row[pos];
+                const unsigned img = in.obs_image[pos];
+                if (ok && row >= 0 && (uint64_t)row < in.n_rows && img < in.n_images && (sc.head[2 * (uint64_t)img + 1] & kBaCamUsable) &&
+                    (!obs_state || obs_state[pos] == 2u)) {
+                    uint64_t ilo, ihi;
+                    image_range(in, img, ilo, ihi);
+                    const float *k = in.kps + 5 * (uint64_t)row;
+                    act = (uint64_t)row >= ilo && (uint64_t)row < ihi && tri_keypoint_usable(k[0], k[1]);
+                    if (act) sc.rowmap[row] = (unsigned long long)pos | (unsigned long long)t << 32;
+                }
+                sc.oflag[pos] = act ? kBaActive : 0u;
+            }
+            n_active += (unsigned)__popc(group_bits(act, w.base));
+        }
+        if (alive && w.l == 0) {
+            sc.tflag[t] = (ok ? kBaPointOk : 0u) | (n_active ? kBaPointFree : 0u);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sc.pt[3 * t + k] = X[k], sc.pt[3 * (in.tcap + t) + k] = X[k];
+            if (n_active) atomicAdd(sc.words + kWFreePoints, 1u), atomicAdd(sc.words + kWActive, n_active);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch sc) {
+    __shared__ unsigned s_cnt[kWaves];
+    const unsigned img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!(sc.head[2 * (uint64_t)img + 1] & kBaCamFree)) return;                   // block-uniform; M stays 0
+    uint64_t lo, hi;
+    image_range(in, img, lo, hi);
+    uint64_t base = lo;
+    for (uint64_t r0 = lo; r0 < hi; r0 += kThreads) {                             // block-uniform
+        const uint64_t r = r0 + tid;
+        bool is = false;
+        if (r < hi) {
+            const unsigned long long m = sc.rowmap[r];
+            is = m != kBaNoRow && in.obs_image[(unsigned)m] == img;
+        }
+        const uint64_t bits = __ballot(is);
+        if (lane == 0) s_cnt[wave] = (unsigned)__popcll(bits);
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            before += (unsigned)w < wave ? s_cnt[w] : 0u;
+            total += s_cnt[w];
+        }
+        if (is) sc.idx[base + before + (unsigned)__popcll(bits & ((1ull << lane) - 1ull))] = (unsigned)r;
+        base += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sc.head[2 * (uint64_t)img] = (unsigned)(base - lo);
+        atomicAdd(sc.words + kWFreeCams, 1u);
+    }
+}
+
+// ---- an LM iteration -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, double thr2, BaScratch sc) {
+    const TrackWalk w = track_walk(in);
+    const unsigned cur = sc.words[kWCur];
+    const double lambda = sc.scal[kSLambda];
+    const RsPose *cam = sc.cam + (uint64_t)cur * in.n_images;
+    const double *pt = sc.pt + (uint64_t)cur * in.tcap * 3;
+    for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool alive = t < w.T;
+        uint64_t lo = 0, hi = 0;
+        if (alive) track_range(in, t, w.O, lo, hi);
+        const unsigned nch = (unsigned)((hi - lo + G - 1) / G);
+        double acc[kBaPointTerms + 1];
+#pragma unroll
+        for (int k = 0; k <= kBaPointTerms; ++k) acc[k] = 0.0;
+        unsigned n_in = 0;
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            const bool on = ch < nch && pos < hi && (sc.oflag[pos] & kBaActive);
+            bool inl = false;
+            if (on) {
+                const unsigned img = in.obs_image[pos];
+                float K[4];
+                load_k(in, img, K);
+                BaLin o;
+                ba_linearise(cam[img], K, load_corr(in, (uint64_t)in.obs_row[pos], pt, t), thr2, o);
+                inl = o.inlier;
+                acc[kBaPointTerms] = acc[kBaPointTerms] + (inl ? o.e2 : thr2);
+                if (inl) {
+                    double v[kBaPointTerms];
+                    ba_point_terms(o, v);
+#pragma unroll
+                    for (int k = 0; k < kBaPointTerms; ++k) acc[k] = acc[k] + v[k];
+                }
+            }
+            n_in += (unsigned)__popc(group_bits(inl, w.base));
+        }
+        double v[kBaPointTerms], y[3];
+#pragma unroll
+        for (int k = 0; k < kBaPointTerms; ++k) v[k] = combine(acc[k]);
+        const double cost = combine(acc[kBaPointTerms]);
+        ba_damp_v(v, lambda);
+        const bool ok = ba_solve_v(v, v + 6, y);
+        if (alive && w.l == 0) {
+            const unsigned tf = sc.tflag[t] & (kBaPointOk | kBaPointFree);
+            const bool is_free = (tf & kBaPointFree) != 0, held = is_free && (n_in < 2 || !ok);
+            sc.tflag[t] = tf | (held ? kBaPointHeld : 0u);
+            sc.tcost[t] = cost;
+#pragma unroll
+            for (int k = 0; k < kBaPointTerms; ++k) sc.V[kBaPointTerms * t + k] = v[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sc.y[3 * t + k] = is_free && !held ? y[k] : 0.0;
+            if (n_in) atomicAdd(sc.words + kWInliers, n_in);
+            if (held) atomicAdd(sc.words + kWHeldPoints, 1u);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, BaScratch sc) {
+    __shared__ double s_red[kWaves * kRsTerms];
+    const unsigned img = blockIdx.x, tid = threadIdx.x;
+    const unsigned hf = sc.head[2 * (uint64_t)img + 1] & (kBaCamUsable | kBaCamFree);
+    if (!(hf & kBaCamFree)) {                                                     // block-uniform
+        if (tid < 6) {
+#pragma unroll
+            for (int k = 0; k < kVecs; ++k) vec_of(sc, in, k, img)[tid] = 0.0;
+        }
+        if (tid == 0) sc.dots[img] = 0.0;
+        return;
+    }
+    const unsigned cur = sc.words[kWCur], M = sc.head[2 * (uint64_t)img];
+    const double lambda = sc.scal[kSLambda];
+    const RsPose P = sc.cam[(uint64_t)cur * in.n_images + img];
+    const double *pt = sc.pt + (uint64_t)cur * in.tcap * 3;
+    uint64_t lo, hi;
+    image_range(in, img, lo, hi);
+    float K[4];
+    load_k(in, img, K);
+
+    double acc[kRsTerms];
+#pragma unroll
+    for (int i = 0; i < kRsTerms; ++i) acc[i] = 0.0;
+    for (unsigned k = tid; k < M; k += kThreads) {
+        const unsigned row = sc.idx[lo + k];
+        const unsigned long long m = sc.rowmap[row];
+        BaLin o;
+        ba_linearise(P, K, load_corr(in, row, pt, m >> 32), thr2, o);
+        if (o.inlier) {
+            double v[kRsTerms];
+            rs_gn_products(o.r, v);
+#pragma unroll
+            for (int i = 0; i < kRsTerms; ++i) acc[i] = acc[i] + v[i];
+        }
+    }
+    block_sum<double, kRsTerms>(acc, s_red);
+    ba_damp_u(acc, lambda);
+    double z[6];
+    const bool held = !ba_solve_u(acc, acc + 21, z);                              // every thread the same bits
+    if (tid == 0) {
+        sc.head[2 * (uint64_t)img + 1] = hf | (held ? kBaCamHeld : 0u);
+        if (held) atomicAdd(sc.words + kWHeldCams, 1u);
+    }
+    if (tid < kRsTerms) {
+        double v = acc[0];
+#pragma unroll
+        for (int i = 1; i < kRsTerms; ++i) v = tid == (unsigned)i ? acc[i] : v;
+        sc.U[(uint64_t)kRsTerms * img + tid] = v;
+    }
+
+    // which entries are coupled, and sum W y
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (unsigned k = tid; k < M; k += kThreads) {
+        const unsigned row = sc.idx[lo + k];
+        const unsigned long long m = sc.rowmap[row];
+        const uint64_t pos = (unsigned)m, t = m >> 32;
+        BaLin o;
+        ba_linearise(P, K, load_corr(in, row, pt, t), thr2, o);
+        const bool coupled = !held && o.inlier && (sc.tflag[t] & (kBaPointFree | kBaPointHeld)) == kBaPointFree;
+        if (coupled) {
+            double W[kBaW], wy[6];
+            ba_coupling(o, W);
+#ifdef LF_BA_STORE_W
+            double *dst = sc.W + kBaW * pos;
+#pragma unroll
+            for (int i = 0; i < kBaW; ++i) dst[i] = W[i];
+#endif
+            ba_w_y(W, sc.y + 3 * t, wy);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) s[i] = s[i] + wy[i];
+        }
+        sc.oflag[pos] = kBaActive | (coupled ? kBaCoupled : 0u);
+    }
+    block_sum<double, 6>(s, s_red);
+    if (tid == 0) {
+        double r[6], zz[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) r[i] = held ? 0.0 : acc[21 + i] - s[i];
+        const bool ok = ba_solve_u(acc, r, zz);
+        (void)ok;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const double zi = held ? 0.0 : zz[i];
+            vec_of(sc, in, kVecX, img)[i] = 0.0;
+            vec_of(sc, in, kVecR, img)[i] = r[i];
+            vec_of(sc, in, kVecZ, img)[i] = zi;
+            vec_of(sc, in, kVecP, img)[i] = zi;
+            vec_of(sc, in, kVecAp, img)[i] = 0.0;
+            zz[i] = zi;
+        }
+        sc.dots[img] = held ? 0.0 : ba_dot6(r, zz);
+    }
+}
+
+// y = V*^-1 sum W^T p over the track's coupled positions (0 for a point that is not free, or held)
+__global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaScratch sc) {
+    if (sc.words[kWStopped]) return;                                              // grid-uniform
+    const TrackWalk w = track_walk(in);
+    for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool go = t < w.T && (sc.tflag[t] & (kBaPointFree | kBaPointHeld)) == kBaPointFree;
+        uint64_t lo = 0, hi = 0;
+        if (go) track_range(in, t, w.O, lo, hi);
+        const unsigned nch = (unsigned)((hi - lo + G - 1) / G);
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            if (ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
+                double W[kBaW], v[3];
+                load_w(in, sc, pos, t, W);
+                ba_wt_v(W, vec_of(sc, in, kVecP, in.obs_image[pos]), v);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) acc[k] = acc[k] + v[k];
+            }
+        }
+        double b[3], y[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b[k] = combine(acc[k]);
+        if (go) ba_solve_v(sc.V + kBaPointTerms * t, b, y);
+        if (go && w.l == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sc.y[3 * t + k] = y[k];
+        }
+    }
+}
+
+// Ap = U* p - sum W y over the image's coupled entries, and p.Ap
+__global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaScratch sc) {
+    __shared__ double s_red[kWaves * 6];
+    if (sc.words[kWStopped]) return;                                              // grid-uniform
+    const unsigned img = blockIdx.x, tid = threadIdx.x;
+    if ((sc.head[2 * (uint64_t)img + 1] & (kBaCamFree | kBaCamHeld)) != kBaCamFree) {   // block-uniform
+        if (tid == 0) sc.dots[img] = 0.0;
+        return;
+    }
+    const unsigned M = sc.head[2 * (uint64_t)img];
+    uint64_t lo, hi;
+    image_range(in, img, lo, hi);
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (unsigned k = tid; k < M; k += kThreads) {
+        const unsigned long long m = sc.rowmap[sc.idx[lo + k]];
+        const uint64_t pos = (unsigned)m, t = m >> 32;
+        if (sc.oflag[pos] & kBaCoupled) {
+            double W[kBaW], wy[6];
+            load_w(in, sc, pos, t, W);
+            ba_w_y(W, sc.y + 3 * t, wy);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) s[i] = s[i] + wy[i];
+        }
+    }
+    block_sum<double, 6>(s, s_red);
+    if (tid == 0) {
+        double p[6], up[6], ap[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) p[i] = vec_of(sc, in, kVecP, img)[i];
+        ba_u_times(sc.U + (uint64_t)kRsTerms * img, p, up);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            ap[i] = up[i] - s[i];
+            vec_of(sc, in, kVecAp, img)[i] = ap[i];
+        }
+        sc.dots[img] = ba_dot6(p, ap);
+    }
+}
+
+// x += alpha p, r -= alpha Ap, z = U*^-1 r, and r.z: a thread per image
+__global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaScratch sc) {
+    if (sc.words[kWStopped]) return;                                              // grid-uniform
+    const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (img >= in.n_images) return;
+    if ((sc.head[2 * img + 1] & (kBaCamFree | kBaCamHeld)) != kBaCamFree) {
+        sc.dots[img] = 0.0;
+        return;
+    }
+    const double alpha = sc.scal[kSAlpha];
+    double *x = vec_of(sc, in, kVecX, (unsigned)img), *r = vec_of(sc, in, kVecR, (unsigned)img);
+    const double *p = vec_of(sc, in, kVecP, (unsigned)img), *ap = vec_of(sc, in, kVecAp, (unsigned)img);
+    double rn[6], z[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        x[i] = x[i] + alpha * p[i];
+        rn[i] = r[i] - alpha * ap[i];
+        r[i] = rn[i];
+    }
+    ba_solve_u(sc.U + kRsTerms * img, rn, z);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) vec_of(sc, in, kVecZ, (unsigned)img)[i] = z[i];
+    sc.dots[img] = ba_dot6(rn, z);
+}
+
+// ONE workgroup: a global sum in the 256-slot order (over image id of dots, over track index of tcost) and the scalars
+__global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, unsigned mode, double tol2, unsigned iteration, BaScratch sc,
+                                                      double *__restrict__ trace) {
+    __shared__ double s_red[kWaves * 2];
+    const unsigned tid = threadIdx.x;
+    if ((mode == kModeAlpha || mode == kModeBeta) && sc.words[kWStopped]) return;
+    const uint64_t T = clamp_to(in.counts[0], in.tcap);
+    double v[2] = {0.0, 0.0};
+    if (mode != kModeAccept)
+        for (uint64_t i = tid; i < in.n_images; i += kThreads) v[0] = v[0] + sc.dots[i];
+    if (mode == kModeStart || mode == kModeAccept)
+        for (uint64_t t = tid; t < T; t += kThreads) v[1] = v[1] + sc.tcost[t];
+    block_sum<double, 2>(v, s_red);
+    BaCg cg = {sc.scal[kSRz], sc.scal[kSRz0], sc.scal[kSAlpha], sc.scal[kSBeta], sc.words[kWStopped], sc.words[kWSteps]};
+    __syncthreads();                                                              // everyone has read the scalars
+    if (mode == kModeStart) ba_cg_start(cg, v[0]);
+    if (mode == kModeAlpha) ba_cg_alpha(cg, v[0]);
+    if (mode == kModeBeta) {
+        ba_cg_beta(cg, v[0], tol2);
+        if (!cg.stopped)
+            for (uint64_t i = tid; i < 6 * (uint64_t)in.n_images; i += kThreads) {
+                double *p = sc.vec + (uint64_t)kVecP * in.n_images * 6, *z = sc.vec + (uint64_t)kVecZ * in.n_images * 6;
+                p[i] = z[i] + cg.beta * p[i];
+            }
+    }
+    if (tid != 0) return;
+    if (mode == kModeAccept) {
+        double lambda = sc.scal[kSLambda];
+        const double used = lambda, cost = sc.scal[kSCost];
+        const bool ok = ba_accept(v[1], cost, lambda);
+        double *row = trace + (uint64_t)kBaTrace * iteration;
+        row[0] = cost, row[1] = v[1], row[2] = used, row[3] = ok ? 1.0 : 0.0, row[4] = double(sc.words[kWSteps]);
+        row[5] = double(sc.words[kWInliers]), row[6] = double(sc.words[kWHeldCams]), row[7] = double(sc.words[kWHeldPoints]);
+        sc.scal[kSLambda] = lambda;
+        if (ok) sc.words[kWCur] ^= 1u, sc.words[kWAccepted] += 1u;
+        sc.words[kWInliers] = 0, sc.words[kWHeldCams] = 0, sc.words[kWHeldPoints] = 0;
+        return;
+    }
+    if (mode == kModeStart) sc.scal[kSCost] = v[1];
+    sc.scal[kSRz] = cg.rz, sc.scal[kSRz0] = cg.rz0, sc.scal[kSAlpha] = cg.alpha, sc.scal[kSBeta] = cg.beta;
+    sc.words[kWStopped] = cg.stopped, sc.words[kWSteps] = cg.steps;
+}
+
+// the candidate cameras: a thread per image
+__global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaScratch sc) {
+    const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (img >= in.n_images) return;
+    const unsigned cur = sc.words[kWCur];
+    const RsPose P = sc.cam[(uint64_t)cur * in.n_images + img];
+    RsPose next = P;
+    if ((sc.head[2 * img + 1] & (kBaCamFree | kBaCamHeld)) == kBaCamFree) {
+        double d[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[i] = vec_of(sc, in, kVecX, (unsigned)img)[i];
+        rs_update(P, d, next);
+    }
+    sc.cam[(uint64_t)(cur ^ 1u) * in.n_images + img] = next;
+}
+
+// the candidate points X - V*^-1 (g_p - sum W^T x) and the candidate's cost per track
+__global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, double thr2, BaScratch sc) {
+    const TrackWalk w = track_walk(in);
+    const unsigned cur = sc.words[kWCur];
+    const RsPose *cam_c = sc.cam + (uint64_t)(cur ^ 1u) * in.n_images;
+    const double *pt = sc.pt + (uint64_t)cur * in.tcap * 3;
+    double *pt_c = sc.pt + (uint64_t)(cur ^ 1u) * in.tcap * 3;
+    for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool alive = t < w.T;
+        const bool go = alive && (sc.tflag[t] & (kBaPointFree | kBaPointHeld)) == kBaPointFree;
+        uint64_t lo = 0, hi = 0;
+        if (alive) track_range(in, t, w.O, lo, hi);
+        const unsigned nch = (unsigned)((hi - lo + G - 1) / G);
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            if (go && ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
+                double W[kBaW], v[3];
+                load_w(in, sc, pos, t, W);
+                ba_wt_v(W, vec_of(sc, in, kVecX, in.obs_image[pos]), v);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) acc[k] = acc[k] + v[k];
+            }
+        }
+        BaCorr c = {0.f, 0.f, 0.0, 0.0, 0.0};
+        if (alive) c.X = pt[3 * t], c.Y = pt[3 * t + 1], c.Z = pt[3 * t + 2];
+        double b[3], dp[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) b[k] = combine(acc[k]);
+        if (go) {
+            const double *V = sc.V + kBaPointTerms * t;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) b[k] = V[6 + k] - b[k];
+            ba_solve_v(V, b, dp);
+            c.X = c.X - dp[0], c.Y = c.Y - dp[1], c.Z = c.Z - dp[2];
+        }
+        double cost = 0.0;
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            if (ch < nch && pos < hi && (sc.oflag[pos] & kBaActive)) {
+                const unsigned img = in.obs_image[pos];
+                float K[4];
+                load_k(in, img, K);
+                const float *k = in.kps + 5 * (uint64_t)in.obs_row[pos];
+                c.x = k[0], c.y = k[1];
+                cost = cost + rs_cost(cam_c[img], K, c, thr2);
+            }
+        }
+        cost = combine(cost);
+        if (alive && w.l == 0) {
+            pt_c[3 * t] = c.X, pt_c[3 * t + 1] = c.Y, pt_c[3 * t + 2] = c.Z;
+            sc.tcost[t] = cost;
+        }
+    }
+}
+
+// ---- the end ----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, const float *poses, BaScratch sc, float *poses_out) {
+    const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (img >= in.n_images) return;
+    const unsigned *src = reinterpret_cast<const unsigned *>(poses) + 12 * img;
+    unsigned *dst = reinterpret_cast<unsigned *>(poses_out) + 12 * img;
+    unsigned words[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) words[i] = src[i];
+    if (sc.head[2 * img + 1] & kBaCamFree) {
+        float P[12];
+        ba_round_pose(sc.cam[(uint64_t)sc.words[kWCur] * in.n_images + img], P);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) words[i] = __float_as_uint(P[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = words[i];
+}
+
+__global__ __launch_bounds__(kThreads) void ba_final_tracks(BaIn in, const float *points, double thr2, BaScratch sc,
+                                                            const float *__restrict__ poses_out, float *points_out,
+                                                            unsigned *obs_state_out, unsigned *__restrict__ counts_out) {
+    const TrackWalk w = track_walk(in);
+    const double *pt = sc.pt + (uint64_t)sc.words[kWCur] * in.tcap * 3;
+    if (blockIdx.x == 0 && threadIdx.x < 4) {
+        const int which = threadIdx.x == 0 ? kWFreeCams : threadIdx.x == 1 ? kWFreePoints : threadIdx.x == 2 ? kWActive : kWAccepted;
+        counts_out[threadIdx.x] = sc.words[which];
+    }
+    for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool alive = t < w.T;
+        uint64_t lo = 0, hi = 0;
+        unsigned words[4] = {0, 0, 0, 0};
+        double X[3] = {0.0, 0.0, 0.0};
+        if (alive) {
+            track_range(in, t, w.O, lo, hi);
+            const unsigned *src = reinterpret_cast<const unsigned *>(points) + 4 * t;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) words[k] = src[k];
+            if (sc.tflag[t] & kBaPointFree) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) words[k] = __float_as_uint(float(pt[3 * t + k]));
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) X[k] = double(__uint_as_float(words[k]));
+        }
+        const unsigned nch = obs_state_out ? (unsigned)((hi - lo + G - 1) / G) : 0u;
+        for (unsigned ch = 0; __any(ch < nch); ++ch) {
+            const uint64_t pos = lo + (uint64_t)ch * G + w.l;
+            if (ch < nch && pos < hi) {
+                unsigned state = 0;
+                if (sc.oflag[pos] & kBaActive) {
+                    const unsigned img = in.obs_image[pos];
+                    const float *k = in.kps + 5 * (uint64_t)in.obs_row[pos];
+                    TriObs o;
+                    o.x = k[0], o.y = k[1];
+                    load_k(in, img, o.K);
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) o.P[i] = poses_out[12 * (uint64_t)img + i];
+                    double e2;
+                    state = tri_inlier(o, X, thr2, e2) ? 2u : 1u;
+                }
+                obs_state_out[pos] = state;
+            }
+        }
+        if (alive && w.l == 0) {
+            unsigned *dst = reinterpret_cast<unsigned *>(points_out) + 4 * t;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[k] = words[k];
+        }
+    }
+}
+
+// ---- the host side ------------------------------------------------------------------------------------------------------------------
+namespace {
+struct BaLayout {
+    uint64_t cam, pt, U, V, W, vec, y, tcost, dots, scal, rowmap, idx, head, oflag, tflag, words, total;
+};
+BaLayout layout(uint64_t n_images, uint64_t n_rows, uint64_t tcap, uint64_t ocap) {
+    BaLayout L;
+    uint64_t at = 0;
+    const auto take = [&](uint64_t bytes) {
+        const uint64_t here = at;
+        at += (bytes + 15) / 16 * 16;
+        return here;
+    };
+    L.cam = take(8 * 2 * 12 * n_images);
+    L.pt = take(8 * 2 * 3 * tcap);
+    L.U = take(8 * kRsTerms * n_images);
+    L.V = take(8 * kBaPointTerms * tcap);
+#ifdef LF_BA_STORE_W
+    L.W = take(8 * kBaW * ocap);
+#else
+    L.W = take(0);
+#endif
+    L.vec = take(8 * kVecs * 6 * n_images);
+    L.y = take(8 * 3 * tcap);
+    L.tcost = take(8 * tcap);
+    L.dots = take(8 * n_images);
+    L.scal = take(8 * kScalars);
+    L.rowmap = take(8 * n_rows);
+    L.idx = take(4 * n_rows);
+    L.head = take(4 * 2 * n_images);
+    L.oflag = take(4 * ocap);
+    L.tflag = take(4 * tcap);
+    L.words = take(4 * kWords);
+    L.total = at;
+    return L;
+}
+}  // namespace
+
+uint64_t bundle_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity) {
+    return layout(n_images, n_rows, track_capacity, obs_capacity).total;
+}
+unsigned bundle_launches(unsigned iterations, unsigned cg_iterations) { return 5 + iterations * (6 + 5 * cg_iterations); }
+
+void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
+                          const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row, const unsigned *obs_image,
+                          uint64_t obs_capacity, const unsigned *table_counts, const float *points, const float *intrinsics,
+                          const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0,
+                          unsigned iterations, unsigned cg_iterations, double tol2, float *poses_out, float *points_out,
+                          unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
+    if (n_images == 0) return;
+    const BaIn in = {kps, image_offsets, n_rows, n_images, track_offsets, track_capacity, obs_row, obs_image, obs_capacity, table_counts,
+                     intrinsics};
+    unsigned char *b = static_cast<unsigned char *>(scratch);
+    const BaLayout L = layout(n_images, n_rows, track_capacity, obs_capacity);
+    const auto f64 = [&](uint64_t at) { return reinterpret_cast<double *>(b + at); };
+    const auto u32 = [&](uint64_t at) { return reinterpret_cast<unsigned *>(b + at); };
+    const BaScratch sc = {reinterpret_cast<RsPose *>(b + L.cam), f64(L.pt), f64(L.U), f64(L.V), f64(L.W), f64(L.vec), f64(L.y),
+                          f64(L.tcost), f64(L.dots), f64(L.scal), reinterpret_cast<unsigned long long *>(b + L.rowmap), u32(L.idx),
+                          u32(L.head), u32(L.oflag), u32(L.tflag), u32(L.words)};
+    const auto blocks = [](uint64_t items, uint64_t per_block) {
+        const uint64_t want = (items + per_block - 1) / per_block;
+        return dim3((unsigned)(want < 1 ? 1 : want < kMaxBlocks ? want : kMaxBlocks));
+    };
+    const dim3 threads(kThreads), per_image(n_images), by_image((n_images + kThreads - 1) / kThreads);
+    const dim3 by_track = blocks(track_capacity, kThreads / G);
+    const uint64_t most = n_rows > n_images ? n_rows : n_images;
+    hipLaunchKernelGGL(ba_init, blocks(most > 16 ? most : 16, kThreads), threads, 0, stream, in, poses, camera_fixed, lambda0, sc);
+    hipLaunchKernelGGL(ba_setup_tracks, by_track, threads, 0, stream, in, points, obs_state, sc);
+    hipLaunchKernelGGL(ba_setup_images, per_image, threads, 0, stream, in, sc);
+    for (unsigned it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL(ba_track_lin, by_track, threads, 0, stream, in, thr2, sc);
+        hipLaunchKernelGGL(ba_image_lin, per_image, threads, 0, stream, in, thr2, sc);
+        hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeStart, tol2, it, sc, trace);
+        for (unsigned s = 0; s < cg_iterations; ++s) {
+            hipLaunchKernelGGL(ba_track_apply, by_track, threads, 0, stream, in, sc);
+            hipLaunchKernelGGL(ba_image_apply, per_image, threads, 0, stream, in, sc);
+            hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeAlpha, tol2, it, sc, trace);
+            hipLaunchKernelGGL(ba_cg_update, by_image, threads, 0, stream, in, sc);
+            hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeBeta, tol2, it, sc, trace);
+        }
+        hipLaunchKernelGGL(ba_cam_step, by_image, threads, 0, stream, in, sc);
+        hipLaunchKernelGGL(ba_track_step, by_track, threads, 0, stream, in, thr2, sc);
+        hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeAccept, tol2, it, sc, trace);
+    }
+    hipLaunchKernelGGL(ba_final_images, by_image, threads, 0, stream, in, poses, sc, poses_out);
+    hipLaunchKernelGGL(ba_final_tracks, by_track, threads, 0, stream, in, points, thr2, sc, poses_out, points_out, obs_state_out, counts);
+}
+
+}  // namespace lfmkd

@@ -370,6 +370,17 @@ void launch_resect_cameras(void *scratch, const float *kps, const uint64_t *imag
                            const float *intrinsics, const float *poses, double thr2, double cmin, unsigned n_samples,
                            unsigned min_inliers, unsigned rounds, unsigned seed, bool all, float *poses_out, unsigned *stats,
                            float *err, unsigned *row_state, hipStream_t stream);
+// bundle adjustment (csrc/mkd_bundle.hip, lf_mkd_bundle_adjust_device): bundle_launches(..) launches over `scratch` of
+// bundle_scratch_bytes(..) bytes, 16-byte aligned.  thr2 = the squared reprojection threshold and tol2 = the squared CG
+// tolerance, both formed by the host in double.  poses_out may be poses, points_out points, obs_state_out obs_state.
+uint64_t bundle_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity);
+unsigned bundle_launches(unsigned iterations, unsigned cg_iterations);
+void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
+                          const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row, const unsigned *obs_image,
+                          uint64_t obs_capacity, const unsigned *table_counts, const float *points, const float *intrinsics,
+                          const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0,
+                          unsigned iterations, unsigned cg_iterations, double tol2, float *poses_out, float *points_out,
+                          unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

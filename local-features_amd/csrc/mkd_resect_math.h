@@ -37,10 +37,14 @@ constexpr unsigned kRsNone = 0xFFFFFFFFu;
 constexpr int kRsTerms = 27;                // the refit's sums: 21 of J^T J's upper triangle, row by row, then 6 of J^T e
 enum : unsigned { kRsPose = 0, kRsNotCandidate = 1, kRsNoCandidate = 2, kRsFewInliers = 3 };
 
-// a correspondence: the keypoint and its track's point
-struct RsCorr {
-    float x, y, X, Y, Z;
+// a correspondence: the keypoint and its track's point (T = float as the arrays hold it; bundle adjustment's f64 state reads
+// the same functions with T = double, where the widening double(c.X) is the identity)
+template <typename T>
+struct RsCorrT {
+    float x, y;
+    T X, Y, Z;
 };
+using RsCorr = RsCorrT<float>;
 struct RsPose {
     double R[9], t[3];
 };
@@ -287,7 +291,8 @@ __host__ __device__ __forceinline__ bool rs_candidate_pose(const RsCorr (&s)[3],
 }
 
 // Step 4 for an f64 pose, tri_error2's operations: p = R X + t (each row summed left to right); false if not in front.
-__host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const float *K, const RsCorr &c, double &e2) {
+template <typename T>
+__host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const float *K, const RsCorrT<T> &c, double &e2) {
     double p[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) p[r] = P.R[3 * r] * double(c.X) + P.R[3 * r + 1] * double(c.Y) + P.R[3 * r + 2] * double(c.Z) + P.t[r];
@@ -296,12 +301,14 @@ __host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const float 
     e2 = ex * ex + ey * ey;
     return p[2] > 0.0;
 }
-__host__ __device__ __forceinline__ bool rs_inlier(const RsPose &P, const float *K, const RsCorr &c, double thr2, double &e2) {
+template <typename T>
+__host__ __device__ __forceinline__ bool rs_inlier(const RsPose &P, const float *K, const RsCorrT<T> &c, double thr2, double &e2) {
     const bool front = rs_error2(P, K, c, e2);
     return front && e2 <= thr2;
 }
 // the MSAC term of a correspondence: min(e^2, thr2), thr2 for a point not in front (or a NaN)
-__host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const float *K, const RsCorr &c, double thr2) {
+template <typename T>
+__host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const float *K, const RsCorrT<T> &c, double thr2) {
     double e2;
     return rs_inlier(P, K, c, thr2, e2) ? e2 : thr2;
 }
@@ -309,7 +316,13 @@ __host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const float 
 // Step 5: the 27 values an inlier adds to the normal equations of the step (w, dt), R' = C(w) R, t' = t + dt.  With q = R X,
 // p = q + t, a = fx / p_z, b = fy / p_z: d e_x / d p = (a, 0, -a p_x / p_z), d e_y / d p = (0, b, -b p_y / p_z), d p / d w =
 // -2 [q]x (C(w) = I + 2 [w]x + O(w^2)), d p / d dt = I.
-__host__ __device__ __forceinline__ void rs_gn_terms(const RsPose &P, const float *K, const RsCorr &c, double *w) {
+// The rows themselves (bundle adjustment, mkd_bundle_math.h, needs them beside the point's): Jx, Jy, the residual and the
+// factors a, b, gx, gy of d e / d p.
+struct RsRows {
+    double Jx[6], Jy[6], ex, ey, a, b, gx, gy;
+};
+template <typename T>
+__host__ __device__ __forceinline__ void rs_gn_rows(const RsPose &P, const float *K, const RsCorrT<T> &c, RsRows &o) {
     double q[3], p[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -317,18 +330,31 @@ __host__ __device__ __forceinline__ void rs_gn_terms(const RsPose &P, const floa
         p[r] = q[r] + P.t[r];
     }
     const double px = p[0] / p[2], py = p[1] / p[2];
-    const double ex = double(K[0]) * px + double(K[2]) - double(c.x), ey = double(K[1]) * py + double(K[3]) - double(c.y);
+    o.ex = double(K[0]) * px + double(K[2]) - double(c.x);
+    o.ey = double(K[1]) * py + double(K[3]) - double(c.y);
     const double a = double(K[0]) / p[2], b = double(K[1]) / p[2];
     const double gx = 0.0 - a * px, gy = 0.0 - b * py;
     const double Jx[6] = {2.0 * (gx * q[1]), 2.0 * (a * q[2] - gx * q[0]), 2.0 * (0.0 - a * q[1]), a, 0.0, gx};
     const double Jy[6] = {2.0 * (gy * q[1] - b * q[2]), 2.0 * (0.0 - gy * q[0]), 2.0 * (b * q[0]), 0.0, b, gy};
+#pragma unroll
+    for (int i = 0; i < 6; ++i) o.Jx[i] = Jx[i], o.Jy[i] = Jy[i];
+    o.a = a, o.b = b, o.gx = gx, o.gy = gy;
+}
+// the 27 values of two rows and their residual: J^T J's upper triangle row by row, then J^T e
+__host__ __device__ __forceinline__ void rs_gn_products(const RsRows &r, double *w) {
     int n = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i)
 #pragma unroll
-        for (int j = i; j < 6; ++j) w[n++] = Jx[i] * Jx[j] + Jy[i] * Jy[j];
+        for (int j = i; j < 6; ++j) w[n++] = r.Jx[i] * r.Jx[j] + r.Jy[i] * r.Jy[j];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) w[21 + i] = Jx[i] * ex + Jy[i] * ey;
+    for (int i = 0; i < 6; ++i) w[21 + i] = r.Jx[i] * r.ex + r.Jy[i] * r.ey;
+}
+template <typename T>
+__host__ __device__ __forceinline__ void rs_gn_terms(const RsPose &P, const float *K, const RsCorrT<T> &c, double *w) {
+    RsRows r;
+    rs_gn_rows(P, K, c, r);
+    rs_gn_products(r, w);
 }
 
 // Solves H d = g for the symmetric 6x6 H of the 27 sums by Cholesky (d returned in x); false at the first pivot that is not

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -48,6 +48,9 @@ descriptor row is copied for it.
   --triangulate) the other images registered from     place on the pose array -- P3P samples over the keypoints an image owns in
   the points and the points triangulated again       tracks with a point, 512 samples, at least 12 inliers at 4 px -- and then
                                                      triangulate_tracks again, nothing read back in between
+  with --bundle ITERS (1 .. 64; needs --pose; implies LocalFeatures.bundle_adjust (lf_mkd_bundle_adjust_device) after the rounds, in
+  --triangulate) poses and points refined jointly     place: ITERS Levenberg-Marquardt iterations of 10 CG steps over the
+                                                     triangulation's inlier observations, the images posed before the rounds held
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
@@ -58,7 +61,7 @@ them kept a verified match, and the track lines once more for the expanded fores
 the direction of t, the links in front of both cameras out of the edge's links, those with at least 1 degree of parallax and
 s2/s1 of the essential matrix (1 for a true one); with --triangulate the tracks, the registered images, the points, the inlier
 observations and the median parallax; with --register per round the images registered so far, those the round added and the
-points.  Nothing is read back before those counts: the
+points; with --bundle the counts, one line per iteration of the trace and the rms reprojection error before and after.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
 keypoints bounds that side's layout.
 
@@ -110,7 +113,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0, bundle=0):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -144,7 +147,9 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     implies `triangulate`, those after ROUNDS rounds of resect_cameras in place on tri_poses and triangulate_tracks, and
     register_rounds = per round (the resection's stats [n,4], the triangulation's stats [tracks,4])); `triangulate` is an [n,12] array of
     poses, or True: the edge with the most links with parallax is the initial pair, [I | 0] and its [R | t], and every other
-    image stays all zero, which says "not registered"; without, those five are None."""
+    image stays all zero, which says "not registered"; without, those five are None.  `bundle` = ITERS > 0 (needs `triangulate`)
+    then runs LocalFeatures.bundle_adjust in place on tri_poses and tri_points and adds bundle_trace [ITERS,8], bundle_counts [4],
+    bundle_obs_state and bundle_rms [2] (before, after); None without."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -199,7 +204,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             p_R, p_t, p_stats, p_sigma, p_points = feats.two_view_pose(model.contiguous(), intr, kps, (ea, eb), (l_off, l_a, l_b))
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
-        if register and triangulate is None:
+        if (register or bundle) and triangulate is None:
             triangulate = True
         if tracks or table or expand or triangulate is not None:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
@@ -241,6 +246,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
         tri_poses = tri_points = tri_stats = tri_err = tri_state = None
         register_rounds = [] if register else None       # (None without `register`, like every output that was not asked for)
+        bundle_trace = bundle_counts = bundle_state = bundle_rms = None
         if triangulate is not None and triangulate is not False:
             if pose is None:
                 raise RuntimeError("match_collection: triangulate needs pose (the cameras' intrinsics)")
@@ -255,6 +261,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             else:
                 tri_poses = torch.as_tensor(np.ascontiguousarray(triangulate, np.float32).reshape(n, 12), device=dev)
             tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr, tri_poses)
+            held = (tri_poses[:, :9] != 0).any(1).to(torch.int32)
             for _ in range(register or 0):
                 # the images without a pose from the points there are, in place; then the points under every pose there is
                 _, r_stats, _, _ = feats.resect_cameras(kps, o, t_row_track, tri_points, t_counts, intr, tri_poses, seed=seed,
@@ -262,7 +269,17 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr,
                                                                                      tri_poses)
                 register_rounds.append((r_stats, tri_stats))
-    return dict(register_rounds=register_rounds, tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
+            if bundle:
+                # poses and points jointly, in place; the images that had a pose before the rounds hold theirs (the gauge)
+                before = (tri_poses.clone(), tri_points.clone())
+                tri_poses, tri_points, bundle_state, bundle_trace, bundle_counts = feats.bundle_adjust(
+                    kps, o, (t_off, t_rows, t_img, t_counts), tri_points, intr, tri_poses, obs_state=tri_state, camera_fixed=held,
+                    iterations=bundle, out_poses=tri_poses, out_points=tri_points)
+                active = bundle_state >= 1
+                bundle_rms = torch.stack([reprojection_rms(kps, t_off, t_rows, t_img, intr, P, X, active) for P, X in
+                                          (before, (tri_poses, tri_points))])
+    return dict(bundle_trace=bundle_trace, bundle_counts=bundle_counts, bundle_obs_state=bundle_state, bundle_rms=bundle_rms,
+                register_rounds=register_rounds, tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
                 edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
                 table_offsets=t_off, table_rows=t_rows, table_images=t_img, table_row_track=t_row_track, table_counts=t_counts,
@@ -272,6 +289,36 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 expand_edge_a=x_ea, expand_edge_b=x_eb, expand_counts=x_counts, expand_layout_a=x_la, expand_verified=x_ver,
                 expand_per_edge=x_per_edge, first_round=first, pose_R=p_R, pose_t=p_t, pose_stats=p_stats,
                 pose_sigma=p_sigma, pose_points=p_points)
+
+
+def reprojection_rms(kps, t_off, t_rows, t_img, intr, poses, points, active, max_reproj_px=4.0):
+    """the rms reprojection error (px) of the observations in `active` that are inliers at max_reproj_px, on the device"""
+    import torch
+    n_obs = t_rows.numel()
+    track = torch.searchsorted(t_off[1:].contiguous(), torch.arange(n_obs, device=t_off.device), right=True).clamp_(max=points.shape[0] - 1)
+    at = torch.nonzero(active).reshape(-1)
+    img, row, X = t_img[at].long(), t_rows[at].long(), points[track[at], :3].double()
+    P = poses[img].double()
+    p = torch.einsum("nij,nj->ni", P[:, :9].reshape(-1, 3, 3), X) + P[:, 9:]
+    K = intr[img].double()
+    e = K[:, :2] * p[:, :2] / p[:, 2:3] + K[:, 2:] - kps[row, :2].double()
+    e2 = (e * e).sum(1)
+    inl = (p[:, 2] > 0) & (e2 <= max_reproj_px * max_reproj_px)
+    return torch.sqrt((e2 * inl).sum() / inl.sum().clamp(min=1))
+
+
+def bundle_lines(out):
+    """one line per Levenberg-Marquardt iteration of `bundle`, then the rms before and after"""
+    if out["bundle_trace"] is None:
+        return []
+    free_c, free_p, active, accepted = out["bundle_counts"].cpu().tolist()
+    lines = [f"{free_c} free cameras, {free_p} free points, {active} active observations, {accepted} steps accepted"]
+    for k, (cost, new, lam, ok, steps, inl, hc, hp) in enumerate(out["bundle_trace"].cpu().tolist()):
+        lines.append(f"iteration {k + 1}: cost {cost:.1f} -> {new:.1f} at lambda {lam:.2e}, {'accepted' if ok else 'rejected'}, "
+                     f"{int(steps)} CG steps, {int(inl)} inliers, {int(hc)} cameras and {int(hp)} points held")
+    before, after = out["bundle_rms"].cpu().tolist()
+    lines.append(f"rms reprojection error {before:.3f} px -> {after:.3f} px")
+    return lines
 
 
 def register_lines(out):
@@ -303,7 +350,7 @@ def parse_pose(text):
 def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
-    expand, min_shared, pose, triangulate, register = None, 8, None, None, 0
+    expand, min_shared, pose, triangulate, register, bundle = None, 8, None, None, 0, 0
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -331,6 +378,10 @@ def main():
             tracks = table = True
             register = int(args.pop(0))
             triangulate = True if triangulate is None else triangulate
+        elif a == "--bundle" and args and args[0].isdigit() and 0 < int(args[0]) <= 64:
+            tracks = table = True
+            bundle = int(args.pop(0))
+            triangulate = True if triangulate is None else triangulate
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -341,10 +392,10 @@ def main():
         else:
             paths.append(a)
     if len(paths) < 2 or (triangulate is not None and pose is None) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images; --triangulate and --register need --pose)", file=sys.stderr)
+              "number of images; --triangulate, --register and --bundle need --pose)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -353,7 +404,7 @@ def main():
     if pose is not None and pose[1] is None:                    # the principal point: the middle of the frame
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register, bundle=bundle)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -408,6 +459,8 @@ def main():
               f"{int(st[have, 1].sum())} inlier observations, median parallax {median:.2f} deg")
         for line in register_lines(out):
             print("Registered, " + line)
+        for line in bundle_lines(out):
+            print("Bundle adjustment, " + line)
     if expand:
         proposed = out["expand_counts"].cpu().tolist()[0]
         kept = int((out["expand_per_edge"][:proposed, 1] > 0).sum())

@@ -1007,6 +1007,74 @@ class LocalFeatures:
                                                   min_inliers, rounds, seed, RESECT_ALL if resect_all else 0, s.cuda_stream)
         return out, st, er, rs
 
+    def bundle_adjust(self, kps, offsets, table, points, intrinsics, poses, obs_state=None, camera_fixed=None, max_reproj_px=4.0,
+                      lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, out_poses=None, out_points=None,
+                      obs_state_out=True, stream=None):
+        """Bundle adjustment (lf_mkd_bundle_adjust_device): Levenberg-Marquardt on the reprojection error over every free
+        camera (registered, and not marked in camera_fixed) and every free point (a track with an active observation), the
+        reduced camera system solved by `cg_iterations` preconditioned conjugate-gradient steps per iteration
+        (include/lf_mkd.h states the algorithm).  kps [rows, 5] float32 is the pool and offsets [n_images + 1] int64 its image
+        offsets; table = (offsets, rows, images, counts) as track_table returned them (its 5-tuple passes as it is); points
+        [track_capacity, 4] float32 are triangulate_tracks' points; intrinsics [n_images, 4] and poses [n_images, 12] float32
+        as the calls before it take them; obs_state [obs_capacity] int32 are triangulate_tracks' states (only its inliers, 2,
+        are then used) and camera_fixed [n_images] int32 marks the poses to hold (hold two to fix the gauge).  out_poses /
+        out_points name the tensors to write, `poses` / `points` themselves for a call in place (default: new tensors).
+        Returns device tensors (poses [n_images, 12] float32, points [track_capacity, 4] float32, obs_state [obs_capacity] int32
+        (0 inactive, 1 active, 2 inlier of the result; -1 outside every track) or None, trace [iterations, 8] float64 = cost,
+        the candidate's cost, lambda, accepted, CG steps, inliers, held cameras, held points; counts [4] int32 = free cameras,
+        free points, active observations, accepted steps).  Nothing is read back: asynchronous on `stream` (default: torch's
+        current stream on the handle's device), capturable once warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if len(table) == 5:
+            t_off, rows, images, _, counts = table
+        else:
+            t_off, rows, images, counts = table
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (ok(t_off, torch.int64) and t_off.dim() == 1 and t_off.numel() >= 1 and ok(rows, torch.int32)
+                    and images is not None and ok(images, torch.int32) and rows.numel() == images.numel()
+                    and ok(counts, torch.int32) and counts.numel() >= 2):
+                raise RuntimeError("bundle_adjust: table must be (offsets int64, rows int32, images int32, counts int32) "
+                                   "contiguous device tensors as track_table returned them with image_offsets")
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("bundle_adjust: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1):
+                raise RuntimeError("bundle_adjust: offsets must be a contiguous int64 [n_images + 1] device tensor")
+            n_images, tcap, ocap = offsets.numel() - 1, t_off.numel() - 1, rows.numel()
+            if not (ok(points, torch.float32) and points.numel() == 4 * tcap):
+                raise RuntimeError("bundle_adjust: points must be a contiguous float32 [track_capacity, 4] device tensor")
+            if not (ok(intrinsics, torch.float32) and intrinsics.numel() == 4 * n_images and ok(poses, torch.float32)
+                    and poses.numel() == 12 * n_images):
+                raise RuntimeError("bundle_adjust: intrinsics must be float32 [n_images, 4] and poses float32 [n_images, 12] "
+                                   "contiguous device tensors")
+            if obs_state is not None and not (ok(obs_state, torch.int32) and obs_state.numel() == ocap):
+                raise RuntimeError("bundle_adjust: obs_state must be a contiguous int32 [obs_capacity] device tensor")
+            if camera_fixed is not None and not (ok(camera_fixed, torch.int32) and camera_fixed.numel() == n_images):
+                raise RuntimeError("bundle_adjust: camera_fixed must be a contiguous int32 [n_images] device tensor")
+            if out_poses is None:
+                out_poses = torch.empty((n_images, 12), dtype=torch.float32, device=dev)
+            elif not (ok(out_poses, torch.float32) and out_poses.numel() == 12 * n_images):
+                raise RuntimeError("bundle_adjust: out_poses must be a contiguous float32 [n_images, 12] device tensor")
+            if out_points is None:
+                out_points = torch.empty((tcap, 4), dtype=torch.float32, device=dev)
+            elif not (ok(out_points, torch.float32) and out_points.numel() == 4 * tcap):
+                raise RuntimeError("bundle_adjust: out_points must be a contiguous float32 [track_capacity, 4] device tensor")
+            so = torch.full((ocap,), -1, dtype=torch.int32, device=dev) if obs_state_out else None
+            trace = torch.zeros((iterations, 8), dtype=torch.float64, device=dev)
+            cnt = torch.zeros((4,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.bundle_adjust_device(ptr(kps), offsets.data_ptr(), n_images, kps.shape[0], t_off.data_ptr(), tcap,
+                                                 ptr(rows), ptr(images), ocap, counts.data_ptr(), ptr(points), ptr(intrinsics),
+                                                 ptr(poses), ptr(out_poses), ptr(out_points), trace.data_ptr(), cnt.data_ptr(),
+                                                 d_obs_state=ptr(obs_state), d_camera_fixed=ptr(camera_fixed),
+                                                 d_obs_state_out=ptr(so), max_reproj_px=max_reproj_px, lambda0=lambda0,
+                                                 iterations=iterations, cg_iterations=cg_iterations, cg_tol=cg_tol,
+                                                 stream=s.cuda_stream)
+        return out_poses, out_points, so, trace, cnt
+
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):
         """match_guided_batch over 8-bit descriptors (lf_mkd_match_q8_guided_pairs_device: one launch, three with `mutual`):

@@ -51,6 +51,7 @@ SYMBOLS = (
     "lf_mkd_two_view_pose", "lf_mkd_two_view_pose_device",
     "lf_mkd_triangulate_tracks", "lf_mkd_triangulate_tracks_device",
     "lf_mkd_resect_camera", "lf_mkd_resect_cameras_device",
+    "lf_mkd_bundle_adjust", "lf_mkd_bundle_adjust_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -188,6 +189,10 @@ def load_library():
                                                u32, u32, u32, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_resect_camera.argtypes = [vp, vp, u64, vp, vp, u64, vp, ctypes.c_float, ctypes.c_float, u32, u32, u32, u32, u32, vp,
                                        vp, vp, vp]
+    L.lf_mkd_bundle_adjust_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.c_float,
+                                              ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_bundle_adjust.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, ctypes.c_float,
+                                       ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -669,6 +674,41 @@ class MkdHandle:
                     "lf_mkd_resect_camera")
         return pose, st, er, rs[:len(k)] if row_state else None
 
+    def bundle_adjust(self, kps, image_offsets, track_offsets, obs_row, obs_image, points, intrinsics, poses, obs_state=None,
+                      camera_fixed=None, max_reproj_px=4.0, lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, flags=0,
+                      obs_state_out=True):
+        """lf_mkd_bundle_adjust: kps [rows,5] f32, image_offsets uint64 [n_images + 1], the track table (track_offsets uint64
+        [n_tracks + 1], obs_row int32 / obs_image uint32 [n_obs]), points [n_tracks,4] f32, intrinsics [n_images,4] f32, poses
+        [n_images,12] f32, optional obs_state uint32 [n_obs] (the triangulation call's) and camera_fixed uint32 [n_images]
+        (non-zero: the pose is held) -> (poses [n_images,12] f32, points [n_tracks,4] f32, obs_state uint32 [n_obs] or None,
+        trace float64 [iterations,8] = cost, cost', lambda, accepted, CG steps, inliers, held cameras, held points; counts
+        uint32 [4] = free cameras, free points, active observations, accepted steps)."""
+        k = np.ascontiguousarray(kps, np.float32).reshape(-1, 5)
+        ioff = np.ascontiguousarray(image_offsets, np.uint64).reshape(-1)
+        toff = np.ascontiguousarray(track_offsets, np.uint64).reshape(-1)
+        row, img = np.ascontiguousarray(obs_row, np.int32).reshape(-1), np.ascontiguousarray(obs_image, np.uint32).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        K = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        n_images, n_tracks, n_obs = len(K), len(pts), len(row)
+        st = None if obs_state is None else np.ascontiguousarray(obs_state, np.uint32).reshape(-1)
+        fx = None if camera_fixed is None else np.ascontiguousarray(camera_fixed, np.uint32).reshape(-1)
+        if (len(ioff) != n_images + 1 or len(toff) != n_tracks + 1 or len(img) != n_obs or len(P) != n_images or
+                (st is not None and len(st) != n_obs) or (fx is not None and len(fx) != n_images)):
+            raise RuntimeError("bundle_adjust: image_offsets needs n_images + 1 entries, track_offsets n_tracks + 1, obs_row, "
+                               "obs_image and obs_state one entry per observation, intrinsics, poses and camera_fixed one row per "
+                               "image")
+        po, xo = np.zeros((max(n_images, 1), 12), np.float32), np.zeros((max(n_tracks, 1), 4), np.float32)
+        so = np.zeros(max(n_obs, 1), np.uint32) if obs_state_out else None
+        trace, counts = np.zeros((max(iterations, 1), 8), np.float64), np.zeros(4, np.uint32)
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_bundle_adjust(self._h, at(k), ioff.ctypes.data, n_images, len(k), toff.ctypes.data, n_tracks,
+                                                at(row), at(img), n_obs, at(pts), at(K), at(P), at(st), at(fx), max_reproj_px, lambda0,
+                                                iterations, cg_iterations, cg_tol, flags, po.ctypes.data, xo.ctypes.data,
+                                                so.ctypes.data if obs_state_out else None, trace.ctypes.data, counts.ctypes.data),
+                    "lf_mkd_bundle_adjust")
+        return po[:n_images], xo[:n_tracks], so[:n_obs] if obs_state_out else None, trace, counts
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -952,6 +992,21 @@ class MkdHandle:
             self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_row_track, d_points, track_capacity, d_table_counts,
             d_intrinsics, d_poses, max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed & 0xFFFFFFFF, flags,
             d_poses_out, d_stats, d_err, d_row_state, s), "lf_mkd_resect_cameras_device")
+
+    def bundle_adjust_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row,
+                             d_obs_image, obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_poses_out, d_points_out,
+                             d_trace, d_counts, d_obs_state=None, d_camera_fixed=None, d_obs_state_out=None, max_reproj_px=4.0,
+                             lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, flags=0, stream=None):
+        """lf_mkd_bundle_adjust_device: Levenberg-Marquardt over the free cameras of d_poses [n_images][12] and the free points
+        of d_points [track_capacity][4] on the track table's observations, the reduced camera system by preconditioned
+        conjugate gradients -- d_poses_out (may be d_poses), d_points_out (may be d_points), d_trace f64 [iterations][8],
+        d_counts uint32 [4], d_obs_state_out uint32 [obs_capacity] (nullable); d_obs_state and d_camera_fixed uint32
+        [n_images] are optional inputs (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_bundle_adjust_device(
+            self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image,
+            obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_obs_state, d_camera_fixed, max_reproj_px, lambda0,
+            iterations, cg_iterations, cg_tol, flags, d_poses_out, d_points_out, d_obs_state_out, d_trace, d_counts, s),
+            "lf_mkd_bundle_adjust_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
