@@ -360,6 +360,29 @@ extern "C" {
                                 lambda0: f32, iterations: u32, cg_iterations: u32, cg_tol: f32, flags: u32,
                                 poses_out: *mut f32, points_out: *mut f32, obs_state_out: *mut u32, trace: *mut f64,
                                 counts: *mut u32) -> c_int;
+    // the same with the intrinsics of the images that share a lens refined: d_camera_group [n_images] (nullable: one group),
+    // refine = LF_MKD_BA_REFINE_FOCAL (1) | LF_MKD_BA_REFINE_PRINCIPAL (2); intrinsics_out [n_images][4] (may be d_intrinsics),
+    // an optional group_out [n_groups][3] = (s, dx, dy), trace f64 [iterations][9], counts [5]
+    pub fn lf_mkd_bundle_adjust_intrinsics_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, d_image_offsets: *const u64,
+                                                  n_images: u32, n_rows_total: u64, d_track_offsets: *const u64,
+                                                  track_capacity: u64, d_obs_row: *const i32, d_obs_image: *const u32,
+                                                  obs_capacity: u64, d_table_counts: *const u32, d_points: *const f32,
+                                                  d_intrinsics: *const f32, d_poses: *const f32, d_obs_state: *const u32,
+                                                  d_camera_fixed: *const u32, d_camera_group: *const u32, n_groups: u32,
+                                                  refine: u32, max_reproj_px: f32, lambda0: f32, iterations: u32,
+                                                  cg_iterations: u32, cg_tol: f32, flags: u32, d_poses_out: *mut f32,
+                                                  d_points_out: *mut f32, d_intrinsics_out: *mut f32, d_group_out: *mut f32,
+                                                  d_obs_state_out: *mut u32, d_trace: *mut f64, d_counts: *mut u32,
+                                                  stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_bundle_adjust_intrinsics(h: *mut lf_mkd, kps: *const lf_mkd_keypoint, image_offsets: *const u64, n_images: u32,
+                                           n_rows_total: u64, track_offsets: *const u64, n_tracks: u64, obs_row: *const i32,
+                                           obs_image: *const u32, n_obs: u64, points: *const f32, intrinsics: *const f32,
+                                           poses: *const f32, obs_state: *const u32, camera_fixed: *const u32,
+                                           camera_group: *const u32, n_groups: u32, refine: u32, max_reproj_px: f32,
+                                           lambda0: f32, iterations: u32, cg_iterations: u32, cg_tol: f32, flags: u32,
+                                           poses_out: *mut f32, points_out: *mut f32, intrinsics_out: *mut f32,
+                                           group_out: *mut f32, obs_state_out: *mut u32, trace: *mut f64,
+                                           counts: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -100,6 +100,9 @@ pub const SELECT_MAX_K: u32 = 32;
 pub const COVIS_ACCUMULATE: u32 = 1;
 /// `flags` of `lf_mkd_resect_cameras_device` (`include/lf_mkd.h`, `LF_MKD_RESECT_ALL`): registered images are resected too.
 pub const RESECT_ALL: u32 = 1;
+/// `refine` of `lf_mkd_bundle_adjust_intrinsics` (`include/lf_mkd.h`, `LF_MKD_BA_REFINE_FOCAL`, `LF_MKD_BA_REFINE_PRINCIPAL`).
+pub const BA_REFINE_FOCAL: u32 = 1;
+pub const BA_REFINE_PRINCIPAL: u32 = 2;
 
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
@@ -704,6 +707,53 @@ impl LocalFeaturesHip {
         points_out.truncate(n_tracks);
         state.truncate(n_obs);
         Ok((poses_out, points_out, state, trace, counts))
+    }
+
+    /// Self-calibrating bundle adjustment (`lf_mkd_bundle_adjust_intrinsics`): `bundle_adjust` with the intrinsics of the images
+    /// that share a lens refined beside the poses and the points.  `camera_group` names the lens of every image (`None`: one
+    /// lens; an id >= `n_groups`: that image's intrinsics stay); `refine` is `BA_REFINE_FOCAL | BA_REFINE_PRINCIPAL`: a group's
+    /// focal lengths are scaled by one factor s, its principal points shifted by one (dx, dy).
+    /// Returns (poses, points, intrinsics, the groups' (s, dx, dy), the states, the trace: `bundle_adjust`'s eight and the held
+    /// groups; `bundle_adjust`'s four counts and the free groups).
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn bundle_adjust_intrinsics(&mut self, kps: &[ffi::lf_mkd_keypoint], image_offsets: &[u64], track_offsets: &[u64],
+                                    obs_row: &[i32], obs_image: &[u32], points: &[[f32; 4]], intrinsics: &[[f32; 4]],
+                                    poses: &[[f32; 12]], obs_state: Option<&[u32]>, camera_fixed: Option<&[u32]>,
+                                    camera_group: Option<&[u32]>, n_groups: u32, refine: u32, max_reproj_px: f32, lambda0: f32,
+                                    iterations: u32, cg_iterations: u32, cg_tol: f32)
+                                    -> Result<(Vec<[f32; 12]>, Vec<[f32; 4]>, Vec<[f32; 4]>, Vec<[f32; 3]>, Vec<u32>, Vec<[f64; 9]>,
+                                               [u32; 5]), Error> {
+        let (n_images, n_tracks, n_obs) = (intrinsics.len(), points.len(), obs_row.len());
+        if image_offsets.len() != n_images + 1 || track_offsets.len() != n_tracks + 1 || obs_image.len() != n_obs
+            || poses.len() != n_images || obs_state.map_or(false, |s| s.len() != n_obs)
+            || camera_fixed.map_or(false, |f| f.len() != n_images) || camera_group.map_or(false, |g| g.len() != n_images) {
+            return Err(Error::BadArgument("bundle_adjust_intrinsics: image_offsets needs n_images + 1 entries, track_offsets                                            n_tracks + 1, obs_row, obs_image and obs_state one entry per observation, intrinsics,                                            poses, camera_fixed and camera_group one row per image".into()));
+        }
+        let mut poses_out = vec![[0f32; 12]; n_images.max(1)];
+        let mut points_out = vec![[0f32; 4]; n_tracks.max(1)];
+        let mut intrinsics_out = vec![[0f32; 4]; n_images.max(1)];
+        let mut groups = vec![[0f32; 3]; (n_groups as usize).max(1)];
+        let mut state = vec![0u32; n_obs.max(1)];
+        let mut trace = vec![[0f64; 9]; iterations.max(1) as usize];
+        let mut counts = [0u32; 5];
+        // SAFETY: host arrays sized as declared; the counts bound what is read, the outputs have their stated sizes
+        unsafe {
+            check(self.h, ffi::lf_mkd_bundle_adjust_intrinsics(
+                self.h, kps.as_ptr(), image_offsets.as_ptr(), n_images as u32, kps.len() as u64, track_offsets.as_ptr(),
+                n_tracks as u64, obs_row.as_ptr(), obs_image.as_ptr(), n_obs as u64, points.as_ptr() as *const f32,
+                intrinsics.as_ptr() as *const f32, poses.as_ptr() as *const f32,
+                obs_state.map_or(std::ptr::null(), |s| s.as_ptr()), camera_fixed.map_or(std::ptr::null(), |f| f.as_ptr()),
+                camera_group.map_or(std::ptr::null(), |g| g.as_ptr()), n_groups, refine, max_reproj_px, lambda0, iterations,
+                cg_iterations, cg_tol, 0, poses_out.as_mut_ptr() as *mut f32, points_out.as_mut_ptr() as *mut f32,
+                intrinsics_out.as_mut_ptr() as *mut f32, groups.as_mut_ptr() as *mut f32, state.as_mut_ptr(),
+                trace.as_mut_ptr() as *mut f64, counts.as_mut_ptr()))?;
+        }
+        poses_out.truncate(n_images);
+        points_out.truncate(n_tracks);
+        intrinsics_out.truncate(n_images);
+        groups.truncate(n_groups as usize);
+        state.truncate(n_obs);
+        Ok((poses_out, points_out, intrinsics_out, groups, state, trace, counts))
     }
 
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches

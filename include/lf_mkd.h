@@ -1407,6 +1407,79 @@ int lf_mkd_bundle_adjust(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *
                          float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
                          float *poses_out, float *points_out, uint32_t *obs_state_out, double *trace, uint32_t *counts);
 
+/* lf_mkd_bundle_adjust_intrinsics_device is lf_mkd_bundle_adjust_device with the intrinsics of the images that share a lens
+ * REFINED beside the poses and the points (self-calibration).  Every input of that call in its order up to d_camera_fixed,
+ * then d_camera_group uint32 [n_images] (the lens an image was taken with; null: every image is in group 0 and n_groups must
+ * be 1; an id >= n_groups: the image's intrinsics are constant), n_groups, and refine = LF_MKD_BA_REFINE_FOCAL |
+ * LF_MKD_BA_REFINE_PRINCIPAL.  Group g has three parameters (s, dx, dy), (1, 0, 0) at the start; image i of the group has
+ * fx = s fx0_i, fy = s fy0_i, cx = cx0_i + dx, cy = cy0_i + dy (fx0 .. the f32 input widened), so the aspect ratio and the
+ * images' differences are kept.  A parameter refine does not name stays at its start.
+ * Outputs: the sibling's, with d_trace f64 [iterations][9] and d_counts uint32 [5], and d_intrinsics_out [n_images][4] (may be
+ * d_intrinsics), optional d_group_out [n_groups][3].
+ * The algorithm is the sibling's seven steps with these additions, exactly (csrc/mkd_bundle_math.h):
+ *   2. A group is FREE iff refine != 0 and one of its images is usable and has an active row (a camera held by d_camera_fixed
+ *      informs its group all the same: every camera fixed is calibration under known poses).  The intrinsics an observation
+ *      is read under are f64: for an image of a free group the products above of the group's state, else the input widened.
+ *   3. An inlier's group rows are J_k = d e / d (s, dx, dy) = ((fx0 u, 1, 0), (fy0 v, 0, 1)), (u, v) = (p_x / p_z, p_y / p_z),
+ *      a column refine does not name being zero.  Per usable image of a free group, in the 256-slot order over the image's
+ *      list: U_kk = J_k^T J_k (6 distinct) and g_k = J_k^T e (3), the inlier count, and (free cameras) U_ck = J_c^T J_k
+ *      (18); per group those nine and the count are then summed over the group's usable images in the 256-slot order over
+ *      the image id (slot = id mod 256).
+ *   4. U_kk gets lambda max(d, 1e-6) on its diagonal, then the rows and columns of the parameters not refined are replaced by
+ *      the identity's, scaled by a refined parameter's damped entry (s's for dx and dy, dx's for s: the determinant test
+ *      compares magnitudes), with a zero right-hand side; a free group with no inlier or whose block is singular by the triangulation call's determinant rule is
+ *      HELD for the iteration.  The block U_ck enters iff camera and group both move (free, not held); the coupling W_k =
+ *      J_k^T J_p of an inlier enters iff its group and its point both move, whatever its camera.
+ *   5. The unknowns are the free cameras' 6 and the free groups' 3; the right-hand side of a group is g_k - (the sum of
+ *      W_k y, y = V*^-1 g_p, per image then per group in the two orders above); the preconditioner is block-Jacobi, U*^-1
+ *      per camera and U_kk*^-1 per group (the cofactor solve).  The operator: per track y_j = V*^-1 (the 4-slot sum of, per
+ *      position, W^T p_c + W_k^T p_k, or the one of them that enters); per image Ap_c = (U* p_c + U_ck p_k) - (the sum of W y) and
+ *      the image's share (U_ck^T p_c, or 0 for a camera that does not move) - (the sum of W_k y); per group Ap_k = U_kk* p_k +
+ *      (the sum of its images' shares over the image id).  A global dot product is the 256-slot sum over the image id of
+ *      the cameras' dots plus the 256-slot sum over the group id of the groups' 3-term dots, in that order.
+ *   6. dp_j = V*^-1 (g_p - the same sum with x); a moving group's candidate is (s, dx, dy) - x_k in the parameters refined.  A
+ *      candidate in which a moving group's s is not finite or not > 0 is REJECTED whatever its cost (the trace still shows
+ *      the cost computed).
+ *   7. d_intrinsics_out: for an image of a free group the f64 products rounded to f32, else the input's four words;
+ *      d_group_out [g] = the state rounded, (1, 0, 0) for a group that is not free.  d_obs_state_out is judged under the
+ *      rounded poses, points AND d_intrinsics_out, so lf_mkd_triangulate_tracks_device's test with them agrees.  d_trace [k]
+ *      [8] = held groups; d_counts [4] = free groups.
+ * With refine == 0 no group is free and every word this call shares with lf_mkd_bundle_adjust_device is that call's, bit for
+ * bit (the widened intrinsics give the same bits); d_intrinsics_out is then a copy.  tests/cpp/bundle_intr_twin.cpp gives
+ * every output word on the host.
+ * How (csrc/mkd_bundle.hip): the sibling's kernels in their double-intrinsics form plus three with a workgroup per group:
+ * 6 + iterations x (7 + 6 cg_iterations) launches fixed by the scalars alone, capturable once warmed up; no floating-point
+ * atomic, nobody waits for another workgroup, no kernel spills.  Scratch is the sibling's plus 244 bytes an image and 252 a
+ * group, the handle's.  COST: each per-group workgroup walks ALL image ids, so a group sum costs n_groups x n_images reads a
+ * CG step: fine for the few lenses of a collection, quadratic with a group per image (profiles/bundle_intrinsics.md); the
+ * per-image kernels now also walk every usable fixed image of a free group.
+ * LF_MKD_ERR_BAD_ARG, before any device is touched ("bundle_adjust_intrinsics_device: "): the sibling's list in its order
+ * with a null d_intrinsics_out among the required pointers; then refine above 3; n_groups == 0 with n_images > 0, or a null
+ * d_camera_group with n_groups != 1; then the scalars, the alignment (d_camera_group, d_intrinsics_out and d_group_out 4-byte)
+ * and the totals (n_groups too) as there. */
+#define LF_MKD_BA_REFINE_FOCAL (1u)       /* refine every free group's focal scale s */
+#define LF_MKD_BA_REFINE_PRINCIPAL (2u)   /* refine every free group's principal-point shift (dx, dy) */
+int lf_mkd_bundle_adjust_intrinsics_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                           uint64_t n_rows_total, const uint64_t *d_track_offsets, uint64_t track_capacity,
+                                           const int32_t *d_obs_row, const uint32_t *d_obs_image, uint64_t obs_capacity,
+                                           const uint32_t *d_table_counts, const float *d_points, const float *d_intrinsics,
+                                           const float *d_poses, const uint32_t *d_obs_state, const uint32_t *d_camera_fixed,
+                                           const uint32_t *d_camera_group, uint32_t n_groups, uint32_t refine, float max_reproj_px,
+                                           float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
+                                           float *d_poses_out, float *d_points_out, float *d_intrinsics_out, float *d_group_out,
+                                           uint32_t *d_obs_state_out, double *d_trace, uint32_t *d_counts, void *stream);
+/* Host pointers, synchronous, through the device call: the sibling's arrays, camera_group [n_images] or null,
+ * intrinsics_out [n_images][4], optional group_out [n_groups][3], trace [iterations][9], counts [5].
+ * LF_MKD_ERR_BAD_ARG ("bundle_adjust_intrinsics: "): as the device form, without the alignment. */
+int lf_mkd_bundle_adjust_intrinsics(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *image_offsets, uint32_t n_images,
+                                    uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks, const int32_t *obs_row,
+                                    const uint32_t *obs_image, uint64_t n_obs, const float *points, const float *intrinsics,
+                                    const float *poses, const uint32_t *obs_state, const uint32_t *camera_fixed,
+                                    const uint32_t *camera_group, uint32_t n_groups, uint32_t refine, float max_reproj_px,
+                                    float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
+                                    float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
+                                    uint32_t *obs_state_out, double *trace, uint32_t *counts);
+
 /* ---- geometric verification: RANSAC homography of matched keypoints ---------------------------------------------
  * For one pair of images, or for n_pairs independent pairs in one call: a homography H with b ~ H a fitted robustly to the
  * matches, and the matches that agree with it.  Inputs are what the entry points above produce: lf_mkd_keypoint rows and the

@@ -497,4 +497,121 @@ int lf_mkd_bundle_adjust(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *
     return LF_MKD_OK;
 }
 
+// Bundle adjustment with shared intrinsics refined: the same kernels in their double-intrinsics form (csrc/mkd_bundle.hip),
+// the same scalars formed the same way (tests/cpp/bundle_intr_twin.cpp).
+static const char *bundle_groups(uint32_t n_images, const void *camera_group, uint32_t n_groups, uint32_t refine) {
+    if (refine > (LF_MKD_BA_REFINE_FOCAL | LF_MKD_BA_REFINE_PRINCIPAL))
+        return "unknown refine bits (LF_MKD_BA_REFINE_FOCAL | LF_MKD_BA_REFINE_PRINCIPAL)";
+    if (n_images && n_groups == 0) return "n_groups must be at least 1";
+    if (n_images && !camera_group && n_groups != 1) return "a null camera_group puts every image in group 0: n_groups must be 1";
+    return nullptr;
+}
+
+int lf_mkd_bundle_adjust_intrinsics_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                           uint64_t n_rows_total, const uint64_t *d_track_offsets, uint64_t track_capacity,
+                                           const int32_t *d_obs_row, const uint32_t *d_obs_image, uint64_t obs_capacity,
+                                           const uint32_t *d_table_counts, const float *d_points, const float *d_intrinsics,
+                                           const float *d_poses, const uint32_t *d_obs_state, const uint32_t *d_camera_fixed,
+                                           const uint32_t *d_camera_group, uint32_t n_groups, uint32_t refine, float max_reproj_px,
+                                           float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
+                                           float *d_poses_out, float *d_points_out, float *d_intrinsics_out, float *d_group_out,
+                                           uint32_t *d_obs_state_out, double *d_trace, uint32_t *d_counts, void *stream) {
+    const char *msg = nullptr;
+    if (n_images && (!d_image_offsets || !d_table_counts || !d_intrinsics || !d_poses || !d_poses_out || !d_intrinsics_out || !d_trace ||
+                     !d_counts))
+        msg = "null d_image_offsets, d_table_counts, d_intrinsics, d_poses, d_poses_out, d_intrinsics_out, d_trace or d_counts";
+    else if (n_images && track_capacity && (!d_track_offsets || !d_points || !d_points_out))
+        msg = "null d_track_offsets, d_points or d_points_out";
+    else if (n_images && track_capacity && obs_capacity && (!d_obs_row || !d_obs_image)) msg = "null d_obs_row or d_obs_image";
+    else if (n_images && track_capacity && obs_capacity && n_rows_total && !d_kps) msg = "null d_kps";
+    else if ((msg = bundle_groups(n_images, d_camera_group, n_groups, refine))) {}
+    else if ((msg = bundle_scalars(max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, flags))) {}
+    else if (misaligned(7, d_image_offsets) || misaligned(7, d_track_offsets) || misaligned(7, d_trace))
+        msg = "d_image_offsets, d_track_offsets and d_trace must be 8-byte aligned";
+    else if (misaligned(3, d_kps, d_obs_row, d_obs_image, d_table_counts, d_points, d_intrinsics, d_poses, d_obs_state, d_camera_fixed,
+                        d_camera_group, d_poses_out, d_points_out, d_intrinsics_out, d_group_out, d_obs_state_out, d_counts))
+        msg = "the keypoint, observation, count, point, intrinsics, pose, state, mask, group and output arrays must be 4-byte aligned";
+    else if (above(kRowMax, n_images, n_rows_total, track_capacity, obs_capacity, n_groups)) msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "bundle_adjust_intrinsics_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    if (int rc = grow(h, h->d_bundle, bundle_intrinsics_scratch_bytes(n_images, n_rows_total, track_capacity, obs_capacity, n_groups)))
+        return rc;
+    const double thr2 = double(max_reproj_px) * double(max_reproj_px), tol2 = double(cg_tol) * double(cg_tol);
+    launch_bundle_adjust_intrinsics(h->d_bundle.get(), reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total,
+                                    d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_points,
+                                    d_intrinsics, d_poses, d_obs_state, d_camera_fixed, d_camera_group, n_groups, refine, thr2,
+                                    double(lambda0), iterations, cg_iterations, tol2, d_poses_out, d_points_out, d_intrinsics_out,
+                                    d_group_out, d_obs_state_out, d_trace, d_counts, stream_of(h, stream));
+    return launched(h);
+}
+
+// The host form, staged as lf_mkd_bundle_adjust stages its arrays; in place on the staged poses, points and intrinsics.
+int lf_mkd_bundle_adjust_intrinsics(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *image_offsets, uint32_t n_images,
+                                    uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks, const int32_t *obs_row,
+                                    const uint32_t *obs_image, uint64_t n_obs, const float *points, const float *intrinsics,
+                                    const float *poses, const uint32_t *obs_state, const uint32_t *camera_fixed,
+                                    const uint32_t *camera_group, uint32_t n_groups, uint32_t refine, float max_reproj_px,
+                                    float lambda0, uint32_t iterations, uint32_t cg_iterations, float cg_tol, uint32_t flags,
+                                    float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
+                                    uint32_t *obs_state_out, double *trace, uint32_t *counts) {
+    const char *msg = nullptr;
+    if (n_images && (!image_offsets || !intrinsics || !poses || !poses_out || !intrinsics_out || !trace || !counts))
+        msg = "null image_offsets, intrinsics, poses, poses_out, intrinsics_out, trace or counts";
+    else if (n_images && n_tracks && (!track_offsets || !points || !points_out)) msg = "null track_offsets, points or points_out";
+    else if (n_images && n_tracks && n_obs && (!obs_row || !obs_image)) msg = "null obs_row or obs_image";
+    else if (n_images && n_tracks && n_obs && n_rows_total && !kps) msg = "null kps";
+    else if ((msg = bundle_groups(n_images, camera_group, n_groups, refine))) {}
+    else if ((msg = bundle_scalars(max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, flags))) {}
+    else if (above(kRowMax, n_images, n_rows_total, n_tracks, n_obs, n_groups)) msg = "a total above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "bundle_adjust_intrinsics", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    Stager io(h, h->d_ver_io);
+    const auto d_trace = io.part<double>(uint64_t(iterations) * 9);
+    const auto d_ioff = io.part<uint64_t>(uint64_t(n_images) + 1), d_toff = io.part<uint64_t>(n_tracks + 1);
+    const auto d_tc = io.part<uint32_t>(2), d_counts = io.part<uint32_t>(5);
+    const auto d_kps = io.part<lf_mkd_keypoint>(n_rows_total);
+    const auto d_row = io.part<int32_t>(n_obs);
+    const auto d_image = io.part<uint32_t>(n_obs);
+    const auto d_points = io.part<float>(n_tracks * 4), d_K = io.part<float>(uint64_t(n_images) * 4);
+    const auto d_poses = io.part<float>(uint64_t(n_images) * 12);
+    const auto d_state = io.part<uint32_t>(obs_state ? n_obs : 0), d_fixed = io.part<uint32_t>(camera_fixed ? n_images : 0);
+    const auto d_group = io.part<uint32_t>(camera_group ? n_images : 0);
+    const auto d_gout = io.part<float>(group_out ? uint64_t(n_groups) * 3 : 0);
+    const auto d_state_out = io.part<uint32_t>(obs_state_out ? n_obs : 0);
+    if (int rc = io.reserve()) return rc;
+    const uint32_t tc[2] = {uint32_t(n_tracks), uint32_t(n_obs)};
+    LF_HIP(h, io.up(d_ioff, image_offsets, uint64_t(n_images) + 1));
+    LF_HIP(h, io.up(d_toff, track_offsets, n_tracks ? n_tracks + 1 : 0));
+    LF_HIP(h, io.up(d_tc, tc, 2));
+    LF_HIP(h, io.up(d_kps, kps, n_tracks && n_obs ? n_rows_total : 0));
+    LF_HIP(h, io.up(d_row, obs_row, n_tracks ? n_obs : 0));
+    LF_HIP(h, io.up(d_image, obs_image, n_tracks ? n_obs : 0));
+    LF_HIP(h, io.up(d_points, points, n_tracks * 4));
+    LF_HIP(h, io.up(d_K, intrinsics, uint64_t(n_images) * 4));
+    LF_HIP(h, io.up(d_poses, poses, uint64_t(n_images) * 12));
+    LF_HIP(h, io.up(d_state, obs_state, obs_state && n_tracks ? n_obs : 0));
+    LF_HIP(h, io.up(d_fixed, camera_fixed, camera_fixed ? n_images : 0));
+    LF_HIP(h, io.up(d_group, camera_group, camera_group ? n_images : 0));
+    if (obs_state_out && n_obs) LF_HIP(h, hipMemsetAsync(d_state_out.get(), 0, n_obs * 4, h->stream));
+    if (int rc = lf_mkd_bundle_adjust_intrinsics_device(
+            h, d_kps, d_ioff, n_images, n_rows_total, d_toff, n_tracks, d_row, d_image, n_obs, d_tc, d_points, d_K, d_poses,
+            obs_state ? d_state.get() : nullptr, camera_fixed ? d_fixed.get() : nullptr, camera_group ? d_group.get() : nullptr, n_groups,
+            refine, max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, flags, d_poses, d_points, d_K,
+            group_out ? d_gout.get() : nullptr, obs_state_out ? d_state_out.get() : nullptr, d_trace, d_counts, h->stream))
+        return rc;
+    LF_HIP(h, io.down(poses_out, d_poses, uint64_t(n_images) * 12));
+    LF_HIP(h, io.down(points_out, d_points, n_tracks * 4));
+    LF_HIP(h, io.down(intrinsics_out, d_K, uint64_t(n_images) * 4));
+    LF_HIP(h, io.down(group_out, d_gout, group_out ? uint64_t(n_groups) * 3 : 0));
+    LF_HIP(h, io.down(obs_state_out, d_state_out, obs_state_out ? n_obs : 0));
+    LF_HIP(h, io.down(trace, d_trace, uint64_t(iterations) * 9));
+    LF_HIP(h, io.down(counts, d_counts, 5));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
 }  // extern "C"

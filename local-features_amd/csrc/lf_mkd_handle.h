@@ -249,7 +249,8 @@ struct lf_mkd {
     HipArray<unsigned char> d_covisibility;
     // lf_mkd_resect_cameras_device's scratch (resect_scratch_bytes), in the same way
     HipArray<unsigned char> d_resect;
-    // lf_mkd_bundle_adjust_device's scratch (bundle_scratch_bytes), in the same way
+    // lf_mkd_bundle_adjust_device's scratch (bundle_scratch_bytes), in the same way; lf_mkd_bundle_adjust_intrinsics_device's
+    // too (bundle_intrinsics_scratch_bytes: the same layout with the groups' arrays behind it)
     HipArray<unsigned char> d_bundle;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;

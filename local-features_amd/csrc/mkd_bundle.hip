@@ -33,10 +33,21 @@
 // serialises the per-image kernels on one workgroup: its passes are M / 256 rounds of one workgroup, the cost stated in
 // the header and measured in profiles/bundle.md.
 //
+// lf_mkd_bundle_adjust_intrinsics_device is the SAME kernels instantiated with kI = true: the intrinsics an
+// observation is read under are then doubles, the f32 input widened or, for an image of a free group, the products of the
+// group's state (s, dx, dy); the per-image kernels also walk the usable images that are not free but inform a free group, and
+// gather the group's own terms, the block U_ck between camera and group and, per CG step, the image's share of the group's
+// operator row; ba_setup_groups, ba_group_lin and ba_group_apply (a workgroup per group, walking every image id in the
+// 256-slot order: n_groups x n_images reads a CG step, the cost stated in the header) sum those shares, and the thread-per-
+// image kernels take the groups as further threads.  With nothing refined no group is free and every shared word is the
+// fixed-intrinsics call's.
+//
 // No floating-point atomic (the integer counts of the trace are integer atomics, exact in any order), no LDS beyond the block
 // sums, scratch belongs to the handle, nobody waits for another workgroup.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "mkd_bundle_math.h"
 #include "mkd_device.h"
@@ -53,7 +64,7 @@ constexpr unsigned kMaxBlocks = 16384;      // grid-stride beyond
 enum : int { kVecX = 0, kVecR = 1, kVecZ = 2, kVecP = 3, kVecAp = 4, kVecs = 5 };
 enum : int { kSLambda = 0, kSCost = 1, kSRz = 2, kSRz0 = 3, kSAlpha = 4, kSBeta = 5, kScalars = 8 };
 enum : int { kWCur = 0, kWStopped = 1, kWSteps = 2, kWInliers = 3, kWHeldCams = 4, kWHeldPoints = 5, kWFreeCams = 6,
-             kWFreePoints = 7, kWActive = 8, kWAccepted = 9, kWords = 16 };
+             kWFreePoints = 7, kWActive = 8, kWAccepted = 9, kWHeldGroups = 10, kWFreeGroups = 11, kWBadSigma = 12, kWords = 16 };
 enum : unsigned { kModeStart = 0, kModeAlpha = 1, kModeBeta = 2, kModeAccept = 3 };
 
 struct BaIn {
@@ -89,6 +100,23 @@ struct BaScratch {
     unsigned *words;             // [kWords]
 };
 
+// What the intrinsics call adds: its arguments and, behind the scratch above, its own (nothing of it is read when kI is false)
+struct BaIntr {
+    const unsigned *__restrict__ group;        // may be null: every image is in group 0
+    unsigned n_groups, refine;
+    BaGroup *gstate;             // [2][n_groups]: the state and the candidate, as cam
+    double *gU;                  // [n_groups][9]: damped U_kk*, then g_k
+    double *gvec;                // [5][n_groups][3]: x, r, z, p, Ap
+    double *gdots;               // [n_groups]
+    double *Uck;                 // [n_images][18]
+    double *ipart;               // [n_images][12]: an image's share of its group's sums (ba_image_lin: the nine terms and sum W_k y;
+                                 // ba_image_apply: U_ck^T p_c - sum W_k y in the first three)
+    unsigned *icount;            // [n_images]: the image's inliers
+    unsigned *gflag;             // [n_groups]
+};
+template <bool kI>
+using KOf = std::conditional_t<kI, double, float>;
+
 __device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
 __device__ __forceinline__ void image_range(const BaIn &in, unsigned img, uint64_t &lo, uint64_t &hi) {
     lo = clamp_to(in.off[img], in.n_rows);
@@ -103,9 +131,31 @@ __device__ __forceinline__ void track_range(const BaIn &in, uint64_t t, uint64_t
 __device__ __forceinline__ double *vec_of(const BaScratch &sc, const BaIn &in, int which, unsigned img) {
     return sc.vec + ((uint64_t)which * in.n_images + img) * 6;
 }
-__device__ __forceinline__ void load_k(const BaIn &in, unsigned img, float *K) {
+__device__ __forceinline__ void load_k0(const BaIn &in, unsigned img, float *K) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) K[i] = in.intrinsics[4 * (uint64_t)img + i];
+}
+__device__ __forceinline__ double *gvec_of(const BaIntr &gi, int which, unsigned g) {
+    return gi.gvec + ((uint64_t)which * gi.n_groups + g) * 3;
+}
+__device__ __forceinline__ unsigned group_of(const BaIntr &gi, unsigned img) { return gi.group ? gi.group[img] : 0u; }
+__device__ __forceinline__ bool group_free(const BaIntr &gi, unsigned g) { return g < gi.n_groups && (gi.gflag[g] & kBaGroupFree); }
+__device__ __forceinline__ bool group_moves(const BaIntr &gi, unsigned g) {
+    return g < gi.n_groups && (gi.gflag[g] & (kBaGroupFree | kBaGroupHeld)) == kBaGroupFree;
+}
+// the intrinsics an image is read under: the input, or (kI) doubles -- the input widened, or for an image of a free group the
+// products of the group's state `st` (words[kWCur], or the other one for the candidate)
+template <bool kI>
+__device__ __forceinline__ void load_k(const BaIn &in, const BaIntr &gi, unsigned st, unsigned img, KOf<kI> *K) {
+    if constexpr (!kI) {
+        load_k0(in, img, K);
+    } else {
+        float K0[4];
+        load_k0(in, img, K0);
+        ba_widen_k(K0, K);
+        const unsigned g = group_of(gi, img);
+        if (group_free(gi, g)) ba_group_k(K0, gi.gstate[(uint64_t)st * gi.n_groups + g], K);
+    }
 }
 // the correspondence of an ACTIVE position's row under the points `pt`
 __device__ __forceinline__ BaCorr load_corr(const BaIn &in, uint64_t row, const double *pt, uint64_t t) {
@@ -121,7 +171,7 @@ __device__ __forceinline__ void load_w(const BaIn &in, const BaScratch &sc, uint
 #ifndef LF_BA_STORE_W
     const unsigned cur = sc.words[kWCur], img = in.obs_image[pos];
     float K[4];
-    load_k(in, img, K);
+    load_k0(in, img, K);
     BaLin o;
     ba_rows(sc.cam[(uint64_t)cur * in.n_images + img], K,
             load_corr(in, (uint64_t)in.obs_row[pos], sc.pt + (uint64_t)cur * in.tcap * 3, t), o);
@@ -131,6 +181,47 @@ __device__ __forceinline__ void load_w(const BaIn &in, const BaScratch &sc, uint
 #pragma unroll
     for (int i = 0; i < kBaW; ++i) W[i] = src[i];
 #endif
+}
+
+// (kI) the rows of a position at the state, from which both its coupling blocks are formed, and its image's input intrinsics
+__device__ __forceinline__ void load_lin(const BaIn &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, BaLin &o,
+                                         float *K0) {
+    const unsigned cur = sc.words[kWCur], img = in.obs_image[pos];
+    double K[4];
+    load_k<true>(in, gi, cur, img, K);
+    load_k0(in, img, K0);
+    ba_rows(sc.cam[(uint64_t)cur * in.n_images + img], K,
+            load_corr(in, (uint64_t)in.obs_row[pos], sc.pt + (uint64_t)cur * in.tcap * 3, t), o);
+}
+// what a coupled or group-coupled position adds to sum W^T v over its track: W_c^T v_c + W_k^T v_k, or the one that enters (v = p
+// or x)
+__device__ __forceinline__ void add_wt(const BaIn &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, int which,
+                                       double *acc) {
+    const unsigned of = sc.oflag[pos];
+    if (!(of & (kBaCoupled | kBaInlier))) return;
+    const unsigned img = in.obs_image[pos], g = group_of(gi, img);
+    const bool kc = (of & kBaInlier) && group_moves(gi, g);
+    if (!(of & kBaCoupled) && !kc) return;
+    BaLin o;
+    float K0[4];
+    load_lin(in, gi, sc, pos, t, o, K0);
+    double w[3] = {0.0, 0.0, 0.0};
+    if (of & kBaCoupled) {
+        double W[kBaW];
+        ba_coupling(o, W);
+        ba_wt_v(W, vec_of(sc, in, which, img), w);
+    }
+    if (kc) {
+        BaGRows gr;
+        double W[kBaWk], v[3];
+        ba_group_rows(o, K0, gi.refine, gr);
+        ba_coupling_k(o, gr, W);
+        ba_wkt_v(W, gvec_of(gi, which, g), v);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = (of & kBaCoupled) ? w[k] + v[k] : v[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w[k];
 }
 
 // Workgroup sum of N values per thread in the canonical order: the butterfly within a wave, then ((w0 + w1) + w2) + w3.
@@ -148,6 +239,18 @@ __device__ __forceinline__ void block_sum(T *v, T *red) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
     __syncthreads();
+}
+// the workgroup's total of an integer per thread (exact in any order)
+__device__ __forceinline__ unsigned block_count(unsigned n, unsigned *s_cnt) {
+    if (threadIdx.x == 0) *s_cnt = 0;
+    __syncthreads();
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m, 64);
+    if ((threadIdx.x & 63) == 0) atomicAdd(s_cnt, n);
+    __syncthreads();
+    const unsigned total = *s_cnt;
+    __syncthreads();
+    return total;
 }
 // the butterfly of the 4-slot sum over the group's lanes
 __device__ __forceinline__ double combine(double v) {
@@ -177,13 +280,14 @@ __device__ __forceinline__ unsigned group_bits(bool p, unsigned base) { return (
 }  // namespace
 
 // ---- setup ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ba_init(BaIn in, const float *__restrict__ poses, const unsigned *__restrict__ fixed,
-                                                    double lambda0, BaScratch sc) {
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_init(BaIn in, BaIntr gi, const float *__restrict__ poses,
+                                                    const unsigned *__restrict__ fixed, double lambda0, BaScratch sc) {
     const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x, n = (uint64_t)gridDim.x * kThreads;
     for (uint64_t r = gid; r < in.n_rows; r += n) sc.rowmap[r] = kBaNoRow;
     for (uint64_t i = gid; i < in.n_images; i += n) {
         float K[4], P[12];
-        load_k(in, (unsigned)i, K);
+        load_k0(in, (unsigned)i, K);
 #pragma unroll
         for (int k = 0; k < 12; ++k) P[k] = poses[12 * i + k];
         const bool usable = tri_camera_usable(K, P), is_free = usable && !(fixed && fixed[i] != 0);
@@ -197,6 +301,11 @@ __global__ __launch_bounds__(kThreads) void ba_init(BaIn in, const float *__rest
         sc.cam[i] = S;
         sc.cam[in.n_images + i] = S;
     }
+    if constexpr (kI)
+        for (uint64_t g = gid; g < gi.n_groups; g += n) {
+            gi.gstate[g] = gi.gstate[gi.n_groups + g] = BaGroup{1.0, 0.0, 0.0};
+            gi.gflag[g] = 0;
+        }
     if (gid < kWords) sc.words[gid] = 0;
     if (gid < kScalars) sc.scal[gid] = gid == kSLambda ? lambda0 : 0.0;
 }
@@ -247,10 +356,13 @@ __global__ __launch_bounds__(kThreads) void ba_setup_tracks(BaIn in, const float
     }
 }
 
+// (kI: a list for every usable image, since a camera that is not free still informs its group)
+template <bool kI>
 __global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch sc) {
     __shared__ unsigned s_cnt[kWaves];
     const unsigned img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (!(sc.head[2 * (uint64_t)img + 1] & kBaCamFree)) return;                   // block-uniform; M stays 0
+    const unsigned hf0 = sc.head[2 * (uint64_t)img + 1];
+    if (!(hf0 & (kI ? kBaCamUsable : kBaCamFree))) return;                        // block-uniform; M stays 0
     uint64_t lo, hi;
     image_range(in, img, lo, hi);
     uint64_t base = lo;
@@ -276,12 +388,26 @@ __global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch s
     }
     if (tid == 0) {
         sc.head[2 * (uint64_t)img] = (unsigned)(base - lo);
-        atomicAdd(sc.words + kWFreeCams, 1u);
+        if (hf0 & kBaCamFree) atomicAdd(sc.words + kWFreeCams, 1u);
+    }
+}
+
+// a workgroup per group: FREE iff something is refined and a usable image of the group has an active row
+__global__ __launch_bounds__(kThreads) void ba_setup_groups(BaIn in, BaIntr gi, BaScratch sc) {
+    const unsigned g = blockIdx.x;
+    int found = 0;
+    for (uint64_t i = threadIdx.x; i < in.n_images; i += kThreads)
+        found |= group_of(gi, (unsigned)i) == g && (sc.head[2 * i + 1] & kBaCamUsable) && sc.head[2 * i] != 0;
+    found = __syncthreads_or(found);
+    if (threadIdx.x == 0 && gi.refine && found) {
+        gi.gflag[g] = kBaGroupFree;
+        atomicAdd(sc.words + kWFreeGroups, 1u);
     }
 }
 
 // ---- an LM iteration -------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, double thr2, BaScratch sc) {
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
     const TrackWalk w = track_walk(in);
     const unsigned cur = sc.words[kWCur];
     const double lambda = sc.scal[kSLambda];
@@ -303,8 +429,8 @@ __global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, double thr2, B
             bool inl = false;
             if (on) {
                 const unsigned img = in.obs_image[pos];
-                float K[4];
-                load_k(in, img, K);
+                KOf<kI> K[4];
+                load_k<kI>(in, gi, cur, img, K);
                 BaLin o;
                 ba_linearise(cam[img], K, load_corr(in, (uint64_t)in.obs_row[pos], pt, t), thr2, o);
                 inl = o.inlier;
@@ -339,17 +465,22 @@ __global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, double thr2, B
     }
 }
 
-__global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, BaScratch sc) {
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
     __shared__ double s_red[kWaves * kRsTerms];
+    __shared__ unsigned s_cnt;
     const unsigned img = blockIdx.x, tid = threadIdx.x;
     const unsigned hf = sc.head[2 * (uint64_t)img + 1] & (kBaCamUsable | kBaCamFree);
-    if (!(hf & kBaCamFree)) {                                                     // block-uniform
+    const bool is_free = (hf & kBaCamFree) != 0;
+    bool informs = false;                                                         // (kI) a usable image of a free group
+    if constexpr (kI) informs = (hf & kBaCamUsable) && group_free(gi, group_of(gi, img));
+    if (!is_free) {                                                               // block-uniform
         if (tid < 6) {
 #pragma unroll
             for (int k = 0; k < kVecs; ++k) vec_of(sc, in, k, img)[tid] = 0.0;
         }
         if (tid == 0) sc.dots[img] = 0.0;
-        return;
+        if (!informs) return;
     }
     const unsigned cur = sc.words[kWCur], M = sc.head[2 * (uint64_t)img];
     const double lambda = sc.scal[kSLambda];
@@ -357,13 +488,51 @@ __global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, B
     const double *pt = sc.pt + (uint64_t)cur * in.tcap * 3;
     uint64_t lo, hi;
     image_range(in, img, lo, hi);
-    float K[4];
-    load_k(in, img, K);
+    KOf<kI> K[4];
+    load_k<kI>(in, gi, cur, img, K);
+    float K0[4];
+    load_k0(in, img, K0);
+
+    if constexpr (kI) {
+        // the image's share of its group's sums: the nine terms, its inliers, and U_ck (block-uniform)
+        if (informs) {
+            double ga[kBaGroupTerms + kBaCk];
+#pragma unroll
+            for (int i = 0; i < kBaGroupTerms + kBaCk; ++i) ga[i] = 0.0;
+            unsigned n_in = 0;
+            for (unsigned k = tid; k < M; k += kThreads) {
+                const unsigned row = sc.idx[lo + k];
+                const unsigned long long m = sc.rowmap[row];
+                BaLin o;
+                ba_linearise(P, K, load_corr(in, row, pt, m >> 32), thr2, o);
+                if (o.inlier) {
+                    BaGRows gr;
+                    double v[kBaGroupTerms + kBaCk];
+                    ba_group_rows(o, K0, gi.refine, gr);
+                    ba_group_terms(o, gr, v);
+                    ba_cross(o, gr, v + kBaGroupTerms);
+#pragma unroll
+                    for (int i = 0; i < kBaGroupTerms + kBaCk; ++i) ga[i] = ga[i] + v[i];
+                    ++n_in;
+                }
+            }
+            block_sum<double, kBaGroupTerms + kBaCk>(ga, s_red);
+            n_in = block_count(n_in, &s_cnt);
+            if (tid < kBaGroupTerms + kBaCk) {
+                double v = ga[0];
+#pragma unroll
+                for (int i = 1; i < kBaGroupTerms + kBaCk; ++i) v = tid == (unsigned)i ? ga[i] : v;
+                if (tid < kBaGroupTerms) gi.ipart[12 * (uint64_t)img + tid] = v;
+                else gi.Uck[(uint64_t)kBaCk * img + (tid - kBaGroupTerms)] = v;
+            }
+            if (tid == 0) gi.icount[img] = n_in;
+        }
+    }
 
     double acc[kRsTerms];
 #pragma unroll
     for (int i = 0; i < kRsTerms; ++i) acc[i] = 0.0;
-    for (unsigned k = tid; k < M; k += kThreads) {
+    for (unsigned k = tid; k < (is_free ? M : 0u); k += kThreads) {               // (a camera that is not free has no block)
         const unsigned row = sc.idx[lo + k];
         const unsigned long long m = sc.rowmap[row];
         BaLin o;
@@ -378,20 +547,22 @@ __global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, B
     block_sum<double, kRsTerms>(acc, s_red);
     ba_damp_u(acc, lambda);
     double z[6];
-    const bool held = !ba_solve_u(acc, acc + 21, z);                              // every thread the same bits
-    if (tid == 0) {
+    const bool held = !ba_solve_u(acc, acc + 21, z) || !is_free;                  // every thread the same bits
+    if (tid == 0 && is_free) {
         sc.head[2 * (uint64_t)img + 1] = hf | (held ? kBaCamHeld : 0u);
         if (held) atomicAdd(sc.words + kWHeldCams, 1u);
     }
-    if (tid < kRsTerms) {
+    if (tid < kRsTerms && is_free) {
         double v = acc[0];
 #pragma unroll
         for (int i = 1; i < kRsTerms; ++i) v = tid == (unsigned)i ? acc[i] : v;
         sc.U[(uint64_t)kRsTerms * img + tid] = v;
     }
 
-    // which entries are coupled, and sum W y
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // which entries are coupled, and sum W y (kI: and sum W_k y over the inliers whose point moves)
+    double s[kI ? 9 : 6];
+#pragma unroll
+    for (int i = 0; i < (kI ? 9 : 6); ++i) s[i] = 0.0;
     for (unsigned k = tid; k < M; k += kThreads) {
         const unsigned row = sc.idx[lo + k];
         const unsigned long long m = sc.rowmap[row];
@@ -411,10 +582,29 @@ __global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, B
 #pragma unroll
             for (int i = 0; i < 6; ++i) s[i] = s[i] + wy[i];
         }
-        sc.oflag[pos] = kBaActive | (coupled ? kBaCoupled : 0u);
+        if constexpr (kI) {
+            if (informs && o.inlier && (sc.tflag[t] & (kBaPointFree | kBaPointHeld)) == kBaPointFree) {
+                BaGRows gr;
+                double W[kBaWk], wy[3];
+                ba_group_rows(o, K0, gi.refine, gr);
+                ba_coupling_k(o, gr, W);
+                ba_wk_y(W, sc.y + 3 * t, wy);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) s[6 + i] = s[6 + i] + wy[i];
+            }
+            sc.oflag[pos] = kBaActive | (coupled ? kBaCoupled : 0u) | (o.inlier ? kBaInlier : 0u);
+        } else {
+            sc.oflag[pos] = kBaActive | (coupled ? kBaCoupled : 0u);
+        }
     }
-    block_sum<double, 6>(s, s_red);
-    if (tid == 0) {
+    block_sum<double, kI ? 9 : 6>(s, s_red);
+    if constexpr (kI) {
+        if (tid == 0 && informs) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) gi.ipart[12 * (uint64_t)img + 9 + i] = s[6 + i];
+        }
+    }
+    if (tid == 0 && is_free) {
         double r[6], zz[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) r[i] = held ? 0.0 : acc[21 + i] - s[i];
@@ -434,8 +624,61 @@ __global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, double thr2, B
     }
 }
 
+// A workgroup per group: the group's nine sums and its inliers over the shares of its usable images (slot = image id mod 256),
+// the damped block, HELD, b_k = g_k - sum W_k y, and the start of CG for the group's three.
+__global__ __launch_bounds__(kThreads) void ba_group_lin(BaIn in, BaIntr gi, BaScratch sc) {
+    __shared__ double s_red[kWaves * 12];
+    __shared__ unsigned s_cnt;
+    const unsigned g = blockIdx.x, tid = threadIdx.x;
+    if (!(gi.gflag[g] & kBaGroupFree)) {                                          // block-uniform
+        if (tid < 3) {
+#pragma unroll
+            for (int k = 0; k < kVecs; ++k) gvec_of(gi, k, g)[tid] = 0.0;
+        }
+        if (tid == 0) gi.gdots[g] = 0.0;
+        return;
+    }
+    double acc[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = 0.0;
+    unsigned n_in = 0;
+    for (uint64_t i = tid; i < in.n_images; i += kThreads)
+        if (group_of(gi, (unsigned)i) == g && (sc.head[2 * i + 1] & kBaCamUsable)) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) acc[k] = acc[k] + gi.ipart[12 * i + k];
+            n_in += gi.icount[i];
+        }
+    block_sum<double, 12>(acc, s_red);
+    n_in = block_count(n_in, &s_cnt);
+    ba_group_block(acc, sc.scal[kSLambda], gi.refine);
+    double z[3];
+    const bool held = !ba_solve_v(acc, acc + 6, z) || n_in == 0;                  // every thread the same bits
+    if (tid != 0) return;
+    gi.gflag[g] = kBaGroupFree | (held ? kBaGroupHeld : 0u);
+    if (held) atomicAdd(sc.words + kWHeldGroups, 1u);
+    double r[3], zz[3];
+#pragma unroll
+    for (int k = 0; k < kBaGroupTerms; ++k) gi.gU[(uint64_t)kBaGroupTerms * g + k] = acc[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[k] = held ? 0.0 : acc[6 + k] - acc[9 + k];
+    ba_group_mask(r, gi.refine);
+    ba_solve_v(acc, r, zz);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double zk = held ? 0.0 : zz[k];
+        gvec_of(gi, kVecX, g)[k] = 0.0;
+        gvec_of(gi, kVecR, g)[k] = r[k];
+        gvec_of(gi, kVecZ, g)[k] = zk;
+        gvec_of(gi, kVecP, g)[k] = zk;
+        gvec_of(gi, kVecAp, g)[k] = 0.0;
+        zz[k] = zk;
+    }
+    gi.gdots[g] = held ? 0.0 : ba_dot3(r, zz);
+}
+
 // y = V*^-1 sum W^T p over the track's coupled positions (0 for a point that is not free, or held)
-__global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaScratch sc) {
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaIntr gi, BaScratch sc) {
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const TrackWalk w = track_walk(in);
     for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
@@ -447,7 +690,9 @@ __global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaScratch sc
         double acc[3] = {0.0, 0.0, 0.0};
         for (unsigned ch = 0; __any(ch < nch); ++ch) {
             const uint64_t pos = lo + (uint64_t)ch * G + w.l;
-            if (ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
+            if constexpr (kI) {
+                if (ch < nch && pos < hi) add_wt(in, gi, sc, pos, t, kVecP, acc);
+            } else if (ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
                 double W[kBaW], v[3];
                 load_w(in, sc, pos, t, W);
                 ba_wt_v(W, vec_of(sc, in, kVecP, in.obs_image[pos]), v);
@@ -467,22 +712,58 @@ __global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaScratch sc
 }
 
 // Ap = U* p - sum W y over the image's coupled entries, and p.Ap
-__global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaScratch sc) {
-    __shared__ double s_red[kWaves * 6];
+// (kI, the image's group moving: Ap = (U* p + U_ck p_k) - sum W y, and the image's share U_ck^T p - sum W_k y of the group's row)
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaIntr gi, BaScratch sc) {
+    __shared__ double s_red[kWaves * 9];
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const unsigned img = blockIdx.x, tid = threadIdx.x;
-    if ((sc.head[2 * (uint64_t)img + 1] & (kBaCamFree | kBaCamHeld)) != kBaCamFree) {   // block-uniform
+    const unsigned hf = sc.head[2 * (uint64_t)img + 1];
+    const bool moves = (hf & (kBaCamFree | kBaCamHeld)) == kBaCamFree;
+    unsigned g = 0;
+    bool gmoves = false;                                                          // (kI) a usable image of a moving group
+    if constexpr (kI) {
+        g = group_of(gi, img);
+        gmoves = (hf & kBaCamUsable) && group_moves(gi, g);
+    }
+    if (!moves) {                                                                 // block-uniform
         if (tid == 0) sc.dots[img] = 0.0;
-        return;
+        if (!gmoves) return;
     }
     const unsigned M = sc.head[2 * (uint64_t)img];
     uint64_t lo, hi;
     image_range(in, img, lo, hi);
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double s[kI ? 9 : 6];
+#pragma unroll
+    for (int i = 0; i < (kI ? 9 : 6); ++i) s[i] = 0.0;
     for (unsigned k = tid; k < M; k += kThreads) {
         const unsigned long long m = sc.rowmap[sc.idx[lo + k]];
         const uint64_t pos = (unsigned)m, t = m >> 32;
-        if (sc.oflag[pos] & kBaCoupled) {
+        if constexpr (kI) {
+            const unsigned of = sc.oflag[pos];
+            const bool kc = gmoves && (of & kBaInlier) && (sc.tflag[t] & (kBaPointFree | kBaPointHeld)) == kBaPointFree;
+            if ((of & kBaCoupled) || kc) {
+                BaLin o;
+                float K0[4];
+                load_lin(in, gi, sc, pos, t, o, K0);
+                if (of & kBaCoupled) {
+                    double W[kBaW], wy[6];
+                    ba_coupling(o, W);
+                    ba_w_y(W, sc.y + 3 * t, wy);
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) s[i] = s[i] + wy[i];
+                }
+                if (kc) {
+                    BaGRows gr;
+                    double W[kBaWk], wy[3];
+                    ba_group_rows(o, K0, gi.refine, gr);
+                    ba_coupling_k(o, gr, W);
+                    ba_wk_y(W, sc.y + 3 * t, wy);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) s[6 + i] = s[6 + i] + wy[i];
+                }
+            }
+        } else if (sc.oflag[pos] & kBaCoupled) {
             double W[kBaW], wy[6];
             load_w(in, sc, pos, t, W);
             ba_w_y(W, sc.y + 3 * t, wy);
@@ -490,25 +771,98 @@ __global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaScratch sc
             for (int i = 0; i < 6; ++i) s[i] = s[i] + wy[i];
         }
     }
-    block_sum<double, 6>(s, s_red);
+    block_sum<double, kI ? 9 : 6>(s, s_red);
     if (tid == 0) {
         double p[6], up[6], ap[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) p[i] = vec_of(sc, in, kVecP, img)[i];
-        ba_u_times(sc.U + (uint64_t)kRsTerms * img, p, up);
+        if (moves) {
+            ba_u_times(sc.U + (uint64_t)kRsTerms * img, p, up);
+            if constexpr (kI) {
+                if (gmoves) {
+                    double ck[6];
+                    ba_w_y(gi.Uck + (uint64_t)kBaCk * img, gvec_of(gi, kVecP, g), ck);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            ap[i] = up[i] - s[i];
-            vec_of(sc, in, kVecAp, img)[i] = ap[i];
+                    for (int i = 0; i < 6; ++i) up[i] = up[i] + ck[i];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                ap[i] = up[i] - s[i];
+                vec_of(sc, in, kVecAp, img)[i] = ap[i];
+            }
+            sc.dots[img] = ba_dot6(p, ap);
         }
-        sc.dots[img] = ba_dot6(p, ap);
+        if constexpr (kI) {
+            if (gmoves) {
+                double part[3] = {0.0, 0.0, 0.0};
+                if (moves) ba_wt_v(gi.Uck + (uint64_t)kBaCk * img, p, part);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) gi.ipart[12 * (uint64_t)img + i] = part[i] - s[6 + i];
+            }
+        }
     }
 }
 
-// x += alpha p, r -= alpha Ap, z = U*^-1 r, and r.z: a thread per image
-__global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaScratch sc) {
+// A workgroup per moving group: Ap_k = U_kk* p_k + the sum over its usable images' shares (slot = image id mod 256), and p_k.Ap_k
+__global__ __launch_bounds__(kThreads) void ba_group_apply(BaIn in, BaIntr gi, BaScratch sc) {
+    __shared__ double s_red[kWaves * 3];
+    if (sc.words[kWStopped]) return;                                              // grid-uniform
+    const unsigned g = blockIdx.x, tid = threadIdx.x;
+    if (!group_moves(gi, g)) {                                                    // block-uniform
+        if (tid == 0) gi.gdots[g] = 0.0;
+        return;
+    }
+    double s[3] = {0.0, 0.0, 0.0};
+    for (uint64_t i = tid; i < in.n_images; i += kThreads)
+        if (group_of(gi, (unsigned)i) == g && (sc.head[2 * i + 1] & kBaCamUsable)) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] = s[k] + gi.ipart[12 * i + k];
+        }
+    block_sum<double, 3>(s, s_red);
+    if (tid == 0) {
+        double p[3], up[3], ap[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = gvec_of(gi, kVecP, g)[k];
+        ba_v_times(gi.gU + (uint64_t)kBaGroupTerms * g, p, up);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ap[k] = up[k] + s[k];
+        ba_group_mask(ap, gi.refine);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gvec_of(gi, kVecAp, g)[k] = ap[k];
+        gi.gdots[g] = ba_dot3(p, ap);
+    }
+}
+
+// x += alpha p, r -= alpha Ap, z = U*^-1 r, and r.z: a thread per image (kI: then a thread per group)
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaIntr gi, BaScratch sc) {
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if constexpr (kI) {
+        if (img >= in.n_images && img - in.n_images < gi.n_groups) {
+            const unsigned g = (unsigned)(img - in.n_images);
+            if (!group_moves(gi, g)) {
+                gi.gdots[g] = 0.0;
+                return;
+            }
+            const double alpha = sc.scal[kSAlpha];
+            double *x = gvec_of(gi, kVecX, g), *r = gvec_of(gi, kVecR, g);
+            const double *p = gvec_of(gi, kVecP, g), *ap = gvec_of(gi, kVecAp, g);
+            double rn[3], z[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                x[i] = x[i] + alpha * p[i];
+                rn[i] = r[i] - alpha * ap[i];
+                r[i] = rn[i];
+            }
+            ba_solve_v(gi.gU + (uint64_t)kBaGroupTerms * g, rn, z);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) gvec_of(gi, kVecZ, g)[i] = z[i];
+            gi.gdots[g] = ba_dot3(rn, z);
+            return;
+        }
+    }
     if (img >= in.n_images) return;
     if ((sc.head[2 * img + 1] & (kBaCamFree | kBaCamHeld)) != kBaCamFree) {
         sc.dots[img] = 0.0;
@@ -531,18 +885,28 @@ __global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaScratch sc) 
 }
 
 // ONE workgroup: a global sum in the 256-slot order (over image id of dots, over track index of tcost) and the scalars
-__global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, unsigned mode, double tol2, unsigned iteration, BaScratch sc,
+// (kI: a dot product is the 256-slot sum over the image ids plus the 256-slot sum over the group ids, in that order)
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, BaIntr gi, unsigned mode, double tol2, unsigned iteration, BaScratch sc,
                                                       double *__restrict__ trace) {
-    __shared__ double s_red[kWaves * 2];
+    constexpr int kSums = kI ? 3 : 2;
+    __shared__ double s_red[kWaves * kSums];
     const unsigned tid = threadIdx.x;
     if ((mode == kModeAlpha || mode == kModeBeta) && sc.words[kWStopped]) return;
     const uint64_t T = clamp_to(in.counts[0], in.tcap);
-    double v[2] = {0.0, 0.0};
+    double v[kSums];
+#pragma unroll
+    for (int i = 0; i < kSums; ++i) v[i] = 0.0;
     if (mode != kModeAccept)
         for (uint64_t i = tid; i < in.n_images; i += kThreads) v[0] = v[0] + sc.dots[i];
     if (mode == kModeStart || mode == kModeAccept)
         for (uint64_t t = tid; t < T; t += kThreads) v[1] = v[1] + sc.tcost[t];
-    block_sum<double, 2>(v, s_red);
+    if constexpr (kI) {
+        if (mode != kModeAccept)
+            for (uint64_t g = tid; g < gi.n_groups; g += kThreads) v[2] = v[2] + gi.gdots[g];
+    }
+    block_sum<double, kSums>(v, s_red);
+    if constexpr (kI) v[0] = v[0] + v[2];
     BaCg cg = {sc.scal[kSRz], sc.scal[kSRz0], sc.scal[kSAlpha], sc.scal[kSBeta], sc.words[kWStopped], sc.words[kWSteps]};
     __syncthreads();                                                              // everyone has read the scalars
     if (mode == kModeStart) ba_cg_start(cg, v[0]);
@@ -554,17 +918,25 @@ __global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, unsigned mode, do
                 double *p = sc.vec + (uint64_t)kVecP * in.n_images * 6, *z = sc.vec + (uint64_t)kVecZ * in.n_images * 6;
                 p[i] = z[i] + cg.beta * p[i];
             }
+        if constexpr (kI) {
+            if (!cg.stopped)
+                for (uint64_t i = tid; i < 3 * (uint64_t)gi.n_groups; i += kThreads) {
+                    double *p = gi.gvec + (uint64_t)kVecP * gi.n_groups * 3, *z = gi.gvec + (uint64_t)kVecZ * gi.n_groups * 3;
+                    p[i] = z[i] + cg.beta * p[i];
+                }
+        }
     }
     if (tid != 0) return;
     if (mode == kModeAccept) {
         double lambda = sc.scal[kSLambda];
         const double used = lambda, cost = sc.scal[kSCost];
-        const bool ok = ba_accept(v[1], cost, lambda);
-        double *row = trace + (uint64_t)kBaTrace * iteration;
+        const bool ok = ba_accept(v[1], cost, lambda, !(kI && sc.words[kWBadSigma]));
+        double *row = trace + (uint64_t)(kI ? kBaTraceI : kBaTrace) * iteration;
         row[0] = cost, row[1] = v[1], row[2] = used, row[3] = ok ? 1.0 : 0.0, row[4] = double(sc.words[kWSteps]);
         row[5] = double(sc.words[kWInliers]), row[6] = double(sc.words[kWHeldCams]), row[7] = double(sc.words[kWHeldPoints]);
         sc.scal[kSLambda] = lambda;
         if (ok) sc.words[kWCur] ^= 1u, sc.words[kWAccepted] += 1u;
+        if constexpr (kI) row[8] = double(sc.words[kWHeldGroups]), sc.words[kWHeldGroups] = 0, sc.words[kWBadSigma] = 0;
         sc.words[kWInliers] = 0, sc.words[kWHeldCams] = 0, sc.words[kWHeldPoints] = 0;
         return;
     }
@@ -573,11 +945,28 @@ __global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, unsigned mode, do
     sc.words[kWStopped] = cg.stopped, sc.words[kWSteps] = cg.steps;
 }
 
-// the candidate cameras: a thread per image
-__global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaScratch sc) {
+// the candidate cameras: a thread per image (kI: then the candidate groups, a thread per group; a moving group whose candidate s
+// is not finite and positive marks the whole candidate as one to reject)
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaIntr gi, BaScratch sc) {
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (img >= in.n_images) return;
     const unsigned cur = sc.words[kWCur];
+    if constexpr (kI) {
+        if (img >= in.n_images && img - in.n_images < gi.n_groups) {
+            const unsigned g = (unsigned)(img - in.n_images);
+            const BaGroup S = gi.gstate[(uint64_t)cur * gi.n_groups + g];
+            BaGroup next = S;
+            if (group_moves(gi, g)) {
+                double d[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) d[i] = gvec_of(gi, kVecX, g)[i];
+                if (!ba_group_step(S, d, gi.refine, next)) atomicOr(sc.words + kWBadSigma, 1u);
+            }
+            gi.gstate[(uint64_t)(cur ^ 1u) * gi.n_groups + g] = next;
+            return;
+        }
+    }
+    if (img >= in.n_images) return;
     const RsPose P = sc.cam[(uint64_t)cur * in.n_images + img];
     RsPose next = P;
     if ((sc.head[2 * img + 1] & (kBaCamFree | kBaCamHeld)) == kBaCamFree) {
@@ -590,7 +979,8 @@ __global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaScratch sc) {
 }
 
 // the candidate points X - V*^-1 (g_p - sum W^T x) and the candidate's cost per track
-__global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, double thr2, BaScratch sc) {
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
     const TrackWalk w = track_walk(in);
     const unsigned cur = sc.words[kWCur];
     const RsPose *cam_c = sc.cam + (uint64_t)(cur ^ 1u) * in.n_images;
@@ -606,7 +996,9 @@ __global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, double thr2, 
         double acc[3] = {0.0, 0.0, 0.0};
         for (unsigned ch = 0; __any(ch < nch); ++ch) {
             const uint64_t pos = lo + (uint64_t)ch * G + w.l;
-            if (go && ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
+            if constexpr (kI) {
+                if (go && ch < nch && pos < hi) add_wt(in, gi, sc, pos, t, kVecX, acc);
+            } else if (go && ch < nch && pos < hi && (sc.oflag[pos] & kBaCoupled)) {
                 double W[kBaW], v[3];
                 load_w(in, sc, pos, t, W);
                 ba_wt_v(W, vec_of(sc, in, kVecX, in.obs_image[pos]), v);
@@ -631,8 +1023,8 @@ __global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, double thr2, 
             const uint64_t pos = lo + (uint64_t)ch * G + w.l;
             if (ch < nch && pos < hi && (sc.oflag[pos] & kBaActive)) {
                 const unsigned img = in.obs_image[pos];
-                float K[4];
-                load_k(in, img, K);
+                KOf<kI> K[4];
+                load_k<kI>(in, gi, cur ^ 1u, img, K);
                 const float *k = in.kps + 5 * (uint64_t)in.obs_row[pos];
                 c.x = k[0], c.y = k[1];
                 cost = cost + rs_cost(cam_c[img], K, c, thr2);
@@ -647,8 +1039,37 @@ __global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, double thr2, 
 }
 
 // ---- the end ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, const float *poses, BaScratch sc, float *poses_out) {
+// (kI: and the image's intrinsics, the f64 products rounded for an image of a free group, the input's words elsewhere; then a
+// thread per group for d_group_out)
+template <bool kI>
+__global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, BaIntr gi, const float *poses, BaScratch sc, float *poses_out,
+                                                            float *intrinsics_out, float *group_out) {
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if constexpr (kI) {
+        if (img >= in.n_images && img - in.n_images < gi.n_groups && group_out) {
+            const uint64_t g = img - in.n_images;
+            const BaGroup S = gi.gstate[(uint64_t)sc.words[kWCur] * gi.n_groups + g];
+            group_out[3 * g] = float(S.s), group_out[3 * g + 1] = float(S.dx), group_out[3 * g + 2] = float(S.dy);
+        }
+        if (img < in.n_images) {
+            const unsigned *ksrc = reinterpret_cast<const unsigned *>(in.intrinsics) + 4 * img;
+            unsigned kw[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) kw[i] = ksrc[i];
+            const unsigned g = group_of(gi, (unsigned)img);
+            if (group_free(gi, g)) {
+                float K0[4], Kr[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) K0[i] = __uint_as_float(kw[i]);
+                ba_round_k(K0, gi.gstate[(uint64_t)sc.words[kWCur] * gi.n_groups + g], Kr);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) kw[i] = __float_as_uint(Kr[i]);
+            }
+            unsigned *kdst = reinterpret_cast<unsigned *>(intrinsics_out) + 4 * img;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) kdst[i] = kw[i];
+        }
+    }
     if (img >= in.n_images) return;
     const unsigned *src = reinterpret_cast<const unsigned *>(poses) + 12 * img;
     unsigned *dst = reinterpret_cast<unsigned *>(poses_out) + 12 * img;
@@ -665,13 +1086,17 @@ __global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, const float
     for (int i = 0; i < 12; ++i) dst[i] = words[i];
 }
 
+// (kI: judged under intrinsics_out, and a fifth count)
+template <bool kI>
 __global__ __launch_bounds__(kThreads) void ba_final_tracks(BaIn in, const float *points, double thr2, BaScratch sc,
-                                                            const float *__restrict__ poses_out, float *points_out,
+                                                            const float *__restrict__ poses_out,
+                                                            const float *__restrict__ intrinsics_out, float *points_out,
                                                             unsigned *obs_state_out, unsigned *__restrict__ counts_out) {
     const TrackWalk w = track_walk(in);
     const double *pt = sc.pt + (uint64_t)sc.words[kWCur] * in.tcap * 3;
-    if (blockIdx.x == 0 && threadIdx.x < 4) {
-        const int which = threadIdx.x == 0 ? kWFreeCams : threadIdx.x == 1 ? kWFreePoints : threadIdx.x == 2 ? kWActive : kWAccepted;
+    if (blockIdx.x == 0 && threadIdx.x < (kI ? 5 : 4)) {
+        const int which = threadIdx.x == 0 ? kWFreeCams : threadIdx.x == 1 ? kWFreePoints : threadIdx.x == 2 ? kWActive
+                          : threadIdx.x == 3 ? kWAccepted : kWFreeGroups;
         counts_out[threadIdx.x] = sc.words[which];
     }
     for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
@@ -702,7 +1127,8 @@ __global__ __launch_bounds__(kThreads) void ba_final_tracks(BaIn in, const float
                     const float *k = in.kps + 5 * (uint64_t)in.obs_row[pos];
                     TriObs o;
                     o.x = k[0], o.y = k[1];
-                    load_k(in, img, o.K);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o.K[i] = (kI ? intrinsics_out : in.intrinsics)[4 * (uint64_t)img + i];
 #pragma unroll
                     for (int i = 0; i < 12; ++i) o.P[i] = poses_out[12 * (uint64_t)img + i];
                     double e2;
@@ -722,9 +1148,10 @@ __global__ __launch_bounds__(kThreads) void ba_final_tracks(BaIn in, const float
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
 namespace {
 struct BaLayout {
-    uint64_t cam, pt, U, V, W, vec, y, tcost, dots, scal, rowmap, idx, head, oflag, tflag, words, total;
+    uint64_t cam, pt, U, V, W, vec, y, tcost, dots, scal, rowmap, idx, head, oflag, tflag, words;
+    uint64_t gstate, gU, gvec, gdots, Uck, ipart, icount, gflag, total;      // the intrinsics call's own, behind the rest
 };
-BaLayout layout(uint64_t n_images, uint64_t n_rows, uint64_t tcap, uint64_t ocap) {
+BaLayout layout(uint64_t n_images, uint64_t n_rows, uint64_t tcap, uint64_t ocap, bool intrinsics, uint64_t n_groups) {
     BaLayout L;
     uint64_t at = 0;
     const auto take = [&](uint64_t bytes) {
@@ -752,13 +1179,77 @@ BaLayout layout(uint64_t n_images, uint64_t n_rows, uint64_t tcap, uint64_t ocap
     L.oflag = take(4 * ocap);
     L.tflag = take(4 * tcap);
     L.words = take(4 * kWords);
+    L.gstate = L.gU = L.gvec = L.gdots = L.Uck = L.ipart = L.icount = L.gflag = at;
+    if (intrinsics) {
+        L.gstate = take(8 * 2 * 3 * n_groups);
+        L.gU = take(8 * kBaGroupTerms * n_groups);
+        L.gvec = take(8 * kVecs * 3 * n_groups);
+        L.gdots = take(8 * n_groups);
+        L.Uck = take(8 * kBaCk * n_images);
+        L.ipart = take(8 * 12 * n_images);
+        L.icount = take(4 * n_images);
+        L.gflag = take(4 * n_groups);
+    }
     L.total = at;
     return L;
+}
+
+// The one launch sequence of both calls: kI = false is lf_mkd_bundle_adjust_device's, kI = true adds ba_setup_groups, a
+// ba_group_lin per iteration and a ba_group_apply per CG step, and the thread-per-image kernels take n_groups more threads.
+template <bool kI>
+void launch(void *scratch, const BaIn &in, const unsigned *group, unsigned n_groups, unsigned refine, const float *points,
+            const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0, unsigned iterations,
+            unsigned cg_iterations, double tol2, float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
+            unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
+    const unsigned n_images = in.n_images;
+    const uint64_t n_rows = in.n_rows, track_capacity = in.tcap;
+    unsigned char *b = static_cast<unsigned char *>(scratch);
+    const BaLayout L = layout(n_images, n_rows, track_capacity, in.ocap, kI, n_groups);
+    const auto f64 = [&](uint64_t at) { return reinterpret_cast<double *>(b + at); };
+    const auto u32 = [&](uint64_t at) { return reinterpret_cast<unsigned *>(b + at); };
+    const BaScratch sc = {reinterpret_cast<RsPose *>(b + L.cam), f64(L.pt), f64(L.U), f64(L.V), f64(L.W), f64(L.vec), f64(L.y),
+                          f64(L.tcost), f64(L.dots), f64(L.scal), reinterpret_cast<unsigned long long *>(b + L.rowmap), u32(L.idx),
+                          u32(L.head), u32(L.oflag), u32(L.tflag), u32(L.words)};
+    const BaIntr gi = {group, n_groups, refine, reinterpret_cast<BaGroup *>(b + L.gstate), f64(L.gU), f64(L.gvec), f64(L.gdots),
+                       f64(L.Uck), f64(L.ipart), u32(L.icount), u32(L.gflag)};
+    const auto blocks = [](uint64_t items, uint64_t per_block) {
+        const uint64_t want = (items + per_block - 1) / per_block;
+        return dim3((unsigned)(want < 1 ? 1 : want < kMaxBlocks ? want : kMaxBlocks));
+    };
+    const uint64_t singles = (uint64_t)n_images + (kI ? n_groups : 0u);             // a thread per image, then one per group
+    const dim3 threads(kThreads), per_image(n_images), by_image((unsigned)((singles + kThreads - 1) / kThreads)), per_group(n_groups);
+    const dim3 by_track = blocks(track_capacity, kThreads / G);
+    uint64_t most = n_rows > n_images ? n_rows : n_images;
+    if (kI && n_groups > most) most = n_groups;
+    hipLaunchKernelGGL(ba_init<kI>, blocks(most > 16 ? most : 16, kThreads), threads, 0, stream, in, gi, poses, camera_fixed, lambda0, sc);
+    hipLaunchKernelGGL(ba_setup_tracks, by_track, threads, 0, stream, in, points, obs_state, sc);
+    hipLaunchKernelGGL(ba_setup_images<kI>, per_image, threads, 0, stream, in, sc);
+    if constexpr (kI) hipLaunchKernelGGL(ba_setup_groups, per_group, threads, 0, stream, in, gi, sc);
+    for (unsigned it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL(ba_track_lin<kI>, by_track, threads, 0, stream, in, gi, thr2, sc);
+        hipLaunchKernelGGL(ba_image_lin<kI>, per_image, threads, 0, stream, in, gi, thr2, sc);
+        if constexpr (kI) hipLaunchKernelGGL(ba_group_lin, per_group, threads, 0, stream, in, gi, sc);
+        hipLaunchKernelGGL(ba_scalar<kI>, dim3(1), threads, 0, stream, in, gi, (unsigned)kModeStart, tol2, it, sc, trace);
+        for (unsigned s = 0; s < cg_iterations; ++s) {
+            hipLaunchKernelGGL(ba_track_apply<kI>, by_track, threads, 0, stream, in, gi, sc);
+            hipLaunchKernelGGL(ba_image_apply<kI>, per_image, threads, 0, stream, in, gi, sc);
+            if constexpr (kI) hipLaunchKernelGGL(ba_group_apply, per_group, threads, 0, stream, in, gi, sc);
+            hipLaunchKernelGGL(ba_scalar<kI>, dim3(1), threads, 0, stream, in, gi, (unsigned)kModeAlpha, tol2, it, sc, trace);
+            hipLaunchKernelGGL(ba_cg_update<kI>, by_image, threads, 0, stream, in, gi, sc);
+            hipLaunchKernelGGL(ba_scalar<kI>, dim3(1), threads, 0, stream, in, gi, (unsigned)kModeBeta, tol2, it, sc, trace);
+        }
+        hipLaunchKernelGGL(ba_cam_step<kI>, by_image, threads, 0, stream, in, gi, sc);
+        hipLaunchKernelGGL(ba_track_step<kI>, by_track, threads, 0, stream, in, gi, thr2, sc);
+        hipLaunchKernelGGL(ba_scalar<kI>, dim3(1), threads, 0, stream, in, gi, (unsigned)kModeAccept, tol2, it, sc, trace);
+    }
+    hipLaunchKernelGGL(ba_final_images<kI>, by_image, threads, 0, stream, in, gi, poses, sc, poses_out, intrinsics_out, group_out);
+    hipLaunchKernelGGL(ba_final_tracks<kI>, by_track, threads, 0, stream, in, points, thr2, sc, poses_out, intrinsics_out, points_out,
+                       obs_state_out, counts);
 }
 }  // namespace
 
 uint64_t bundle_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity) {
-    return layout(n_images, n_rows, track_capacity, obs_capacity).total;
+    return layout(n_images, n_rows, track_capacity, obs_capacity, false, 0).total;
 }
 unsigned bundle_launches(unsigned iterations, unsigned cg_iterations) { return 5 + iterations * (6 + 5 * cg_iterations); }
 
@@ -771,40 +1262,29 @@ void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image
     if (n_images == 0) return;
     const BaIn in = {kps, image_offsets, n_rows, n_images, track_offsets, track_capacity, obs_row, obs_image, obs_capacity, table_counts,
                      intrinsics};
-    unsigned char *b = static_cast<unsigned char *>(scratch);
-    const BaLayout L = layout(n_images, n_rows, track_capacity, obs_capacity);
-    const auto f64 = [&](uint64_t at) { return reinterpret_cast<double *>(b + at); };
-    const auto u32 = [&](uint64_t at) { return reinterpret_cast<unsigned *>(b + at); };
-    const BaScratch sc = {reinterpret_cast<RsPose *>(b + L.cam), f64(L.pt), f64(L.U), f64(L.V), f64(L.W), f64(L.vec), f64(L.y),
-                          f64(L.tcost), f64(L.dots), f64(L.scal), reinterpret_cast<unsigned long long *>(b + L.rowmap), u32(L.idx),
-                          u32(L.head), u32(L.oflag), u32(L.tflag), u32(L.words)};
-    const auto blocks = [](uint64_t items, uint64_t per_block) {
-        const uint64_t want = (items + per_block - 1) / per_block;
-        return dim3((unsigned)(want < 1 ? 1 : want < kMaxBlocks ? want : kMaxBlocks));
-    };
-    const dim3 threads(kThreads), per_image(n_images), by_image((n_images + kThreads - 1) / kThreads);
-    const dim3 by_track = blocks(track_capacity, kThreads / G);
-    const uint64_t most = n_rows > n_images ? n_rows : n_images;
-    hipLaunchKernelGGL(ba_init, blocks(most > 16 ? most : 16, kThreads), threads, 0, stream, in, poses, camera_fixed, lambda0, sc);
-    hipLaunchKernelGGL(ba_setup_tracks, by_track, threads, 0, stream, in, points, obs_state, sc);
-    hipLaunchKernelGGL(ba_setup_images, per_image, threads, 0, stream, in, sc);
-    for (unsigned it = 0; it < iterations; ++it) {
-        hipLaunchKernelGGL(ba_track_lin, by_track, threads, 0, stream, in, thr2, sc);
-        hipLaunchKernelGGL(ba_image_lin, per_image, threads, 0, stream, in, thr2, sc);
-        hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeStart, tol2, it, sc, trace);
-        for (unsigned s = 0; s < cg_iterations; ++s) {
-            hipLaunchKernelGGL(ba_track_apply, by_track, threads, 0, stream, in, sc);
-            hipLaunchKernelGGL(ba_image_apply, per_image, threads, 0, stream, in, sc);
-            hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeAlpha, tol2, it, sc, trace);
-            hipLaunchKernelGGL(ba_cg_update, by_image, threads, 0, stream, in, sc);
-            hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeBeta, tol2, it, sc, trace);
-        }
-        hipLaunchKernelGGL(ba_cam_step, by_image, threads, 0, stream, in, sc);
-        hipLaunchKernelGGL(ba_track_step, by_track, threads, 0, stream, in, thr2, sc);
-        hipLaunchKernelGGL(ba_scalar, dim3(1), threads, 0, stream, in, (unsigned)kModeAccept, tol2, it, sc, trace);
-    }
-    hipLaunchKernelGGL(ba_final_images, by_image, threads, 0, stream, in, poses, sc, poses_out);
-    hipLaunchKernelGGL(ba_final_tracks, by_track, threads, 0, stream, in, points, thr2, sc, poses_out, points_out, obs_state_out, counts);
+    launch<false>(scratch, in, nullptr, 0, 0, points, poses, obs_state, camera_fixed, thr2, lambda0, iterations, cg_iterations, tol2,
+                  poses_out, points_out, nullptr, nullptr, obs_state_out, trace, counts, stream);
+}
+
+uint64_t bundle_intrinsics_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity,
+                                         unsigned n_groups) {
+    return layout(n_images, n_rows, track_capacity, obs_capacity, true, n_groups).total;
+}
+unsigned bundle_intrinsics_launches(unsigned iterations, unsigned cg_iterations) { return 6 + iterations * (7 + 6 * cg_iterations); }
+
+void launch_bundle_adjust_intrinsics(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
+                                     const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row,
+                                     const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts, const float *points,
+                                     const float *intrinsics, const float *poses, const unsigned *obs_state,
+                                     const unsigned *camera_fixed, const unsigned *camera_group, unsigned n_groups, unsigned refine,
+                                     double thr2, double lambda0, unsigned iterations, unsigned cg_iterations, double tol2,
+                                     float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
+                                     unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
+    if (n_images == 0) return;
+    const BaIn in = {kps, image_offsets, n_rows, n_images, track_offsets, track_capacity, obs_row, obs_image, obs_capacity, table_counts,
+                     intrinsics};
+    launch<true>(scratch, in, camera_group, n_groups, refine, points, poses, obs_state, camera_fixed, thr2, lambda0, iterations,
+                 cg_iterations, tol2, poses_out, points_out, intrinsics_out, group_out, obs_state_out, trace, counts, stream);
 }
 
 }  // namespace lfmkd

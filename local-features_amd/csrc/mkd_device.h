@@ -381,6 +381,20 @@ void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image
                           const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0,
                           unsigned iterations, unsigned cg_iterations, double tol2, float *poses_out, float *points_out,
                           unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
+// the same with shared intrinsics refined (lf_mkd_bundle_adjust_intrinsics_device): the same kernels in their double-K form
+// and three per-group ones, bundle_intrinsics_launches(..) launches over bundle_intrinsics_scratch_bytes(..) bytes.
+// camera_group and group_out may be null; intrinsics_out may be intrinsics.
+uint64_t bundle_intrinsics_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity,
+                                         unsigned n_groups);
+unsigned bundle_intrinsics_launches(unsigned iterations, unsigned cg_iterations);
+void launch_bundle_adjust_intrinsics(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
+                                     const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row,
+                                     const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts, const float *points,
+                                     const float *intrinsics, const float *poses, const unsigned *obs_state,
+                                     const unsigned *camera_fixed, const unsigned *camera_group, unsigned n_groups, unsigned refine,
+                                     double thr2, double lambda0, unsigned iterations, unsigned cg_iterations, double tol2,
+                                     float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
+                                     unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -291,8 +291,10 @@ __host__ __device__ __forceinline__ bool rs_candidate_pose(const RsCorr (&s)[3],
 }
 
 // Step 4 for an f64 pose, tri_error2's operations: p = R X + t (each row summed left to right); false if not in front.
-template <typename T>
-__host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const float *K, const RsCorrT<T> &c, double &e2) {
+// (K is float as the arrays hold it, or double for bundle adjustment's refined intrinsics: double(K[i]) is then the identity,
+// and a widened f32 value gives the same bits either way)
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const KT *K, const RsCorrT<T> &c, double &e2) {
     double p[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) p[r] = P.R[3 * r] * double(c.X) + P.R[3 * r + 1] * double(c.Y) + P.R[3 * r + 2] * double(c.Z) + P.t[r];
@@ -301,14 +303,14 @@ __host__ __device__ __forceinline__ bool rs_error2(const RsPose &P, const float 
     e2 = ex * ex + ey * ey;
     return p[2] > 0.0;
 }
-template <typename T>
-__host__ __device__ __forceinline__ bool rs_inlier(const RsPose &P, const float *K, const RsCorrT<T> &c, double thr2, double &e2) {
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ bool rs_inlier(const RsPose &P, const KT *K, const RsCorrT<T> &c, double thr2, double &e2) {
     const bool front = rs_error2(P, K, c, e2);
     return front && e2 <= thr2;
 }
 // the MSAC term of a correspondence: min(e^2, thr2), thr2 for a point not in front (or a NaN)
-template <typename T>
-__host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const float *K, const RsCorrT<T> &c, double thr2) {
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const KT *K, const RsCorrT<T> &c, double thr2) {
     double e2;
     return rs_inlier(P, K, c, thr2, e2) ? e2 : thr2;
 }
@@ -317,12 +319,12 @@ __host__ __device__ __forceinline__ double rs_cost(const RsPose &P, const float 
 // p = q + t, a = fx / p_z, b = fy / p_z: d e_x / d p = (a, 0, -a p_x / p_z), d e_y / d p = (0, b, -b p_y / p_z), d p / d w =
 // -2 [q]x (C(w) = I + 2 [w]x + O(w^2)), d p / d dt = I.
 // The rows themselves (bundle adjustment, mkd_bundle_math.h, needs them beside the point's): Jx, Jy, the residual and the
-// factors a, b, gx, gy of d e / d p.
+// factors a, b, gx, gy of d e / d p, and the normalised projection (u, v) = (p_x / p_z, p_y / p_z) the residual was formed from.
 struct RsRows {
-    double Jx[6], Jy[6], ex, ey, a, b, gx, gy;
+    double Jx[6], Jy[6], ex, ey, a, b, gx, gy, u, v;
 };
-template <typename T>
-__host__ __device__ __forceinline__ void rs_gn_rows(const RsPose &P, const float *K, const RsCorrT<T> &c, RsRows &o) {
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ void rs_gn_rows(const RsPose &P, const KT *K, const RsCorrT<T> &c, RsRows &o) {
     double q[3], p[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -338,7 +340,7 @@ __host__ __device__ __forceinline__ void rs_gn_rows(const RsPose &P, const float
     const double Jy[6] = {2.0 * (gy * q[1] - b * q[2]), 2.0 * (0.0 - gy * q[0]), 2.0 * (b * q[0]), 0.0, b, gy};
 #pragma unroll
     for (int i = 0; i < 6; ++i) o.Jx[i] = Jx[i], o.Jy[i] = Jy[i];
-    o.a = a, o.b = b, o.gx = gx, o.gy = gy;
+    o.a = a, o.b = b, o.gx = gx, o.gy = gy, o.u = px, o.v = py;
 }
 // the 27 values of two rows and their residual: J^T J's upper triangle row by row, then J^T e
 __host__ __device__ __forceinline__ void rs_gn_products(const RsRows &r, double *w) {
@@ -350,8 +352,8 @@ __host__ __device__ __forceinline__ void rs_gn_products(const RsRows &r, double 
 #pragma unroll
     for (int i = 0; i < 6; ++i) w[21 + i] = r.Jx[i] * r.ex + r.Jy[i] * r.ey;
 }
-template <typename T>
-__host__ __device__ __forceinline__ void rs_gn_terms(const RsPose &P, const float *K, const RsCorrT<T> &c, double *w) {
+template <typename T, typename KT>
+__host__ __device__ __forceinline__ void rs_gn_terms(const RsPose &P, const KT *K, const RsCorrT<T> &c, double *w) {
     RsRows r;
     rs_gn_rows(P, K, c, r);
     rs_gn_products(r, w);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -51,6 +51,9 @@ descriptor row is copied for it.
   with --bundle ITERS (1 .. 64; needs --pose; implies LocalFeatures.bundle_adjust (lf_mkd_bundle_adjust_device) after the rounds, in
   --triangulate) poses and points refined jointly     place: ITERS Levenberg-Marquardt iterations of 10 CG steps over the
                                                      triangulation's inlier observations, the images posed before the rounds held
+  with --refine-focal / --refine-principal (need      LocalFeatures.bundle_adjust_intrinsics (lf_mkd_bundle_adjust_intrinsics_device)
+  --bundle) the one lens of the images refined too    in its place: one group, the focal scale and / or the principal point's shift;
+                                                     the refined focal is printed beside the bundle lines
 
 and prints one line per edge, ranked by the matches the geometry keeps; with --tracks also how many tracks of two and of three
 or more keypoints there are, how many of them are consistent (no two keypoints of one image), the longest one, and the share
@@ -113,7 +116,8 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
-                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0, bundle=0):
+                     table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0, bundle=0,
+                     refine_focal=False, refine_principal=False):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -149,7 +153,10 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     poses, or True: the edge with the most links with parallax is the initial pair, [I | 0] and its [R | t], and every other
     image stays all zero, which says "not registered"; without, those five are None.  `bundle` = ITERS > 0 (needs `triangulate`)
     then runs LocalFeatures.bundle_adjust in place on tri_poses and tri_points and adds bundle_trace [ITERS,8], bundle_counts [4],
-    bundle_obs_state and bundle_rms [2] (before, after); None without."""
+    bundle_obs_state and bundle_rms [2] (before, after); None without.  With `refine_focal` / `refine_principal` the bundle step
+    is LocalFeatures.bundle_adjust_intrinsics with every image in one group: the shared focal length (its scale) and / or the
+    principal point (its shift) are refined too, bundle_trace is [ITERS,9] and bundle_counts [5], bundle_groups [1,3] = (s, dx,
+    dy), and `intrinsics` [n,4] (what `pose` gave, per image) is updated in place for everything after."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -246,7 +253,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             t_kps = feats.gather_track_rows(kps, t_rows, t_counts)
         tri_poses = tri_points = tri_stats = tri_err = tri_state = None
         register_rounds = [] if register else None       # (None without `register`, like every output that was not asked for)
-        bundle_trace = bundle_counts = bundle_state = bundle_rms = None
+        bundle_trace = bundle_counts = bundle_state = bundle_rms = bundle_groups = None
         if triangulate is not None and triangulate is not False:
             if pose is None:
                 raise RuntimeError("match_collection: triangulate needs pose (the cameras' intrinsics)")
@@ -271,14 +278,21 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 register_rounds.append((r_stats, tri_stats))
             if bundle:
                 # poses and points jointly, in place; the images that had a pose before the rounds hold theirs (the gauge)
-                before = (tri_poses.clone(), tri_points.clone())
-                tri_poses, tri_points, bundle_state, bundle_trace, bundle_counts = feats.bundle_adjust(
-                    kps, o, (t_off, t_rows, t_img, t_counts), tri_points, intr, tri_poses, obs_state=tri_state, camera_fixed=held,
-                    iterations=bundle, out_poses=tri_poses, out_points=tri_points)
+                before = (tri_poses.clone(), tri_points.clone(), intr.clone())
+                if refine_focal or refine_principal:
+                    # ... and the one lens all the images share, in place too
+                    tri_poses, tri_points, intr, bundle_groups, bundle_state, bundle_trace, bundle_counts = feats.bundle_adjust_intrinsics(
+                        kps, o, (t_off, t_rows, t_img, t_counts), tri_points, intr, tri_poses, obs_state=tri_state, camera_fixed=held,
+                        refine_focal=refine_focal, refine_principal=refine_principal, iterations=bundle, out_poses=tri_poses,
+                        out_points=tri_points, out_intrinsics=intr)
+                else:
+                    tri_poses, tri_points, bundle_state, bundle_trace, bundle_counts = feats.bundle_adjust(
+                        kps, o, (t_off, t_rows, t_img, t_counts), tri_points, intr, tri_poses, obs_state=tri_state, camera_fixed=held,
+                        iterations=bundle, out_poses=tri_poses, out_points=tri_points)
                 active = bundle_state >= 1
-                bundle_rms = torch.stack([reprojection_rms(kps, t_off, t_rows, t_img, intr, P, X, active) for P, X in
-                                          (before, (tri_poses, tri_points))])
-    return dict(bundle_trace=bundle_trace, bundle_counts=bundle_counts, bundle_obs_state=bundle_state, bundle_rms=bundle_rms,
+                bundle_rms = torch.stack([reprojection_rms(kps, t_off, t_rows, t_img, K, P, X, active) for P, X, K in
+                                          (before, (tri_poses, tri_points, intr))])
+    return dict(bundle_groups=bundle_groups, intrinsics=intr if pose is not None else None, bundle_trace=bundle_trace, bundle_counts=bundle_counts, bundle_obs_state=bundle_state, bundle_rms=bundle_rms,
                 register_rounds=register_rounds, tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
                 edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
@@ -311,11 +325,15 @@ def bundle_lines(out):
     """one line per Levenberg-Marquardt iteration of `bundle`, then the rms before and after"""
     if out["bundle_trace"] is None:
         return []
-    free_c, free_p, active, accepted = out["bundle_counts"].cpu().tolist()
+    free_c, free_p, active, accepted = out["bundle_counts"].cpu().tolist()[:4]
     lines = [f"{free_c} free cameras, {free_p} free points, {active} active observations, {accepted} steps accepted"]
-    for k, (cost, new, lam, ok, steps, inl, hc, hp) in enumerate(out["bundle_trace"].cpu().tolist()):
+    for k, (cost, new, lam, ok, steps, inl, hc, hp, *hg) in enumerate(out["bundle_trace"].cpu().tolist()):
         lines.append(f"iteration {k + 1}: cost {cost:.1f} -> {new:.1f} at lambda {lam:.2e}, {'accepted' if ok else 'rejected'}, "
-                     f"{int(steps)} CG steps, {int(inl)} inliers, {int(hc)} cameras and {int(hp)} points held")
+                     f"{int(steps)} CG steps, {int(inl)} inliers, {int(hc)} cameras and {int(hp)} points held"
+                     + (f", {int(hg[0])} lenses held" if hg else ""))
+    if out.get("bundle_groups") is not None:
+        (s, dx, dy), K = out["bundle_groups"].cpu().tolist()[0], out["intrinsics"].cpu().tolist()[0]
+        lines.append(f"refined focal {K[0]:.2f} (x {s:.5f}), principal point ({K[2]:.2f}, {K[3]:.2f}) (moved by ({dx:.2f}, {dy:.2f}))")
     before, after = out["bundle_rms"].cpu().tolist()
     lines.append(f"rms reprojection error {before:.3f} px -> {after:.3f} px")
     return lines
@@ -351,6 +369,7 @@ def main():
     args = sys.argv[1:]
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
     expand, min_shared, pose, triangulate, register, bundle = None, 8, None, None, 0, 0
+    refine_focal = refine_principal = False
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -382,6 +401,10 @@ def main():
             tracks = table = True
             bundle = int(args.pop(0))
             triangulate = True if triangulate is None else triangulate
+        elif a == "--refine-focal":
+            refine_focal = True
+        elif a == "--refine-principal":
+            refine_principal = True
         elif a == "--all":
             mode = "all"
         elif a in ("--window", "--retrieve", "--select") and args and args[0].isdigit() and int(args[0]) > 0:
@@ -391,11 +414,11 @@ def main():
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (triangulate is not None and pose is None) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (triangulate is not None and pose is None) or ((refine_focal or refine_principal) and not bundle) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images; --triangulate, --register and --bundle need --pose)", file=sys.stderr)
+              "number of images; --triangulate, --register and --bundle need --pose, --refine-focal and --refine-principal --bundle)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -404,7 +427,8 @@ def main():
     if pose is not None and pose[1] is None:                    # the principal point: the middle of the frame
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
-                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register, bundle=bundle)
+                           min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register, bundle=bundle,
+                           refine_focal=refine_focal, refine_principal=refine_principal)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]

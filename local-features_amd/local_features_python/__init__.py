@@ -14,7 +14,7 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, VERIFY_NO_REFINE, Comm,
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, VERIFY_NO_REFINE, Comm,
                    MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
@@ -23,7 +23,7 @@ __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXAC
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
            "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan",
-           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "covisibility_plan"]
+           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "BA_REFINE_FOCAL", "BA_REFINE_PRINCIPAL", "covisibility_plan"]
 
 
 class Keypoint:
@@ -1074,6 +1074,73 @@ class LocalFeatures:
                                                  iterations=iterations, cg_iterations=cg_iterations, cg_tol=cg_tol,
                                                  stream=s.cuda_stream)
         return out_poses, out_points, so, trace, cnt
+
+    def bundle_adjust_intrinsics(self, kps, offsets, table, points, intrinsics, poses, obs_state=None, camera_fixed=None,
+                                 camera_group=None, n_groups=1, refine_focal=True, refine_principal=False, max_reproj_px=4.0,
+                                 lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, out_poses=None, out_points=None,
+                                 out_intrinsics=None, obs_state_out=True, stream=None):
+        """Self-calibrating bundle adjustment (lf_mkd_bundle_adjust_intrinsics_device): bundle_adjust with the intrinsics of the
+        images that share a lens refined beside the poses and the points.  The arguments are bundle_adjust's; camera_group
+        [n_images] int32 names the lens of every image (None: one lens; an id >= n_groups: that image's intrinsics stay), and
+        a group's focal lengths are scaled by one factor s (refine_focal) and its principal points shifted by one (dx, dy)
+        (refine_principal).  out_intrinsics names the tensor to write, `intrinsics` itself for a call in place.  Returns device
+        tensors (poses, points, intrinsics [n_images, 4] float32, groups [n_groups, 3] float32 = (s, dx, dy), obs_state or
+        None, trace [iterations, 9] float64 = bundle_adjust's eight and the held groups, counts [5] int32 = its four and the
+        free groups).  With nothing refined every value shared with bundle_adjust is that call's, bit for bit.  Nothing is read
+        back: asynchronous on `stream`, capturable once warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if len(table) == 5:
+            t_off, rows, images, _, counts = table
+        else:
+            t_off, rows, images, counts = table
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (ok(t_off, torch.int64) and t_off.dim() == 1 and t_off.numel() >= 1 and ok(rows, torch.int32)
+                    and images is not None and ok(images, torch.int32) and rows.numel() == images.numel()
+                    and ok(counts, torch.int32) and counts.numel() >= 2):
+                raise RuntimeError("bundle_adjust_intrinsics: table must be (offsets int64, rows int32, images int32, counts int32) "
+                                   "contiguous device tensors as track_table returned them with image_offsets")
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("bundle_adjust_intrinsics: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1):
+                raise RuntimeError("bundle_adjust_intrinsics: offsets must be a contiguous int64 [n_images + 1] device tensor")
+            n_images, tcap, ocap = offsets.numel() - 1, t_off.numel() - 1, rows.numel()
+            if not (ok(points, torch.float32) and points.numel() == 4 * tcap):
+                raise RuntimeError("bundle_adjust_intrinsics: points must be a contiguous float32 [track_capacity, 4] device tensor")
+            if not (ok(intrinsics, torch.float32) and intrinsics.numel() == 4 * n_images and ok(poses, torch.float32)
+                    and poses.numel() == 12 * n_images):
+                raise RuntimeError("bundle_adjust_intrinsics: intrinsics must be float32 [n_images, 4] and poses float32 "
+                                   "[n_images, 12] contiguous device tensors")
+            for name, x in (("obs_state", obs_state), ("camera_fixed", camera_fixed), ("camera_group", camera_group)):
+                if x is not None and not (ok(x, torch.int32) and x.numel() == (ocap if name == "obs_state" else n_images)):
+                    raise RuntimeError("bundle_adjust_intrinsics: %s must be a contiguous int32 device tensor, one entry per %s"
+                                       % (name, "observation" if name == "obs_state" else "image"))
+            outs = []
+            for name, x, width, n in (("out_poses", out_poses, 12, n_images), ("out_points", out_points, 4, tcap),
+                                      ("out_intrinsics", out_intrinsics, 4, n_images)):
+                if x is None:
+                    x = torch.empty((n, width), dtype=torch.float32, device=dev)
+                elif not (ok(x, torch.float32) and x.numel() == width * n):
+                    raise RuntimeError("bundle_adjust_intrinsics: %s must be a contiguous float32 [., %d] device tensor" % (name, width))
+                outs.append(x)
+            out_poses, out_points, out_intrinsics = outs
+            groups = torch.zeros((n_groups, 3), dtype=torch.float32, device=dev)
+            so = torch.full((ocap,), -1, dtype=torch.int32, device=dev) if obs_state_out else None
+            trace = torch.zeros((iterations, 9), dtype=torch.float64, device=dev)
+            cnt = torch.zeros((5,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            refine = (BA_REFINE_FOCAL if refine_focal else 0) | (BA_REFINE_PRINCIPAL if refine_principal else 0)
+            with self._lock:
+                self._inner.bundle_adjust_intrinsics_device(
+                    ptr(kps), offsets.data_ptr(), n_images, kps.shape[0], t_off.data_ptr(), tcap, ptr(rows), ptr(images), ocap,
+                    counts.data_ptr(), ptr(points), ptr(intrinsics), ptr(poses), ptr(out_poses), ptr(out_points), ptr(out_intrinsics),
+                    trace.data_ptr(), cnt.data_ptr(), d_obs_state=ptr(obs_state), d_camera_fixed=ptr(camera_fixed),
+                    d_camera_group=ptr(camera_group), n_groups=n_groups, refine=refine, d_group_out=ptr(groups),
+                    d_obs_state_out=ptr(so), max_reproj_px=max_reproj_px, lambda0=lambda0, iterations=iterations,
+                    cg_iterations=cg_iterations, cg_tol=cg_tol, stream=s.cuda_stream)
+        return out_poses, out_points, out_intrinsics, groups, so, trace, cnt
 
     def match_q8_guided_batch(self, qa, kps_a, offsets_a, qb, kps_b, offsets_b, model, kind="homography", threshold=None,
                               ratio=0.8, mutual=True, both=False, stream=None):

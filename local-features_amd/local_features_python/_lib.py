@@ -52,6 +52,7 @@ SYMBOLS = (
     "lf_mkd_triangulate_tracks", "lf_mkd_triangulate_tracks_device",
     "lf_mkd_resect_camera", "lf_mkd_resect_cameras_device",
     "lf_mkd_bundle_adjust", "lf_mkd_bundle_adjust_device",
+    "lf_mkd_bundle_adjust_intrinsics", "lf_mkd_bundle_adjust_intrinsics_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -62,6 +63,8 @@ LINK_TABLE_LOCAL = 1     # LF_MKD_LINK_TABLE_LOCAL: lf_mkd_link_table_device wri
 SELECT_SKIP_SELF = 1     # LF_MKD_SELECT_SKIP_SELF: lf_mkd_select_edges_device does not offer column i to row i
 SELECT_UNIQUE = 2        # LF_MKD_SELECT_UNIQUE: one pool, every unordered pair at most once, as (smaller, larger)
 COVIS_ACCUMULATE = 1     # LF_MKD_COVIS_ACCUMULATE: lf_mkd_covisibility_device adds to what d_covis holds
+BA_REFINE_FOCAL = 1      # LF_MKD_BA_REFINE_FOCAL: lf_mkd_bundle_adjust_intrinsics_device refines the groups' focal scale
+BA_REFINE_PRINCIPAL = 2  # LF_MKD_BA_REFINE_PRINCIPAL: ... and the groups' principal-point shift
 RESECT_ALL = 1           # LF_MKD_RESECT_ALL: lf_mkd_resect_cameras_device resects registered images too
 COVIS_FORM_LDS = 256     # LF_MKD_COVIS_FORM_LDS: in covisibility_plan's form, workgroups count in LDS first
 SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
@@ -193,6 +196,12 @@ def load_library():
                                               ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_bundle_adjust.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, ctypes.c_float,
                                        ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp]
+    L.lf_mkd_bundle_adjust_intrinsics_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, u32, u32,
+                                                         ctypes.c_float, ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp,
+                                                         vp, vp, vp, vp]
+    L.lf_mkd_bundle_adjust_intrinsics.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u32,
+                                                  ctypes.c_float, ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp,
+                                                  vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -709,6 +718,43 @@ class MkdHandle:
                     "lf_mkd_bundle_adjust")
         return po[:n_images], xo[:n_tracks], so[:n_obs] if obs_state_out else None, trace, counts
 
+    def bundle_adjust_intrinsics(self, kps, image_offsets, track_offsets, obs_row, obs_image, points, intrinsics, poses,
+                                 obs_state=None, camera_fixed=None, camera_group=None, n_groups=1, refine=BA_REFINE_FOCAL,
+                                 max_reproj_px=4.0, lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, flags=0,
+                                 obs_state_out=True):
+        """lf_mkd_bundle_adjust_intrinsics: bundle_adjust's arrays, camera_group uint32 [n_images] (the lens of an image; None:
+        one group; an id >= n_groups: constant intrinsics) and refine = BA_REFINE_FOCAL | BA_REFINE_PRINCIPAL -> (poses, points,
+        intrinsics [n_images,4] f32, groups [n_groups,3] f32 = (s, dx, dy), obs_state or None, trace float64 [iterations,9] =
+        bundle_adjust's eight and the held groups, counts uint32 [5] = its four and the free groups)."""
+        k = np.ascontiguousarray(kps, np.float32).reshape(-1, 5)
+        ioff = np.ascontiguousarray(image_offsets, np.uint64).reshape(-1)
+        toff = np.ascontiguousarray(track_offsets, np.uint64).reshape(-1)
+        row, img = np.ascontiguousarray(obs_row, np.int32).reshape(-1), np.ascontiguousarray(obs_image, np.uint32).reshape(-1)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        K = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        n_images, n_tracks, n_obs = len(K), len(pts), len(row)
+        st = None if obs_state is None else np.ascontiguousarray(obs_state, np.uint32).reshape(-1)
+        fx = None if camera_fixed is None else np.ascontiguousarray(camera_fixed, np.uint32).reshape(-1)
+        gr = None if camera_group is None else np.ascontiguousarray(camera_group, np.uint32).reshape(-1)
+        if (len(ioff) != n_images + 1 or len(toff) != n_tracks + 1 or len(img) != n_obs or len(P) != n_images or
+                (st is not None and len(st) != n_obs) or (fx is not None and len(fx) != n_images) or
+                (gr is not None and len(gr) != n_images)):
+            raise RuntimeError("bundle_adjust_intrinsics: image_offsets needs n_images + 1 entries, track_offsets n_tracks + 1, "
+                               "obs_row, obs_image and obs_state one entry per observation, intrinsics, poses, camera_fixed and "
+                               "camera_group one row per image")
+        po, xo = np.zeros((max(n_images, 1), 12), np.float32), np.zeros((max(n_tracks, 1), 4), np.float32)
+        ko, go = np.zeros((max(n_images, 1), 4), np.float32), np.zeros((max(n_groups, 1), 3), np.float32)
+        so = np.zeros(max(n_obs, 1), np.uint32) if obs_state_out else None
+        trace, counts = np.zeros((max(iterations, 1), 9), np.float64), np.zeros(5, np.uint32)
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_bundle_adjust_intrinsics(
+            self._h, at(k), ioff.ctypes.data, n_images, len(k), toff.ctypes.data, n_tracks, at(row), at(img), n_obs, at(pts), at(K),
+            at(P), at(st), at(fx), at(gr), n_groups, refine, max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, flags,
+            po.ctypes.data, xo.ctypes.data, ko.ctypes.data, go.ctypes.data, so.ctypes.data if obs_state_out else None,
+            trace.ctypes.data, counts.ctypes.data), "lf_mkd_bundle_adjust_intrinsics")
+        return po[:n_images], xo[:n_tracks], ko[:n_images], go[:n_groups], so[:n_obs] if obs_state_out else None, trace, counts
+
     def orient_keypoints_blocked(self, extremum_data, n_extrema, indices, max_out, block_len=256):
         """The reference's ExtremumLocations.data (blocked) + FilteredExtrema.indices in, KeypointIndices-style arrays out:
         (extremum index per keypoint, orientation per keypoint, keypoints [m,5])."""
@@ -1007,6 +1053,22 @@ class MkdHandle:
             obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_obs_state, d_camera_fixed, max_reproj_px, lambda0,
             iterations, cg_iterations, cg_tol, flags, d_poses_out, d_points_out, d_obs_state_out, d_trace, d_counts, s),
             "lf_mkd_bundle_adjust_device")
+
+    def bundle_adjust_intrinsics_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity,
+                                        d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses,
+                                        d_poses_out, d_points_out, d_intrinsics_out, d_trace, d_counts, d_obs_state=None,
+                                        d_camera_fixed=None, d_camera_group=None, n_groups=1, refine=BA_REFINE_FOCAL,
+                                        d_group_out=None, d_obs_state_out=None, max_reproj_px=4.0, lambda0=1e-3, iterations=10,
+                                        cg_iterations=10, cg_tol=0.1, flags=0, stream=None):
+        """lf_mkd_bundle_adjust_intrinsics_device: bundle_adjust_device with the intrinsics of the images that share a lens
+        refined -- d_camera_group uint32 [n_images] (nullable: one group), refine = BA_REFINE_FOCAL | BA_REFINE_PRINCIPAL;
+        d_intrinsics_out [n_images][4] (may be d_intrinsics), d_group_out [n_groups][3] (nullable), d_trace f64
+        [iterations][9], d_counts uint32 [5] (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_bundle_adjust_intrinsics_device(
+            self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image,
+            obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_obs_state, d_camera_fixed, d_camera_group, n_groups,
+            refine, max_reproj_px, lambda0, iterations, cg_iterations, cg_tol, flags, d_poses_out, d_points_out, d_intrinsics_out,
+            d_group_out, d_obs_state_out, d_trace, d_counts, s), "lf_mkd_bundle_adjust_intrinsics_device")
 
     def match_guided_pairs_device(self, d_a, d_kps_a, d_offsets_a, na_total, d_b, d_kps_b, d_offsets_b, nb_total, d_model, n_pairs,
                                   d_match_ab, d_match_ba=None, kind=GUIDE_HOMOGRAPHY, threshold=3.0, ratio=0.8, flags=0,
