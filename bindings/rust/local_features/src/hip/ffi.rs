@@ -383,6 +383,23 @@ extern "C" {
                                            poses_out: *mut f32, points_out: *mut f32, intrinsics_out: *mut f32,
                                            group_out: *mut f32, obs_state_out: *mut u32, trace: *mut f64,
                                            counts: *mut u32) -> c_int;
+    // view-graph checks: the triangle vote over the posed edges (R [n_edges][9] and stats [n_edges][4] of the pose call), global
+    // rotations [n_images][9] by a tree and quaternion averaging over the kept edges, edge stats [4], an optional residual, image
+    // stats [4], an optional filtered match array (may be d_match), counts [8]; flags = LF_MKD_VIEW_GRAPH_USE_UNCHECKED (1),
+    // root = an image id or 0xFFFFFFFF; the plan needs no device; the host form takes host arrays
+    pub fn lf_mkd_view_graph_plan(n_images: u32, n_edges: u32, tree_rounds: u32, iterations: u32, flags: u32, with_match: u32,
+                                  launches: *mut u32, scratch_bytes: *mut u64, form: *mut u32) -> c_int;
+    pub fn lf_mkd_view_graph_device(h: *mut lf_mkd, d_edge_a: *const u32, d_edge_b: *const u32, n_edges: u32, d_R: *const f32,
+                                    d_pose_stats: *const u32, n_images: u32, max_loop_deg: f32, min_front: u32, root: u32,
+                                    tree_rounds: u32, iterations: u32, flags: u32, d_edge_offsets_a: *const u64,
+                                    ea_capacity: u64, d_match: *const i32, d_match_out: *mut i32, d_rotations: *mut f32,
+                                    d_edge_stats: *mut u32, d_edge_residual: *mut f32, d_image_stats: *mut u32,
+                                    d_counts: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_view_graph(h: *mut lf_mkd, edge_a: *const u32, edge_b: *const u32, n_edges: u32, R: *const f32,
+                             pose_stats: *const u32, n_images: u32, max_loop_deg: f32, min_front: u32, root: u32,
+                             tree_rounds: u32, iterations: u32, flags: u32, edge_offsets_a: *const u64, n_entries: u64,
+                             matches: *const i32, match_out: *mut i32, rotations: *mut f32, edge_stats: *mut u32,
+                             edge_residual: *mut f32, image_stats: *mut u32, counts: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -103,6 +103,10 @@ pub const RESECT_ALL: u32 = 1;
 /// `refine` of `lf_mkd_bundle_adjust_intrinsics` (`include/lf_mkd.h`, `LF_MKD_BA_REFINE_FOCAL`, `LF_MKD_BA_REFINE_PRINCIPAL`).
 pub const BA_REFINE_FOCAL: u32 = 1;
 pub const BA_REFINE_PRINCIPAL: u32 = 2;
+/// `flags` of `lf_mkd_view_graph` (`include/lf_mkd.h`, `LF_MKD_VIEW_GRAPH_USE_UNCHECKED`): edges that close no triangle are kept.
+pub const VIEW_GRAPH_USE_UNCHECKED: u32 = 1;
+/// `root` of `lf_mkd_view_graph` (`LF_MKD_VIEW_GRAPH_AUTO_ROOT`): the image with the most kept incident edges.
+pub const VIEW_GRAPH_AUTO_ROOT: u32 = 0xFFFF_FFFF;
 
 pub struct LocalFeaturesHip {
     h: *mut ffi::lf_mkd,
@@ -754,6 +758,43 @@ impl LocalFeaturesHip {
         groups.truncate(n_groups as usize);
         state.truncate(n_obs);
         Ok((poses_out, points_out, intrinsics_out, groups, state, trace, counts))
+    }
+
+    /// View-graph checks (`lf_mkd_view_graph`): the triangle vote over the posed `edges` (`rotations` and `pose_stats` as
+    /// `two_view_pose` returned them, one row per edge), global rotations of the `n_images` images by a breadth-first tree of
+    /// `tree_rounds` rounds and `iterations` sweeps of quaternion averaging over the kept edges.  `root` is an image id or
+    /// `VIEW_GRAPH_AUTO_ROOT`; `use_unchecked` keeps the edges that close no triangle too.
+    /// Returns (rotations, edge stats = closed, consistent, state, representative; the residual cosines; image stats = kept
+    /// edges, round, tree edge, rejected edges; counts = usable, supported, rejected, unchecked, kept, labelled, root, 0).
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn view_graph(&mut self, edges: &[(u32, u32)], rotations: &[[f32; 9]], pose_stats: &[[u32; 4]], n_images: u32,
+                      max_loop_deg: f32, min_front: u32, root: u32, tree_rounds: u32, iterations: u32, use_unchecked: bool)
+                      -> Result<(Vec<[f32; 9]>, Vec<[u32; 4]>, Vec<f32>, Vec<[u32; 4]>, [u32; 8]), Error> {
+        let n_edges = edges.len();
+        if rotations.len() != n_edges || pose_stats.len() != n_edges {
+            return Err(Error::BadArgument("view_graph: rotations and pose_stats need one row per edge".into()));
+        }
+        let edge_a: Vec<u32> = edges.iter().map(|e| e.0).collect();
+        let edge_b: Vec<u32> = edges.iter().map(|e| e.1).collect();
+        let mut out = vec![[0f32; 9]; (n_images as usize).max(1)];
+        let mut edge_stats = vec![[0u32; 4]; n_edges.max(1)];
+        let mut residual = vec![2f32; n_edges.max(1)];
+        let mut image_stats = vec![[0u32; 4]; (n_images as usize).max(1)];
+        let mut counts = [0u32; 8];
+        // SAFETY: host arrays sized as declared; n_edges and n_images bound what is read and written
+        unsafe {
+            check(self.h, ffi::lf_mkd_view_graph(
+                self.h, edge_a.as_ptr(), edge_b.as_ptr(), n_edges as u32, rotations.as_ptr() as *const f32,
+                pose_stats.as_ptr() as *const u32, n_images, max_loop_deg, min_front, root, tree_rounds, iterations,
+                if use_unchecked { VIEW_GRAPH_USE_UNCHECKED } else { 0 }, std::ptr::null(), 0, std::ptr::null(),
+                std::ptr::null_mut(), out.as_mut_ptr() as *mut f32, edge_stats.as_mut_ptr() as *mut u32, residual.as_mut_ptr(),
+                image_stats.as_mut_ptr() as *mut u32, counts.as_mut_ptr()))?;
+        }
+        out.truncate(n_images as usize);
+        edge_stats.truncate(n_edges);
+        residual.truncate(n_edges);
+        image_stats.truncate(n_images as usize);
+        Ok((out, edge_stats, residual, image_stats, counts))
     }
 
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches

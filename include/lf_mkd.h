@@ -1691,6 +1691,97 @@ int lf_mkd_get_pyramid_level(lf_mkd *h, uint32_t level, float *out, uint32_t *w,
  * Any of out / w / hgt / apron may be NULL. */
 int lf_mkd_get_pyramid_level_apron(lf_mkd *h, uint32_t level, float *out, uint32_t *w, uint32_t *hgt, uint32_t *apron);
 
+/* lf_mkd_view_graph_device checks the POSED edges of an edge list against each other and gives the images GLOBAL ROTATIONS:
+ * the relative rotations around every triangle of images must compose to the identity, an edge between two views of a
+ * repeated structure breaks every triangle it closes, and averaging the relative rotations over the edges that survive gives
+ * every image a drift-free rotation.  It reads d_edge_a / d_edge_b uint32 [n_edges], d_R f32 [n_edges][9] and d_pose_stats
+ * uint32 [n_edges][4] as lf_mkd_two_view_pose_device wrote them (x_b = R x_a + t, so R_b = R R_a for world-to-camera
+ * rotations) and, optionally, the matches' edge layout; it writes what the next calls take.
+ *  1 usable      edge e = (a, b) is USABLE iff a < n_images, b < n_images, a != b, d_pose_stats[e][2] != 0xFFFFFFFF,
+ *                d_pose_stats[e][0] >= min_front and all nine entries of R are finite.  lf_mkd_select_edges_device's 0xFFFFFFFF
+ *                padding, self edges and edges without a pose are ordinary input: not usable.
+ *  2 quaternion  a usable edge has the unit quaternion q_e (a -> b; (w, x, y, z), Hamilton product, the rotation of p (x) q
+ *                is the rotation of p times that of q) of R by Shepperd's method in f64 (+ - * / and sqrt, no contraction):
+ *                the largest of (trace, R00, R11, R22), the lowest index on a tie, says which component comes from the
+ *                diagonal (1 + 2 max - trace), the other three are the off-diagonal sums and differences; one normalisation.
+ *  3 representative   the lowest-indexed usable edge of an unordered pair {i, j}, whichever way it is stored.  q(x -> y) of a
+ *                pair is its representative's quaternion, conjugated if it is stored as (y, x).
+ *  4 vote        for a usable edge e = (a, b) and every image c outside {a, b} for which both pairs {b, c} and {c, a} have
+ *                representatives: closed += 1, L = q(c -> a) (x) (q(b -> c) (x) q_e), consistent += 1 iff
+ *                2 L_w^2 - 1 >= cos(max_loop_deg) (the cosine is formed once by the host, in double; no transcendental runs
+ *                on the device).  A duplicate edge votes with its own q_e and the other pairs' representatives.  Integer
+ *                counts: no order, run or CU count in them.
+ *  5 state       0 not usable; 1 rejected (closed > 0, consistent == 0); 2 unchecked (closed == 0); 3 supported
+ *                (consistent > 0).
+ *  6 kept        the supported representatives; under LF_MKD_VIEW_GRAPH_USE_UNCHECKED the unchecked representatives too.
+ *                (On synthetic rings of 24 .. 64 cameras with 10 .. 15 % wrong edges a wrong edge was never supported, but a
+ *                wrong edge that closes no triangle, let into the tree, ruined the rotations in about a quarter of the scenes:
+ *                hence the default.)
+ *  7 root        `root` if it is an image id; for LF_MKD_VIEW_GRAPH_AUTO_ROOT the image with the most kept incident edges, the
+ *                lowest id on a tie, chosen on the device.  It gets the identity and is labelled in round 0.
+ *  8 tree        in round r = 1 .. tree_rounds an image without a rotation that has kept edges to images labelled in rounds
+ *                < r takes q_i = normalise(q(j -> i) (x) q_j) over the best of them: the state first (larger), then
+ *                d_pose_stats[.][0] (larger), then the edge index (lower).  Rounds are level-synchronous.
+ *  9 averaging   `iterations` sweeps, double-buffered; every labelled image but the root takes part in each.  The predictions
+ *                p = q(j -> i) (x) q_j over its kept edges to labelled images are taken in ascending j, each negated iff
+ *                p . q_i < 0, and summed per component in the 4-SLOT canonical order of track triangulation: term k (k = 0,
+ *                1, .. in ascending j) is added to slot k mod 4 in ascending k, the slots are combined as (s0 + s2) + (s1 + s3);
+ *                the lazy term n q_i (n terms) is added and the result normalised.  n == 0: the value stays.
+ * 10 outputs     d_rotations f32 [n_images][9], row-major: the rotation of the final q_i; all zero for an image never
+ *                  labelled (the pose arrays' "not registered").
+ *                d_edge_stats uint32 [n_edges][4] = {closed, consistent, state, the pair's representative (its own index if
+ *                  it is one); {0, 0, 0, 0xFFFFFFFF} if not usable}.
+ *                d_edge_residual optional, f32 [n_edges]: for a usable edge with both ends labelled the cosine of the angle
+ *                  between R and R_b R_a^T under the final rotations, 2 (q_b . (q_e (x) q_a))^2 - 1 in f64; 2 otherwise (the
+ *                  pose call's "none").
+ *                d_image_stats uint32 [n_images][4] = {kept incident edges, the round it was labelled in (0 the root,
+ *                  0xFFFFFFFF never), its tree edge (0xFFFFFFFF none), rejected incident edges (state 1, duplicates counted)}.
+ *                d_match_out optional, with d_edge_offsets_a (uint64 [n_edges + 1]) / ea_capacity and d_match as
+ *                  lf_mkd_link_table_device reads them: for every entry of edge e's range (both ends clamped to ea_capacity,
+ *                  an inverted range empty) d_match[.] if e is kept and -1 otherwise -- a duplicate of a kept pair is not
+ *                  kept, so a pair is linked once.  Entries outside every range are untouched.  It may be d_match (every
+ *                  entry is read before it is written, by the same thread); lf_mkd_build_tracks_device takes it as d_match.
+ *                d_counts uint32 [8] = {usable, supported, rejected, unchecked, kept, images labelled, root, 0}.
+ * 11 degenerate  n_edges == 0 with n_images > 0: zero rotations except that a given root gets the identity (its round is 0);
+ *                  nothing is labelled under LF_MKD_VIEW_GRAPH_AUTO_ROOT; all eight counts are 0.
+ *                n_images == 0: LF_MKD_OK, nothing is written.  tree_rounds == 0: only the root is labelled.
+ * Device form: a table uint32 [n_images][n_images] of representatives in the handle's scratch (zeroed by a kernel, filled by
+ * an integer atomic min), the quaternions as f64 beside it; a wave per edge votes over two rows of it, a wave per image walks
+ * its row for the tree and the sweeps.  No floating-point atomic, no workgroup waits for another, nothing is read back.
+ * Launches (lf_mkd_view_graph_plan's `launches`): 3 + tree_rounds + iterations (zero, root, the rounds, the sweeps, final),
+ * + 2 with n_edges > 0 (edges, vote), + 1 more with the match arrays; none for n_images == 0.  Asynchronous on `stream`
+ * (NULL: the handle's own); the scratch belongs to the handle and only grows, so a warmed-up call is capturable in a hipGraph.
+ * Calls of one handle are stream-ordered.  d_image_stats and d_edge_stats also carry the call's state between its launches.
+ * LF_MKD_ERR_BAD_ARG ("view_graph_device: "), before any device is touched: with n_images > 0 a null d_rotations,
+ * d_image_stats or d_counts, and with n_edges > 0 too a null d_edge_a, d_edge_b, d_R, d_pose_stats or d_edge_stats; only part
+ * of d_edge_offsets_a, d_match, d_match_out; unknown flags; max_loop_deg outside [0, 180] or a NaN; a root at or beyond
+ * n_images other than LF_MKD_VIEW_GRAPH_AUTO_ROOT; tree_rounds or iterations above LF_MKD_VIEW_GRAPH_MAX_ROUNDS; n_images^2
+ * above 2^31 - 1; n_edges above 2^31 - 1; d_edge_offsets_a not 8-byte or any other array not 4-byte aligned; ea_capacity
+ * above 2^31 - 1. */
+#define LF_MKD_VIEW_GRAPH_USE_UNCHECKED (1u)        /* keep the representatives that close no triangle too */
+#define LF_MKD_VIEW_GRAPH_AUTO_ROOT (0xFFFFFFFFu)   /* `root`: the image with the most kept incident edges */
+#define LF_MKD_VIEW_GRAPH_MAX_ROUNDS (4096u)        /* the largest tree_rounds and the largest iterations */
+#define LF_MKD_VIEW_GRAPH_FORM_TABLE (0u)           /* the plan's form: the dense table of representatives */
+/* Host only: the launches and the scratch of lf_mkd_view_graph_device for these sizes (with_match != 0: the match arrays are
+ * given), and its form (LF_MKD_VIEW_GRAPH_FORM_TABLE, the only one).  Any output may be NULL.  LF_MKD_ERR_BAD_ARG
+ * ("view_graph_plan: "): the sizes, rounds and flags the device call refuses. */
+int lf_mkd_view_graph_plan(uint32_t n_images, uint32_t n_edges, uint32_t tree_rounds, uint32_t iterations, uint32_t flags,
+                           uint32_t with_match, uint32_t *launches, uint64_t *scratch_bytes, uint32_t *form);
+int lf_mkd_view_graph_device(lf_mkd *h, const uint32_t *d_edge_a, const uint32_t *d_edge_b, uint32_t n_edges, const float *d_R,
+                             const uint32_t *d_pose_stats, uint32_t n_images, float max_loop_deg, uint32_t min_front, uint32_t root,
+                             uint32_t tree_rounds, uint32_t iterations, uint32_t flags, const uint64_t *d_edge_offsets_a,
+                             uint64_t ea_capacity, const int32_t *d_match, int32_t *d_match_out, float *d_rotations,
+                             uint32_t *d_edge_stats, float *d_edge_residual, uint32_t *d_image_stats, uint32_t *d_counts,
+                             void *stream);
+/* The host form: host arrays in and out, staged through the handle; synchronous.  match has n_entries entries and is filtered
+ * on its staged copy, so match_out (which may be match) gets match's value in every entry outside the edges' ranges.
+ * LF_MKD_ERR_BAD_ARG ("view_graph: ") as above, without the alignment rules. */
+int lf_mkd_view_graph(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b, uint32_t n_edges, const float *R,
+                      const uint32_t *pose_stats, uint32_t n_images, float max_loop_deg, uint32_t min_front, uint32_t root,
+                      uint32_t tree_rounds, uint32_t iterations, uint32_t flags, const uint64_t *edge_offsets_a, uint64_t n_entries,
+                      const int32_t *match, int32_t *match_out, float *rotations, uint32_t *edge_stats, float *edge_residual,
+                      uint32_t *image_stats, uint32_t *counts);
+
 /* Host-only verification tap: the constants upload_constant_data (mod.rs:1587-1713) would place in
  * ConstantData (common.glsl:34-40), as this library builds them.  Any output pointer may be NULL.
  * gradient_angle[1024], embedding_polar[25*1024], embedding_cartesian[9*1024], w_t[128*238].

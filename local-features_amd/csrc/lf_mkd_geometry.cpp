@@ -1,4 +1,5 @@
-// C ABI, the geometry: both RANSAC verifiers, two-view poses, track triangulation, camera resection, bundle adjustment.
+// C ABI, the geometry: both RANSAC verifiers, two-view poses, track triangulation, camera resection, bundle adjustment,
+// view-graph checks.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -611,6 +612,122 @@ int lf_mkd_bundle_adjust_intrinsics(lf_mkd *h, const lf_mkd_keypoint *kps, const
     LF_HIP(h, io.down(trace, d_trace, uint64_t(iterations) * 9));
     LF_HIP(h, io.down(counts, d_counts, 5));
     LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// View-graph checks (csrc/mkd_view_graph.hip).  The cosine of the loop threshold is formed here, once, in double: no
+// transcendental runs on the device (tests/cpp/view_graph_twin.cpp forms it with the same expression).
+static const char *view_graph_scalars(uint32_t n_images, uint32_t n_edges, float max_loop_deg, uint32_t root, uint32_t tree_rounds,
+                                      uint32_t iterations, uint32_t flags) {
+    if (flags & ~uint32_t(LF_MKD_VIEW_GRAPH_USE_UNCHECKED)) return "unknown flag bits";
+    if (!(max_loop_deg >= 0.f && max_loop_deg <= 180.f)) return "max_loop_deg must be in [0, 180]";
+    if (n_images && root != LF_MKD_VIEW_GRAPH_AUTO_ROOT && root >= n_images) return "root must be an image id or LF_MKD_VIEW_GRAPH_AUTO_ROOT";
+    if (tree_rounds > LF_MKD_VIEW_GRAPH_MAX_ROUNDS || iterations > LF_MKD_VIEW_GRAPH_MAX_ROUNDS)
+        return "tree_rounds and iterations must be 0 .. 4096 (each is a launch)";
+    if (above(kRowMax, uint64_t(n_images) * n_images)) return "a table of more than 2^31 - 1 entries (n_images^2)";
+    if (above(kRowMax, n_edges)) return "n_edges above 2^31 - 1";
+    return nullptr;
+}
+
+int lf_mkd_view_graph_plan(uint32_t n_images, uint32_t n_edges, uint32_t tree_rounds, uint32_t iterations, uint32_t flags,
+                           uint32_t with_match, uint32_t *launches, uint64_t *scratch_bytes, uint32_t *form) {
+    if (const char *msg = view_graph_scalars(n_images, n_edges, 0.f, LF_MKD_VIEW_GRAPH_AUTO_ROOT, tree_rounds, iterations, flags))
+        return refuse(nullptr, "view_graph_plan", msg);
+    const ViewGraphPlan p = view_graph_plan(n_images, n_edges, tree_rounds, iterations, with_match != 0);
+    if (launches) *launches = p.launches;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    if (form) *form = LF_MKD_VIEW_GRAPH_FORM_TABLE;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_view_graph_device(lf_mkd *h, const uint32_t *d_edge_a, const uint32_t *d_edge_b, uint32_t n_edges, const float *d_R,
+                             const uint32_t *d_pose_stats, uint32_t n_images, float max_loop_deg, uint32_t min_front, uint32_t root,
+                             uint32_t tree_rounds, uint32_t iterations, uint32_t flags, const uint64_t *d_edge_offsets_a,
+                             uint64_t ea_capacity, const int32_t *d_match, int32_t *d_match_out, float *d_rotations,
+                             uint32_t *d_edge_stats, float *d_edge_residual, uint32_t *d_image_stats, uint32_t *d_counts,
+                             void *stream) {
+    const int filter = (d_edge_offsets_a != nullptr) + (d_match != nullptr) + (d_match_out != nullptr);
+    const char *msg = nullptr;
+    if (n_images && (!d_rotations || !d_image_stats || !d_counts)) msg = "null d_rotations, d_image_stats or d_counts";
+    else if (n_images && n_edges && (!d_edge_a || !d_edge_b || !d_R || !d_pose_stats || !d_edge_stats))
+        msg = "null d_edge_a, d_edge_b, d_R, d_pose_stats or d_edge_stats";
+    else if (filter != 0 && filter != 3) msg = "d_edge_offsets_a, d_match and d_match_out go together (all three, or none)";
+    else if ((msg = view_graph_scalars(n_images, n_edges, max_loop_deg, root, tree_rounds, iterations, flags))) {}
+    else if (misaligned(7, d_edge_offsets_a)) msg = "d_edge_offsets_a must be 8-byte aligned";
+    else if (misaligned(3, d_edge_a, d_edge_b, d_R, d_pose_stats, d_match, d_match_out, d_rotations, d_edge_stats, d_edge_residual,
+                        d_image_stats, d_counts))
+        msg = "the edge, rotation, statistics, match and output arrays must be 4-byte aligned";
+    else if (above(kRowMax, ea_capacity)) msg = "ea_capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "view_graph_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const ViewGraphPlan plan = view_graph_plan(n_images, n_edges, tree_rounds, iterations, filter == 3);
+    unsigned char *work;
+    if (int rc = scratch(h, h->d_view_graph, plan.scratch_bytes, &work)) return rc;
+    const double cmax = std::cos(double(max_loop_deg) * (3.14159265358979323846 / 180.0));
+    const unsigned issued =
+        launch_view_graph(plan, work, d_edge_a, d_edge_b, n_edges, d_R, d_pose_stats, n_images, cmax, min_front, root, tree_rounds,
+                      iterations, (flags & LF_MKD_VIEW_GRAPH_USE_UNCHECKED) != 0, d_edge_offsets_a, ea_capacity, d_match, d_match_out,
+                      d_rotations, d_edge_stats, d_edge_residual, d_image_stats, d_counts, stream_of(h, stream));
+    if (issued != plan.launches)
+        return fail(h, LF_MKD_ERR_HIP, "view_graph_device: issued " + std::to_string(issued) + " launches, the plan says " +
+                                           std::to_string(plan.launches));
+    return launched(h);
+}
+
+// The host form: the arrays staged through the handle's d_ver_io with the outputs, and the device call does the rest.  The
+// match array is filtered in place on its staged copy, so match_out's entries outside every edge's range come back as match's.
+int lf_mkd_view_graph(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b, uint32_t n_edges, const float *R,
+                      const uint32_t *pose_stats, uint32_t n_images, float max_loop_deg, uint32_t min_front, uint32_t root,
+                      uint32_t tree_rounds, uint32_t iterations, uint32_t flags, const uint64_t *edge_offsets_a, uint64_t n_entries,
+                      const int32_t *match, int32_t *match_out, float *rotations, uint32_t *edge_stats, float *edge_residual,
+                      uint32_t *image_stats, uint32_t *counts) {
+    const int filter = (edge_offsets_a != nullptr) + (match != nullptr) + (match_out != nullptr);
+    const char *msg = nullptr;
+    if (n_images && (!rotations || !image_stats || !counts)) msg = "null rotations, image_stats or counts";
+    else if (n_images && n_edges && (!edge_a || !edge_b || !R || !pose_stats || !edge_stats))
+        msg = "null edge_a, edge_b, R, pose_stats or edge_stats";
+    else if (filter != 0 && filter != 3) msg = "edge_offsets_a, match and match_out go together (all three, or none)";
+    else if ((msg = view_graph_scalars(n_images, n_edges, max_loop_deg, root, tree_rounds, iterations, flags))) {}
+    else if (above(kRowMax, n_entries)) msg = "n_entries above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "view_graph", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const uint64_t n_match = filter == 3 && n_edges ? n_entries : 0;
+    Stager io(h, h->d_ver_io);
+    const auto d_off = io.part<uint64_t>(filter == 3 ? uint64_t(n_edges) + 1 : 0);
+    const auto d_ea = io.part<uint32_t>(n_edges), d_eb = io.part<uint32_t>(n_edges);
+    const auto d_R = io.part<float>(uint64_t(n_edges) * 9);
+    const auto d_ps = io.part<uint32_t>(uint64_t(n_edges) * 4);
+    const auto d_match = io.part<int32_t>(n_match);
+    const auto d_rot = io.part<float>(uint64_t(n_images) * 9);
+    const auto d_es = io.part<uint32_t>(uint64_t(n_edges) * 4);
+    const auto d_res = io.part<float>(edge_residual ? n_edges : 0);
+    const auto d_is = io.part<uint32_t>(uint64_t(n_images) * 4);
+    const auto d_counts = io.part<uint32_t>(8);
+    if (int rc = io.reserve()) return rc;
+    LF_HIP(h, io.up(d_off, edge_offsets_a, filter == 3 ? uint64_t(n_edges) + 1 : 0));
+    LF_HIP(h, io.up(d_ea, edge_a, n_edges));
+    LF_HIP(h, io.up(d_eb, edge_b, n_edges));
+    LF_HIP(h, io.up(d_R, R, uint64_t(n_edges) * 9));
+    LF_HIP(h, io.up(d_ps, pose_stats, uint64_t(n_edges) * 4));
+    LF_HIP(h, io.up(d_match, match, n_match));
+    if (int rc = lf_mkd_view_graph_device(h, d_ea, d_eb, n_edges, d_R, d_ps, n_images, max_loop_deg, min_front, root, tree_rounds,
+                                          iterations, flags, filter == 3 ? d_off.get() : nullptr, n_match,
+                                          filter == 3 ? d_match.get() : nullptr, filter == 3 ? d_match.get() : nullptr, d_rot, d_es,
+                                          edge_residual ? d_res.get() : nullptr, d_is, d_counts, h->stream))
+        return rc;
+    LF_HIP(h, io.down(rotations, d_rot, uint64_t(n_images) * 9));
+    LF_HIP(h, io.down(edge_stats, d_es, uint64_t(n_edges) * 4));
+    LF_HIP(h, io.down(edge_residual, d_res, edge_residual ? n_edges : 0));
+    LF_HIP(h, io.down(image_stats, d_is, uint64_t(n_images) * 4));
+    LF_HIP(h, io.down(counts, d_counts, 8));
+    LF_HIP(h, io.down(match_out, d_match, n_match));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    // (without edges there is nothing to filter: match_out is match)
+    if (filter == 3 && !n_edges && match_out != match) std::memcpy(match_out, match, n_entries * sizeof(int32_t));
     return LF_MKD_OK;
 }
 

@@ -252,6 +252,8 @@ struct lf_mkd {
     // lf_mkd_bundle_adjust_device's scratch (bundle_scratch_bytes), in the same way; lf_mkd_bundle_adjust_intrinsics_device's
     // too (bundle_intrinsics_scratch_bytes: the same layout with the groups' arrays behind it)
     HipArray<unsigned char> d_bundle;
+    // lf_mkd_view_graph_device's scratch (view_graph_plan's scratch_bytes), in the same way
+    HipArray<unsigned char> d_view_graph;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;

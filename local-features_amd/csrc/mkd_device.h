@@ -395,6 +395,23 @@ void launch_bundle_adjust_intrinsics(void *scratch, const float *kps, const uint
                                      double thr2, double lambda0, unsigned iterations, unsigned cg_iterations, double tol2,
                                      float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
                                      unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
+// view-graph checks (csrc/mkd_view_graph.hip, lf_mkd_view_graph_device).  The plan is the one place that knows the launches and
+// the layout of the scratch (byte offsets, 8-byte aligned): the edges' quaternions f64 [n_edges][4], the images' quaternions
+// f64 [2][n_images][4] (the sweeps go from one to the other), then the pair table uint32 [n_images][n_images].
+// Launches: n_images == 0: none.  Otherwise zero, edges and vote (n_edges > 0 only), root, tree_rounds, iterations, final,
+// filter (a match array and n_edges > 0 only): 3 + tree_rounds + iterations, + 2 or 3 with edges.
+// cmax = the cosine of the loop threshold, formed by the host in double.  match_out may be match.  Returns the launches it
+// issued, which the entry point holds against the plan's.
+struct ViewGraphPlan {
+    unsigned launches;
+    uint64_t off_edge_quat, off_quat[2], off_table, scratch_bytes;
+};
+ViewGraphPlan view_graph_plan(unsigned n_images, unsigned n_edges, unsigned tree_rounds, unsigned iterations, bool filter);
+unsigned launch_view_graph(const ViewGraphPlan &plan, unsigned char *scratch, const unsigned *edge_a, const unsigned *edge_b,
+                       unsigned n_edges, const float *R, const unsigned *pose_stats, unsigned n_images, double cmax,
+                       unsigned min_front, unsigned root, unsigned tree_rounds, unsigned iterations, bool use_unchecked,
+                       const uint64_t *edge_off, uint64_t capacity, const int *match, int *match_out, float *rotations,
+                       unsigned *edge_stats, float *residual, unsigned *image_stats, unsigned *counts, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -39,6 +39,9 @@ descriptor row is copied for it.
   every image, the principal point in the middle     table: E = K^T F K per edge, its four (R, t) candidates voted by the edge's
   of the frame unless given; implies --fundamental   links, the links triangulated; nothing leaves the device before the lines
   and --pairs) the relative pose of every edge       are printed
+  with --view-graph DEG (needs --pose) the posed      LocalFeatures.view_graph (lf_mkd_view_graph_device) after the poses: an edge
+  edges checked against each other and a global      none of whose triangles closes within DEG degrees is dropped, its matches
+  rotation per image                                 go to -1 before build_tracks, and the initial pair is a supported edge
   with --triangulate [POSES.npy] (needs --pose;       LocalFeatures.triangulate_tracks (lf_mkd_triangulate_tracks_device) on the track
   implies --table) a 3-D point per track under the   table: pair hypotheses, least squares over the winner's inliers, two trimming
   [images][12] poses of the file (R row-major, then  rounds at 4 px; without a file the edge with the most links with parallax is
@@ -62,7 +65,8 @@ first three tracks as image:x,y lists; with --pairs also the number of edges and
 first three correspondences of the best edge as x,y -> x,y; with --expand also one line with the proposed edges and how many of
 them kept a verified match, and the track lines once more for the expanded forest; with --pose per edge the rotation angle,
 the direction of t, the links in front of both cameras out of the edge's links, those with at least 1 degree of parallax and
-s2/s1 of the essential matrix (1 for a true one); with --triangulate the tracks, the registered images, the points, the inlier
+s2/s1 of the essential matrix (1 for a true one); with --view-graph the usable, supported, rejected, unchecked and kept edges
+and the images that got a rotation; with --triangulate the tracks, the registered images, the points, the inlier
 observations and the median parallax; with --register per round the images registered so far, those the round added and the
 points; with --bundle the counts, one line per iteration of the trace and the rms reprojection error before and after.  Nothing is read back before those counts: the
 output arrays are sized from a bound the host knows -- an image sits on at most D edges of a side, so D times the number of
@@ -117,7 +121,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
                      table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0, bundle=0,
-                     refine_focal=False, refine_principal=False):
+                     refine_focal=False, refine_principal=False, view_graph=None):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -156,7 +160,11 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
     bundle_obs_state and bundle_rms [2] (before, after); None without.  With `refine_focal` / `refine_principal` the bundle step
     is LocalFeatures.bundle_adjust_intrinsics with every image in one group: the shared focal length (its scale) and / or the
     principal point (its shift) are refined too, bundle_trace is [ITERS,9] and bundle_counts [5], bundle_groups [1,3] = (s, dx,
-    dy), and `intrinsics` [n,4] (what `pose` gave, per image) is updated in place for everything after."""
+    dy), and `intrinsics` [n,4] (what `pose` gave, per image) is updated in place for everything after.  With `view_graph` =
+    DEG (the loop threshold in degrees; it wants `pose`) LocalFeatures.view_graph runs after the poses: vg_rotations [n,3,3],
+    vg_edge_stats [E,4], vg_residual [E], vg_image_stats [n,4], vg_counts [8] and vg_match, the matches with the entries of the
+    edges it does not keep at -1 -- the tracks are then built from vg_match, and the initial pair is chosen among the supported
+    edges only; None without, and nothing else changes."""
     import torch
     n, hgt, w = frames.shape
     if feats is None:
@@ -209,12 +217,20 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         if pose is not None:
             intr = torch.tensor([[pose[0], pose[0], pose[1], pose[2]]], dtype=torch.float32, device=dev).repeat(n, 1)
             p_R, p_t, p_stats, p_sigma, p_points = feats.two_view_pose(model.contiguous(), intr, kps, (ea, eb), (l_off, l_a, l_b))
+        vg_rot = vg_es = vg_res = vg_ims = vg_counts = vg_match = None
+        links_for_tracks = ver if l_kept is None else l_kept
+        if view_graph is not None:
+            if pose is None:
+                raise RuntimeError("match_collection: view_graph needs pose (the edges' relative rotations)")
+            vg_rot, vg_es, vg_res, vg_ims, vg_counts, vg_match = feats.view_graph((ea, eb), p_R, p_stats, n, max_loop_deg=view_graph,
+                                                                                  layout=la, match=links_for_tracks)
+            links_for_tracks = vg_match
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
         if (register or bundle) and triangulate is None:
             triangulate = True
         if tracks or table or expand or triangulate is not None:
-            track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, ver if l_kept is None else l_kept, capacity=cap_a, n_rows=m)
+            track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, links_for_tracks, capacity=cap_a, n_rows=m)
             two, three, ok = track_len >= 2, track_len >= 3, track_dup == 0
             track_counts = torch.stack([two.sum(), (two & ok).sum(), three.sum(), (three & ok).sum(), track_len.max().long(),
                                         (track_len * (two & ok)).sum()])
@@ -260,6 +276,8 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             if triangulate is True:
                 # the initial pair, chosen on the device: nothing is read back
                 with_pose = torch.where(p_stats[:, 2] >= 0, p_stats[:, 3], torch.full_like(p_stats[:, 3], -1))
+                if vg_es is not None:                           # ... among the edges the view graph supports
+                    with_pose = torch.where(vg_es[:, 2] == 3, with_pose, torch.full_like(with_pose, -1))
                 e = torch.argmax(with_pose).reshape(1)
                 eye = torch.tensor([[1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]], dtype=torch.float32, device=dev)
                 tri_poses = torch.zeros((n, 12), dtype=torch.float32, device=dev)
@@ -302,7 +320,8 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 edge_votes=e_votes, rank=rank, rank_votes=rank_votes, select_counts=s_counts, covisibility=covis,
                 expand_edge_a=x_ea, expand_edge_b=x_eb, expand_counts=x_counts, expand_layout_a=x_la, expand_verified=x_ver,
                 expand_per_edge=x_per_edge, first_round=first, pose_R=p_R, pose_t=p_t, pose_stats=p_stats,
-                pose_sigma=p_sigma, pose_points=p_points)
+                pose_sigma=p_sigma, pose_points=p_points, vg_rotations=vg_rot, vg_edge_stats=vg_es, vg_residual=vg_res,
+                vg_image_stats=vg_ims, vg_counts=vg_counts, vg_match=vg_match)
 
 
 def reprojection_rms(kps, t_off, t_rows, t_img, intr, poses, points, active, max_reproj_px=4.0):
@@ -339,6 +358,15 @@ def bundle_lines(out):
     return lines
 
 
+def view_graph_lines(out):
+    """one line of `view_graph`'s counts"""
+    if out.get("vg_counts") is None:
+        return []
+    usable, supported, rejected, unchecked, kept, labelled, root = out["vg_counts"].cpu().tolist()[:7]
+    return [f"{usable} usable edges: {supported} supported, {rejected} rejected, {unchecked} unchecked, {kept} kept; "
+            f"{labelled} of {out['vg_image_stats'].shape[0]} images with a rotation, root {root + 1}"]
+
+
 def register_lines(out):
     """one line per round of `register`: the images registered after it, those it added, and the points"""
     n_tracks = out["table_counts"].cpu().tolist()[0]
@@ -370,6 +398,7 @@ def main():
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
     expand, min_shared, pose, triangulate, register, bundle = None, 8, None, None, 0, 0
     refine_focal = refine_principal = False
+    view_graph = None
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -390,6 +419,8 @@ def main():
         elif a == "--pose" and args and parse_pose(args[0]) is not None:
             pose = parse_pose(args.pop(0))
             fundamental = pairs = True
+        elif a == "--view-graph" and args and parse_pose(args[0]) is not None and "," not in args[0] and float(args[0]) <= 180:
+            view_graph = float(args.pop(0))
         elif a == "--triangulate":
             tracks = table = True
             triangulate = np.load(args.pop(0)) if args and args[0].endswith(".npy") else True
@@ -414,11 +445,11 @@ def main():
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (triangulate is not None and pose is None) or ((refine_focal or refine_principal) and not bundle) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (triangulate is not None and pose is None) or (view_graph is not None and pose is None) or ((refine_focal or refine_principal) and not bundle) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images; --triangulate, --register and --bundle need --pose, --refine-focal and --refine-principal --bundle)", file=sys.stderr)
+              "number of images; --view-graph, --triangulate, --register and --bundle need --pose, --refine-focal and --refine-principal --bundle)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -428,7 +459,7 @@ def main():
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
                            min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register, bundle=bundle,
-                           refine_focal=refine_focal, refine_principal=refine_principal)
+                           refine_focal=refine_focal, refine_principal=refine_principal, view_graph=view_graph)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -473,6 +504,8 @@ def main():
             angle = np.degrees(np.arccos(np.clip((np.trace(R[e].astype(np.float64)) - 1) / 2, -1, 1)))
             print(f"Pose {ea[e] + 1} -> {eb[e] + 1}: rotation {angle:.2f} deg, t {t[e][0]:+.3f} {t[e][1]:+.3f} {t[e][2]:+.3f}, "
                   f"{st[e][0]} / {links[e]} links in front, {st[e][3]} with parallax, s2/s1 {sg[e][1]:.3f}")
+    for line in view_graph_lines(out):
+        print("View graph, " + line)
     if triangulate is not None:
         n_tracks = out["table_counts"].cpu().tolist()[0]
         st, pts = out["tri_stats"][:n_tracks].cpu().numpy(), out["tri_points"][:n_tracks].cpu().numpy()

@@ -14,8 +14,8 @@ import threading
 import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
-                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan)
+                   POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, VIEW_GRAPH_USE_UNCHECKED, VIEW_GRAPH_AUTO_ROOT, BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, VERIFY_NO_REFINE, Comm,
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan, view_graph_plan)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
@@ -23,7 +23,8 @@ __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXAC
            "VERIFY_NO_REFINE", "MATCH_MUTUAL", "GUIDE_HOMOGRAPHY", "GUIDE_FUNDAMENTAL", "Q8_SCALE", "match_q8_plan", "match_q8_pairs_plan",
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
            "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan",
-           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "BA_REFINE_FOCAL", "BA_REFINE_PRINCIPAL", "covisibility_plan"]
+           "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "BA_REFINE_FOCAL", "BA_REFINE_PRINCIPAL", "covisibility_plan",
+           "VIEW_GRAPH_USE_UNCHECKED", "VIEW_GRAPH_AUTO_ROOT", "view_graph_plan"]
 
 
 class Keypoint:
@@ -1006,6 +1007,60 @@ class LocalFeatures:
                                                   ptr(st), ptr(er), ptr(rs), max_reproj_px, min_parallax_deg, n_samples,
                                                   min_inliers, rounds, seed, RESECT_ALL if resect_all else 0, s.cuda_stream)
         return out, st, er, rs
+
+    def view_graph(self, edges, R, pose_stats, n_images, max_loop_deg=3.0, min_front=0, root=None, tree_rounds=16, iterations=10,
+                   use_unchecked=False, layout=None, match=None, out_match=None, residual=True, stream=None):
+        """View-graph checks and global rotations (lf_mkd_view_graph_device): the relative rotations around every triangle of
+        images must compose to the identity within max_loop_deg; an edge none of whose triangles closes is rejected, and the
+        images get rotations by a breadth-first tree and `iterations` sweeps of quaternion averaging over the kept edges
+        (include/lf_mkd.h states the algorithm).  edges = (edge_a, edge_b) 32-bit image ids, R [n_edges, 3, 3] (or [n_edges,
+        9]) float32 and pose_stats [n_edges, 4] int32 as two_view_pose returned them; root is an image id or None (the image
+        with the most kept edges); layout / match are edge_layout's offsets int64 [n_edges + 1] and the match array int32, and
+        out_match the tensor to write (`match` itself for a call in place; default: a copy of match).  Returns device tensors
+        (rotations [n_images, 3, 3] float32, all zero for an image without one; edge_stats [n_edges, 4] int32 = triangles
+        closed, consistent, state (0 not usable, 1 rejected, 2 unchecked, 3 supported), the pair's representative (-1: not
+        usable); residual [n_edges] float32, the cosine of the angle between R and the final rotations' R_b R_a^T (2: none), or
+        None; image_stats [n_images, 4] int32 = kept edges, the round it was labelled in (-1: never), its tree edge, rejected
+        edges; counts [8] int32 = usable, supported, rejected, unchecked, kept, labelled, root, 0; the filtered match array,
+        build_tracks' input, or None).  Nothing is read back: asynchronous on `stream` (default: torch's current stream on
+        the handle's device), capturable once warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            ea, eb = self._words(edges[0], dev), self._words(edges[1], dev)
+            n_edges = ea.numel()
+            if not (ok(R, torch.float32) and R.numel() == 9 * n_edges and eb.numel() == n_edges):
+                raise RuntimeError("view_graph: R must be a contiguous float32 device tensor with 9 values per edge, edges one id "
+                                   "per edge in each of its two arrays")
+            if not (ok(pose_stats, torch.int32) and pose_stats.numel() == 4 * n_edges):
+                raise RuntimeError("view_graph: pose_stats must be a contiguous int32 [n_edges, 4] device tensor")
+            if (layout is None) != (match is None):
+                raise RuntimeError("view_graph: layout and match go together")
+            if match is not None:
+                if not (ok(layout, torch.int64) and layout.numel() == n_edges + 1 and ok(match, torch.int32)):
+                    raise RuntimeError("view_graph: layout must be int64 [n_edges + 1] and match int32 contiguous device tensors")
+                if out_match is None:
+                    out_match = match.clone()
+                elif not (ok(out_match, torch.int32) and out_match.numel() == match.numel()):
+                    raise RuntimeError("view_graph: out_match must be a contiguous int32 device tensor of match's size")
+            rot = torch.empty((n_images, 3, 3), dtype=torch.float32, device=dev)
+            es = torch.empty((n_edges, 4), dtype=torch.int32, device=dev)
+            res = torch.empty((n_edges,), dtype=torch.float32, device=dev) if residual else None
+            ims = torch.empty((n_images, 4), dtype=torch.int32, device=dev)
+            counts = torch.empty((8,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.view_graph_device(ptr(ea), ptr(eb), n_edges, ptr(R), ptr(pose_stats), n_images, ptr(rot), ptr(es),
+                                              ptr(ims), counts.data_ptr(), ptr(res),
+                                              layout.data_ptr() if match is not None else None,
+                                              match.numel() if match is not None else 0,
+                                              match.data_ptr() if match is not None else None,
+                                              out_match.data_ptr() if match is not None else None, max_loop_deg, min_front,
+                                              VIEW_GRAPH_AUTO_ROOT if root is None else root, tree_rounds, iterations,
+                                              VIEW_GRAPH_USE_UNCHECKED if use_unchecked else 0, s.cuda_stream)
+        return rot, es, res, ims, counts, out_match
 
     def bundle_adjust(self, kps, offsets, table, points, intrinsics, poses, obs_state=None, camera_fixed=None, max_reproj_px=4.0,
                       lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, out_poses=None, out_points=None,

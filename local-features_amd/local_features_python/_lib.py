@@ -53,6 +53,7 @@ SYMBOLS = (
     "lf_mkd_resect_camera", "lf_mkd_resect_cameras_device",
     "lf_mkd_bundle_adjust", "lf_mkd_bundle_adjust_device",
     "lf_mkd_bundle_adjust_intrinsics", "lf_mkd_bundle_adjust_intrinsics_device",
+    "lf_mkd_view_graph_plan", "lf_mkd_view_graph", "lf_mkd_view_graph_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -66,6 +67,8 @@ COVIS_ACCUMULATE = 1     # LF_MKD_COVIS_ACCUMULATE: lf_mkd_covisibility_device a
 BA_REFINE_FOCAL = 1      # LF_MKD_BA_REFINE_FOCAL: lf_mkd_bundle_adjust_intrinsics_device refines the groups' focal scale
 BA_REFINE_PRINCIPAL = 2  # LF_MKD_BA_REFINE_PRINCIPAL: ... and the groups' principal-point shift
 RESECT_ALL = 1           # LF_MKD_RESECT_ALL: lf_mkd_resect_cameras_device resects registered images too
+VIEW_GRAPH_USE_UNCHECKED = 1     # LF_MKD_VIEW_GRAPH_USE_UNCHECKED: lf_mkd_view_graph_device keeps edges that close no triangle
+VIEW_GRAPH_AUTO_ROOT = 0xFFFFFFFF    # LF_MKD_VIEW_GRAPH_AUTO_ROOT: its root is the image with the most kept incident edges
 COVIS_FORM_LDS = 256     # LF_MKD_COVIS_FORM_LDS: in covisibility_plan's form, workgroups count in LDS first
 SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
 COMM_ID_BYTES = 128
@@ -202,6 +205,11 @@ def load_library():
     L.lf_mkd_bundle_adjust_intrinsics.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u32,
                                                   ctypes.c_float, ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp,
                                                   vp, vp]
+    L.lf_mkd_view_graph_plan.argtypes = [u32, u32, u32, u32, u32, u32, vp, vp, vp]
+    L.lf_mkd_view_graph_device.argtypes = [vp, vp, vp, u32, vp, vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, vp, u64, vp, vp,
+                                           vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_view_graph.argtypes = [vp, vp, vp, u32, vp, vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, vp, u64, vp, vp, vp, vp,
+                                    vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -350,6 +358,20 @@ def covisibility_plan(n_images, track_capacity, obs_capacity, n_edges=0, flags=0
     if rc != 0:
         raise RuntimeError(f"lf_mkd_covisibility_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return f.value, w.value, l.value, b.value
+
+
+def view_graph_plan(n_images, n_edges, tree_rounds=16, iterations=10, flags=0, with_match=False):
+    """(launches, scratch_bytes, form) of lf_mkd_view_graph_device: the launches of the call (3 + tree_rounds + iterations, 2
+    more with edges, one more with the match arrays), the handle's scratch and the form (0: the dense table of
+    representatives) (lf_mkd_view_graph_plan; needs no device)."""
+    l, f = ctypes.c_uint32(), ctypes.c_uint32()
+    b = ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_view_graph_plan(n_images, n_edges, tree_rounds, iterations, flags, 1 if with_match else 0, ctypes.byref(l),
+                                  ctypes.byref(b), ctypes.byref(f))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_view_graph_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return l.value, b.value, f.value
 
 
 class Comm:
@@ -682,6 +704,44 @@ class MkdHandle:
                                                 pose.ctypes.data, st.ctypes.data, at(er), rs.ctypes.data if row_state else None),
                     "lf_mkd_resect_camera")
         return pose, st, er, rs[:len(k)] if row_state else None
+
+    def view_graph(self, edge_a, edge_b, R, pose_stats, n_images, max_loop_deg=3.0, min_front=0, root=VIEW_GRAPH_AUTO_ROOT,
+                   tree_rounds=16, iterations=10, flags=0, edge_offsets_a=None, match=None, residual=True):
+        """lf_mkd_view_graph: edge_a / edge_b uint32 [n_edges], R f32 [n_edges, 9] and pose_stats uint32 [n_edges, 4] as
+        two_view_pose gave them, optionally the matches' edge layout (edge_offsets_a uint64 [n_edges + 1]) and the match array
+        -> (rotations f32 [n_images, 9], all zero for an image without one; edge_stats uint32 [n_edges, 4] = closed,
+        consistent, state (0 not usable, 1 rejected, 2 unchecked, 3 supported), the pair's representative; residual f32
+        [n_edges] or None; image_stats uint32 [n_images, 4] = kept edges, round, tree edge, rejected edges; counts uint32 [8] =
+        usable, supported, rejected, unchecked, kept, labelled, root, 0; the match array with the entries of the edges that are
+        not kept at -1, or None)."""
+        ea = np.ascontiguousarray(edge_a, np.uint32).reshape(-1)
+        eb = np.ascontiguousarray(edge_b, np.uint32).reshape(-1)
+        r = np.ascontiguousarray(R, np.float32).reshape(-1, 9)
+        ps = np.ascontiguousarray(pose_stats, np.uint32).reshape(-1, 4)
+        n = len(ea)
+        if len(eb) != n or len(r) != n or len(ps) != n:
+            raise RuntimeError("view_graph: edge_b, R and pose_stats need one row per entry of edge_a")
+        if (edge_offsets_a is None) != (match is None):
+            raise RuntimeError("view_graph: edge_offsets_a and match go together")
+        off = m = out = None
+        if match is not None:
+            off = np.ascontiguousarray(edge_offsets_a, np.uint64).reshape(-1)
+            m = np.ascontiguousarray(match, np.int32).reshape(-1)
+            if len(off) != n + 1:
+                raise RuntimeError("view_graph: edge_offsets_a needs n_edges + 1 entries")
+            out = np.empty(max(len(m), 1), np.int32)
+        rot, es = np.zeros((max(n_images, 1), 9), np.float32), np.zeros((max(n, 1), 4), np.uint32)
+        res = np.zeros(max(n, 1), np.float32) if residual else None
+        ims, counts = np.zeros((max(n_images, 1), 4), np.uint32), np.zeros(8, np.uint32)
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_view_graph(self._h, at(ea), at(eb), n, at(r), at(ps), n_images, max_loop_deg, min_front, root,
+                                             tree_rounds, iterations, flags, off.ctypes.data if off is not None else None,
+                                             len(m) if m is not None else 0, m.ctypes.data if m is not None else None,
+                                             out.ctypes.data if out is not None else None, rot.ctypes.data, es.ctypes.data,
+                                             res.ctypes.data if residual else None, ims.ctypes.data, counts.ctypes.data),
+                    "lf_mkd_view_graph")
+        return (rot[:n_images], es[:n], res[:n] if residual else None, ims[:n_images], counts,
+                out[:len(m)] if out is not None else None)
 
     def bundle_adjust(self, kps, image_offsets, track_offsets, obs_row, obs_image, points, intrinsics, poses, obs_state=None,
                       camera_fixed=None, max_reproj_px=4.0, lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, flags=0,
@@ -1038,6 +1098,20 @@ class MkdHandle:
             self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_row_track, d_points, track_capacity, d_table_counts,
             d_intrinsics, d_poses, max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed & 0xFFFFFFFF, flags,
             d_poses_out, d_stats, d_err, d_row_state, s), "lf_mkd_resect_cameras_device")
+
+    def view_graph_device(self, d_edge_a, d_edge_b, n_edges, d_R, d_pose_stats, n_images, d_rotations, d_edge_stats,
+                          d_image_stats, d_counts, d_edge_residual=None, d_edge_offsets_a=None, ea_capacity=0, d_match=None,
+                          d_match_out=None, max_loop_deg=3.0, min_front=0, root=VIEW_GRAPH_AUTO_ROOT, tree_rounds=16,
+                          iterations=10, flags=0, stream=None):
+        """lf_mkd_view_graph_device: the triangle vote over the posed edges (d_edge_a / d_edge_b uint32 [n_edges], d_R f32
+        [n_edges][9], d_pose_stats uint32 [n_edges][4]), the images' global rotations by a tree and quaternion averaging over
+        the kept edges -- d_rotations f32 [n_images][9], d_edge_stats uint32 [n_edges][4], d_image_stats uint32 [n_images][4],
+        d_counts uint32 [8], d_edge_residual f32 [n_edges] (nullable), and with d_edge_offsets_a / ea_capacity / d_match the
+        filtered d_match_out (may be d_match) (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_view_graph_device(
+            self._h, d_edge_a, d_edge_b, n_edges, d_R, d_pose_stats, n_images, max_loop_deg, min_front, root, tree_rounds,
+            iterations, flags, d_edge_offsets_a, ea_capacity, d_match, d_match_out, d_rotations, d_edge_stats, d_edge_residual,
+            d_image_stats, d_counts, s), "lf_mkd_view_graph_device")
 
     def bundle_adjust_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row,
                              d_obs_image, obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_poses_out, d_points_out,
