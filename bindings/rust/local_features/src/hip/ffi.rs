@@ -400,6 +400,31 @@ extern "C" {
                              tree_rounds: u32, iterations: u32, flags: u32, edge_offsets_a: *const u64, n_entries: u64,
                              matches: *const i32, match_out: *mut i32, rotations: *mut f32, edge_stats: *mut u32,
                              edge_residual: *mut f32, image_stats: *mut u32, counts: *mut u32) -> c_int;
+    // initial poses [n_images][12] from the view graph's rotations, its tree (image_stats) and the tree edges' translations
+    pub fn lf_mkd_tree_poses_device(h: *mut lf_mkd, d_edge_a: *const u32, d_edge_b: *const u32, d_t: *const f32, n_edges: u32,
+                                    d_rotations: *const f32, d_image_stats: *const u32, n_images: u32, max_depth: u32,
+                                    d_poses: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_tree_poses(h: *mut lf_mkd, edge_a: *const u32, edge_b: *const u32, t: *const f32, n_edges: u32,
+                             rotations: *const f32, image_stats: *const u32, n_images: u32, max_depth: u32,
+                             poses: *mut f32) -> c_int;
+    // global positions: all camera centres and track points at once under held rotations -- poses_out (may be poses), optional
+    // points [4], observation states and trace f64 [sweeps][4], image stats [4], counts [8]; the plan needs no device
+    pub fn lf_mkd_global_positions_plan(n_images: u32, track_capacity: u64, sweeps: u32, launches: *mut u32,
+                                        scratch_bytes: *mut u64) -> c_int;
+    pub fn lf_mkd_global_positions_device(h: *mut lf_mkd, d_kps: *const lf_mkd_keypoint, d_image_offsets: *const u64,
+                                          n_images: u32, n_rows_total: u64, d_track_offsets: *const u64, track_capacity: u64,
+                                          d_obs_row: *const i32, d_obs_image: *const u32, obs_capacity: u64,
+                                          d_table_counts: *const u32, d_row_track: *const i32, d_intrinsics: *const f32,
+                                          d_poses: *const f32, sweeps: u32, warm: u32, robust_deg: f32, min_obs: u32, flags: u32,
+                                          d_poses_out: *mut f32, d_points_out: *mut f32, d_obs_state: *mut u32,
+                                          d_image_stats: *mut u32, d_trace: *mut f64, d_counts: *mut u32,
+                                          stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_global_positions(h: *mut lf_mkd, kps: *const lf_mkd_keypoint, image_offsets: *const u64, n_images: u32,
+                                   n_rows_total: u64, track_offsets: *const u64, n_tracks: u64, obs_row: *const i32,
+                                   obs_image: *const u32, n_obs: u64, row_track: *const i32, intrinsics: *const f32,
+                                   poses: *const f32, sweeps: u32, warm: u32, robust_deg: f32, min_obs: u32, flags: u32,
+                                   poses_out: *mut f32, points_out: *mut f32, obs_state: *mut u32, image_stats: *mut u32,
+                                   trace: *mut f64, counts: *mut u32) -> c_int;
 
     // RANSAC homography verification of matches: one pair from host memory, or n_pairs pairs on the device in one call
     pub fn lf_mkd_verify_homography(h: *mut lf_mkd, kps_a: *const lf_mkd_keypoint, na: u64, kps_b: *const lf_mkd_keypoint,

@@ -797,6 +797,70 @@ impl LocalFeaturesHip {
         Ok((out, edge_stats, residual, image_stats, counts))
     }
 
+    /// Initial poses from the view graph's tree (`lf_mkd_tree_poses`): `rotations` and `image_stats` as `view_graph` returned
+    /// them, `edges` and `translations` as `two_view_pose` returned them.  Every labelled image gets its rotation and a centre
+    /// one unit step from its tree parent's; an image whose chain does not reach the root within `max_depth` steps gets the
+    /// all-zero row.  What `global_positions` starts from.
+    pub fn tree_poses(&mut self, edges: &[(u32, u32)], translations: &[[f32; 3]], rotations: &[[f32; 9]],
+                      image_stats: &[[u32; 4]], max_depth: u32) -> Result<Vec<[f32; 12]>, Error> {
+        let (n_edges, n_images) = (edges.len(), rotations.len());
+        if translations.len() != n_edges || image_stats.len() != n_images {
+            return Err(Error::BadArgument("tree_poses: translations need one row per edge, image_stats one per rotation".into()));
+        }
+        let edge_a: Vec<u32> = edges.iter().map(|e| e.0).collect();
+        let edge_b: Vec<u32> = edges.iter().map(|e| e.1).collect();
+        let mut poses = vec![[0f32; 12]; n_images.max(1)];
+        // SAFETY: host arrays sized as declared; n_edges and n_images bound what is read and written
+        unsafe {
+            check(self.h, ffi::lf_mkd_tree_poses(
+                self.h, edge_a.as_ptr(), edge_b.as_ptr(), translations.as_ptr() as *const f32, n_edges as u32,
+                rotations.as_ptr() as *const f32, image_stats.as_ptr() as *const u32, n_images as u32, max_depth,
+                poses.as_mut_ptr() as *mut f32))?;
+        }
+        poses.truncate(n_images);
+        Ok(poses)
+    }
+
+    /// Global positioning (`lf_mkd_global_positions`): all camera centres and all track points at once under the rotations of
+    /// `poses`, by `sweeps` alternations of the points' and the cameras' weighted 3x3 solves (unit weights for the first
+    /// `warm`, then weights floored at the sine of `robust_deg`), each followed by a similarity that puts the centres'
+    /// centroid at 0 and their rms radius at 1.
+    /// Returns (poses, points = X, Y, Z, smallest cosine; the observations' states; image stats = usable rows, weighted rows,
+    /// sweeps held, reason; the trace = cost, weighted observations, held cameras, unsolved points; the eight counts).
+    #[allow(clippy::type_complexity, clippy::too_many_arguments)]
+    pub fn global_positions(&mut self, kps: &[ffi::lf_mkd_keypoint], image_offsets: &[u64], track_offsets: &[u64],
+                            obs_row: &[i32], obs_image: &[u32], row_track: &[i32], intrinsics: &[[f32; 4]], poses: &[[f32; 12]],
+                            sweeps: u32, warm: u32, robust_deg: f32, min_obs: u32)
+                            -> Result<(Vec<[f32; 12]>, Vec<[f32; 4]>, Vec<u32>, Vec<[u32; 4]>, Vec<[f64; 4]>, [u32; 8]), Error> {
+        let (n_images, n_obs) = (intrinsics.len(), obs_row.len());
+        if image_offsets.len() != n_images + 1 || track_offsets.is_empty() || obs_image.len() != n_obs || poses.len() != n_images
+            || row_track.len() != kps.len() {
+            return Err(Error::BadArgument("global_positions: the arrays' lengths do not agree (include/lf_mkd.h)".into()));
+        }
+        let n_tracks = track_offsets.len() - 1;
+        let mut poses_out = vec![[0f32; 12]; n_images.max(1)];
+        let mut points_out = vec![[0f32; 4]; n_tracks.max(1)];
+        let mut state = vec![0u32; n_obs.max(1)];
+        let mut image_stats = vec![[0u32; 4]; n_images.max(1)];
+        let mut trace = vec![[0f64; 4]; sweeps.max(1) as usize];
+        let mut counts = [0u32; 8];
+        // SAFETY: host arrays sized as declared; the counts bound what is read, the outputs have their stated sizes
+        unsafe {
+            check(self.h, ffi::lf_mkd_global_positions(
+                self.h, kps.as_ptr(), image_offsets.as_ptr(), n_images as u32, kps.len() as u64, track_offsets.as_ptr(),
+                n_tracks as u64, obs_row.as_ptr(), obs_image.as_ptr(), n_obs as u64, row_track.as_ptr(),
+                intrinsics.as_ptr() as *const f32, poses.as_ptr() as *const f32, sweeps, warm, robust_deg, min_obs, 0,
+                poses_out.as_mut_ptr() as *mut f32, points_out.as_mut_ptr() as *mut f32, state.as_mut_ptr(),
+                image_stats.as_mut_ptr() as *mut u32, trace.as_mut_ptr() as *mut f64, counts.as_mut_ptr()))?;
+        }
+        poses_out.truncate(n_images);
+        points_out.truncate(n_tracks);
+        state.truncate(n_obs);
+        image_stats.truncate(n_images);
+        trace.truncate(sweeps as usize);
+        Ok((poses_out, points_out, state, image_stats, trace, counts))
+    }
+
     /// The link table of a matched collection (`lf_mkd_link_table_device`): per edge the compact list of the matches
     /// `match_q8_edges` or a verifier returned for `edges` over the pool `image_offsets` describes (`n_rows` rows), edges with
     /// fewer than `min_links` of them left out.  Returns (offsets, link_a, link_b, edge_links): edge e's correspondences are

@@ -1782,6 +1782,124 @@ int lf_mkd_view_graph(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b,
                       const int32_t *match, int32_t *match_out, float *rotations, uint32_t *edge_stats, float *edge_residual,
                       uint32_t *image_stats, uint32_t *counts);
 
+/* lf_mkd_tree_poses_device gives every image the view graph labelled an INITIAL POSE: the rotation the view graph gave it and
+ * a centre one unit step from its tree parent's, along the direction of the tree edge's translation.  It reads d_edge_a /
+ * d_edge_b uint32 [n_edges] and d_t f32 [n_edges][3] as lf_mkd_two_view_pose_device wrote them (x_b = R x_a + t, so c_b - c_a
+ * is parallel to 0 - R_b^T t), and d_rotations f32 [n_images][9] and d_image_stats uint32 [n_images][4] as
+ * lf_mkd_view_graph_device wrote them (word 1 the round, word 2 the tree edge).  It writes d_poses f32 [n_images][12] (R
+ * row-major, then t; world to camera), the array lf_mkd_global_positions_device starts from.
+ *  1 chain     image i's chain is i, its tree edge's other end, that image's, .. up to an image of round 0 (the root).  The
+ *              chain BREAKS at an image whose round is 0xFFFFFFFF or whose rotation is all zero, at a tree edge at or beyond
+ *              n_edges, at an edge with an end at or beyond n_images, with equal ends or that the image is no end of, at a
+ *              non-finite t or rotation of the edge's b, at a step of no length, and after max_depth steps without a root.
+ *  2 step      of a tree edge (a, b): d = 0 - R_b^T t under the view graph's R_b, u = d / sqrt(d.d), f64 (+ - * / and sqrt,
+ *              no contraction).  The image at end b stands at its parent's centre + u, the image at end a at its parent's - u.
+ *  3 centre    the root's is 0; every other image's is the sum of its chain's steps from the root down, in that order, so
+ *              c_i = c_parent +/- u to the bit and every word depends on the image's own chain alone.
+ *  4 output    a broken chain: the all-zero row ("not registered").  Otherwise R as given and t = 0 - R c, rounded once to
+ *              f32 (the root: [R | 0]).
+ * One launch, a thread per image, no scratch; a thread takes its chain 32 images at a time from the root's end and walks up
+ * to each run again, so an image at depth d costs d steps and d^2 / 64 reads of a parent.  Asynchronous on `stream` (NULL: the handle's own); capturable.  n_images == 0: LF_MKD_OK, nothing written.
+ * LF_MKD_ERR_BAD_ARG ("tree_poses_device: "), before any device is touched: with n_images > 0 a null d_rotations,
+ * d_image_stats or d_poses, and with n_edges > 0 too a null d_edge_a, d_edge_b or d_t; max_depth above
+ * LF_MKD_VIEW_GRAPH_MAX_ROUNDS; an array not 4-byte aligned; n_images or n_edges above 2^31 - 1. */
+int lf_mkd_tree_poses_device(lf_mkd *h, const uint32_t *d_edge_a, const uint32_t *d_edge_b, const float *d_t, uint32_t n_edges,
+                             const float *d_rotations, const uint32_t *d_image_stats, uint32_t n_images, uint32_t max_depth,
+                             float *d_poses, void *stream);
+/* The host form: host arrays in and out, staged through the handle; synchronous.  LF_MKD_ERR_BAD_ARG ("tree_poses: ") as
+ * above, without the alignment rule. */
+int lf_mkd_tree_poses(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b, const float *t, uint32_t n_edges,
+                      const float *rotations, const uint32_t *image_stats, uint32_t n_images, uint32_t max_depth, float *poses);
+
+/* lf_mkd_global_positions_device finds ALL CAMERA CENTRES AND ALL TRACK POINTS AT ONCE under held rotations: with R_i known an
+ * observation constrains X_k - c_i to a known world ray, so each adds a linear term in the two unknown positions, and
+ * alternating the points' and the cameras' 3x3 solves under robust weights converges without an initial pair and without
+ * resection rounds.  It reads the keypoints, the images' row ranges, the track table, the intrinsics and the poses as
+ * lf_mkd_bundle_adjust_device reads them, and d_row_track int32 [n_rows_total] as lf_mkd_resect_cameras_device reads it; the
+ * rotations of d_poses are held and 0 - R^T t is the initial centre (lf_mkd_tree_poses_device writes such an array).  T and O
+ * are d_table_counts[0] and [1] clamped to the capacities; ranges are clamped as in the sibling calls.
+ *  1 registered  image i takes part iff tri-usable: finite intrinsics with fx, fy > 0, twelve finite pose values, R not all zero.
+ *  2 usable      position p of the observation arrays is USABLE iff 0 <= d_obs_row[p] < n_rows_total, d_obs_image[p] is a
+ *                registered image and the row's x and y are finite.  A ROW r of registered image i (in its clamped range)
+ *                is usable iff 0 <= d_row_track[r] < T and its x and y are finite.  (The two agree on a table and a row map
+ *                from the same lf_mkd_track_table_device call.)  Its ray is v = R_i^T f / |f|, f = ((x - cx) / fx,
+ *                (y - cy) / fy, 1), as track triangulation forms it; its projector is P = I - v v^T.
+ *  3 weight      of an observation against a point X and a centre c, r = X - c: 1 under unit weights.  Under robust
+ *                weights 0 if v . r <= 0, r is zero or anything is not finite; else s0 / s if s = sqrt(|P r|^2 / |r|^2) > s0
+ *                and 1 otherwise, s0 = sin(robust_deg) formed once by the host in double.  Sweep s = 0, 1, .. has unit
+ *                weights iff s < warm.
+ *  4 point step  for track k < T: A = sum w P, g = sum w P c_i over its usable positions in table order, per component in
+ *                the 4-SLOT canonical order of track triangulation (position lo + j in slot j mod 4, ascending; (s0 + s2) +
+ *                (s1 + s3)); w against the point's previous value, and 1 if the point was unsolved in the previous sweep
+ *                (every point before the first).  If at least min_obs positions have w > 0 and the cofactor solve of track
+ *                triangulation accepts A with a finite result, X_k = A^-1 g and the point is SOLVED; otherwise it is
+ *                unsolved for this sweep, keeps its value, and its observations add nothing to the camera step.
+ *  5 camera step for registered image i: A = sum w P, g = sum w P X_k over its usable rows in solved tracks in ascending
+ *                row order, per component in the 256-SLOT canonical order of resection (row lo + j in slot j mod 256; the
+ *                butterfly within each 64 slots, then ((w0 + w1) + w2) + w3); w against the new points and the camera's
+ *                previous centre.  Solved under the same two conditions; otherwise HELD: it keeps its centre and the sweep
+ *                counts it.
+ *  6 gauge       before the first sweep and after every sweep, over the registered cameras (camera i in slot i mod 256 of
+ *                the 256-slot order): the mean m of their centres, rho = sqrt(sum |c - m|^2 / n); centres and all T points
+ *                become (. - m) / rho.  If there is no registered camera or m or rho is not finite and positive, nothing is
+ *                rescaled and d_counts[5] counts it.  The output lives in this gauge: centroid 0, rms radius 1.  (The gauge
+ *                before the first sweep makes the call invariant to a similarity of the input's centres.)
+ *  7 final       the final weights are against the final points and centres, under the last sweep's rule (unit without a
+ *                sweep); an observation of an unsolved track has none.
+ *  8 outputs     d_poses_out f32 [n_images][12], may be d_poses: R as given and t = 0 - R c rounded to f32; the zero row
+ *                  for an image that is not registered.
+ *                d_points_out optional, f32 [track_capacity][4] = {X, Y, Z, c} for the tracks below T, c the smallest
+ *                  cosine between the ray of the track's first position of final weight > 0 and each later such one (2 if
+ *                  there is none); {0, 0, 0, 2} for an unsolved track.  These points are what the sweeps minimised; the
+ *                  canonical points for the bundle still come from lf_mkd_triangulate_tracks_device under d_poses_out.
+ *                d_obs_state optional, uint32 [obs_capacity], for the positions inside the ranges of the tracks below T: 0
+ *                  not usable, 1 usable, 2 final weight at least 1/2.  Other entries are untouched.
+ *                d_image_stats uint32 [n_images][4] = {usable rows in solved tracks, those of final weight at least 1/2,
+ *                  sweeps in which it was held, reason of its last step: 0 solved (or no sweep), 1 not registered, 2 fewer
+ *                  than min_obs weighted rows, 3 singular}.
+ *                d_trace optional, f64 [sweeps][4] = {the weighted cost sum w |P r|^2 after the sweep's gauge under the
+ *                  sweep's rule over the usable positions p < O whose row's track is solved, position p in slot p mod 256
+ *                  of the 256-slot order; the positions with w > 0; cameras held; points unsolved}.
+ *                d_counts uint32 [8] = {registered images, solved points, usable rows in solved tracks, those of final
+ *                  weight at least 1/2, cameras held in the last sweep, gauge steps that did not rescale, T, sweeps}.
+ *  9 degenerate  sweeps == 0: the input's centres in the output gauge, every point unsolved.  n_images == 0: LF_MKD_OK,
+ *                  nothing is written.
+ * Device form: launches (lf_mkd_global_positions_plan's `launches`) 4 + 3 sweeps: init, gauge, then per sweep points (4 lanes
+ * own a track), cameras (a workgroup owns an image) and gauge (ONE workgroup), final images, final tracks; none for n_images
+ * == 0.  The gauge rescales the centres itself and hands m and rho on: the points are rescaled by whoever reads them next, the
+ * same operations on the same values.  A single image that owns every row is walked by one workgroup, a single track with
+ * every observation by 4 lanes, AND WITH A TRACE THE GAUGE'S COST PASS WALKS ALL O OBSERVATIONS IN ONE WORKGROUP: pass no
+ * d_trace where time matters.  No floating-point atomic, no workgroup waits for another, nothing is read back.
+ * Asynchronous on `stream` (NULL: the handle's own); the scratch belongs to the handle and only grows, so a warmed-up call is
+ * capturable in a hipGraph.  Calls of one handle are stream-ordered.
+ * LF_MKD_ERR_BAD_ARG ("global_positions_device: "), before any device is touched: with n_images > 0 a null d_image_offsets,
+ * d_table_counts, d_intrinsics, d_poses, d_poses_out, d_image_stats or d_counts; with track_capacity > 0 too a null
+ * d_track_offsets, and with obs_capacity > 0 too a null d_obs_row or d_obs_image; with n_images > 0 and n_rows_total > 0 a null
+ * d_kps or d_row_track; flags other than 0; sweeps above LF_MKD_GLOBAL_POSITIONS_MAX_SWEEPS; robust_deg outside (0, 90] or a
+ * NaN; min_obs below 2; d_image_offsets, d_track_offsets or d_trace not 8-byte or any other array not 4-byte aligned; a total
+ * or a capacity above 2^31 - 1. */
+#define LF_MKD_GLOBAL_POSITIONS_MAX_SWEEPS (4096u)  /* the largest sweeps */
+/* Host only: the launches and the scratch of lf_mkd_global_positions_device for these sizes.  Either output may be NULL.
+ * LF_MKD_ERR_BAD_ARG ("global_positions_plan: "): the sweeps and sizes the device call refuses. */
+int lf_mkd_global_positions_plan(uint32_t n_images, uint64_t track_capacity, uint32_t sweeps, uint32_t *launches,
+                                 uint64_t *scratch_bytes);
+int lf_mkd_global_positions_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                   uint64_t n_rows_total, const uint64_t *d_track_offsets, uint64_t track_capacity,
+                                   const int32_t *d_obs_row, const uint32_t *d_obs_image, uint64_t obs_capacity,
+                                   const uint32_t *d_table_counts, const int32_t *d_row_track, const float *d_intrinsics,
+                                   const float *d_poses, uint32_t sweeps, uint32_t warm, float robust_deg, uint32_t min_obs,
+                                   uint32_t flags, float *d_poses_out, float *d_points_out, uint32_t *d_obs_state,
+                                   uint32_t *d_image_stats, double *d_trace, uint32_t *d_counts, void *stream);
+/* The host form: host arrays in and out, staged through the handle, with n_tracks and n_obs as the table's counts;
+ * synchronous.  obs_state's entries outside every track's range come back 0.  LF_MKD_ERR_BAD_ARG ("global_positions: ") as
+ * above, without the alignment rules. */
+int lf_mkd_global_positions(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *image_offsets, uint32_t n_images,
+                            uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks, const int32_t *obs_row,
+                            const uint32_t *obs_image, uint64_t n_obs, const int32_t *row_track, const float *intrinsics,
+                            const float *poses, uint32_t sweeps, uint32_t warm, float robust_deg, uint32_t min_obs, uint32_t flags,
+                            float *poses_out, float *points_out, uint32_t *obs_state, uint32_t *image_stats, double *trace,
+                            uint32_t *counts);
+
 /* Host-only verification tap: the constants upload_constant_data (mod.rs:1587-1713) would place in
  * ConstantData (common.glsl:34-40), as this library builds them.  Any output pointer may be NULL.
  * gradient_angle[1024], embedding_polar[25*1024], embedding_cartesian[9*1024], w_t[128*238].

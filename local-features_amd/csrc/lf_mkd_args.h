@@ -54,6 +54,17 @@ inline const char *reproj_rule(float max_reproj_px) {
     return max_reproj_px > 0.f && std::isfinite(max_reproj_px) ? nullptr : "max_reproj_px must be finite and positive";
 }
 inline const char *rounds_rule(uint32_t rounds) { return rounds > 4 ? "rounds must be 0 .. 4" : nullptr; }
+// The scalars of lf_mkd_global_positions_device, of its host form and of its plan.
+inline const char *positions_sweeps_rule(uint32_t sweeps) {
+    return sweeps > LF_MKD_GLOBAL_POSITIONS_MAX_SWEEPS ? "sweeps must be 0 .. 4096 (each is three launches)" : nullptr;
+}
+inline const char *positions_scalars(uint32_t sweeps, float robust_deg, uint32_t min_obs, uint32_t flags) {
+    if (flags) return "unknown flag bits (no flag is defined: flags must be 0)";
+    if (const char *msg = positions_sweeps_rule(sweeps)) return msg;
+    if (!(robust_deg > 0.f && robust_deg <= 90.f)) return "robust_deg must be in (0, 90]";
+    if (min_obs < 2) return "min_obs must be at least 2";
+    return nullptr;
+}
 
 // The sizes of a flat 8-bit call (and of its plan): the match needs a second candidate for its ratio test (min_candidates 2),
 // the top-k and the grouped match answer from one.

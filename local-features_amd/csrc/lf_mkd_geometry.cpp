@@ -731,4 +731,164 @@ int lf_mkd_view_graph(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b,
     return LF_MKD_OK;
 }
 
+// Tree poses (csrc/mkd_positions.hip): one launch, no scratch.
+int lf_mkd_tree_poses_device(lf_mkd *h, const uint32_t *d_edge_a, const uint32_t *d_edge_b, const float *d_t, uint32_t n_edges,
+                             const float *d_rotations, const uint32_t *d_image_stats, uint32_t n_images, uint32_t max_depth,
+                             float *d_poses, void *stream) {
+    const char *msg = nullptr;
+    if (n_images && (!d_rotations || !d_image_stats || !d_poses)) msg = "null d_rotations, d_image_stats or d_poses";
+    else if (n_images && n_edges && (!d_edge_a || !d_edge_b || !d_t)) msg = "null d_edge_a, d_edge_b or d_t";
+    else if (max_depth > LF_MKD_VIEW_GRAPH_MAX_ROUNDS) msg = "max_depth must be 0 .. 4096";
+    else if (misaligned(3, d_edge_a, d_edge_b, d_t, d_rotations, d_image_stats, d_poses))
+        msg = "the edge, translation, rotation, statistics and pose arrays must be 4-byte aligned";
+    else if (above(kRowMax, n_images, n_edges)) msg = "n_images or n_edges above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "tree_poses_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    launch_tree_poses(d_edge_a, d_edge_b, d_t, n_edges, d_rotations, d_image_stats, n_images, max_depth, d_poses, stream_of(h, stream));
+    return launched(h);
+}
+
+// The host form: the arrays staged through the handle's d_ver_io with the poses, and the device call does the rest.
+int lf_mkd_tree_poses(lf_mkd *h, const uint32_t *edge_a, const uint32_t *edge_b, const float *t, uint32_t n_edges,
+                      const float *rotations, const uint32_t *image_stats, uint32_t n_images, uint32_t max_depth, float *poses) {
+    const char *msg = nullptr;
+    if (n_images && (!rotations || !image_stats || !poses)) msg = "null rotations, image_stats or poses";
+    else if (n_images && n_edges && (!edge_a || !edge_b || !t)) msg = "null edge_a, edge_b or t";
+    else if (max_depth > LF_MKD_VIEW_GRAPH_MAX_ROUNDS) msg = "max_depth must be 0 .. 4096";
+    else if (above(kRowMax, n_images, n_edges)) msg = "n_images or n_edges above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "tree_poses", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    Stager io(h, h->d_ver_io);
+    const auto d_ea = io.part<uint32_t>(n_edges), d_eb = io.part<uint32_t>(n_edges);
+    const auto d_t = io.part<float>(uint64_t(n_edges) * 3);
+    const auto d_rot = io.part<float>(uint64_t(n_images) * 9);
+    const auto d_is = io.part<uint32_t>(uint64_t(n_images) * 4);
+    const auto d_poses = io.part<float>(uint64_t(n_images) * 12);
+    if (int rc = io.reserve()) return rc;
+    LF_HIP(h, io.up(d_ea, edge_a, n_edges));
+    LF_HIP(h, io.up(d_eb, edge_b, n_edges));
+    LF_HIP(h, io.up(d_t, t, uint64_t(n_edges) * 3));
+    LF_HIP(h, io.up(d_rot, rotations, uint64_t(n_images) * 9));
+    LF_HIP(h, io.up(d_is, image_stats, uint64_t(n_images) * 4));
+    if (int rc = lf_mkd_tree_poses_device(h, d_ea, d_eb, d_t, n_edges, d_rot, d_is, n_images, max_depth, d_poses, h->stream)) return rc;
+    LF_HIP(h, io.down(poses, d_poses, uint64_t(n_images) * 12));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
+// Global positions (csrc/mkd_positions.hip).  The sine of the robust angle is formed here, once, in double: no transcendental
+// runs on the device (tests/cpp/positions_twin.cpp forms it with the same expression).
+int lf_mkd_global_positions_plan(uint32_t n_images, uint64_t track_capacity, uint32_t sweeps, uint32_t *launches,
+                                 uint64_t *scratch_bytes) {
+    const char *msg = positions_sweeps_rule(sweeps);
+    if (!msg && above(kRowMax, n_images, track_capacity)) msg = "n_images or track_capacity above 2^31 - 1";
+    if (msg) return refuse(nullptr, "global_positions_plan", msg);
+    const GlobalPositionsPlan p = global_positions_plan(n_images, track_capacity, sweeps);
+    if (launches) *launches = p.launches;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    return LF_MKD_OK;
+}
+
+int lf_mkd_global_positions_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const uint64_t *d_image_offsets, uint32_t n_images,
+                                   uint64_t n_rows_total, const uint64_t *d_track_offsets, uint64_t track_capacity,
+                                   const int32_t *d_obs_row, const uint32_t *d_obs_image, uint64_t obs_capacity,
+                                   const uint32_t *d_table_counts, const int32_t *d_row_track, const float *d_intrinsics,
+                                   const float *d_poses, uint32_t sweeps, uint32_t warm, float robust_deg, uint32_t min_obs,
+                                   uint32_t flags, float *d_poses_out, float *d_points_out, uint32_t *d_obs_state,
+                                   uint32_t *d_image_stats, double *d_trace, uint32_t *d_counts, void *stream) {
+    const char *msg = nullptr;
+    if (n_images && (!d_image_offsets || !d_table_counts || !d_intrinsics || !d_poses || !d_poses_out || !d_image_stats || !d_counts))
+        msg = "null d_image_offsets, d_table_counts, d_intrinsics, d_poses, d_poses_out, d_image_stats or d_counts";
+    else if (n_images && track_capacity && !d_track_offsets) msg = "null d_track_offsets";
+    else if (n_images && track_capacity && obs_capacity && (!d_obs_row || !d_obs_image)) msg = "null d_obs_row or d_obs_image";
+    else if (n_images && n_rows_total && (!d_kps || !d_row_track)) msg = "null d_kps or d_row_track";
+    else if ((msg = positions_scalars(sweeps, robust_deg, min_obs, flags))) {}
+    else if (misaligned(7, d_image_offsets) || misaligned(7, d_track_offsets) || misaligned(7, d_trace))
+        msg = "d_image_offsets, d_track_offsets and d_trace must be 8-byte aligned";
+    else if (misaligned(3, d_kps, d_obs_row, d_obs_image, d_table_counts, d_row_track, d_intrinsics, d_poses, d_poses_out, d_points_out,
+                        d_obs_state, d_image_stats, d_counts))
+        msg = "the keypoint, observation, count, track, intrinsics, pose, point, state, statistics and count arrays must be 4-byte aligned";
+    else if (above(kRowMax, n_images, n_rows_total, track_capacity, obs_capacity)) msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "global_positions_device", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const GlobalPositionsPlan plan = global_positions_plan(n_images, track_capacity, sweeps);
+    unsigned char *work;
+    if (int rc = scratch(h, h->d_positions, plan.scratch_bytes, &work)) return rc;
+    const double s0 = std::sin(double(robust_deg) * (3.14159265358979323846 / 180.0));
+    const unsigned issued = launch_global_positions(
+        plan, work, reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity,
+        d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_row_track, d_intrinsics, d_poses, sweeps, warm, s0, min_obs, d_poses_out,
+        d_points_out, d_obs_state, d_image_stats, d_trace, d_counts, stream_of(h, stream));
+    if (issued != plan.launches)
+        return fail(h, LF_MKD_ERR_HIP, "global_positions_device: issued " + std::to_string(issued) + " launches, the plan says " +
+                                           std::to_string(plan.launches));
+    return launched(h);
+}
+
+// The host form: the arrays staged through the handle's d_ver_io with the outputs, counts = {n_tracks, n_obs}, in place on the
+// staged poses.  The staged obs_state starts as zeros, so its entries outside every track's range come back 0.
+int lf_mkd_global_positions(lf_mkd *h, const lf_mkd_keypoint *kps, const uint64_t *image_offsets, uint32_t n_images,
+                            uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks, const int32_t *obs_row,
+                            const uint32_t *obs_image, uint64_t n_obs, const int32_t *row_track, const float *intrinsics,
+                            const float *poses, uint32_t sweeps, uint32_t warm, float robust_deg, uint32_t min_obs, uint32_t flags,
+                            float *poses_out, float *points_out, uint32_t *obs_state, uint32_t *image_stats, double *trace,
+                            uint32_t *counts) {
+    const char *msg = nullptr;
+    if (n_images && (!image_offsets || !intrinsics || !poses || !poses_out || !image_stats || !counts))
+        msg = "null image_offsets, intrinsics, poses, poses_out, image_stats or counts";
+    else if (n_images && n_tracks && !track_offsets) msg = "null track_offsets";
+    else if (n_images && n_tracks && n_obs && (!obs_row || !obs_image)) msg = "null obs_row or obs_image";
+    else if (n_images && n_rows_total && (!kps || !row_track)) msg = "null kps or row_track";
+    else if ((msg = positions_scalars(sweeps, robust_deg, min_obs, flags))) {}
+    else if (above(kRowMax, n_images, n_rows_total, n_tracks, n_obs)) msg = "a total above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "global_positions", msg);
+    if (n_images == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const uint64_t n_used = n_tracks ? n_obs : 0;
+    Stager io(h, h->d_ver_io);
+    const auto d_trace = io.part<double>(trace ? uint64_t(sweeps) * 4 : 0);
+    const auto d_ioff = io.part<uint64_t>(uint64_t(n_images) + 1), d_toff = io.part<uint64_t>(n_tracks + 1);
+    const auto d_tc = io.part<uint32_t>(2), d_counts = io.part<uint32_t>(8);
+    const auto d_kps = io.part<lf_mkd_keypoint>(n_rows_total);
+    const auto d_rt = io.part<int32_t>(n_rows_total);
+    const auto d_row = io.part<int32_t>(n_used);
+    const auto d_image = io.part<uint32_t>(n_used);
+    const auto d_K = io.part<float>(uint64_t(n_images) * 4), d_poses = io.part<float>(uint64_t(n_images) * 12);
+    const auto d_points = io.part<float>(points_out ? n_tracks * 4 : 0);
+    const auto d_state = io.part<uint32_t>(obs_state ? n_used : 0);
+    const auto d_is = io.part<uint32_t>(uint64_t(n_images) * 4);
+    if (int rc = io.reserve()) return rc;
+    const uint32_t tc[2] = {uint32_t(n_tracks), uint32_t(n_used)};
+    LF_HIP(h, io.up(d_ioff, image_offsets, uint64_t(n_images) + 1));
+    LF_HIP(h, io.up(d_toff, track_offsets, n_tracks ? n_tracks + 1 : 0));
+    LF_HIP(h, io.up(d_tc, tc, 2));
+    LF_HIP(h, io.up(d_kps, kps, n_rows_total));
+    LF_HIP(h, io.up(d_rt, row_track, n_rows_total));
+    LF_HIP(h, io.up(d_row, obs_row, n_used));
+    LF_HIP(h, io.up(d_image, obs_image, n_used));
+    LF_HIP(h, io.up(d_K, intrinsics, uint64_t(n_images) * 4));
+    LF_HIP(h, io.up(d_poses, poses, uint64_t(n_images) * 12));
+    if (obs_state && n_used) LF_HIP(h, hipMemsetAsync(d_state.get(), 0, n_used * 4, h->stream));
+    if (int rc = lf_mkd_global_positions_device(h, d_kps, d_ioff, n_images, n_rows_total, d_toff, n_tracks, d_row, d_image, n_used, d_tc,
+                                                d_rt, d_K, d_poses, sweeps, warm, robust_deg, min_obs, flags, d_poses,
+                                                points_out ? d_points.get() : nullptr, obs_state ? d_state.get() : nullptr, d_is,
+                                                trace ? d_trace.get() : nullptr, d_counts, h->stream))
+        return rc;
+    LF_HIP(h, io.down(poses_out, d_poses, uint64_t(n_images) * 12));
+    LF_HIP(h, io.down(points_out, d_points, points_out ? n_tracks * 4 : 0));
+    LF_HIP(h, io.down(obs_state, d_state, obs_state ? n_used : 0));
+    LF_HIP(h, io.down(image_stats, d_is, uint64_t(n_images) * 4));
+    LF_HIP(h, io.down(trace, d_trace, trace ? uint64_t(sweeps) * 4 : 0));
+    LF_HIP(h, io.down(counts, d_counts, 8));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
+}
+
 }  // extern "C"

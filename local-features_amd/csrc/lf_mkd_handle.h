@@ -254,6 +254,8 @@ struct lf_mkd {
     HipArray<unsigned char> d_bundle;
     // lf_mkd_view_graph_device's scratch (view_graph_plan's scratch_bytes), in the same way
     HipArray<unsigned char> d_view_graph;
+    // lf_mkd_global_positions_device's scratch (global_positions_plan's scratch_bytes), in the same way
+    HipArray<unsigned char> d_positions;
     HipArray<VerifyPair> d_ver_pairs;
     HipArray<unsigned> d_ver_counts;
     HipArray<unsigned char> d_ver_io;

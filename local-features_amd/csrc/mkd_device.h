@@ -412,6 +412,26 @@ unsigned launch_view_graph(const ViewGraphPlan &plan, unsigned char *scratch, co
                        unsigned min_front, unsigned root, unsigned tree_rounds, unsigned iterations, bool use_unchecked,
                        const uint64_t *edge_off, uint64_t capacity, const int *match, int *match_out, float *rotations,
                        unsigned *edge_stats, float *residual, unsigned *image_stats, unsigned *counts, hipStream_t stream);
+// tree poses (csrc/mkd_positions.hip, lf_mkd_tree_poses_device): one launch, a thread per image, no scratch.
+void launch_tree_poses(const unsigned *edge_a, const unsigned *edge_b, const float *t, unsigned n_edges, const float *rotations,
+                       const unsigned *image_stats, unsigned n_images, unsigned max_depth, float *poses, hipStream_t stream);
+// global positions (csrc/mkd_positions.hip, lf_mkd_global_positions_device).  The plan is the one place that knows the launches
+// (4 + 3 sweeps: init, gauge, then points, cameras and gauge per sweep, final images, final tracks; none for n_images == 0)
+// and the layout of the scratch (byte offsets, 16-byte aligned): the centres f64 [n_images][3], the points f64
+// [track_capacity][3], the rotations f32 [n_images][9], registered, held and reason uint32 [n_images] each, the points' flags
+// uint32 [track_capacity], four words, the latest gauge f64 [4].  s0 = the sine of the robust angle, formed by the host in double.  poses_out may be
+// poses.  Returns the launches it issued, which the entry point holds against the plan's.
+struct GlobalPositionsPlan {
+    unsigned launches;
+    uint64_t off_cen, off_pt, off_rot, off_reg, off_held, off_reason, off_tflag, off_words, off_gauge, scratch_bytes;
+};
+GlobalPositionsPlan global_positions_plan(unsigned n_images, uint64_t track_capacity, unsigned sweeps);
+unsigned launch_global_positions(const GlobalPositionsPlan &plan, unsigned char *scratch, const float *kps,
+                                 const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows, const uint64_t *track_offsets,
+                                 uint64_t track_capacity, const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity,
+                                 const unsigned *table_counts, const int *row_track, const float *intrinsics, const float *poses,
+                                 unsigned sweeps, unsigned warm, double s0, unsigned min_obs, float *poses_out, float *points_out,
+                                 unsigned *obs_state, unsigned *image_stats, double *trace, unsigned *counts, hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
+"""match_collection [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--global SWEEPS] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...] -- N images of one size,
 matched along any list of image pairs ("edges") on the device: an image sits on as many edges as the list says, and no
 descriptor row is copied for it.
 
@@ -47,6 +47,10 @@ descriptor row is copied for it.
   [images][12] poses of the file (R row-major, then  rounds at 4 px; without a file the edge with the most links with parallax is
   t; world to camera)                                the initial pair, [I | 0] and its [R | t], chosen on the device, and every
                                                      other image stays all zero: not registered
+  with --global SWEEPS (needs --pose and              LocalFeatures.tree_poses (lf_mkd_tree_poses_device) on the view graph's rotations
+  --view-graph; implies --triangulate) every image    and tree, then LocalFeatures.global_positions (lf_mkd_global_positions_device) in
+  posed at once: no initial pair, no rounds           place: all centres and points by SWEEPS alternating solves; then the
+                                                     triangulation, and with --bundle the bundle with two images held
   with --register ROUNDS (needs --pose; implies       ROUNDS times LocalFeatures.resect_cameras (lf_mkd_resect_cameras_device) in
   --triangulate) the other images registered from     place on the pose array -- P3P samples over the keypoints an image owns in
   the points and the points triangulated again       tracks with a point, 512 samples, at least 12 inliers at 4 px -- and then
@@ -121,7 +125,7 @@ def retrieved_edges(feats, q, o, frame_of, n, k, ratio=RATIO):
 
 def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fundamental=False, ratio=RATIO, seed=0, feats=None, tracks=False,
                      table=False, pairs=False, min_inliers=None, expand=None, min_shared=8, pose=None, triangulate=None, register=0, bundle=0,
-                     refine_focal=False, refine_principal=False, view_graph=None):
+                     refine_focal=False, refine_principal=False, view_graph=None, global_sweeps=0):
     """frames [n, h, w] float32 in [0, 1]; mode "window" (arg = W), "all", "retrieve" or "select" (arg = K).  Returns a dict of device
     tensors: edge_a / edge_b [E]; offsets [n + 1] of the frames; keypoints [m,5] and q8 [m,128], the pool; layout_a / layout_b
     [E + 1], the two edge layouts; match and verified, the mutual and the verified matches in the a side's layout; model
@@ -227,7 +231,9 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
             links_for_tracks = vg_match
         track = track_len = track_dup = track_counts = None
         t_off = t_rows = t_img = t_row_track = t_counts = t_kps = None
-        if (register or bundle) and triangulate is None:
+        if global_sweeps and view_graph is None:
+            raise RuntimeError("match_collection: global_sweeps needs view_graph (the images' global rotations and the tree)")
+        if (register or bundle or global_sweeps) and triangulate is None:
             triangulate = True
         if tracks or table or expand or triangulate is not None:
             track, track_len, track_dup = feats.build_tracks(o, ea, eb, la, links_for_tracks, capacity=cap_a, n_rows=m)
@@ -270,10 +276,17 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
         tri_poses = tri_points = tri_stats = tri_err = tri_state = None
         register_rounds = [] if register else None       # (None without `register`, like every output that was not asked for)
         bundle_trace = bundle_counts = bundle_state = bundle_rms = bundle_groups = None
+        gp_points = gp_state = gp_ims = gp_counts = None
         if triangulate is not None and triangulate is not False:
             if pose is None:
                 raise RuntimeError("match_collection: triangulate needs pose (the cameras' intrinsics)")
-            if triangulate is True:
+            if global_sweeps:
+                # the global route: no initial pair and no rounds -- the view graph's rotations, unit steps along its tree,
+                # then every centre and every point at once, in place on the pose array
+                tri_poses = feats.tree_poses((ea, eb), p_t, vg_rot, vg_ims)
+                tri_poses, gp_points, gp_state, gp_ims, _, gp_counts = feats.global_positions(
+                    kps, o, (t_off, t_rows, t_img, t_row_track, t_counts), intr, tri_poses, sweeps=global_sweeps, out_poses=tri_poses)
+            elif triangulate is True:
                 # the initial pair, chosen on the device: nothing is read back
                 with_pose = torch.where(p_stats[:, 2] >= 0, p_stats[:, 3], torch.full_like(p_stats[:, 3], -1))
                 if vg_es is not None:                           # ... among the edges the view graph supports
@@ -287,6 +300,9 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 tri_poses = torch.as_tensor(np.ascontiguousarray(triangulate, np.float32).reshape(n, 12), device=dev)
             tri_points, tri_stats, tri_err, tri_state = feats.triangulate_tracks(kps, (t_off, t_rows, t_img, t_counts), intr, tri_poses)
             held = (tri_poses[:, :9] != 0).any(1).to(torch.int32)
+            if global_sweeps:
+                # every image has a pose: the two with the most weighted rows hold the bundle's gauge
+                held = torch.zeros_like(held).index_fill_(0, torch.topk(gp_ims[:, 1], min(2, n)).indices, 1)
             for _ in range(register or 0):
                 # the images without a pose from the points there are, in place; then the points under every pose there is
                 _, r_stats, _, _ = feats.resect_cameras(kps, o, t_row_track, tri_points, t_counts, intr, tri_poses, seed=seed,
@@ -310,7 +326,7 @@ def match_collection(frames, mode="window", arg=2, top_n=2000, min_size=0.0, fun
                 active = bundle_state >= 1
                 bundle_rms = torch.stack([reprojection_rms(kps, t_off, t_rows, t_img, K, P, X, active) for P, X, K in
                                           (before, (tri_poses, tri_points, intr))])
-    return dict(bundle_groups=bundle_groups, intrinsics=intr if pose is not None else None, bundle_trace=bundle_trace, bundle_counts=bundle_counts, bundle_obs_state=bundle_state, bundle_rms=bundle_rms,
+    return dict(gp_points=gp_points, gp_obs_state=gp_state, gp_image_stats=gp_ims, gp_counts=gp_counts, bundle_groups=bundle_groups, intrinsics=intr if pose is not None else None, bundle_trace=bundle_trace, bundle_counts=bundle_counts, bundle_obs_state=bundle_state, bundle_rms=bundle_rms,
                 register_rounds=register_rounds, tri_poses=tri_poses, tri_points=tri_points, tri_stats=tri_stats, tri_err=tri_err, tri_obs_state=tri_state,
                 edge_a=ea, edge_b=eb, offsets=o, keypoints=kps, q8=q, layout_a=la, layout_b=lb, match=m_ab, verified=ver, model=model,
                 stats=stats, per_edge=per_edge, track=track, track_len=track_len, track_dup=track_dup, track_counts=track_counts,
@@ -367,6 +383,15 @@ def view_graph_lines(out):
             f"{labelled} of {out['vg_image_stats'].shape[0]} images with a rotation, root {root + 1}"]
 
 
+def global_lines(out):
+    """one line of `global_sweeps`' counts"""
+    if out.get("gp_counts") is None:
+        return []
+    reg, solved, usable, weighted, held, failed, tracks, sweeps = out["gp_counts"].cpu().tolist()
+    return [f"global positions, {sweeps} sweeps: {reg} images, {solved} of {tracks} points solved, {weighted} of {usable} observations "
+            f"weighted at least 1/2, {held} cameras held in the last sweep"]
+
+
 def register_lines(out):
     """one line per round of `register`: the images registered after it, those it added, and the points"""
     n_tracks = out["table_counts"].cpu().tolist()[0]
@@ -398,7 +423,7 @@ def main():
     mode, arg, fundamental, tracks, table, pairs, min_inliers, paths = "window", 2, False, False, False, False, None, []
     expand, min_shared, pose, triangulate, register, bundle = None, 8, None, None, 0, 0
     refine_focal = refine_principal = False
-    view_graph = None
+    view_graph, global_sweeps = None, 0
     while args:
         a = args.pop(0)
         if a == "--fundamental":
@@ -424,6 +449,10 @@ def main():
         elif a == "--triangulate":
             tracks = table = True
             triangulate = np.load(args.pop(0)) if args and args[0].endswith(".npy") else True
+        elif a == "--global" and args and args[0].isdigit() and 0 < int(args[0]) <= 4096:
+            tracks = table = True
+            global_sweeps = int(args.pop(0))
+            triangulate = True if triangulate is None else triangulate
         elif a == "--register" and args and args[0].isdigit() and int(args[0]) > 0:
             tracks = table = True
             register = int(args.pop(0))
@@ -445,11 +474,11 @@ def main():
             break
         else:
             paths.append(a)
-    if len(paths) < 2 or (triangulate is not None and pose is None) or (view_graph is not None and pose is None) or ((refine_focal or refine_principal) and not bundle) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
-        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
+    if len(paths) < 2 or (triangulate is not None and pose is None) or (view_graph is not None and pose is None) or (global_sweeps and view_graph is None) or ((refine_focal or refine_principal) and not bundle) or (mode in ("retrieve", "select") and arg > len(paths) - 1) or (expand or 0) > min(len(paths) - 1, 32):
+        print("Required arguments: [--window W | --all | --retrieve K | --select K] [--fundamental] [--tracks] [--table] [--pairs] [--min-inliers M] [--expand K [--min-shared M]] [--pose FOCAL[,CX,CY]] [--view-graph DEG] [--global SWEEPS] [--triangulate [POSES.npy]] [--register ROUNDS] [--bundle ITERS [--refine-focal] [--refine-principal]] IMAGE_1 IMAGE_2 [IMAGE_3 ...]  (K "
               "below "
               "the "
-              "number of images; --view-graph, --triangulate, --register and --bundle need --pose, --refine-focal and --refine-principal --bundle)", file=sys.stderr)
+              "number of images; --view-graph, --triangulate, --register and --bundle need --pose, --global --pose and --view-graph, --refine-focal and --refine-principal --bundle)", file=sys.stderr)
         return 1
     imgs = [load_gray(p) for p in paths]
     if any(i.shape != imgs[0].shape for i in imgs):
@@ -459,7 +488,7 @@ def main():
         pose = (pose[0], imgs[0].shape[1] / 2.0, imgs[0].shape[0] / 2.0)
     out = match_collection(np.stack(imgs), mode, arg, fundamental=fundamental, tracks=tracks, table=table, pairs=pairs,
                            min_inliers=min_inliers, expand=expand, min_shared=min_shared, pose=pose, triangulate=triangulate, register=register, bundle=bundle,
-                           refine_focal=refine_focal, refine_principal=refine_principal, view_graph=view_graph)
+                           refine_focal=refine_focal, refine_principal=refine_principal, view_graph=view_graph, global_sweeps=global_sweeps)
     ea, eb, o, per_edge = (out[k].cpu().tolist() for k in ("edge_a", "edge_b", "offsets", "per_edge"))
     if mode == "select":                                        # the entries behind the edges name no image
         kept = out["select_counts"].cpu().tolist()[0]
@@ -514,6 +543,8 @@ def main():
         median = np.degrees(np.arccos(np.clip(np.median(pts[have, 3]), -1, 1))) if have.any() else 0.0
         print(f"Triangulated: {n_tracks} tracks under {registered} registered images, {int(have.sum())} points, "
               f"{int(st[have, 1].sum())} inlier observations, median parallax {median:.2f} deg")
+        for line in global_lines(out):
+            print(line)
         for line in register_lines(out):
             print("Registered, " + line)
         for line in bundle_lines(out):

@@ -15,7 +15,7 @@ import numpy as np
 
 from ._lib import (ANGLE_EXACT, ANGLE_EXACT_ZERO, ANGLE_SHADER, FLAG_DETECT_STEPWISE, FLAG_KERNEL_TIMING, FLAG_UNFUSED_KEYPOINTS, KEYPOINT_DTYPE, KNN_MAX, LIB_PATH, MODEL_DIR, PCA_NAMES,
                    POOL_DEFAULT, POOL_F16X3, POOL_F32, POOL_F16_FP6, SYMBOLS, COMM_ID_BYTES, GATHER_DIRECT, GATHER_RING, GUIDE_FUNDAMENTAL, GUIDE_HOMOGRAPHY, MATCH_MUTUAL, TRACKS_ACCUMULATE, TRACKS_DUP_TILE, TRACK_TABLE_CONSISTENT, LINK_TABLE_LOCAL, SELECT_SKIP_SELF, SELECT_UNIQUE, SELECT_MAX_K, COVIS_ACCUMULATE, COVIS_FORM_LDS, RESECT_ALL, VIEW_GRAPH_USE_UNCHECKED, VIEW_GRAPH_AUTO_ROOT, BA_REFINE_FOCAL, BA_REFINE_PRINCIPAL, VERIFY_NO_REFINE, Comm,
-                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan, view_graph_plan)
+                   MkdHandle, Q8_SCALE, comm_unique_id, knn_q8_plan, load_library, match_q8_grouped_plan, match_q8_pairs_plan, match_q8_plan, model_path, plan_upload, track_table_plan, link_table_plan, select_edges_plan, covisibility_plan, view_graph_plan, global_positions_plan, GLOBAL_POSITIONS_MAX_SWEEPS)
 
 __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXACT", "ANGLE_EXACT_ZERO", "POOL_DEFAULT", "POOL_F32", "POOL_F16_FP6",
            "POOL_F16X3", "FLAG_KERNEL_TIMING", "FLAG_UNFUSED_KEYPOINTS", "FLAG_DETECT_STEPWISE", "KEYPOINT_DTYPE", "PCA_NAMES", "SYMBOLS", "LIB_PATH", "MODEL_DIR",
@@ -24,7 +24,8 @@ __all__ = ["Keypoint", "LocalFeatures", "MkdHandle", "ANGLE_SHADER", "ANGLE_EXAC
            "KNN_MAX", "knn_q8_plan", "match_q8_grouped_plan", "TRACKS_ACCUMULATE", "TRACKS_DUP_TILE", "TRACK_TABLE_CONSISTENT", "track_table_plan",
            "LINK_TABLE_LOCAL", "link_table_plan", "SELECT_SKIP_SELF", "SELECT_UNIQUE", "SELECT_MAX_K", "select_edges_plan",
            "COVIS_ACCUMULATE", "COVIS_FORM_LDS", "RESECT_ALL", "BA_REFINE_FOCAL", "BA_REFINE_PRINCIPAL", "covisibility_plan",
-           "VIEW_GRAPH_USE_UNCHECKED", "VIEW_GRAPH_AUTO_ROOT", "view_graph_plan"]
+           "VIEW_GRAPH_USE_UNCHECKED", "VIEW_GRAPH_AUTO_ROOT", "view_graph_plan", "GLOBAL_POSITIONS_MAX_SWEEPS",
+           "global_positions_plan"]
 
 
 class Keypoint:
@@ -1061,6 +1062,94 @@ class LocalFeatures:
                                               VIEW_GRAPH_AUTO_ROOT if root is None else root, tree_rounds, iterations,
                                               VIEW_GRAPH_USE_UNCHECKED if use_unchecked else 0, s.cuda_stream)
         return rot, es, res, ims, counts, out_match
+
+    def tree_poses(self, edges, t, rotations, image_stats, max_depth=64, stream=None):
+        """Initial poses from the view graph's tree (lf_mkd_tree_poses_device): every labelled image gets the rotation
+        view_graph gave it and a centre one unit step from its tree parent's, along the tree edge's translation; the root
+        gets [R | 0].  edges = (edge_a, edge_b) 32-bit image ids and t [n_edges, 3] float32 as two_view_pose returned them;
+        rotations [n_images, 3, 3] (or [n_images, 9]) float32 and image_stats [n_images, 4] int32 as view_graph returned
+        them.  Returns poses [n_images, 12] float32 (R row-major, then t; world to camera), the all-zero row for an image
+        whose chain of tree edges does not reach the root within max_depth steps: what global_positions starts from.
+        Nothing is read back: asynchronous on `stream`, capturable."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, ty: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == ty and x.is_contiguous()
+            ea, eb = self._words(edges[0], dev), self._words(edges[1], dev)
+            n_edges = ea.numel()
+            if not (ok(t, torch.float32) and t.numel() == 3 * n_edges and eb.numel() == n_edges):
+                raise RuntimeError("tree_poses: t must be a contiguous float32 device tensor with 3 values per edge, edges one id "
+                                   "per edge in each of its two arrays")
+            if not (ok(rotations, torch.float32) and rotations.numel() % 9 == 0):
+                raise RuntimeError("tree_poses: rotations must be a contiguous float32 [n_images, 9] device tensor")
+            n_images = rotations.numel() // 9
+            if not (ok(image_stats, torch.int32) and image_stats.numel() == 4 * n_images):
+                raise RuntimeError("tree_poses: image_stats must be a contiguous int32 [n_images, 4] device tensor")
+            poses = torch.empty((n_images, 12), dtype=torch.float32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.tree_poses_device(ptr(ea), ptr(eb), ptr(t), n_edges, ptr(rotations), ptr(image_stats), n_images,
+                                              ptr(poses), max_depth, s.cuda_stream)
+        return poses
+
+    def global_positions(self, kps, offsets, table, intrinsics, poses, sweeps=50, warm=3, robust_deg=0.2, min_obs=2,
+                         out_poses=None, points=True, obs_state=True, trace=False, stream=None):
+        """Global positioning (lf_mkd_global_positions_device): all camera centres and all track points at once under the
+        rotations of `poses`, by `sweeps` alternations of the points' and the cameras' weighted 3x3 solves (unit weights for
+        the first `warm`, then weights that floor at the sine of robust_deg), each followed by a similarity that puts the
+        centres' centroid at 0 and their rms radius at 1 (include/lf_mkd.h states the algorithm).  kps [rows, 5] float32 is
+        the pool and offsets [n_images + 1] int64 its image offsets; table = (offsets, rows, images, row_track, counts) as
+        track_table returned it with image_offsets; intrinsics [n_images, 4] float32; poses [n_images, 12] float32 as
+        tree_poses returned them (an all-zero rotation: the image takes no part).  out_poses names the tensor to write,
+        `poses` itself for a call in place.  Returns device tensors (poses [n_images, 12] float32, points [track_capacity, 4]
+        float32 = X, Y, Z and the track's smallest cosine ({0, 0, 0, 2}: unsolved) or None, obs_state [obs_capacity] int32 (0
+        not usable, 1 usable, 2 final weight at least 1/2; -1 outside every track) or None, image_stats [n_images, 4] int32 =
+        usable rows in solved tracks, those of weight at least 1/2, sweeps held, reason; trace [sweeps, 4] float64 = cost,
+        weighted observations, held cameras, unsolved points, or None -- THE TRACE'S COST IS SUMMED BY ONE WORKGROUP; counts
+        [8] int32).  triangulate_tracks under the returned poses gives the points bundle_adjust takes.  Nothing is read back:
+        asynchronous on `stream`, capturable once warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if len(table) != 5:
+            raise RuntimeError("global_positions: table must be track_table's (offsets, rows, images, row_track, counts)")
+        t_off, rows, images, row_track, counts = table
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, ty: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == ty and x.is_contiguous()
+            if not (ok(t_off, torch.int64) and t_off.dim() == 1 and t_off.numel() >= 1 and ok(rows, torch.int32)
+                    and images is not None and ok(images, torch.int32) and rows.numel() == images.numel()
+                    and ok(counts, torch.int32) and counts.numel() >= 2):
+                raise RuntimeError("global_positions: table must be (offsets int64, rows int32, images int32, row_track int32, "
+                                   "counts int32) contiguous device tensors as track_table returned them with image_offsets")
+            if not (ok(kps, torch.float32) and kps.dim() == 2 and kps.shape[1] == 5):
+                raise RuntimeError("global_positions: kps must be a contiguous float32 [rows, 5] device tensor")
+            if not (ok(row_track, torch.int32) and row_track.numel() == kps.shape[0]):
+                raise RuntimeError("global_positions: row_track must be a contiguous int32 [rows] device tensor")
+            if not (ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1):
+                raise RuntimeError("global_positions: offsets must be a contiguous int64 [n_images + 1] device tensor")
+            n_images, tcap, ocap = offsets.numel() - 1, t_off.numel() - 1, rows.numel()
+            if not (ok(intrinsics, torch.float32) and intrinsics.numel() == 4 * n_images and ok(poses, torch.float32)
+                    and poses.numel() == 12 * n_images):
+                raise RuntimeError("global_positions: intrinsics must be float32 [n_images, 4] and poses float32 [n_images, 12] "
+                                   "contiguous device tensors")
+            if out_poses is None:
+                out_poses = torch.empty((n_images, 12), dtype=torch.float32, device=dev)
+            elif not (ok(out_poses, torch.float32) and out_poses.numel() == 12 * n_images):
+                raise RuntimeError("global_positions: out_poses must be a contiguous float32 [n_images, 12] device tensor")
+            xo = torch.zeros((tcap, 4), dtype=torch.float32, device=dev) if points else None
+            so = torch.full((ocap,), -1, dtype=torch.int32, device=dev) if obs_state else None
+            ims = torch.zeros((n_images, 4), dtype=torch.int32, device=dev)
+            tr = torch.zeros((sweeps, 4), dtype=torch.float64, device=dev) if trace else None
+            cnt = torch.zeros((8,), dtype=torch.int32, device=dev)
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.global_positions_device(ptr(kps), offsets.data_ptr(), n_images, kps.shape[0], t_off.data_ptr(), tcap,
+                                                    ptr(rows), ptr(images), ocap, counts.data_ptr(), ptr(row_track), ptr(intrinsics),
+                                                    ptr(poses), ptr(out_poses), ptr(ims), cnt.data_ptr(), d_points_out=ptr(xo),
+                                                    d_obs_state=ptr(so), d_trace=ptr(tr), sweeps=sweeps, warm=warm,
+                                                    robust_deg=robust_deg, min_obs=min_obs, stream=s.cuda_stream)
+        return out_poses, xo, so, ims, tr, cnt
 
     def bundle_adjust(self, kps, offsets, table, points, intrinsics, poses, obs_state=None, camera_fixed=None, max_reproj_px=4.0,
                       lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, out_poses=None, out_points=None,

@@ -54,6 +54,8 @@ SYMBOLS = (
     "lf_mkd_bundle_adjust", "lf_mkd_bundle_adjust_device",
     "lf_mkd_bundle_adjust_intrinsics", "lf_mkd_bundle_adjust_intrinsics_device",
     "lf_mkd_view_graph_plan", "lf_mkd_view_graph", "lf_mkd_view_graph_device",
+    "lf_mkd_tree_poses", "lf_mkd_tree_poses_device",
+    "lf_mkd_global_positions_plan", "lf_mkd_global_positions", "lf_mkd_global_positions_device",
 )
 Q8_SCALE = 256.0         # the default scale of the 8-bit descriptors (lf_mkd.h: byte = clamp(rint(x * scale), -127, 127) + 128)
 KNN_MAX = 16             # LF_MKD_KNN_MAX: the largest k of lf_mkd_knn_q8_device
@@ -69,6 +71,7 @@ BA_REFINE_PRINCIPAL = 2  # LF_MKD_BA_REFINE_PRINCIPAL: ... and the groups' princ
 RESECT_ALL = 1           # LF_MKD_RESECT_ALL: lf_mkd_resect_cameras_device resects registered images too
 VIEW_GRAPH_USE_UNCHECKED = 1     # LF_MKD_VIEW_GRAPH_USE_UNCHECKED: lf_mkd_view_graph_device keeps edges that close no triangle
 VIEW_GRAPH_AUTO_ROOT = 0xFFFFFFFF    # LF_MKD_VIEW_GRAPH_AUTO_ROOT: its root is the image with the most kept incident edges
+GLOBAL_POSITIONS_MAX_SWEEPS = 4096   # LF_MKD_GLOBAL_POSITIONS_MAX_SWEEPS: the largest sweeps of lf_mkd_global_positions_device
 COVIS_FORM_LDS = 256     # LF_MKD_COVIS_FORM_LDS: in covisibility_plan's form, workgroups count in LDS first
 SELECT_MAX_K = 32        # LF_MKD_SELECT_MAX_K: the largest k of lf_mkd_select_edges_device
 COMM_ID_BYTES = 128
@@ -210,6 +213,13 @@ def load_library():
                                            vp, vp, vp, vp, vp, vp]
     L.lf_mkd_view_graph.argtypes = [vp, vp, vp, u32, vp, vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, vp, u64, vp, vp, vp, vp,
                                     vp, vp, vp]
+    L.lf_mkd_tree_poses_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, u32, vp, vp]
+    L.lf_mkd_tree_poses.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, u32, vp]
+    L.lf_mkd_global_positions_plan.argtypes = [u32, u64, u32, vp, vp]
+    L.lf_mkd_global_positions_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, u32, u32,
+                                                 ctypes.c_float, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.lf_mkd_global_positions.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, u32, u32, ctypes.c_float, u32,
+                                          u32, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_verify_homography.argtypes = [vp, vp, u64, vp, u64, vp, u32, ctypes.c_float, u32, u32, vp, vp, vp]
     L.lf_mkd_verify_homography_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, u32, u32, vp, vp, vp, vp]
     L.lf_mkd_verify_fundamental.argtypes = L.lf_mkd_verify_homography.argtypes
@@ -372,6 +382,17 @@ def view_graph_plan(n_images, n_edges, tree_rounds=16, iterations=10, flags=0, w
     if rc != 0:
         raise RuntimeError(f"lf_mkd_view_graph_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
     return l.value, b.value, f.value
+
+
+def global_positions_plan(n_images, track_capacity, sweeps=50):
+    """(launches, scratch_bytes) of lf_mkd_global_positions_device: 4 + 3 sweeps launches (none without images) and the
+    handle's scratch (lf_mkd_global_positions_plan; needs no device)."""
+    l, b = ctypes.c_uint32(), ctypes.c_uint64()
+    L = load_library()
+    rc = L.lf_mkd_global_positions_plan(n_images, track_capacity, sweeps, ctypes.byref(l), ctypes.byref(b))
+    if rc != 0:
+        raise RuntimeError(f"lf_mkd_global_positions_plan failed ({rc}): {L.lf_mkd_last_error(None).decode()}")
+    return l.value, b.value
 
 
 class Comm:
@@ -743,6 +764,58 @@ class MkdHandle:
         return (rot[:n_images], es[:n], res[:n] if residual else None, ims[:n_images], counts,
                 out[:len(m)] if out is not None else None)
 
+    def tree_poses(self, edge_a, edge_b, t, rotations, image_stats, max_depth=64):
+        """lf_mkd_tree_poses: edge_a / edge_b uint32 [n_edges] and t f32 [n_edges, 3] as two_view_pose gave them, rotations f32
+        [n_images, 9] and image_stats uint32 [n_images, 4] as view_graph gave them -> poses f32 [n_images, 12]: the view
+        graph's rotation and a centre one unit step from the tree parent's; the zero row for an image whose chain of tree
+        edges does not reach the root within max_depth steps."""
+        ea = np.ascontiguousarray(edge_a, np.uint32).reshape(-1)
+        eb = np.ascontiguousarray(edge_b, np.uint32).reshape(-1)
+        tt = np.ascontiguousarray(t, np.float32).reshape(-1, 3)
+        rot = np.ascontiguousarray(rotations, np.float32).reshape(-1, 9)
+        ims = np.ascontiguousarray(image_stats, np.uint32).reshape(-1, 4)
+        n, n_images = len(ea), len(rot)
+        if len(eb) != n or len(tt) != n or len(ims) != n_images:
+            raise RuntimeError("tree_poses: edge_b and t need one row per entry of edge_a, image_stats one row per rotation")
+        poses = np.zeros((max(n_images, 1), 12), np.float32)
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_tree_poses(self._h, at(ea), at(eb), at(tt), n, at(rot), at(ims), n_images, max_depth,
+                                             poses.ctypes.data), "lf_mkd_tree_poses")
+        return poses[:n_images]
+
+    def global_positions(self, kps, image_offsets, track_offsets, obs_row, obs_image, row_track, intrinsics, poses, sweeps=50,
+                         warm=3, robust_deg=0.2, min_obs=2, flags=0, points=True, obs_state=True, trace=True):
+        """lf_mkd_global_positions: kps [rows,5] f32, image_offsets uint64 [n_images + 1], the track table (track_offsets uint64
+        [n_tracks + 1], obs_row int32 / obs_image uint32 [n_obs]), row_track int32 [rows], intrinsics [n_images,4] f32, poses
+        [n_images,12] f32 (rotations held, centres the start) -> (poses [n_images,12] f32 in the gauge centroid 0 / rms radius
+        1, points [n_tracks,4] f32 or None, obs_state uint32 [n_obs] or None, image_stats uint32 [n_images,4] = usable rows,
+        weighted rows, sweeps held, reason; trace float64 [sweeps,4] = cost, weighted observations, held cameras, unsolved
+        points, or None; counts uint32 [8])."""
+        k = np.ascontiguousarray(kps, np.float32).reshape(-1, 5)
+        ioff = np.ascontiguousarray(image_offsets, np.uint64).reshape(-1)
+        toff = np.ascontiguousarray(track_offsets, np.uint64).reshape(-1)
+        row, img = np.ascontiguousarray(obs_row, np.int32).reshape(-1), np.ascontiguousarray(obs_image, np.uint32).reshape(-1)
+        rt = np.ascontiguousarray(row_track, np.int32).reshape(-1)
+        K = np.ascontiguousarray(intrinsics, np.float32).reshape(-1, 4)
+        P = np.ascontiguousarray(poses, np.float32).reshape(-1, 12)
+        n_images, n_tracks, n_obs = len(K), max(len(toff), 1) - 1, len(row)
+        if len(ioff) != n_images + 1 or len(img) != n_obs or len(P) != n_images or len(rt) != len(k):
+            raise RuntimeError("global_positions: image_offsets needs n_images + 1 entries, obs_row and obs_image one entry per "
+                               "observation, row_track one per row, intrinsics and poses one row per image")
+        po, xo = np.zeros((max(n_images, 1), 12), np.float32), np.zeros((max(n_tracks, 1), 4), np.float32) if points else None
+        so = np.zeros(max(n_obs, 1), np.uint32) if obs_state else None
+        ims, counts = np.zeros((max(n_images, 1), 4), np.uint32), np.zeros(8, np.uint32)
+        tr = np.zeros((max(sweeps, 1), 4), np.float64) if trace else None
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_global_positions(self._h, at(k), ioff.ctypes.data, n_images, len(k), at(toff), n_tracks, at(row),
+                                                   at(img), n_obs, at(rt), at(K), at(P), sweeps, warm, robust_deg, min_obs, flags,
+                                                   po.ctypes.data, xo.ctypes.data if points else None,
+                                                   so.ctypes.data if obs_state else None, ims.ctypes.data,
+                                                   tr.ctypes.data if trace else None, counts.ctypes.data),
+                    "lf_mkd_global_positions")
+        return (po[:n_images], xo[:n_tracks] if points else None, so[:n_obs] if obs_state else None, ims[:n_images],
+                tr[:sweeps] if trace else None, counts)
+
     def bundle_adjust(self, kps, image_offsets, track_offsets, obs_row, obs_image, points, intrinsics, poses, obs_state=None,
                       camera_fixed=None, max_reproj_px=4.0, lambda0=1e-3, iterations=10, cg_iterations=10, cg_tol=0.1, flags=0,
                       obs_state_out=True):
@@ -1112,6 +1185,28 @@ class MkdHandle:
             self._h, d_edge_a, d_edge_b, n_edges, d_R, d_pose_stats, n_images, max_loop_deg, min_front, root, tree_rounds,
             iterations, flags, d_edge_offsets_a, ea_capacity, d_match, d_match_out, d_rotations, d_edge_stats, d_edge_residual,
             d_image_stats, d_counts, s), "lf_mkd_view_graph_device")
+
+    def tree_poses_device(self, d_edge_a, d_edge_b, d_t, n_edges, d_rotations, d_image_stats, n_images, d_poses, max_depth=64,
+                          stream=None):
+        """lf_mkd_tree_poses_device: initial poses d_poses f32 [n_images][12] from the view graph's rotations, its tree
+        (d_image_stats uint32 [n_images][4]) and the tree edges' translations d_t f32 [n_edges][3] (device pointers; see
+        include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_tree_poses_device(
+            self._h, d_edge_a, d_edge_b, d_t, n_edges, d_rotations, d_image_stats, n_images, max_depth, d_poses, s),
+            "lf_mkd_tree_poses_device")
+
+    def global_positions_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row,
+                                d_obs_image, obs_capacity, d_table_counts, d_row_track, d_intrinsics, d_poses, d_poses_out,
+                                d_image_stats, d_counts, d_points_out=None, d_obs_state=None, d_trace=None, sweeps=50, warm=3,
+                                robust_deg=0.2, min_obs=2, flags=0, stream=None):
+        """lf_mkd_global_positions_device: all camera centres and all track points at once under the rotations of d_poses
+        [n_images][12] -- d_poses_out (may be d_poses), d_image_stats uint32 [n_images][4], d_counts uint32 [8], and the
+        optional d_points_out f32 [track_capacity][4], d_obs_state uint32 [obs_capacity] and d_trace f64 [sweeps][4] (device
+        pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_global_positions_device(
+            self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row, d_obs_image,
+            obs_capacity, d_table_counts, d_row_track, d_intrinsics, d_poses, sweeps, warm, robust_deg, min_obs, flags, d_poses_out,
+            d_points_out, d_obs_state, d_image_stats, d_trace, d_counts, s), "lf_mkd_global_positions_device")
 
     def bundle_adjust_device(self, d_kps, d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity, d_obs_row,
                              d_obs_image, obs_capacity, d_table_counts, d_points, d_intrinsics, d_poses, d_poses_out, d_points_out,
