@@ -6,6 +6,7 @@
 
 #include "lf_mkd_args.h"
 #include "mkd_consts.hpp"
+#include "mkd_scene.h"
 
 extern "C" {
 
@@ -239,9 +240,9 @@ int lf_mkd_triangulate_tracks_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, ui
     if (track_capacity == 0) return LF_MKD_OK;
     LF_ENTER(h);
     const double thr2 = double(max_reproj_px) * double(max_reproj_px);
-    launch_triangulate_tracks(reinterpret_cast<const float *>(d_kps), n_rows_total, d_track_offsets, track_capacity, d_obs_row,
-                              d_obs_image, obs_capacity, d_table_counts, d_intrinsics, d_poses, n_images, thr2, rounds, d_points,
-                              d_stats, d_err, d_obs_state, stream_of(h, stream));
+    const SceneTables tables = {reinterpret_cast<const float *>(d_kps), n_rows_total, nullptr, n_images, d_track_offsets,
+                                track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, nullptr, d_intrinsics};
+    launch_triangulate_tracks(tables, d_poses, thr2, rounds, d_points, d_stats, d_err, d_obs_state, stream_of(h, stream));
     return launched(h);
 }
 
@@ -331,10 +332,10 @@ int lf_mkd_resect_cameras_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const 
     if (int rc = grow(h, h->d_resect, resect_scratch_bytes(n_images, n_rows_total, n_samples))) return rc;
     const double thr2 = double(max_reproj_px) * double(max_reproj_px);
     const double cmin = std::cos(double(min_parallax_deg) * (3.14159265358979323846 / 180.0));
-    launch_resect_cameras(h->d_resect.get(), reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total,
-                          d_row_track, d_points, track_capacity, d_table_counts, d_intrinsics, d_poses, thr2, cmin, n_samples,
-                          min_inliers, rounds, seed, (flags & LF_MKD_RESECT_ALL) != 0, d_poses_out, d_stats, d_err, d_row_state,
-                          stream_of(h, stream));
+    const SceneTables tables = {reinterpret_cast<const float *>(d_kps), n_rows_total, d_image_offsets, n_images, nullptr,
+                                track_capacity, nullptr, nullptr, 0, d_table_counts, d_row_track, d_intrinsics};
+    launch_resect_cameras(h->d_resect.get(), tables, d_points, d_poses, thr2, cmin, n_samples, min_inliers, rounds, seed,
+                          (flags & LF_MKD_RESECT_ALL) != 0, d_poses_out, d_stats, d_err, d_row_state, stream_of(h, stream));
     return launched(h);
 }
 
@@ -430,10 +431,10 @@ int lf_mkd_bundle_adjust_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, const u
     LF_ENTER(h);
     if (int rc = grow(h, h->d_bundle, bundle_scratch_bytes(n_images, n_rows_total, track_capacity, obs_capacity))) return rc;
     const double thr2 = double(max_reproj_px) * double(max_reproj_px), tol2 = double(cg_tol) * double(cg_tol);
-    launch_bundle_adjust(h->d_bundle.get(), reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total,
-                         d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_points, d_intrinsics,
-                         d_poses, d_obs_state, d_camera_fixed, thr2, double(lambda0), iterations, cg_iterations, tol2, d_poses_out,
-                         d_points_out, d_obs_state_out, d_trace, d_counts, stream_of(h, stream));
+    const SceneTables tables = {reinterpret_cast<const float *>(d_kps), n_rows_total, d_image_offsets, n_images, d_track_offsets,
+                                track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, nullptr, d_intrinsics};
+    launch_bundle_adjust(h->d_bundle.get(), tables, d_points, d_poses, d_obs_state, d_camera_fixed, thr2, double(lambda0), iterations,
+                         cg_iterations, tol2, d_poses_out, d_points_out, d_obs_state_out, d_trace, d_counts, stream_of(h, stream));
     return launched(h);
 }
 
@@ -540,11 +541,11 @@ int lf_mkd_bundle_adjust_intrinsics_device(lf_mkd *h, const lf_mkd_keypoint *d_k
     if (int rc = grow(h, h->d_bundle, bundle_intrinsics_scratch_bytes(n_images, n_rows_total, track_capacity, obs_capacity, n_groups)))
         return rc;
     const double thr2 = double(max_reproj_px) * double(max_reproj_px), tol2 = double(cg_tol) * double(cg_tol);
-    launch_bundle_adjust_intrinsics(h->d_bundle.get(), reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total,
-                                    d_track_offsets, track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_points,
-                                    d_intrinsics, d_poses, d_obs_state, d_camera_fixed, d_camera_group, n_groups, refine, thr2,
-                                    double(lambda0), iterations, cg_iterations, tol2, d_poses_out, d_points_out, d_intrinsics_out,
-                                    d_group_out, d_obs_state_out, d_trace, d_counts, stream_of(h, stream));
+    const SceneTables tables = {reinterpret_cast<const float *>(d_kps), n_rows_total, d_image_offsets, n_images, d_track_offsets,
+                                track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, nullptr, d_intrinsics};
+    launch_bundle_adjust_intrinsics(h->d_bundle.get(), tables, d_points, d_poses, d_obs_state, d_camera_fixed, d_camera_group, n_groups,
+                                    refine, thr2, double(lambda0), iterations, cg_iterations, tol2, d_poses_out, d_points_out,
+                                    d_intrinsics_out, d_group_out, d_obs_state_out, d_trace, d_counts, stream_of(h, stream));
     return launched(h);
 }
 
@@ -821,10 +822,10 @@ int lf_mkd_global_positions_device(lf_mkd *h, const lf_mkd_keypoint *d_kps, cons
     unsigned char *work;
     if (int rc = scratch(h, h->d_positions, plan.scratch_bytes, &work)) return rc;
     const double s0 = std::sin(double(robust_deg) * (3.14159265358979323846 / 180.0));
-    const unsigned issued = launch_global_positions(
-        plan, work, reinterpret_cast<const float *>(d_kps), d_image_offsets, n_images, n_rows_total, d_track_offsets, track_capacity,
-        d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_row_track, d_intrinsics, d_poses, sweeps, warm, s0, min_obs, d_poses_out,
-        d_points_out, d_obs_state, d_image_stats, d_trace, d_counts, stream_of(h, stream));
+    const SceneTables tables = {reinterpret_cast<const float *>(d_kps), n_rows_total, d_image_offsets, n_images, d_track_offsets,
+                                track_capacity, d_obs_row, d_obs_image, obs_capacity, d_table_counts, d_row_track, d_intrinsics};
+    const unsigned issued = launch_global_positions(plan, work, tables, d_poses, sweeps, warm, s0, min_obs, d_poses_out, d_points_out,
+                                                    d_obs_state, d_image_stats, d_trace, d_counts, stream_of(h, stream));
     if (issued != plan.launches)
         return fail(h, LF_MKD_ERR_HIP, "global_positions_device: issued " + std::to_string(issued) + " launches, the plan says " +
                                            std::to_string(plan.launches));

@@ -51,6 +51,7 @@
 
 #include "mkd_bundle_math.h"
 #include "mkd_device.h"
+#include "mkd_scene.h"
 
 namespace lfmkd {
 namespace {
@@ -58,7 +59,7 @@ namespace {
 constexpr int kThreads = kRsSlots;
 constexpr int kWaves = kThreads / 64;
 constexpr int G = 4;
-static_assert(kThreads == 256 && kTriSlots == G, "thread s is slot s of the 256-slot sum, lane l slot l of the 4-slot sum");
+static_assert(kThreads == kSumThreads && kTriSlots == G, "thread s is slot s of the 256-slot sum, lane l slot l of the 4-slot sum");
 constexpr unsigned kMaxBlocks = 16384;      // grid-stride beyond
 
 enum : int { kVecX = 0, kVecR = 1, kVecZ = 2, kVecP = 3, kVecAp = 4, kVecs = 5 };
@@ -67,19 +68,6 @@ enum : int { kWCur = 0, kWStopped = 1, kWSteps = 2, kWInliers = 3, kWHeldCams = 
              kWFreePoints = 7, kWActive = 8, kWAccepted = 9, kWHeldGroups = 10, kWFreeGroups = 11, kWBadSigma = 12, kWords = 16 };
 enum : unsigned { kModeStart = 0, kModeAlpha = 1, kModeBeta = 2, kModeAccept = 3 };
 
-struct BaIn {
-    const float *__restrict__ kps;
-    const uint64_t *__restrict__ off;          // image offsets
-    uint64_t n_rows;
-    unsigned n_images;
-    const uint64_t *__restrict__ toff;         // track offsets
-    uint64_t tcap;
-    const int *__restrict__ obs_row;
-    const unsigned *__restrict__ obs_image;
-    uint64_t ocap;
-    const unsigned *__restrict__ counts;
-    const float *__restrict__ intrinsics;
-};
 // scratch, in bundle_scratch_bytes' order: the f64 arrays, the 64-bit map, then the words
 struct BaScratch {
     RsPose *cam;                 // [2][n_images]: the state and the candidate, words[kWCur] says which is which
@@ -117,21 +105,10 @@ struct BaIntr {
 template <bool kI>
 using KOf = std::conditional_t<kI, double, float>;
 
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
-__device__ __forceinline__ void image_range(const BaIn &in, unsigned img, uint64_t &lo, uint64_t &hi) {
-    lo = clamp_to(in.off[img], in.n_rows);
-    hi = clamp_to(in.off[img + 1], in.n_rows);
-    hi = hi > lo ? hi : lo;
-}
-__device__ __forceinline__ void track_range(const BaIn &in, uint64_t t, uint64_t O, uint64_t &lo, uint64_t &hi) {
-    lo = clamp_to(in.toff[t], O);
-    hi = clamp_to(in.toff[t + 1], O);
-    hi = hi > lo ? hi : lo;
-}
-__device__ __forceinline__ double *vec_of(const BaScratch &sc, const BaIn &in, int which, unsigned img) {
+__device__ __forceinline__ double *vec_of(const BaScratch &sc, const SceneTables &in, int which, unsigned img) {
     return sc.vec + ((uint64_t)which * in.n_images + img) * 6;
 }
-__device__ __forceinline__ void load_k0(const BaIn &in, unsigned img, float *K) {
+__device__ __forceinline__ void load_k0(const SceneTables &in, unsigned img, float *K) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) K[i] = in.intrinsics[4 * (uint64_t)img + i];
 }
@@ -146,7 +123,7 @@ __device__ __forceinline__ bool group_moves(const BaIntr &gi, unsigned g) {
 // the intrinsics an image is read under: the input, or (kI) doubles -- the input widened, or for an image of a free group the
 // products of the group's state `st` (words[kWCur], or the other one for the candidate)
 template <bool kI>
-__device__ __forceinline__ void load_k(const BaIn &in, const BaIntr &gi, unsigned st, unsigned img, KOf<kI> *K) {
+__device__ __forceinline__ void load_k(const SceneTables &in, const BaIntr &gi, unsigned st, unsigned img, KOf<kI> *K) {
     if constexpr (!kI) {
         load_k0(in, img, K);
     } else {
@@ -158,7 +135,7 @@ __device__ __forceinline__ void load_k(const BaIn &in, const BaIntr &gi, unsigne
     }
 }
 // the correspondence of an ACTIVE position's row under the points `pt`
-__device__ __forceinline__ BaCorr load_corr(const BaIn &in, uint64_t row, const double *pt, uint64_t t) {
+__device__ __forceinline__ BaCorr load_corr(const SceneTables &in, uint64_t row, const double *pt, uint64_t t) {
     const float *k = in.kps + 5 * row;
     const double *p = pt + 3 * t;
     return BaCorr{k[0], k[1], p[0], p[1], p[2]};
@@ -167,7 +144,7 @@ __device__ __forceinline__ BaCorr load_corr(const BaIn &in, uint64_t row, const 
 // The coupling block of a coupled position, formed again from the state at every use (the state does not move within an
 // iteration, so these are ba_image_lin's bits), or -- the A/B build of profiles/bundle.md, -DLF_BA_STORE_W -- as ba_image_lin
 // stored it, 144 bytes a position.
-__device__ __forceinline__ void load_w(const BaIn &in, const BaScratch &sc, uint64_t pos, uint64_t t, double *W) {
+__device__ __forceinline__ void load_w(const SceneTables &in, const BaScratch &sc, uint64_t pos, uint64_t t, double *W) {
 #ifndef LF_BA_STORE_W
     const unsigned cur = sc.words[kWCur], img = in.obs_image[pos];
     float K[4];
@@ -184,7 +161,7 @@ __device__ __forceinline__ void load_w(const BaIn &in, const BaScratch &sc, uint
 }
 
 // (kI) the rows of a position at the state, from which both its coupling blocks are formed, and its image's input intrinsics
-__device__ __forceinline__ void load_lin(const BaIn &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, BaLin &o,
+__device__ __forceinline__ void load_lin(const SceneTables &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, BaLin &o,
                                          float *K0) {
     const unsigned cur = sc.words[kWCur], img = in.obs_image[pos];
     double K[4];
@@ -195,7 +172,7 @@ __device__ __forceinline__ void load_lin(const BaIn &in, const BaIntr &gi, const
 }
 // what a coupled or group-coupled position adds to sum W^T v over its track: W_c^T v_c + W_k^T v_k, or the one that enters (v = p
 // or x)
-__device__ __forceinline__ void add_wt(const BaIn &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, int which,
+__device__ __forceinline__ void add_wt(const SceneTables &in, const BaIntr &gi, const BaScratch &sc, uint64_t pos, uint64_t t, int which,
                                        double *acc) {
     const unsigned of = sc.oflag[pos];
     if (!(of & (kBaCoupled | kBaInlier))) return;
@@ -224,64 +201,11 @@ __device__ __forceinline__ void add_wt(const BaIn &in, const BaIntr &gi, const B
     for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w[k];
 }
 
-// Workgroup sum of N values per thread in the canonical order: the butterfly within a wave, then ((w0 + w1) + w2) + w3.
-template <typename T, int N>
-__device__ __forceinline__ void block_sum(T *v, T *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        T s = v[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
-        if (lane == 0) red[wave * N + i] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
-    __syncthreads();
-}
-// the workgroup's total of an integer per thread (exact in any order)
-__device__ __forceinline__ unsigned block_count(unsigned n, unsigned *s_cnt) {
-    if (threadIdx.x == 0) *s_cnt = 0;
-    __syncthreads();
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(s_cnt, n);
-    __syncthreads();
-    const unsigned total = *s_cnt;
-    __syncthreads();
-    return total;
-}
-// the butterfly of the 4-slot sum over the group's lanes
-__device__ __forceinline__ double combine(double v) {
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
-// What a per-track kernel knows of where it is: T, O, its wave's first track and stride, its lane's slot.
-struct TrackWalk {
-    uint64_t T, O, first, stride;
-    unsigned l, base;
-};
-__device__ __forceinline__ TrackWalk track_walk(const BaIn &in) {
-    TrackWalk w;
-    w.T = clamp_to(in.counts[0], in.tcap);
-    w.O = clamp_to(in.counts[1], in.ocap);
-    const unsigned lane = threadIdx.x & 63;
-    w.l = lane & (G - 1);
-    w.base = lane & ~(unsigned)(G - 1);
-    w.first = ((uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * (64 / G);
-    w.stride = (uint64_t)gridDim.x * kWaves * (64 / G);
-    return w;
-}
-__device__ __forceinline__ unsigned group_bits(bool p, unsigned base) { return (unsigned)(__ballot(p) >> base) & ((1u << G) - 1u); }
-
 }  // namespace
 
 // ---- setup ------------------------------------------------------------------------------------------------------------------------
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_init(BaIn in, BaIntr gi, const float *__restrict__ poses,
+__global__ __launch_bounds__(kThreads) void ba_init(SceneTables in, BaIntr gi, const float *__restrict__ poses,
                                                     const unsigned *__restrict__ fixed, double lambda0, BaScratch sc) {
     const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x, n = (uint64_t)gridDim.x * kThreads;
     for (uint64_t r = gid; r < in.n_rows; r += n) sc.rowmap[r] = kBaNoRow;
@@ -310,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void ba_init(BaIn in, BaIntr gi, const fl
     if (gid < kScalars) sc.scal[gid] = gid == kSLambda ? lambda0 : 0.0;
 }
 
-__global__ __launch_bounds__(kThreads) void ba_setup_tracks(BaIn in, const float *__restrict__ points,
+__global__ __launch_bounds__(kThreads) void ba_setup_tracks(SceneTables in, const float *__restrict__ points,
                                                             const unsigned *__restrict__ obs_state, BaScratch sc) {
     const TrackWalk w = track_walk(in);
     for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
@@ -358,9 +282,9 @@ __global__ __launch_bounds__(kThreads) void ba_setup_tracks(BaIn in, const float
 
 // (kI: a list for every usable image, since a camera that is not free still informs its group)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_setup_images(SceneTables in, BaScratch sc) {
     __shared__ unsigned s_cnt[kWaves];
-    const unsigned img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned img = blockIdx.x, tid = threadIdx.x;
     const unsigned hf0 = sc.head[2 * (uint64_t)img + 1];
     if (!(hf0 & (kI ? kBaCamUsable : kBaCamFree))) return;                        // block-uniform; M stays 0
     uint64_t lo, hi;
@@ -373,18 +297,7 @@ __global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch s
             const unsigned long long m = sc.rowmap[r];
             is = m != kBaNoRow && in.obs_image[(unsigned)m] == img;
         }
-        const uint64_t bits = __ballot(is);
-        if (lane == 0) s_cnt[wave] = (unsigned)__popcll(bits);
-        __syncthreads();
-        unsigned before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            before += (unsigned)w < wave ? s_cnt[w] : 0u;
-            total += s_cnt[w];
-        }
-        if (is) sc.idx[base + before + (unsigned)__popcll(bits & ((1ull << lane) - 1ull))] = (unsigned)r;
-        base += total;
-        __syncthreads();
+        block_compact(is, (unsigned)r, sc.idx, s_cnt, base);
     }
     if (tid == 0) {
         sc.head[2 * (uint64_t)img] = (unsigned)(base - lo);
@@ -393,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void ba_setup_images(BaIn in, BaScratch s
 }
 
 // a workgroup per group: FREE iff something is refined and a usable image of the group has an active row
-__global__ __launch_bounds__(kThreads) void ba_setup_groups(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_setup_groups(SceneTables in, BaIntr gi, BaScratch sc) {
     const unsigned g = blockIdx.x;
     int found = 0;
     for (uint64_t i = threadIdx.x; i < in.n_images; i += kThreads)
@@ -407,7 +320,7 @@ __global__ __launch_bounds__(kThreads) void ba_setup_groups(BaIn in, BaIntr gi, 
 
 // ---- an LM iteration -------------------------------------------------------------------------------------------------------------
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_track_lin(SceneTables in, BaIntr gi, double thr2, BaScratch sc) {
     const TrackWalk w = track_walk(in);
     const unsigned cur = sc.words[kWCur];
     const double lambda = sc.scal[kSLambda];
@@ -466,7 +379,7 @@ __global__ __launch_bounds__(kThreads) void ba_track_lin(BaIn in, BaIntr gi, dou
 }
 
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_image_lin(SceneTables in, BaIntr gi, double thr2, BaScratch sc) {
     __shared__ double s_red[kWaves * kRsTerms];
     __shared__ unsigned s_cnt;
     const unsigned img = blockIdx.x, tid = threadIdx.x;
@@ -626,7 +539,7 @@ __global__ __launch_bounds__(kThreads) void ba_image_lin(BaIn in, BaIntr gi, dou
 
 // A workgroup per group: the group's nine sums and its inliers over the shares of its usable images (slot = image id mod 256),
 // the damped block, HELD, b_k = g_k - sum W_k y, and the start of CG for the group's three.
-__global__ __launch_bounds__(kThreads) void ba_group_lin(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_group_lin(SceneTables in, BaIntr gi, BaScratch sc) {
     __shared__ double s_red[kWaves * 12];
     __shared__ unsigned s_cnt;
     const unsigned g = blockIdx.x, tid = threadIdx.x;
@@ -678,7 +591,7 @@ __global__ __launch_bounds__(kThreads) void ba_group_lin(BaIn in, BaIntr gi, BaS
 
 // y = V*^-1 sum W^T p over the track's coupled positions (0 for a point that is not free, or held)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_track_apply(SceneTables in, BaIntr gi, BaScratch sc) {
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const TrackWalk w = track_walk(in);
     for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
@@ -714,7 +627,7 @@ __global__ __launch_bounds__(kThreads) void ba_track_apply(BaIn in, BaIntr gi, B
 // Ap = U* p - sum W y over the image's coupled entries, and p.Ap
 // (kI, the image's group moving: Ap = (U* p + U_ck p_k) - sum W y, and the image's share U_ck^T p - sum W_k y of the group's row)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_image_apply(SceneTables in, BaIntr gi, BaScratch sc) {
     __shared__ double s_red[kWaves * 9];
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const unsigned img = blockIdx.x, tid = threadIdx.x;
@@ -805,7 +718,7 @@ __global__ __launch_bounds__(kThreads) void ba_image_apply(BaIn in, BaIntr gi, B
 }
 
 // A workgroup per moving group: Ap_k = U_kk* p_k + the sum over its usable images' shares (slot = image id mod 256), and p_k.Ap_k
-__global__ __launch_bounds__(kThreads) void ba_group_apply(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_group_apply(SceneTables in, BaIntr gi, BaScratch sc) {
     __shared__ double s_red[kWaves * 3];
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const unsigned g = blockIdx.x, tid = threadIdx.x;
@@ -836,7 +749,7 @@ __global__ __launch_bounds__(kThreads) void ba_group_apply(BaIn in, BaIntr gi, B
 
 // x += alpha p, r -= alpha Ap, z = U*^-1 r, and r.z: a thread per image (kI: then a thread per group)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_cg_update(SceneTables in, BaIntr gi, BaScratch sc) {
     if (sc.words[kWStopped]) return;                                              // grid-uniform
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if constexpr (kI) {
@@ -887,7 +800,7 @@ __global__ __launch_bounds__(kThreads) void ba_cg_update(BaIn in, BaIntr gi, BaS
 // ONE workgroup: a global sum in the 256-slot order (over image id of dots, over track index of tcost) and the scalars
 // (kI: a dot product is the 256-slot sum over the image ids plus the 256-slot sum over the group ids, in that order)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, BaIntr gi, unsigned mode, double tol2, unsigned iteration, BaScratch sc,
+__global__ __launch_bounds__(kThreads) void ba_scalar(SceneTables in, BaIntr gi, unsigned mode, double tol2, unsigned iteration, BaScratch sc,
                                                       double *__restrict__ trace) {
     constexpr int kSums = kI ? 3 : 2;
     __shared__ double s_red[kWaves * kSums];
@@ -948,7 +861,7 @@ __global__ __launch_bounds__(kThreads) void ba_scalar(BaIn in, BaIntr gi, unsign
 // the candidate cameras: a thread per image (kI: then the candidate groups, a thread per group; a moving group whose candidate s
 // is not finite and positive marks the whole candidate as one to reject)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaIntr gi, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_cam_step(SceneTables in, BaIntr gi, BaScratch sc) {
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const unsigned cur = sc.words[kWCur];
     if constexpr (kI) {
@@ -980,7 +893,7 @@ __global__ __launch_bounds__(kThreads) void ba_cam_step(BaIn in, BaIntr gi, BaSc
 
 // the candidate points X - V*^-1 (g_p - sum W^T x) and the candidate's cost per track
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, BaIntr gi, double thr2, BaScratch sc) {
+__global__ __launch_bounds__(kThreads) void ba_track_step(SceneTables in, BaIntr gi, double thr2, BaScratch sc) {
     const TrackWalk w = track_walk(in);
     const unsigned cur = sc.words[kWCur];
     const RsPose *cam_c = sc.cam + (uint64_t)(cur ^ 1u) * in.n_images;
@@ -1042,7 +955,7 @@ __global__ __launch_bounds__(kThreads) void ba_track_step(BaIn in, BaIntr gi, do
 // (kI: and the image's intrinsics, the f64 products rounded for an image of a free group, the input's words elsewhere; then a
 // thread per group for d_group_out)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, BaIntr gi, const float *poses, BaScratch sc, float *poses_out,
+__global__ __launch_bounds__(kThreads) void ba_final_images(SceneTables in, BaIntr gi, const float *poses, BaScratch sc, float *poses_out,
                                                             float *intrinsics_out, float *group_out) {
     const uint64_t img = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if constexpr (kI) {
@@ -1088,7 +1001,7 @@ __global__ __launch_bounds__(kThreads) void ba_final_images(BaIn in, BaIntr gi, 
 
 // (kI: judged under intrinsics_out, and a fifth count)
 template <bool kI>
-__global__ __launch_bounds__(kThreads) void ba_final_tracks(BaIn in, const float *points, double thr2, BaScratch sc,
+__global__ __launch_bounds__(kThreads) void ba_final_tracks(SceneTables in, const float *points, double thr2, BaScratch sc,
                                                             const float *__restrict__ poses_out,
                                                             const float *__restrict__ intrinsics_out, float *points_out,
                                                             unsigned *obs_state_out, unsigned *__restrict__ counts_out) {
@@ -1197,7 +1110,7 @@ BaLayout layout(uint64_t n_images, uint64_t n_rows, uint64_t tcap, uint64_t ocap
 // The one launch sequence of both calls: kI = false is lf_mkd_bundle_adjust_device's, kI = true adds ba_setup_groups, a
 // ba_group_lin per iteration and a ba_group_apply per CG step, and the thread-per-image kernels take n_groups more threads.
 template <bool kI>
-void launch(void *scratch, const BaIn &in, const unsigned *group, unsigned n_groups, unsigned refine, const float *points,
+void launch(void *scratch, const SceneTables &in, const unsigned *group, unsigned n_groups, unsigned refine, const float *points,
             const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0, unsigned iterations,
             unsigned cg_iterations, double tol2, float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
             unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
@@ -1253,15 +1166,11 @@ uint64_t bundle_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track
 }
 unsigned bundle_launches(unsigned iterations, unsigned cg_iterations) { return 5 + iterations * (6 + 5 * cg_iterations); }
 
-void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                          const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row, const unsigned *obs_image,
-                          uint64_t obs_capacity, const unsigned *table_counts, const float *points, const float *intrinsics,
-                          const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0,
-                          unsigned iterations, unsigned cg_iterations, double tol2, float *poses_out, float *points_out,
-                          unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
-    if (n_images == 0) return;
-    const BaIn in = {kps, image_offsets, n_rows, n_images, track_offsets, track_capacity, obs_row, obs_image, obs_capacity, table_counts,
-                     intrinsics};
+void launch_bundle_adjust(void *scratch, const SceneTables &in, const float *points, const float *poses, const unsigned *obs_state,
+                          const unsigned *camera_fixed, double thr2, double lambda0, unsigned iterations, unsigned cg_iterations,
+                          double tol2, float *poses_out, float *points_out, unsigned *obs_state_out, double *trace, unsigned *counts,
+                          hipStream_t stream) {
+    if (in.n_images == 0) return;
     launch<false>(scratch, in, nullptr, 0, 0, points, poses, obs_state, camera_fixed, thr2, lambda0, iterations, cg_iterations, tol2,
                   poses_out, points_out, nullptr, nullptr, obs_state_out, trace, counts, stream);
 }
@@ -1272,17 +1181,12 @@ uint64_t bundle_intrinsics_scratch_bytes(unsigned n_images, uint64_t n_rows, uin
 }
 unsigned bundle_intrinsics_launches(unsigned iterations, unsigned cg_iterations) { return 6 + iterations * (7 + 6 * cg_iterations); }
 
-void launch_bundle_adjust_intrinsics(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                                     const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row,
-                                     const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts, const float *points,
-                                     const float *intrinsics, const float *poses, const unsigned *obs_state,
-                                     const unsigned *camera_fixed, const unsigned *camera_group, unsigned n_groups, unsigned refine,
-                                     double thr2, double lambda0, unsigned iterations, unsigned cg_iterations, double tol2,
-                                     float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
-                                     unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
-    if (n_images == 0) return;
-    const BaIn in = {kps, image_offsets, n_rows, n_images, track_offsets, track_capacity, obs_row, obs_image, obs_capacity, table_counts,
-                     intrinsics};
+void launch_bundle_adjust_intrinsics(void *scratch, const SceneTables &in, const float *points, const float *poses,
+                                     const unsigned *obs_state, const unsigned *camera_fixed, const unsigned *camera_group,
+                                     unsigned n_groups, unsigned refine, double thr2, double lambda0, unsigned iterations,
+                                     unsigned cg_iterations, double tol2, float *poses_out, float *points_out, float *intrinsics_out,
+                                     float *group_out, unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream) {
+    if (in.n_images == 0) return;
     launch<true>(scratch, in, camera_group, n_groups, refine, points, poses, obs_state, camera_fixed, thr2, lambda0, iterations,
                  cg_iterations, tol2, poses_out, points_out, intrinsics_out, group_out, obs_state_out, trace, counts, stream);
 }

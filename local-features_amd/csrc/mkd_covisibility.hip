@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "mkd_device.h"
+#include "mkd_scene.h"   // clamp_to
 
 #ifndef LF_COVIS_LDS_IMAGES
 #define LF_COVIS_LDS_IMAGES 64      // the largest n_images that counts in LDS first; 0 builds the plan without that form
@@ -40,8 +41,6 @@ constexpr unsigned kLongChunks = 16;                    // a track of more than 
 constexpr unsigned kLdsImages = LF_COVIS_LDS_IMAGES;
 constexpr unsigned kMaxBlocks = 4096;                   // grid-stride beyond: 16 workgroups a CU
 static_assert(kLdsImages <= 64, "the private table is at most 16 KiB");
-
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
 
 template <bool LDS>
 __device__ __forceinline__ void add_pair(unsigned *covis, unsigned *tab, unsigned n, unsigned i, unsigned j) {

@@ -1,5 +1,10 @@
 // Launch interface between the C ABI (lf_mkd.cpp, lf_mkd_match.cpp, lf_mkd_tables.cpp, lf_mkd_geometry.cpp) and the gfx950 kernels
-// (mkd_describe.hip, mkd_pyramid.hip, mkd_orient.hip, mkd_detect.hip, mkd_match.hip, mkd_match_q8.hip, mkd_match_guided.hip, mkd_verify.hip).
+// (mkd_describe.hip, mkd_pyramid.hip, mkd_orient.hip, mkd_detect.hip; the matchers mkd_match.hip, mkd_match_q8.hip,
+// mkd_match_q8_knn.hip, mkd_match_q8_grouped.hip, mkd_match_guided.hip, mkd_match_q8_guided.hip, mkd_match_q8_edges.hip; the
+// tables mkd_tracks.hip, mkd_track_table.hip, mkd_link_table.hip, mkd_select_edges.hip, mkd_covisibility.hip; the geometry
+// mkd_verify.hip, mkd_two_view_pose.hip, mkd_triangulate.hip, mkd_resect.hip, mkd_bundle.hip, mkd_view_graph.hip,
+// mkd_positions.hip).  The scene struct the reconstruction launchers take is mkd_scene.h's, which the files that fill or read
+// it include themselves, behind their arithmetic headers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +23,7 @@
 namespace lfmkd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct SceneTables;   // mkd_scene.h
 
 constexpr int kMaxPyrLevels = 16;
 
@@ -355,46 +361,41 @@ void launch_two_view_pose(const float *kps, uint64_t n_rows, const unsigned *edg
                           const float *intrinsics, unsigned n_images, const float *F, const uint64_t *link_off, const int *link_a,
                           const int *link_b, uint64_t link_capacity, double cmin, float *R, float *t, unsigned *stats, float *sigma,
                           float *points, hipStream_t stream);
-// track triangulation (csrc/mkd_triangulate.hip, lf_mkd_triangulate_tracks_device): one launch, 8 lanes per track, no scratch.
+// The reconstruction stages below take a scene's tables -- keypoints, image and track offsets, observations, capacities,
+// counts, row_track, intrinsics -- as ONE SceneTables (mkd_scene.h), filled by the entry point after its refusals; a member a
+// stage does not read is null or 0 (triangulation: off, row_track; resection: toff, obs_row, obs_image, ocap; bundle
+// adjustment: row_track).  Points, poses and thresholds stay arguments of their own.
+// track triangulation (csrc/mkd_triangulate.hip, lf_mkd_triangulate_tracks_device): one launch, 4 lanes per track, no scratch.
 // Keypoints are read as rows of 5 floats; thr2 = the squared reprojection threshold, formed by the host in double.
-void launch_triangulate_tracks(const float *kps, uint64_t n_rows, const uint64_t *track_offsets, uint64_t track_capacity,
-                               const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts,
-                               const float *intrinsics, const float *poses, unsigned n_images, double thr2, unsigned rounds,
-                               float *points, unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream);
+void launch_triangulate_tracks(const SceneTables &tables, const float *poses, double thr2, unsigned rounds, float *points,
+                               unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream);
 // camera resection (csrc/mkd_resect.hip, lf_mkd_resect_cameras_device): three launches (rs_gather, rs_score, rs_select) over
 // `scratch` of resect_scratch_bytes(..) bytes, 4-byte aligned.  thr2 = the squared reprojection threshold and cmin = the
 // cosine of the smallest parallax, both formed by the host in double.  poses_out may be poses.
 uint64_t resect_scratch_bytes(unsigned n_images, uint64_t n_rows, unsigned n_samples);
-void launch_resect_cameras(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                           const int *row_track, const float *points, uint64_t track_capacity, const unsigned *table_counts,
-                           const float *intrinsics, const float *poses, double thr2, double cmin, unsigned n_samples,
-                           unsigned min_inliers, unsigned rounds, unsigned seed, bool all, float *poses_out, unsigned *stats,
-                           float *err, unsigned *row_state, hipStream_t stream);
+void launch_resect_cameras(void *scratch, const SceneTables &tables, const float *points, const float *poses, double thr2,
+                           double cmin, unsigned n_samples, unsigned min_inliers, unsigned rounds, unsigned seed, bool all,
+                           float *poses_out, unsigned *stats, float *err, unsigned *row_state, hipStream_t stream);
 // bundle adjustment (csrc/mkd_bundle.hip, lf_mkd_bundle_adjust_device): bundle_launches(..) launches over `scratch` of
 // bundle_scratch_bytes(..) bytes, 16-byte aligned.  thr2 = the squared reprojection threshold and tol2 = the squared CG
 // tolerance, both formed by the host in double.  poses_out may be poses, points_out points, obs_state_out obs_state.
 uint64_t bundle_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity);
 unsigned bundle_launches(unsigned iterations, unsigned cg_iterations);
-void launch_bundle_adjust(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                          const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row, const unsigned *obs_image,
-                          uint64_t obs_capacity, const unsigned *table_counts, const float *points, const float *intrinsics,
-                          const float *poses, const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0,
-                          unsigned iterations, unsigned cg_iterations, double tol2, float *poses_out, float *points_out,
-                          unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
+void launch_bundle_adjust(void *scratch, const SceneTables &tables, const float *points, const float *poses,
+                          const unsigned *obs_state, const unsigned *camera_fixed, double thr2, double lambda0, unsigned iterations,
+                          unsigned cg_iterations, double tol2, float *poses_out, float *points_out, unsigned *obs_state_out,
+                          double *trace, unsigned *counts, hipStream_t stream);
 // the same with shared intrinsics refined (lf_mkd_bundle_adjust_intrinsics_device): the same kernels in their double-K form
 // and three per-group ones, bundle_intrinsics_launches(..) launches over bundle_intrinsics_scratch_bytes(..) bytes.
 // camera_group and group_out may be null; intrinsics_out may be intrinsics.
 uint64_t bundle_intrinsics_scratch_bytes(unsigned n_images, uint64_t n_rows, uint64_t track_capacity, uint64_t obs_capacity,
                                          unsigned n_groups);
 unsigned bundle_intrinsics_launches(unsigned iterations, unsigned cg_iterations);
-void launch_bundle_adjust_intrinsics(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                                     const uint64_t *track_offsets, uint64_t track_capacity, const int *obs_row,
-                                     const unsigned *obs_image, uint64_t obs_capacity, const unsigned *table_counts, const float *points,
-                                     const float *intrinsics, const float *poses, const unsigned *obs_state,
-                                     const unsigned *camera_fixed, const unsigned *camera_group, unsigned n_groups, unsigned refine,
-                                     double thr2, double lambda0, unsigned iterations, unsigned cg_iterations, double tol2,
-                                     float *poses_out, float *points_out, float *intrinsics_out, float *group_out,
-                                     unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
+void launch_bundle_adjust_intrinsics(void *scratch, const SceneTables &tables, const float *points, const float *poses,
+                                     const unsigned *obs_state, const unsigned *camera_fixed, const unsigned *camera_group,
+                                     unsigned n_groups, unsigned refine, double thr2, double lambda0, unsigned iterations,
+                                     unsigned cg_iterations, double tol2, float *poses_out, float *points_out, float *intrinsics_out,
+                                     float *group_out, unsigned *obs_state_out, double *trace, unsigned *counts, hipStream_t stream);
 // view-graph checks (csrc/mkd_view_graph.hip, lf_mkd_view_graph_device).  The plan is the one place that knows the launches and
 // the layout of the scratch (byte offsets, 8-byte aligned): the edges' quaternions f64 [n_edges][4], the images' quaternions
 // f64 [2][n_images][4] (the sweeps go from one to the other), then the pair table uint32 [n_images][n_images].
@@ -426,12 +427,10 @@ struct GlobalPositionsPlan {
     uint64_t off_cen, off_pt, off_rot, off_reg, off_held, off_reason, off_tflag, off_words, off_gauge, scratch_bytes;
 };
 GlobalPositionsPlan global_positions_plan(unsigned n_images, uint64_t track_capacity, unsigned sweeps);
-unsigned launch_global_positions(const GlobalPositionsPlan &plan, unsigned char *scratch, const float *kps,
-                                 const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows, const uint64_t *track_offsets,
-                                 uint64_t track_capacity, const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity,
-                                 const unsigned *table_counts, const int *row_track, const float *intrinsics, const float *poses,
-                                 unsigned sweeps, unsigned warm, double s0, unsigned min_obs, float *poses_out, float *points_out,
-                                 unsigned *obs_state, unsigned *image_stats, double *trace, unsigned *counts, hipStream_t stream);
+unsigned launch_global_positions(const GlobalPositionsPlan &plan, unsigned char *scratch, const SceneTables &tables,
+                                 const float *poses, unsigned sweeps, unsigned warm, double s0, unsigned min_obs, float *poses_out,
+                                 float *points_out, unsigned *obs_state, unsigned *image_stats, double *trace, unsigned *counts,
+                                 hipStream_t stream);
 // guided matching over 8-bit rows (csrc/mkd_match_q8_guided.hip, lf_mkd_match_q8_guided_pairs_device): launch_match_q8_pairs'
 // batch, grid and sums, launch_match_guided_pairs' candidates (the same keypoints, model, kind and threshold)
 void launch_match_q8_guided_pairs(const unsigned char *a, const float *kps_a, const uint64_t *off_a, uint64_t na_total,

@@ -34,32 +34,19 @@
 
 #include "mkd_device.h"
 #include "mkd_positions_math.h"
+#include "mkd_scene.h"
 
 namespace lfmkd {
 namespace {
 
 constexpr int kThreads = kRsSlots, kWaves = kThreads / 64, G = kTriSlots;
-static_assert(kThreads == 256, "thread s is slot s of the canonical sum");
+static_assert(kThreads == kSumThreads, "thread s is slot s of the canonical sum");
 constexpr unsigned kMaxBlocks = 16384;                  // grid-stride beyond
 // the scratch's words: cameras held and points unsolved in this sweep; is the latest gauge still to be applied to the points
 enum : int { kWHeld = 0, kWUnsolved = 1, kWPending = 2 };
 constexpr unsigned kPointSolved = 1u;
 constexpr int kChainRun = 32;                           // images of a chain gp_tree_poses keeps at a time (32 KB of LDS)
 
-struct GpIn {
-    const float *__restrict__ kps;
-    const uint64_t *__restrict__ off;
-    unsigned n_images;
-    uint64_t n_rows;
-    const uint64_t *__restrict__ toff;
-    uint64_t tcap;
-    const int *__restrict__ obs_row;
-    const unsigned *__restrict__ obs_image;
-    uint64_t ocap;
-    const unsigned *__restrict__ counts;
-    const int *__restrict__ row_track;
-    const float *__restrict__ intrinsics;
-};
 // cen f64 [n_images][3], pt f64 [tcap][3], rot f32 [n_images][9], reg / held / reason uint32 [n_images], tflag uint32 [tcap],
 // words uint32 [4], gauge f64 [4] = {m, rho} of the latest gauge
 struct GpScratch {
@@ -74,17 +61,6 @@ struct GpRule {
     bool robust;
 };
 
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
-__device__ __forceinline__ void image_range(const GpIn &in, unsigned img, uint64_t &lo, uint64_t &hi) {
-    lo = clamp_to(in.off[img], in.n_rows);
-    hi = clamp_to(in.off[img + 1], in.n_rows);
-    hi = hi > lo ? hi : lo;
-}
-__device__ __forceinline__ void track_range(const GpIn &in, uint64_t t, uint64_t O, uint64_t &lo, uint64_t &hi) {
-    lo = clamp_to(in.toff[t], O);
-    hi = clamp_to(in.toff[t + 1], O);
-    hi = hi > lo ? hi : lo;
-}
 __device__ __forceinline__ void load3(const double *p, uint64_t i, double *v) { v[0] = p[3 * i], v[1] = p[3 * i + 1], v[2] = p[3 * i + 2]; }
 __device__ __forceinline__ void store3(double *p, uint64_t i, const double *v) { p[3 * i] = v[0], p[3 * i + 1] = v[1], p[3 * i + 2] = v[2]; }
 // The gauge that is still to be applied to the points (kernel-uniform), and point t under it.
@@ -101,7 +77,7 @@ __device__ __forceinline__ void load_point(const GpScratch &sc, const Pending &g
 }
 
 // position `pos` of the observation arrays (pos < O): false if it is not usable; else its image and its world ray
-__device__ __forceinline__ bool obs_ray(const GpIn &in, const GpScratch &sc, uint64_t pos, unsigned &img, double *v) {
+__device__ __forceinline__ bool obs_ray(const SceneTables &in, const GpScratch &sc, uint64_t pos, unsigned &img, double *v) {
     const int row = in.obs_row[pos];
     img = in.obs_image[pos];
     if (row < 0 || (uint64_t)row >= in.n_rows || img >= in.n_images || !sc.reg[img]) return false;
@@ -117,7 +93,7 @@ __device__ __forceinline__ bool obs_ray(const GpIn &in, const GpScratch &sc, uin
 }
 // row r of registered image img (lo <= r < hi <= n_rows): false if it is in no track below T or its keypoint is not finite;
 // else its track and its world ray
-__device__ __forceinline__ bool row_ray(const GpIn &in, uint64_t r, uint64_t T, const float *K, const float *R, uint64_t &t, double *v) {
+__device__ __forceinline__ bool row_ray(const SceneTables &in, uint64_t r, uint64_t T, const float *K, const float *R, uint64_t &t, double *v) {
     const int tr = in.row_track[r];
     if (tr < 0 || (uint64_t)tr >= T) return false;
     const float x = in.kps[5 * r], y = in.kps[5 * r + 1];
@@ -125,63 +101,6 @@ __device__ __forceinline__ bool row_ray(const GpIn &in, uint64_t r, uint64_t T, 
     t = (uint64_t)tr;
     gp_ray(x, y, K, R, v);
     return true;
-}
-
-// Workgroup sum of N values per thread in the canonical order: the butterfly within a wave, then ((w0 + w1) + w2) + w3.
-template <int N>
-__device__ __forceinline__ void block_sum(double *v, double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = v[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
-        if (lane == 0) red[wave * N + i] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
-    __syncthreads();
-}
-// the workgroup's total of an integer per thread (exact in any order)
-__device__ __forceinline__ unsigned block_count(unsigned n, unsigned *s_cnt) {
-    if (threadIdx.x == 0) *s_cnt = 0;
-    __syncthreads();
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m, 64);
-    if ((threadIdx.x & 63) == 0) atomicAdd(s_cnt, n);
-    __syncthreads();
-    const unsigned total = *s_cnt;
-    __syncthreads();
-    return total;
-}
-// the butterfly of the 4-slot sum over the group's lanes
-__device__ __forceinline__ double combine(double v) {
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned group_bits(bool p, unsigned base) { return (unsigned)(__ballot(p) >> base) & ((1u << G) - 1u); }
-// one integer add per wave for a per-lane predicate
-__device__ __forceinline__ void count_wave(bool p, unsigned *word) {
-    const unsigned long long bits = __ballot(p);
-    if ((threadIdx.x & 63) == 0 && bits) atomicAdd(word, (unsigned)__popcll(bits));
-}
-
-struct TrackWalk {
-    uint64_t T, O, first, stride;
-    unsigned l, base;
-};
-__device__ __forceinline__ TrackWalk track_walk(const GpIn &in) {
-    TrackWalk w;
-    w.T = clamp_to(in.counts[0], in.tcap);
-    w.O = clamp_to(in.counts[1], in.ocap);
-    const unsigned lane = threadIdx.x & 63;
-    w.l = lane & (G - 1);
-    w.base = lane & ~(unsigned)(G - 1);
-    w.first = ((uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * (64 / G);
-    w.stride = (uint64_t)gridDim.x * kWaves * (64 / G);
-    return w;
 }
 
 // ---- tree poses ---------------------------------------------------------------------------------------------------------------
@@ -274,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void gp_tree_poses(TreeIn in, unsigned ma
 }
 
 // ---- global positions ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void gp_init(GpIn in, const float *__restrict__ poses, GpScratch sc, unsigned sweeps,
+__global__ __launch_bounds__(kThreads) void gp_init(SceneTables in, const float *__restrict__ poses, GpScratch sc, unsigned sweeps,
                                                     unsigned *__restrict__ counts) {
     const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x, n = (uint64_t)gridDim.x * kThreads;
     for (uint64_t i = gid; i < in.n_images; i += n) {
@@ -303,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void gp_init(GpIn in, const float *__rest
 }
 
 // sweep: kGpNone for the gauge before the first sweep (no trace row)
-__global__ __launch_bounds__(kThreads) void gp_gauge(GpIn in, GpScratch sc, GpRule rule, unsigned sweep, double *__restrict__ trace,
+__global__ __launch_bounds__(kThreads) void gp_gauge(SceneTables in, GpScratch sc, GpRule rule, unsigned sweep, double *__restrict__ trace,
                                                      unsigned *__restrict__ counts) {
     __shared__ double s_red[kWaves * 3];
     __shared__ unsigned s_cnt;
@@ -319,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void gp_gauge(GpIn in, GpScratch sc, GpRu
         for (int k = 0; k < 3; ++k) acc[k] = acc[k] + c[k];
         ++n_reg;
     }
-    block_sum<3>(acc, s_red);
+    block_sum<double, 3>(acc, s_red);
     n_reg = block_count(n_reg, &s_cnt);
     const double m[3] = {acc[0] / double(n_reg), acc[1] / double(n_reg), acc[2] / double(n_reg)};
     double spread[1] = {0.0};
@@ -330,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void gp_gauge(GpIn in, GpScratch sc, GpRu
         const double d[3] = {c[0] - m[0], c[1] - m[1], c[2] - m[2]};
         spread[0] = spread[0] + (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     }
-    block_sum<1>(spread, s_red);
+    block_sum<double, 1>(spread, s_red);
     const double rho = sqrt(spread[0] / double(n_reg));
     const bool ok = n_reg > 0 && gp_finite3(m) && pose_finite(rho) && rho > 0.0;   // block-uniform
     if (ok) {
@@ -362,7 +281,7 @@ __global__ __launch_bounds__(kThreads) void gp_gauge(GpIn in, GpScratch sc, GpRu
             cost[0] = cost[0] + w * pr2;
             ++weighted;
         }
-        block_sum<1>(cost, s_red);
+        block_sum<double, 1>(cost, s_red);
         weighted = block_count(weighted, &s_cnt);
     }
     if (tid != 0) return;
@@ -378,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void gp_gauge(GpIn in, GpScratch sc, GpRu
     sc.words[kWHeld] = 0u, sc.words[kWUnsolved] = 0u;
 }
 
-__global__ __launch_bounds__(kThreads) void gp_points(GpIn in, GpScratch sc, GpRule rule) {
+__global__ __launch_bounds__(kThreads) void gp_points(SceneTables in, GpScratch sc, GpRule rule) {
     const TrackWalk w = track_walk(in);
     const Pending gauge = pending_gauge(sc);
     for (uint64_t t0 = w.first; t0 < w.T; t0 += w.stride) {                       // wave-uniform
@@ -428,7 +347,7 @@ __global__ __launch_bounds__(kThreads) void gp_points(GpIn in, GpScratch sc, GpR
     }
 }
 
-__global__ __launch_bounds__(kThreads) void gp_cameras(GpIn in, GpScratch sc, GpRule rule) {
+__global__ __launch_bounds__(kThreads) void gp_cameras(SceneTables in, GpScratch sc, GpRule rule) {
     __shared__ double s_red[kWaves * kGpTerms];
     __shared__ unsigned s_cnt;
     const unsigned img = blockIdx.x, tid = threadIdx.x;
@@ -460,7 +379,7 @@ __global__ __launch_bounds__(kThreads) void gp_cameras(GpIn in, GpScratch sc, Gp
         for (int k = 0; k < kGpTerms; ++k) acc[k] = acc[k] + term[k];
         ++weighted;
     }
-    block_sum<kGpTerms>(acc, s_red);
+    block_sum<double, kGpTerms>(acc, s_red);
     weighted = block_count(weighted, &s_cnt);
     double cn[3];
     const unsigned reason = gp_solve(acc, weighted, rule.min_obs, cn);
@@ -473,7 +392,7 @@ __global__ __launch_bounds__(kThreads) void gp_cameras(GpIn in, GpScratch sc, Gp
     }
 }
 
-__global__ __launch_bounds__(kThreads) void gp_final_images(GpIn in, GpScratch sc, GpRule rule, float *__restrict__ poses_out,
+__global__ __launch_bounds__(kThreads) void gp_final_images(SceneTables in, GpScratch sc, GpRule rule, float *__restrict__ poses_out,
                                                             unsigned *__restrict__ image_stats, unsigned *__restrict__ counts) {
     __shared__ unsigned s_cnt;
     const unsigned img = blockIdx.x, tid = threadIdx.x;
@@ -520,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void gp_final_images(GpIn in, GpScratch s
     if (weighted) atomicAdd(counts + kGpCWeighted, weighted);
 }
 
-__global__ __launch_bounds__(kThreads) void gp_final_tracks(GpIn in, GpScratch sc, GpRule rule, float *__restrict__ points_out,
+__global__ __launch_bounds__(kThreads) void gp_final_tracks(SceneTables in, GpScratch sc, GpRule rule, float *__restrict__ points_out,
                                                             unsigned *__restrict__ obs_state, unsigned *__restrict__ counts) {
     const TrackWalk w = track_walk(in);
     const Pending gauge = pending_gauge(sc);
@@ -628,20 +547,17 @@ GlobalPositionsPlan global_positions_plan(unsigned n_images, uint64_t track_capa
     return p;
 }
 
-unsigned launch_global_positions(const GlobalPositionsPlan &plan, unsigned char *scratch, const float *kps,
-                                 const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows, const uint64_t *track_offsets,
-                                 uint64_t track_capacity, const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity,
-                                 const unsigned *table_counts, const int *row_track, const float *intrinsics, const float *poses,
+unsigned launch_global_positions(const GlobalPositionsPlan &plan, unsigned char *scratch, const SceneTables &in, const float *poses,
                                  unsigned sweeps, unsigned warm, double s0, unsigned min_obs, float *poses_out, float *points_out,
                                  unsigned *obs_state, unsigned *image_stats, double *trace, unsigned *counts, hipStream_t stream) {
+    const unsigned n_images = in.n_images;
+    const uint64_t track_capacity = in.tcap;
     if (n_images == 0) return 0;
     unsigned issued = 0;
     const auto launch = [&](auto kernel, unsigned grid, auto... args) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, stream, args...);
         ++issued;
     };
-    const GpIn in = {kps, image_offsets, n_images, n_rows, track_offsets, track_capacity, obs_row, obs_image, obs_capacity,
-                     table_counts, row_track, intrinsics};
     const GpScratch sc = {reinterpret_cast<double *>(scratch + plan.off_cen),     reinterpret_cast<double *>(scratch + plan.off_pt),
                           reinterpret_cast<double *>(scratch + plan.off_gauge),
                           reinterpret_cast<float *>(scratch + plan.off_rot),      reinterpret_cast<unsigned *>(scratch + plan.off_reg),

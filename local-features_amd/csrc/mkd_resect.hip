@@ -25,69 +25,36 @@
 
 #include "mkd_device.h"
 #include "mkd_resect_math.h"
+#include "mkd_scene.h"
 
 namespace lfmkd {
 namespace {
 
 constexpr int kThreads = kRsSlots;
 constexpr int kWaves = kThreads / 64;
-static_assert(kThreads == 256, "thread s is slot s of the canonical sum");
+static_assert(kThreads == kSumThreads, "thread s is slot s of the canonical sum");
 constexpr unsigned kRsSliceLen = 1024;      // positions of a run of rs_score: 4 LDS stages
 constexpr unsigned kRsMaxSlices = 16;       // slices a launch has at most; slice z takes the runs z, z + slices, ..
 
-struct RsIn {
-    const float *__restrict__ kps;
-    const uint64_t *__restrict__ off;
-    uint64_t n_rows;
-    const int *__restrict__ row_track;
-    const float *__restrict__ points;
-    uint64_t track_capacity;
-    const unsigned *__restrict__ counts;
-    const float *__restrict__ intrinsics;
-};
 // scratch: idx [n_rows] (image i's correspondences' rows at [lo_i, lo_i + M_i)), head [n_images][2] = {M, candidate},
 // votes [n_images][4 n_samples]
 struct RsScratch {
     unsigned *idx, *head, *votes;
 };
 
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
-
-__device__ __forceinline__ void image_range(const RsIn &in, unsigned img, uint64_t &lo, uint64_t &hi) {
-    lo = clamp_to(in.off[img], in.n_rows);
-    hi = clamp_to(in.off[img + 1], in.n_rows);
-    hi = hi > lo ? hi : lo;
-}
-
 // the correspondence a compacted position names (its row passed rs_gather's test, so the indices are in range)
-__device__ __forceinline__ RsCorr load_corr(const RsIn &in, unsigned row) {
-    const float *k = in.kps + 5 * (uint64_t)row, *p = in.points + 4 * (uint64_t)in.row_track[row];
+__device__ __forceinline__ RsCorr load_corr(const SceneTables &in, const float *points, unsigned row) {
+    const float *k = in.kps + 5 * (uint64_t)row, *p = points + 4 * (uint64_t)in.row_track[row];
     return RsCorr{k[0], k[1], p[0], p[1], p[2]};
-}
-
-// Workgroup sum of N doubles per thread in the canonical order: the butterfly within a wave, then ((w0 + w1) + w2) + w3.
-template <typename T, int N>
-__device__ __forceinline__ void rs_block_sum(T *v, T *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        T s = v[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
-        if (lane == 0) red[wave * N + i] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
-    __syncthreads();
 }
 
 }  // namespace
 
-__global__ __launch_bounds__(kThreads) void rs_gather(RsIn in, const float *__restrict__ poses, unsigned n_samples, double cmin,
-                                                      unsigned all, RsScratch sc, unsigned *__restrict__ row_state) {
+__global__ __launch_bounds__(kThreads) void rs_gather(SceneTables in, const float *points, const float *__restrict__ poses,
+                                                      unsigned n_samples, double cmin, unsigned all, RsScratch sc,
+                                                      unsigned *__restrict__ row_state) {
     __shared__ unsigned s_cnt[kWaves];
-    const unsigned img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned img = blockIdx.x, tid = threadIdx.x;
     float K[4], P[12];
 #pragma unroll
     for (int i = 0; i < 4; ++i) K[i] = in.intrinsics[4 * (uint64_t)img + i];
@@ -99,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void rs_gather(RsIn in, const float *__re
         return;
     }
     for (unsigned c = tid; c < 4 * n_samples; c += kThreads) sc.votes[(uint64_t)img * 4 * n_samples + c] = 0;
-    const uint64_t T = clamp_to(in.counts[0], in.track_capacity);
+    const uint64_t T = clamp_to(in.counts[0], in.tcap);
     uint64_t lo, hi;
     image_range(in, img, lo, hi);
     uint64_t base = lo;
@@ -109,29 +76,19 @@ __global__ __launch_bounds__(kThreads) void rs_gather(RsIn in, const float *__re
         if (r < hi) {
             const int t = in.row_track[r];
             if (t >= 0 && (uint64_t)t < T) {
-                const float *p = in.points + 4 * (uint64_t)t, *k = in.kps + 5 * r;
+                const float *p = points + 4 * (uint64_t)t, *k = in.kps + 5 * r;
                 const float pt[4] = {p[0], p[1], p[2], p[3]};
                 is = rs_point_usable(pt, cmin) && tri_keypoint_usable(k[0], k[1]);
             }
             if (row_state) row_state[r] = is ? 1u : 0u;
         }
-        const uint64_t bits = __ballot(is);
-        if (lane == 0) s_cnt[wave] = (unsigned)__popcll(bits);
-        __syncthreads();
-        unsigned before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            before += (unsigned)w < wave ? s_cnt[w] : 0u;
-            total += s_cnt[w];
-        }
-        if (is) sc.idx[base + before + (unsigned)__popcll(bits & ((1ull << lane) - 1ull))] = (unsigned)r;
-        base += total;
-        __syncthreads();
+        block_compact(is, (unsigned)r, sc.idx, s_cnt, base);
     }
     if (tid == 0) sc.head[2 * (uint64_t)img] = (unsigned)(base - lo), sc.head[2 * (uint64_t)img + 1] = 1;
 }
 
-__global__ __launch_bounds__(kThreads) void rs_score(RsIn in, unsigned n_samples, unsigned seed, double thr2, RsScratch sc) {
+__global__ __launch_bounds__(kThreads) void rs_score(SceneTables in, const float *points, unsigned n_samples, unsigned seed,
+                                                     double thr2, RsScratch sc) {
     __shared__ RsCorr s_c[kThreads];
     const unsigned img = blockIdx.x, tid = threadIdx.x, slice = blockIdx.z, slices = gridDim.z;
     const unsigned M = sc.head[2 * (uint64_t)img];
@@ -146,7 +103,8 @@ __global__ __launch_bounds__(kThreads) void rs_score(RsIn in, unsigned n_samples
     bool valid = false;
     unsigned s[3];
     if (k < n_samples && sample3(seed + img, k, M, s)) {
-        const RsCorr tri[3] = {load_corr(in, sc.idx[lo + s[0]]), load_corr(in, sc.idx[lo + s[1]]), load_corr(in, sc.idx[lo + s[2]])};
+        const RsCorr tri[3] = {load_corr(in, points, sc.idx[lo + s[0]]), load_corr(in, points, sc.idx[lo + s[1]]),
+                               load_corr(in, points, sc.idx[lo + s[2]])};
         valid = rs_candidate_pose(tri, K, j, pose);
     }
     unsigned count = 0;
@@ -154,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void rs_score(RsIn in, unsigned n_samples
         const unsigned end = (unsigned)clamp_to((run + 1) * kRsSliceLen, M);
         for (unsigned p0 = (unsigned)(run * kRsSliceLen); p0 < end; p0 += kThreads) {
             __syncthreads();
-            if (p0 + tid < end) s_c[tid] = load_corr(in, sc.idx[lo + p0 + tid]);
+            if (p0 + tid < end) s_c[tid] = load_corr(in, points, sc.idx[lo + p0 + tid]);
             __syncthreads();
             const unsigned n = end - p0 < (unsigned)kThreads ? end - p0 : (unsigned)kThreads;
             if (valid)
@@ -170,8 +128,9 @@ __global__ __launch_bounds__(kThreads) void rs_score(RsIn in, unsigned n_samples
     }
 }
 
-__global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *poses, unsigned n_samples, unsigned seed, double thr2,
-                                                      unsigned min_inliers, unsigned rounds, RsScratch sc, float *poses_out,
+__global__ __launch_bounds__(kThreads) void rs_select(SceneTables in, const float *points, const float *poses, unsigned n_samples,
+                                                      unsigned seed, double thr2, unsigned min_inliers, unsigned rounds, RsScratch sc,
+                                                      float *poses_out,
                                                       unsigned *__restrict__ stats, float *__restrict__ err,
                                                       unsigned *__restrict__ row_state) {
     __shared__ double s_red[kWaves * (kRsTerms + 1)];
@@ -220,7 +179,8 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
     if (have) {                                                              // block-uniform; every thread the same bits
         unsigned s[3];
         sample3(seed + img, win >> 2, M, s);
-        const RsCorr tri[3] = {load_corr(in, sc.idx[lo + s[0]]), load_corr(in, sc.idx[lo + s[1]]), load_corr(in, sc.idx[lo + s[2]])};
+        const RsCorr tri[3] = {load_corr(in, points, sc.idx[lo + s[0]]), load_corr(in, points, sc.idx[lo + s[1]]),
+                               load_corr(in, points, sc.idx[lo + s[2]])};
         rs_candidate_pose(tri, K, win & 3, pose);
     }
 
@@ -230,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
 #pragma unroll
         for (int i = 0; i <= kRsTerms; ++i) acc[i] = 0.0;
         for (unsigned p = tid; p < M; p += kThreads) {
-            const RsCorr c = load_corr(in, sc.idx[lo + p]);
+            const RsCorr c = load_corr(in, points, sc.idx[lo + p]);
             double e2;
             const bool is = rs_inlier(pose, K, c, thr2, e2);
             acc[kRsTerms] = acc[kRsTerms] + (is ? e2 : thr2);
@@ -241,14 +201,15 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
                 for (int i = 0; i < kRsTerms; ++i) acc[i] = acc[i] + w[i];
             }
         }
-        rs_block_sum<double, kRsTerms + 1>(acc, s_red);
+        block_sum<double, kRsTerms + 1>(acc, s_red);
         double d[6];
         if (!rs_cholesky6(acc, d)) break;
         RsPose next;
         rs_update(pose, d, next);
         double cost[1] = {0.0};
-        for (unsigned p = tid; p < M; p += kThreads) cost[0] = cost[0] + rs_cost(next, K, load_corr(in, sc.idx[lo + p]), thr2);
-        rs_block_sum<double, 1>(cost, s_red);
+        for (unsigned p = tid; p < M; p += kThreads)
+            cost[0] = cost[0] + rs_cost(next, K, load_corr(in, points, sc.idx[lo + p]), thr2);
+        block_sum<double, 1>(cost, s_red);
         if (!(cost[0] <= acc[kRsTerms])) break;
         pose = next;
     }
@@ -260,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
     unsigned n_in[1] = {0};
     double e_sum[1] = {0.0}, e_max = 0.0;
     for (unsigned p = tid; have && p < M; p += kThreads) {
-        const RsCorr c = load_corr(in, sc.idx[lo + p]);
+        const RsCorr c = load_corr(in, points, sc.idx[lo + p]);
         o.x = c.x, o.y = c.y;
         Xd[0] = double(c.X), Xd[1] = double(c.Y), Xd[2] = double(c.Z);
         double e2;
@@ -270,8 +231,8 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
             e_max = e2 > e_max ? e2 : e_max;
         }
     }
-    rs_block_sum<unsigned, 1>(n_in, s_u);
-    rs_block_sum<double, 1>(e_sum, s_red);
+    block_sum<unsigned, 1>(n_in, s_u);
+    block_sum<double, 1>(e_sum, s_red);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const double other = __shfl_xor(e_max, m, 64);
@@ -286,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void rs_select(RsIn in, const float *pose
     if (posed && row_state)
         for (unsigned p = tid; p < M; p += kThreads) {
             const unsigned row = sc.idx[lo + p];
-            const RsCorr c = load_corr(in, row);
+            const RsCorr c = load_corr(in, points, row);
             o.x = c.x, o.y = c.y;
             Xd[0] = double(c.X), Xd[1] = double(c.Y), Xd[2] = double(c.Z);
             double e2;
@@ -310,23 +271,22 @@ uint64_t resect_scratch_bytes(unsigned n_images, uint64_t n_rows, unsigned n_sam
     return 4 * (n_rows + 2 * (uint64_t)n_images + 4 * (uint64_t)n_images * n_samples);
 }
 
-void launch_resect_cameras(void *scratch, const float *kps, const uint64_t *image_offsets, unsigned n_images, uint64_t n_rows,
-                           const int *row_track, const float *points, uint64_t track_capacity, const unsigned *table_counts,
-                           const float *intrinsics, const float *poses, double thr2, double cmin, unsigned n_samples,
-                           unsigned min_inliers, unsigned rounds, unsigned seed, bool all, float *poses_out, unsigned *stats,
-                           float *err, unsigned *row_state, hipStream_t stream) {
+void launch_resect_cameras(void *scratch, const SceneTables &in, const float *points, const float *poses, double thr2, double cmin,
+                           unsigned n_samples, unsigned min_inliers, unsigned rounds, unsigned seed, bool all, float *poses_out,
+                           unsigned *stats, float *err, unsigned *row_state, hipStream_t stream) {
+    const unsigned n_images = in.n_images;
+    const uint64_t n_rows = in.n_rows;
     if (n_images == 0) return;
-    const RsIn in = {kps, image_offsets, n_rows, row_track, points, track_capacity, table_counts, intrinsics};
     unsigned *w = static_cast<unsigned *>(scratch);
     const RsScratch sc = {w, w + n_rows, w + n_rows + 2 * (uint64_t)n_images};
     const uint64_t runs = (n_rows + kRsSliceLen - 1) / kRsSliceLen;
     const unsigned slices = (unsigned)(runs < 1 ? 1 : runs > kRsMaxSlices ? kRsMaxSlices : runs);
-    hipLaunchKernelGGL(rs_gather, dim3(n_images), dim3(kThreads), 0, stream, in, poses, n_samples, cmin, all ? 1u : 0u, sc,
-                       row_state);
+    hipLaunchKernelGGL(rs_gather, dim3(n_images), dim3(kThreads), 0, stream, in, points, poses, n_samples, cmin, all ? 1u : 0u,
+                       sc, row_state);
     hipLaunchKernelGGL(rs_score, dim3(n_images, (4 * n_samples + kThreads - 1) / kThreads, slices), dim3(kThreads), 0, stream, in,
-                       n_samples, seed, thr2, sc);
-    hipLaunchKernelGGL(rs_select, dim3(n_images), dim3(kThreads), 0, stream, in, poses, n_samples, seed, thr2, min_inliers, rounds,
-                       sc, poses_out, stats, err, row_state);
+                       points, n_samples, seed, thr2, sc);
+    hipLaunchKernelGGL(rs_select, dim3(n_images), dim3(kThreads), 0, stream, in, points, poses, n_samples, seed, thr2, min_inliers,
+                       rounds, sc, poses_out, stats, err, row_state);
 }
 
 }  // namespace lfmkd

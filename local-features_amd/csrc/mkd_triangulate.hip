@@ -22,88 +22,59 @@
 
 #include "mkd_device.h"
 #include "mkd_triangulate_math.h"
+#include "mkd_scene.h"   // behind the arithmetic: its walk is kTriSlots lanes wide
 
 namespace lfmkd {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSumThreads;
 constexpr int G = kTriSlots;
 constexpr unsigned kMaxBlocks = 16384;                  // grid-stride beyond
 constexpr int kSets = kTriCandidates / G;              // candidates a lane keeps: lane l has l and l + 4 (one, at 8 lanes)
 static_assert(kSets * G == kTriCandidates, "the candidates fill the group's lanes a whole number of times");
 
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
-
-struct Table {
-    const float *__restrict__ kps;
-    uint64_t n_rows;
-    const int *__restrict__ obs_row;
-    const unsigned *__restrict__ obs_image;
-    const float *__restrict__ intrinsics;
-    const float *__restrict__ poses;
-    unsigned n_images;
-};
-
 // position k of the observation arrays (k < O): false if it is not usable; else what it reads
-__device__ __forceinline__ bool load_obs(const Table &tb, uint64_t k, TriObs &o) {
+__device__ __forceinline__ bool load_obs(const SceneTables &tb, const float *poses, uint64_t k, TriObs &o) {
     const int row = tb.obs_row[k];
     const unsigned img = tb.obs_image[k];
     if (row < 0 || (uint64_t)row >= tb.n_rows || img >= tb.n_images) return false;
 #pragma unroll
     for (int i = 0; i < 4; ++i) o.K[i] = tb.intrinsics[4 * (uint64_t)img + i];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) o.P[i] = tb.poses[12 * (uint64_t)img + i];
+    for (int i = 0; i < 12; ++i) o.P[i] = poses[12 * (uint64_t)img + i];
     o.x = tb.kps[5 * (uint64_t)row];
     o.y = tb.kps[5 * (uint64_t)row + 1];
     return tri_camera_usable(o.K, o.P) && tri_keypoint_usable(o.x, o.y);
 }
 
-// the butterfly of step 2 over the group's lanes
-__device__ __forceinline__ double combine(double v) {
-#pragma unroll
-    for (int m = G / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
 }  // namespace
 
-__global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const uint64_t *__restrict__ off, uint64_t track_capacity,
-                                                               uint64_t obs_capacity, const unsigned *__restrict__ counts,
-                                                               double thr2, unsigned rounds, float *__restrict__ points,
-                                                               unsigned *__restrict__ stats, float *__restrict__ err,
-                                                               unsigned *__restrict__ obs_state) {
-    const uint64_t T = clamp_to(counts[0], track_capacity), O = clamp_to(counts[1], obs_capacity);
-    const unsigned lane = threadIdx.x & 63, l = lane & (G - 1), base = lane & ~(unsigned)(G - 1);
-    const uint64_t wave = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
-    const uint64_t waves = (uint64_t)gridDim.x * (kThreads / 64);
-    const auto group_bits = [&](bool p) { return (unsigned)(__ballot(p) >> base) & ((1u << G) - 1u); };
-
-    for (uint64_t t0 = wave * (64 / G); t0 < T; t0 += waves * (64 / G)) {       // wave-uniform
-        const uint64_t t = t0 + lane / G;
-        const bool alive = t < T;
+__global__ __launch_bounds__(kThreads) void triangulate_tracks(SceneTables tb, const float *poses, double thr2, unsigned rounds,
+                                                               float *__restrict__ points, unsigned *__restrict__ stats,
+                                                               float *__restrict__ err, unsigned *__restrict__ obs_state) {
+    const TrackWalk walk = track_walk(tb);
+    for (uint64_t t0 = walk.first; t0 < walk.T; t0 += walk.stride) {            // wave-uniform
+        const uint64_t t = t0 + (threadIdx.x & 63) / G;
+        const bool alive = t < walk.T;
         uint64_t lo = 0, hi = 0;
-        if (alive) {
-            lo = clamp_to(off[t], O);
-            hi = clamp_to(off[t + 1], O);
-        }
-        hi = hi > lo ? hi : lo;
+        if (alive) track_range(tb, t, walk.O, lo, hi);
         const unsigned nch = (unsigned)((hi - lo + G - 1) / G);
 
         // the first chunk stays in registers
         TriObs o0 = {};
         TriRay r0 = {};
-        const bool u0 = lo + l < hi && load_obs(tb, lo + l, o0);
+        const bool u0 = lo + walk.l < hi && load_obs(tb, poses, lo + walk.l, o0);
         if (u0) tri_ray(o0, r0);
         // position lo + G ch + l under predicate `on`: is it in the track (`in`), usable, and then its observation and ray
         const auto fetch = [&](unsigned ch, bool on, uint64_t &pos, bool &in, TriObs &o, TriRay &r) {
-            pos = lo + (uint64_t)ch * G + l;
+            pos = lo + (uint64_t)ch * G + walk.l;
             in = on && pos < hi;
             if (ch == 0) {
                 o = o0;
                 r = r0;
                 return in && u0;
             }
-            const bool usable = in && load_obs(tb, pos, o);
+            const bool usable = in && load_obs(tb, poses, pos, o);
             if (usable) tri_ray(o, r);
             return usable;
         };
@@ -119,11 +90,11 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
             TriObs o = {};
             TriRay r = {};
             const bool usable = fetch(ch, ch < nch, pos, in, o, r);
-            const unsigned m = group_bits(usable), before = U;
+            const unsigned m = group_bits(usable, walk.base), before = U;
             U += (unsigned)__popc(m);
 #pragma unroll
             for (int set = 0; set < kSets; ++set) {
-                const unsigned c = l + set * G;                               // candidate c is this chunk's (c - before)-th usable
+                const unsigned c = walk.l + set * G;                               // candidate c is this chunk's (c - before)-th usable
                 if (c >= before && c < U) {
                     unsigned mm = m;
 #pragma unroll
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
             for (int i = 0; i < kTriTerms; ++i) cw[set][i] = 0.0;
             TriObs o = {};
             TriRay r = {};
-            if (l + set * G < ncand && load_obs(tb, cand[set], o)) {
+            if (walk.l + set * G < ncand && load_obs(tb, poses, cand[set], o)) {
                 tri_ray(o, r);
                 tri_contribution(r, cw[set]);
             }
@@ -153,13 +124,13 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
             unsigned x = v[0];
 #pragma unroll
             for (int set = 1; set < kSets; ++set) x = c / G == (unsigned)set ? v[set] : x;
-            return (unsigned)__shfl((int)x, (int)(base + c % G), 64);
+            return (unsigned)__shfl((int)x, (int)(walk.base + c % G), 64);
         };
         const auto cand_d = [&](int k, unsigned c) {
             double x = cw[0][k];
 #pragma unroll
             for (int set = 1; set < kSets; ++set) x = c / G == (unsigned)set ? cw[set][k] : x;
-            return __shfl(x, (int)(base + c % G), 64);
+            return __shfl(x, (int)(walk.base + c % G), 64);
         };
 
         // step 5: the pair hypotheses
@@ -176,8 +147,8 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
                 for (int k = 0; k < kTriTerms; ++k) {
                     const double wi = cand_d(k, i), wj = cand_d(k, j);
                     double s = 0.0;
-                    s = si == l ? s + wi : s;
-                    s = sj == l ? s + wj : s;
+                    s = si == walk.l ? s + wi : s;
+                    s = sj == walk.l ? s + wj : s;
                     w[k] = combine(s);
                 }
                 double X[3];
@@ -190,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
                     TriRay r = {};
                     double e2;
                     const bool usable = fetch(ch, ok && ch < nch, pos, in, o, r);
-                    score += (unsigned)__popc(group_bits(usable && tri_inlier(o, X, thr2, e2)));
+                    score += (unsigned)__popc(group_bits(usable && tri_inlier(o, X, thr2, e2), walk.base));
                 }
                 if (ok && (!have || score > best)) {
                     have = true;
@@ -230,8 +201,8 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
 #pragma unroll
                     for (int k = 0; k < kTriTerms; ++k) acc[k] = acc[k] + w[k];
                 }
-                n += (unsigned)__popc(group_bits(is));
-                diff = diff || group_bits(was != is) != 0;
+                n += (unsigned)__popc(group_bits(is, walk.base));
+                diff = diff || group_bits(was != is, walk.base) != 0;
             }
             double w[kTriTerms], Xn[3];
 #pragma unroll
@@ -261,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
                 TriRay ray = {};
                 double e2 = 0.0;
                 const bool is = fetch(ch, act && ch < nch, pos, in, o, ray) && tri_inlier(o, X, thr2, e2);
-                const unsigned m = group_bits(is);
+                const unsigned m = group_bits(is, walk.base);
                 if (m && first == ~0ull) first = lo + (uint64_t)ch * G + ((unsigned)__ffs((int)m) - 1u);
                 n_in += (unsigned)__popc(m);
                 e_sum = is ? e_sum + e2 : e_sum;
@@ -286,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
             if (!__any(act)) continue;                                           // wave-uniform
             TriObs oa = {};
             TriRay ra = {};
-            if (point && load_obs(tb, anchor, oa)) tri_ray(oa, ra);
+            if (point && load_obs(tb, poses, anchor, oa)) tri_ray(oa, ra);
             double v = 4.0;
             uint64_t at = ~0ull;
             for (unsigned ch = 0; __any(act && ch < nch); ++ch) {
@@ -313,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
             cosine = v;
         }
 
-        if (alive && l == 0) {
+        if (alive && walk.l == 0) {
             float *p = points + 4 * t;
             unsigned *st = stats + 4 * t;
             p[0] = point ? float(X[0]) : 0.f;
@@ -332,15 +303,12 @@ __global__ __launch_bounds__(kThreads) void triangulate_tracks(Table tb, const u
     }
 }
 
-void launch_triangulate_tracks(const float *kps, uint64_t n_rows, const uint64_t *track_offsets, uint64_t track_capacity,
-                               const int *obs_row, const unsigned *obs_image, uint64_t obs_capacity, const unsigned *counts,
-                               const float *intrinsics, const float *poses, unsigned n_images, double thr2, unsigned rounds,
-                               float *points, unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream) {
-    if (track_capacity == 0) return;
-    const uint64_t want = (track_capacity * G + kThreads - 1) / kThreads;
-    const Table tb = {kps, n_rows, obs_row, obs_image, intrinsics, poses, n_images};
+void launch_triangulate_tracks(const SceneTables &tb, const float *poses, double thr2, unsigned rounds, float *points, unsigned *stats,
+                               float *err, unsigned *obs_state, hipStream_t stream) {
+    if (tb.tcap == 0) return;
+    const uint64_t want = (tb.tcap * G + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(triangulate_tracks, dim3((unsigned)(want < kMaxBlocks ? want : kMaxBlocks)), dim3(kThreads), 0, stream, tb,
-                       track_offsets, track_capacity, obs_capacity, counts, thr2, rounds, points, stats, err, obs_state);
+                       poses, thr2, rounds, points, stats, err, obs_state);
 }
 
 }  // namespace lfmkd

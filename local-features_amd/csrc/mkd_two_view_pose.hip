@@ -16,13 +16,12 @@
 
 #include "mkd_device.h"
 #include "mkd_pose_math.h"
+#include "mkd_scene.h"   // clamp_to
 
 namespace lfmkd {
 namespace {
 
 constexpr int kThreads = 256, kWaves = kThreads / 64;
-
-__device__ __forceinline__ uint64_t clamp_to(uint64_t v, uint64_t total) { return v < total ? v : total; }
 
 // link k of the table: false if a row is outside the pool; else the two rays
 __device__ __forceinline__ bool load_link(const float *__restrict__ kps, uint64_t n_rows, const int *__restrict__ link_a,

@@ -10,10 +10,12 @@
 
 #pragma clang fp contract(off)
 
+#include "mkd_scene.h"         // block_sum, under the contraction its copy here was compiled under
+
 namespace lfmkd {
 namespace {
 
-constexpr int kThreads = 256;                  // every verification kernel: 4 waves
+constexpr int kThreads = kSumThreads;          // every verification kernel: 4 waves
 constexpr int kWaves = kThreads / 64;
 constexpr unsigned kMaxSlices = 16;            // row slices per (pair, hypothesis block) of a scoring launch
 
@@ -39,31 +41,7 @@ __device__ __forceinline__ bool load_row(const float *ka, const float *kb, const
     return true;
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Workgroup sum of N values per thread, in a fixed order (butterfly within a wave, then the waves in order); every thread
-// gets the totals.  `red` holds kWaves * N values.
-template <typename T, int N>
-__device__ __forceinline__ void block_sum(T *v, T *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const T s = wave_sum(v[i]);
-        if (lane == 0) red[wave * N + i] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        T s = red[i];
-        for (int w = 1; w < kWaves; ++w) s += red[w * N + i];
-        v[i] = s;
-    }
-    __syncthreads();
-}
+// (the workgroup sums are mkd_scene.h's block_sum: the butterfly within a wave, then the waves in order)
 
 }  // namespace
 }  // namespace lfmkd

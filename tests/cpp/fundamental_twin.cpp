@@ -40,7 +40,7 @@ void put(FILE *f, const T *p, size_t n) {
     }
 }
 
-// block_sum of mkd_verify_common.h over per-thread values v[thread][N]
+// block_sum of mkd_scene.h over per-thread values v[thread][N]
 template <typename T>
 void block_sum(const T *v, int N, T *total) {
     std::vector<T> cur(kThreads), nxt(kThreads);
