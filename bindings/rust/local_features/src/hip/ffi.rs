@@ -341,6 +341,18 @@ extern "C" {
                                 points: *const f32, n_tracks: u64, intrinsics: *const f32, max_reproj_px: f32,
                                 min_parallax_deg: f32, n_samples: u32, min_inliers: u32, rounds: u32, seed: u32, flags: u32,
                                 pose: *mut f32, stats: *mut u32, err: *mut f32, row_state: *mut u32) -> c_int;
+    // track descriptors: per track of a track table one 8-bit row [128], the sum of its observations' pool rows normalised and
+    // quantised again (an optional state filter per observation, an optional point filter per track; zero rows, all bytes 128,
+    // elsewhere and up to track_capacity), optional desc_stats [2] = contributors, smallest similarity; lf_mkd_match_q8_device
+    // against the rows gives the d_row_track resection reads; the host form takes host arrays, n_tracks and n_obs
+    pub fn lf_mkd_track_descriptors_device(h: *mut lf_mkd, d_q: *const u8, n_rows_total: u64, d_track_offsets: *const u64,
+                                           track_capacity: u64, d_obs_row: *const i32, obs_capacity: u64,
+                                           d_table_counts: *const u32, d_obs_state: *const u32, min_state: u32,
+                                           d_points: *const f32, min_parallax_deg: f32, scale: f32, d_desc: *mut u8,
+                                           d_desc_stats: *mut i32, stream: *mut c_void) -> c_int;
+    pub fn lf_mkd_track_descriptors(h: *mut lf_mkd, q: *const u8, n_rows_total: u64, track_offsets: *const u64, n_tracks: u64,
+                                    obs_row: *const i32, n_obs: u64, obs_state: *const u32, min_state: u32, points: *const f32,
+                                    min_parallax_deg: f32, scale: f32, desc: *mut u8, desc_stats: *mut i32) -> c_int;
     // bundle adjustment: Levenberg-Marquardt over the free cameras (registered, not marked in d_camera_fixed) and the free
     // points of a track table, the reduced camera system by preconditioned conjugate gradients: poses_out [n_images][12] (may
     // be d_poses), points_out [track_capacity][4] (may be d_points), an optional state per observation, trace f64

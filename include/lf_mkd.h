@@ -1327,6 +1327,67 @@ int lf_mkd_resect_camera(lf_mkd *h, const lf_mkd_keypoint *kps, uint64_t n_rows,
                          uint32_t n_samples, uint32_t min_inliers, uint32_t rounds, uint32_t seed, uint32_t flags, float *pose,
                          uint32_t *stats, float *err, uint32_t *row_state);
 
+/* lf_mkd_track_descriptors_device gives a reconstruction DESCRIPTORS OF ITS OWN: per track of a track table one 8-bit row, the
+ * sum of its observations' rows normalised and quantised again.  With them a photograph that was not part of the collection is
+ * localised by two calls that exist: lf_mkd_match_q8_device of its rows (a) against the track rows (b, nb = track_capacity)
+ * returns per row a table index or -1, which is the d_row_track that lf_mkd_resect_cameras_device reads.  The model is
+ * track_capacity x 128 bytes and the points; the pool's rows need not stay resident.  One launch, nothing read back.
+ * Reads: d_q uint8 [n_rows_total][128], the pool's rows as lf_mkd_quantize_descriptors_device writes them (byte = q + 128);
+ * the track table d_track_offsets [track_capacity + 1], d_obs_row [obs_capacity] and d_table_counts exactly as
+ * lf_mkd_triangulate_tracks_device reads them (T = min(d_table_counts[0], track_capacity) and O = min(d_table_counts[1],
+ * obs_capacity) are formed on the device; track t's positions are [d_track_offsets[t], d_track_offsets[t + 1]), both ends
+ * clamped to O, an inverted range empty); optional d_obs_state uint32 [obs_capacity], the states triangulation and bundle
+ * adjustment write, with min_state 0 .. 2 (NULL: min_state is not looked at); optional d_points f32 [track_capacity][4] as the
+ * triangulation call writes it, with min_parallax_deg (NULL: it is not looked at); scale, the quantiser's (0: 256).
+ * The contract, exactly:
+ *   1. Of a track only its first 65 536 positions are read.  Such a position k CONTRIBUTES iff d_obs_state is NULL or
+ *      d_obs_state[k] >= min_state, and 0 <= d_obs_row[k] < n_rows_total.  C = the contributors' number.
+ *   2. S_k = the sum over the contributors of (byte_k - 128), k = 0 .. 127, and n2 = sum_k S_k^2: integers, whatever bytes the
+ *      rows hold (a byte 0 counts as -128).  With at most 65 536 contributors |S_k| < 2^23 and n2 < 2^53: int64 and f64 hold
+ *      every one of them exactly, and no order of summation changes them.
+ *   3. Track t < T is DESCRIBED iff d_points is NULL or its row there passes resection's rule: finite X, Y, Z and a fourth
+ *      value w <= cmin, cmin = cos(min_parallax_deg) formed once on the host in double (the "none" row {0, 0, 0, 2} and a NaN
+ *      fail).
+ *   4. If the track is described, C > 0 and n2 > 0: v_k = ((double)S_k * (double)scale) / sqrt((double)n2) -- the product is
+ *      exact, sqrt and / are one correctly rounded f64 operation each, contraction off -- q_k = clamp(rint(v_k), -127, 127),
+ *      ties to even, and the row's byte k = q_k + 128.  (|v| = scale: it is the quantiser's row of S / |S|.)
+ *   5. In every other case -- not described, no contributor, sums that cancel -- and for the rows T .. track_capacity - 1 the
+ *      row is the ZERO ROW, all bytes 128: its similarity with every row is 0, so the ratio test passes it only where every
+ *      other similarity is negative, and resection refuses a track without a point anyway.  Exactly track_capacity rows are
+ *      written: the matcher takes nb = track_capacity, and no count is read back.
+ * Outputs: d_desc uint8 [track_capacity][128]; optional d_desc_stats int32 [track_capacity][2] = {C, spread}: C as in 1 (for
+ * a track that is not described too; 0 for the rows from T on), spread = the smallest over the contributors of sum_k (byte_k -
+ * 128) q_k, their similarity with the row as the matcher would score it -- small where a track fuses two things --, and
+ * INT32_MIN for a zero row.
+ * Every output bit depends on the track's own inputs alone: not on the run, the CU count, the grid or the track's place in
+ * the table; a captured call replays to the same bytes, and tests/cpp/track_desc_twin.cpp (csrc/mkd_track_desc_math.h under
+ * g++) gives them on the host.  Whatever the arrays hold the call ends, and nothing at or beyond n_rows_total,
+ * track_capacity (+ 1 for the offsets) or obs_capacity is read or written.  track_capacity == 0 is LF_MKD_OK and writes nothing.
+ * How (csrc/mkd_track_desc.hip): ONE launch sized from track_capacity; a group of 8 lanes owns a track and a lane 16 bytes of
+ * the row, so a contributor's row is one 128-byte request; the walk issues the loads of 4 positions before it adds the
+ * first; 16 integer accumulators a lane, n2 by a butterfly within the group; with d_desc_stats a second walk over the same
+ * rows.  A track of more than 256 positions is taken by its whole wave, group g walking every eighth position.  COST: ONE
+ * track with every row is walked by one wave, 65 536 positions at the most: 1.96 ms, where the torch route takes 1.33 ms
+ * (profiles/track_descriptors.md).  No scratch, no
+ * LDS, no allocation, no atomic, nobody waits; asynchronous on `stream` (NULL: the handle's own), capturable.
+ * LF_MKD_ERR_BAD_ARG, reported before any device is touched (the message starts with "track_descriptors_device: "): a null
+ * handle; with track_capacity > 0 a null d_track_offsets, d_table_counts or d_desc, with obs_capacity > 0 too a null
+ * d_obs_row, and with n_rows_total > 0 too a null d_q; min_state > 2; min_parallax_deg outside [0, 180] or a NaN; scale
+ * negative, not finite or subnormal; d_q or d_desc not 16-byte, d_track_offsets not 8-byte or any other array not 4-byte
+ * aligned; n_rows_total, track_capacity or obs_capacity above 2^31 - 1. */
+int lf_mkd_track_descriptors_device(lf_mkd *h, const uint8_t *d_q, uint64_t n_rows_total, const uint64_t *d_track_offsets,
+                                    uint64_t track_capacity, const int32_t *d_obs_row, uint64_t obs_capacity,
+                                    const uint32_t *d_table_counts, const uint32_t *d_obs_state, uint32_t min_state,
+                                    const float *d_points, float min_parallax_deg, float scale, uint8_t *d_desc,
+                                    int32_t *d_desc_stats, void *stream);
+/* Host pointers, synchronous: the same arrays on the host, track_offsets [n_tracks + 1] and obs_row [n_obs] (the counts are
+ * n_tracks and n_obs), optional obs_state [n_obs] and points [n_tracks][4]; desc [n_tracks][128], optional desc_stats
+ * [n_tracks][2].  Everything goes through the device call.  LF_MKD_ERR_BAD_ARG ("track_descriptors: "): a null handle or
+ * required pointer, the scalars as above, a total above 2^31 - 1. */
+int lf_mkd_track_descriptors(lf_mkd *h, const uint8_t *q, uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks,
+                             const int32_t *obs_row, uint64_t n_obs, const uint32_t *obs_state, uint32_t min_state,
+                             const float *points, float min_parallax_deg, float scale, uint8_t *desc, int32_t *desc_stats);
+
 /* lf_mkd_bundle_adjust_device refines the registered cameras and the tracks' points JOINTLY (bundle adjustment): Levenberg-
  * Marquardt on the reprojection error over all free cameras (6 parameters each, intrinsics fixed) and all free points, the
  * reduced camera system solved matrix-free by preconditioned conjugate gradients.  It is what closes the triangulate / resect

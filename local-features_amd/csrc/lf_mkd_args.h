@@ -54,6 +54,17 @@ inline const char *reproj_rule(float max_reproj_px) {
     return max_reproj_px > 0.f && std::isfinite(max_reproj_px) ? nullptr : "max_reproj_px must be finite and positive";
 }
 inline const char *rounds_rule(uint32_t rounds) { return rounds > 4 ? "rounds must be 0 .. 4" : nullptr; }
+// The quantiser's scale (the 8-bit calls and the track descriptors): 0 -> the default; nullptr: fine.
+inline const char *q8_scale(float &scale) {
+    if (scale == 0.f) scale = 256.f;
+    return scale > 0.f && std::isnormal(scale) ? nullptr : "scale must be a positive, finite, normal f32 (0: the default, 256)";
+}
+// The scalars of lf_mkd_track_descriptors_device and of its host form (the states are triangulation's: 0, 1, 2).
+inline const char *track_desc_scalars(uint32_t min_state, float min_parallax_deg, float &scale) {
+    if (min_state > 2) return "min_state must be 0 .. 2";
+    if (const char *msg = parallax_rule(min_parallax_deg)) return msg;
+    return q8_scale(scale);
+}
 // The scalars of lf_mkd_global_positions_device, of its host form and of its plan.
 inline const char *positions_sweeps_rule(uint32_t sweeps) {
     return sweeps > LF_MKD_GLOBAL_POSITIONS_MAX_SWEEPS ? "sweeps must be 0 .. 4096 (each is three launches)" : nullptr;

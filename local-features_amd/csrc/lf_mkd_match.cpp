@@ -236,12 +236,6 @@ int lf_mkd_match(lf_mkd *h, const float *a, uint64_t na, const float *b, uint64_
 }
 
 // ---- 8-bit descriptors (csrc/mkd_match_q8.hip) --------------------------------------------------------------------------
-// 0 -> the default; nullptr: fine
-static const char *q8_scale(float &scale) {
-    if (scale == 0.f) scale = 256.f;
-    return scale > 0.f && std::isnormal(scale) ? nullptr : "scale must be a positive, finite, normal f32 (0: the default, 256)";
-}
-
 static const char *quantize_args(const lf_mkd *h, const void *desc, uint64_t n, float &scale, const void *q, bool device) {
     if (const char *msg = q8_scale(scale)) return msg;
     if (n && (!desc || !q)) return "null pointer";

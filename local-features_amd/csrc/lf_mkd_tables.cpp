@@ -1,6 +1,9 @@
-// C ABI, the tables built from matches: tracks, track tables, link tables, candidate edges, covisibility.
+// C ABI, the tables built from matches: tracks, track tables, track descriptors, link tables, candidate edges, covisibility.
+#include <cmath>
+
 #include "lf_mkd_args.h"
 #include "mkd_consts.hpp"
+#include "mkd_scene.h"
 
 extern "C" {
 
@@ -90,6 +93,79 @@ int lf_mkd_gather_track_rows_device(lf_mkd *h, const void *d_src, uint32_t row_b
     LF_ENTER(h);
     launch_gather_track_rows(d_src, row_bytes, n_rows_total, d_obs_row, d_counts, obs_capacity, d_dst, stream_of(h, stream));
     return launched(h);
+}
+
+// Track descriptors (csrc/mkd_track_desc.hip).  The parallax cosine is formed here, once, in double, with resection's
+// expression (tests/cpp/track_desc_twin.cpp forms it with the same one).
+int lf_mkd_track_descriptors_device(lf_mkd *h, const uint8_t *d_q, uint64_t n_rows_total, const uint64_t *d_track_offsets,
+                                    uint64_t track_capacity, const int32_t *d_obs_row, uint64_t obs_capacity,
+                                    const uint32_t *d_table_counts, const uint32_t *d_obs_state, uint32_t min_state,
+                                    const float *d_points, float min_parallax_deg, float scale, uint8_t *d_desc,
+                                    int32_t *d_desc_stats, void *stream) {
+    const char *msg = nullptr;
+    if (track_capacity && (!d_track_offsets || !d_table_counts || !d_desc)) msg = "null d_track_offsets, d_table_counts or d_desc";
+    else if (track_capacity && obs_capacity && !d_obs_row) msg = "null d_obs_row";
+    else if (track_capacity && obs_capacity && n_rows_total && !d_q) msg = "null d_q";
+    else if ((msg = track_desc_scalars(min_state, min_parallax_deg, scale))) {}
+    else if (misaligned(15, d_q, d_desc)) msg = "d_q and d_desc must be 16-byte aligned";
+    else if (misaligned(7, d_track_offsets)) msg = "d_track_offsets must be 8-byte aligned";
+    else if (misaligned(3, d_obs_row, d_table_counts, d_obs_state, d_points, d_desc_stats))
+        msg = "the observation, count, state, point and statistics arrays must be 4-byte aligned";
+    else if (above(kRowMax, n_rows_total, track_capacity, obs_capacity)) msg = "a total or a capacity above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "track_descriptors_device", msg);
+    if (track_capacity == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    const double cmin = std::cos(double(min_parallax_deg) * (3.14159265358979323846 / 180.0));
+    const SceneTables tables = {nullptr, n_rows_total, nullptr, 0, d_track_offsets, track_capacity, d_obs_row, nullptr,
+                                obs_capacity, d_table_counts, nullptr, nullptr};
+    launch_track_descriptors(tables, d_q, d_obs_state, min_state, d_points, cmin, scale, d_desc, d_desc_stats, stream_of(h, stream));
+    return launched(h);
+}
+
+// The host form: the arrays staged through the handle's d_ver_io with the outputs, counts = {n_tracks, n_obs}, and the device
+// call does the rest.
+int lf_mkd_track_descriptors(lf_mkd *h, const uint8_t *q, uint64_t n_rows_total, const uint64_t *track_offsets, uint64_t n_tracks,
+                             const int32_t *obs_row, uint64_t n_obs, const uint32_t *obs_state, uint32_t min_state,
+                             const float *points, float min_parallax_deg, float scale, uint8_t *desc, int32_t *desc_stats) {
+    const char *msg = nullptr;
+    if (n_tracks && (!track_offsets || !desc)) msg = "null track_offsets or desc";
+    else if (n_tracks && n_obs && !obs_row) msg = "null obs_row";
+    else if (n_tracks && n_obs && n_rows_total && !q) msg = "null q";
+    else if ((msg = track_desc_scalars(min_state, min_parallax_deg, scale))) {}
+    else if (above(kRowMax, n_rows_total, n_tracks, n_obs)) msg = "a total above 2^31 - 1";
+    else if (!h) msg = "null handle";
+    if (msg) return refuse(h, "track_descriptors", msg);
+    if (n_tracks == 0) return LF_MKD_OK;
+    LF_ENTER(h);
+    // counts [2], the arrays in the device call's order, then the outputs
+    const uint64_t rows_up = n_obs ? n_rows_total : 0;
+    Stager io(h, h->d_ver_io);
+    const auto d_counts = io.part<uint32_t>(2);
+    const auto d_offs = io.part<uint64_t>(n_tracks + 1);
+    const auto d_q = io.part<uint8_t>(rows_up * 128);
+    const auto d_row = io.part<int32_t>(n_obs);
+    const auto d_state = io.part<uint32_t>(obs_state ? n_obs : 0);
+    const auto d_points = io.part<float>(points ? n_tracks * 4 : 0);
+    const auto d_desc = io.part<uint8_t>(n_tracks * 128);
+    const auto d_stats = io.part<int32_t>(desc_stats ? n_tracks * 2 : 0);
+    if (int rc = io.reserve()) return rc;
+    // (counts saturate: the totals are below 2^31)
+    const uint32_t counts[2] = {uint32_t(n_tracks), uint32_t(n_obs)};
+    LF_HIP(h, io.up(d_counts, counts, 2));
+    LF_HIP(h, io.up(d_offs, track_offsets, n_tracks + 1));
+    LF_HIP(h, io.up(d_q, q, rows_up * 128));
+    LF_HIP(h, io.up(d_row, obs_row, n_obs));
+    LF_HIP(h, io.up(d_state, obs_state, obs_state ? n_obs : 0));
+    LF_HIP(h, io.up(d_points, points, points ? n_tracks * 4 : 0));
+    if (int rc = lf_mkd_track_descriptors_device(h, d_q, n_rows_total, d_offs, n_tracks, d_row, n_obs, d_counts,
+                                                 obs_state ? d_state.get() : nullptr, min_state, points ? d_points.get() : nullptr,
+                                                 min_parallax_deg, scale, d_desc, desc_stats ? d_stats.get() : nullptr, h->stream))
+        return rc;
+    LF_HIP(h, io.down(desc, d_desc, n_tracks * 128));
+    LF_HIP(h, io.down(desc_stats, d_stats, desc_stats ? n_tracks * 2 : 0));
+    LF_HIP(h, hipStreamSynchronize(h->stream));
+    return LF_MKD_OK;
 }
 
 // Link tables (csrc/mkd_link_table.hip); the grid is tracks_link's.

@@ -369,6 +369,11 @@ void launch_two_view_pose(const float *kps, uint64_t n_rows, const unsigned *edg
 // Keypoints are read as rows of 5 floats; thr2 = the squared reprojection threshold, formed by the host in double.
 void launch_triangulate_tracks(const SceneTables &tables, const float *poses, double thr2, unsigned rounds, float *points,
                                unsigned *stats, float *err, unsigned *obs_state, hipStream_t stream);
+// track descriptors (csrc/mkd_track_desc.hip, lf_mkd_track_descriptors_device): one launch, 8 lanes per track, no scratch.
+// The tables read are toff, tcap, obs_row, ocap, counts and n_rows (the rows of q); cmin = the cosine of the smallest
+// parallax, formed by the host in double; scale > 0.  obs_state, points and stats may be null.
+void launch_track_descriptors(const SceneTables &tables, const unsigned char *q, const unsigned *obs_state, unsigned min_state,
+                              const float *points, double cmin, float scale, unsigned char *desc, int *stats, hipStream_t stream);
 // camera resection (csrc/mkd_resect.hip, lf_mkd_resect_cameras_device): three launches (rs_gather, rs_score, rs_select) over
 // `scratch` of resect_scratch_bytes(..) bytes, 4-byte aligned.  thr2 = the squared reprojection threshold and cmin = the
 // cosine of the smallest parallax, both formed by the host in double.  poses_out may be poses.

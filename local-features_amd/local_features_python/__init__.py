@@ -1009,6 +1009,85 @@ class LocalFeatures:
                                                   min_inliers, rounds, seed, RESECT_ALL if resect_all else 0, s.cuda_stream)
         return out, st, er, rs
 
+    def track_descriptors(self, q8, table, obs_state=None, min_state=2, points=None, min_parallax_deg=0.0, scale=Q8_SCALE,
+                          stats=False, stream=None):
+        """One 8-bit descriptor per track of a track table (lf_mkd_track_descriptors_device): the sum of the centred rows of
+        the track's observations, normalised and quantised again with `scale` -- the descriptors a reconstruction exports with
+        its points, so that `localize` needs neither the pool's rows nor the table (include/lf_mkd.h states the contract).
+        q8 [rows, 128] uint8 is the pool, quantised; table = (offsets, rows, images, counts) or track_table's 5-tuple (the
+        images are not read).  obs_state [obs_capacity] int32, triangulate_tracks' or bundle_adjust's: an observation
+        contributes iff its state is at least min_state (0 .. 2; None: every observation); points [track_capacity, 4] float32:
+        a track is described iff its point is finite with a parallax cosine <= cos(min_parallax_deg), resect_cameras' rule
+        (None: every track).  Returns the device tensor desc [track_capacity, 128] uint8 -- the zero row, all bytes 128, for a
+        track that is not described, has no contributor or whose rows cancel, and for the rows beyond the table's tracks --
+        and with stats=True (desc, stats [track_capacity, 2] int32 = contributors, the smallest similarity of a contributor
+        with its track's row; INT32_MIN for a zero row).  Nothing is read back: asynchronous on `stream` (default: torch's
+        current stream on the handle's device), capturable."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        offsets, rows, counts = table[0], table[1], table[-1]
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (len(table) in (4, 5) and ok(offsets, torch.int64) and offsets.dim() == 1 and offsets.numel() >= 1
+                    and ok(rows, torch.int32) and ok(counts, torch.int32) and counts.numel() >= 2):
+                raise RuntimeError("track_descriptors: table must be (offsets int64, rows int32, images, counts int32) contiguous "
+                                   "device tensors as track_table returned them")
+            if not (ok(q8, torch.uint8) and q8.dim() == 2 and q8.shape[1] == 128):
+                raise RuntimeError("track_descriptors: q8 must be a contiguous uint8 [rows, 128] device tensor")
+            tcap, ocap = offsets.numel() - 1, rows.numel()
+            if obs_state is not None and not (ok(obs_state, torch.int32) and obs_state.numel() == ocap):
+                raise RuntimeError("track_descriptors: obs_state must be a contiguous int32 [obs_capacity] device tensor")
+            if points is not None and not (ok(points, torch.float32) and points.dim() == 2 and tuple(points.shape) == (tcap, 4)):
+                raise RuntimeError("track_descriptors: points must be a contiguous float32 [track_capacity, 4] device tensor")
+            desc = torch.empty((tcap, 128), dtype=torch.uint8, device=dev)
+            ds = torch.empty((tcap, 2), dtype=torch.int32, device=dev) if stats else None
+            ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+            with self._lock:
+                self._inner.track_descriptors_device(ptr(q8), q8.shape[0], offsets.data_ptr(), tcap, ptr(rows), ocap,
+                                                     counts.data_ptr(), ptr(desc), ptr(ds), ptr(obs_state), min_state, ptr(points),
+                                                     min_parallax_deg, scale, s.cuda_stream)
+        return (desc, ds) if stats else desc
+
+    def localize(self, q8_query, kps_query, query_offsets, model_desc, points, table_counts, intrinsics, ratio=0.8,
+                 max_reproj_px=4.0, min_parallax_deg=0.0, n_samples=512, min_inliers=12, rounds=3, seed=0, stream=None):
+        """The poses of photographs that were not part of a reconstruction, against the model track_descriptors made: ONE
+        lf_mkd_match_q8_device call with all query rows as a and the model's rows as b -- its answer per query row, a table
+        index or -1, is the row_track resection reads -- then ONE lf_mkd_resect_cameras_device call over the query pool with
+        all-zero poses.  No other kernel, and nothing is read back in between.
+        q8_query [rows, 128] uint8 and kps_query [rows, 5] float32 are the query images' pooled rows and query_offsets
+        [n_query + 1] int64 their image offsets; model_desc [track_capacity, 128] uint8, points [track_capacity, 4] float32
+        and table_counts int32 are the model (at least two tracks); intrinsics [n_query, 4] float32 the query cameras'.  The
+        other arguments are resect_cameras'.  A query row matched to a track without a point, or to a zero row, is no
+        correspondence there.  Returns device tensors (poses [n_query, 12] float32, all zero where no pose was found; stats
+        [n_query, 4] int32, err [n_query, 2] float32 and row_state [rows] int32 as resect_cameras returns them; row_track
+        [rows] int32).  Asynchronous on `stream` (default: torch's current stream on the handle's device); capturable once
+        warmed up."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            ok = lambda x, t: hasattr(x, "is_cuda") and x.is_cuda and x.dtype == t and x.is_contiguous()
+            if not (ok(q8_query, torch.uint8) and q8_query.dim() == 2 and q8_query.shape[1] == 128
+                    and ok(model_desc, torch.uint8) and model_desc.dim() == 2 and model_desc.shape[1] == 128):
+                raise RuntimeError("localize: q8_query and model_desc must be contiguous uint8 [rows, 128] device tensors")
+            if not (ok(kps_query, torch.float32) and kps_query.dim() == 2 and tuple(kps_query.shape) == (q8_query.shape[0], 5)):
+                raise RuntimeError("localize: kps_query must be a contiguous float32 [rows, 5] device tensor, a row per row of "
+                                   "q8_query")
+            if not (ok(points, torch.float32) and points.dim() == 2 and tuple(points.shape) == (model_desc.shape[0], 4)):
+                raise RuntimeError("localize: points must be a contiguous float32 [track_capacity, 4] device tensor, a row per "
+                                   "row of model_desc")
+            n_rows, n_query = q8_query.shape[0], query_offsets.numel() - 1 if hasattr(query_offsets, "numel") else -1
+            row_track = torch.full((n_rows,), -1, dtype=torch.int32, device=dev)
+            if n_rows:
+                with self._lock:
+                    self._inner.match_q8_device(q8_query.data_ptr(), n_rows, model_desc.data_ptr(), model_desc.shape[0],
+                                                row_track.data_ptr(), ratio, stream=s.cuda_stream)
+            zero = torch.zeros((max(n_query, 0), 12), dtype=torch.float32, device=dev)
+        poses, st, er, rs = self.resect_cameras(kps_query, query_offsets, row_track, points, table_counts, intrinsics, zero,
+                                                max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed, stream=s)
+        return poses, st, er, rs, row_track
+
     def view_graph(self, edges, R, pose_stats, n_images, max_loop_deg=3.0, min_front=0, root=None, tree_rounds=16, iterations=10,
                    use_unchecked=False, layout=None, match=None, out_match=None, residual=True, stream=None):
         """View-graph checks and global rotations (lf_mkd_view_graph_device): the relative rotations around every triangle of

@@ -51,6 +51,7 @@ SYMBOLS = (
     "lf_mkd_two_view_pose", "lf_mkd_two_view_pose_device",
     "lf_mkd_triangulate_tracks", "lf_mkd_triangulate_tracks_device",
     "lf_mkd_resect_camera", "lf_mkd_resect_cameras_device",
+    "lf_mkd_track_descriptors", "lf_mkd_track_descriptors_device",
     "lf_mkd_bundle_adjust", "lf_mkd_bundle_adjust_device",
     "lf_mkd_bundle_adjust_intrinsics", "lf_mkd_bundle_adjust_intrinsics_device",
     "lf_mkd_view_graph_plan", "lf_mkd_view_graph", "lf_mkd_view_graph_device",
@@ -198,6 +199,9 @@ def load_library():
                                                u32, u32, u32, u32, vp, vp, vp, vp, vp]
     L.lf_mkd_resect_camera.argtypes = [vp, vp, u64, vp, vp, u64, vp, ctypes.c_float, ctypes.c_float, u32, u32, u32, u32, u32, vp,
                                        vp, vp, vp]
+    L.lf_mkd_track_descriptors_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, u32, vp, ctypes.c_float, ctypes.c_float,
+                                                  vp, vp, vp]
+    L.lf_mkd_track_descriptors.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u32, vp, ctypes.c_float, ctypes.c_float, vp, vp]
     L.lf_mkd_bundle_adjust_device.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.c_float,
                                               ctypes.c_float, u32, u32, ctypes.c_float, u32, vp, vp, vp, vp, vp, vp]
     L.lf_mkd_bundle_adjust.argtypes = [vp, vp, vp, u32, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, ctypes.c_float,
@@ -726,6 +730,31 @@ class MkdHandle:
                     "lf_mkd_resect_camera")
         return pose, st, er, rs[:len(k)] if row_state else None
 
+    def track_descriptors(self, q8, track_offsets, obs_row, obs_state=None, min_state=2, points=None, min_parallax_deg=0.0,
+                          scale=Q8_SCALE, stats=True):
+        """lf_mkd_track_descriptors: q8 uint8 [rows,128] (the pool's quantised rows), track_offsets uint64 [n_tracks + 1],
+        obs_row int32 [n_obs], optionally obs_state uint32 [n_obs] with min_state (an observation contributes iff its state is
+        at least min_state) and points [n_tracks,4] f32 with min_parallax_deg (a track is described iff its point passes
+        resection's rule) -> (desc uint8 [n_tracks,128]: the sum of the contributors' centred rows, normalised and quantised
+        with `scale`, or the zero row, all 128; stats int32 [n_tracks,2] = contributors, smallest similarity of a contributor
+        with the row (INT32_MIN for a zero row), or None)."""
+        q = np.ascontiguousarray(q8, np.uint8).reshape(-1, 128)
+        off = np.ascontiguousarray(track_offsets, np.uint64).reshape(-1)
+        row = np.ascontiguousarray(obs_row, np.int32).reshape(-1)
+        st = None if obs_state is None else np.ascontiguousarray(obs_state, np.uint32).reshape(-1)
+        pts = None if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        n, n_obs = len(off) - 1, len(row)
+        if len(off) < 1 or (st is not None and len(st) != n_obs) or (pts is not None and len(pts) != n):
+            raise RuntimeError("track_descriptors: track_offsets needs n_tracks + 1 entries, obs_state one entry per observation, "
+                               "points one row per track")
+        desc = np.empty((max(n, 1), 128), np.uint8)
+        ds = np.empty((max(n, 1), 2), np.int32) if stats else None
+        at = lambda x: x.ctypes.data if x is not None and x.size else None
+        self._check(self.L.lf_mkd_track_descriptors(self._h, at(q), len(q), off.ctypes.data, n, at(row), n_obs, at(st), min_state,
+                                                     at(pts), min_parallax_deg, scale, desc.ctypes.data, at(ds)),
+                    "lf_mkd_track_descriptors")
+        return desc[:n], ds[:n] if stats else None
+
     def view_graph(self, edge_a, edge_b, R, pose_stats, n_images, max_loop_deg=3.0, min_front=0, root=VIEW_GRAPH_AUTO_ROOT,
                    tree_rounds=16, iterations=10, flags=0, edge_offsets_a=None, match=None, residual=True):
         """lf_mkd_view_graph: edge_a / edge_b uint32 [n_edges], R f32 [n_edges, 9] and pose_stats uint32 [n_edges, 4] as
@@ -1171,6 +1200,18 @@ class MkdHandle:
             self._h, d_kps, d_image_offsets, n_images, n_rows_total, d_row_track, d_points, track_capacity, d_table_counts,
             d_intrinsics, d_poses, max_reproj_px, min_parallax_deg, n_samples, min_inliers, rounds, seed & 0xFFFFFFFF, flags,
             d_poses_out, d_stats, d_err, d_row_state, s), "lf_mkd_resect_cameras_device")
+
+    def track_descriptors_device(self, d_q, n_rows_total, d_track_offsets, track_capacity, d_obs_row, obs_capacity, d_table_counts,
+                                 d_desc, d_desc_stats=None, d_obs_state=None, min_state=2, d_points=None, min_parallax_deg=0.0,
+                                 scale=Q8_SCALE, stream=None):
+        """lf_mkd_track_descriptors_device: per track of the table d_track_offsets uint64 [track_capacity + 1] / d_obs_row int32
+        [obs_capacity] / d_table_counts (lf_mkd_track_table_device's outputs) one 8-bit row from the rows d_q uint8
+        [n_rows_total][128] of its observations (d_obs_state uint32 [obs_capacity], nullable: those of at least min_state;
+        d_points f32 [track_capacity][4], nullable: the tracks whose point passes resection's rule) -- d_desc uint8
+        [track_capacity][128], d_desc_stats int32 [track_capacity][2] (nullable) (device pointers; see include/lf_mkd.h)."""
+        self._device_call(stream, lambda s: self.L.lf_mkd_track_descriptors_device(
+            self._h, d_q, n_rows_total, d_track_offsets, track_capacity, d_obs_row, obs_capacity, d_table_counts, d_obs_state,
+            min_state, d_points, min_parallax_deg, scale, d_desc, d_desc_stats, s), "lf_mkd_track_descriptors_device")
 
     def view_graph_device(self, d_edge_a, d_edge_b, n_edges, d_R, d_pose_stats, n_images, d_rotations, d_edge_stats,
                           d_image_stats, d_counts, d_edge_residual=None, d_edge_offsets_a=None, ea_capacity=0, d_match=None,
